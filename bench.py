@@ -5,7 +5,7 @@ A "step" is one pass of the hot path (content encoder -> dual AR -> vocoder) ove
 synthetic 44.1 kHz audio chunks: every stream of every rank consumes one 2048*chunk-sample chunk
 and emits one converted chunk (InferenceWrapper.process_one_chunk, evaluations/infer_arvc.py:492-596).
 
-    python bench.py --gpus 1 --steps 50 --warmup 5 [--streams 1] [--chunk 1]
+    python bench.py --gpus 1 --steps 50 --warmup 5 [--streams 1] [--chunk 1] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,6 +16,7 @@ collective is the gather of per-utterance results + a MAX of the wall time.
 
 Prints ONE JSON line (rank 0).  `value` = frames/s aggregated over all streams of all ranks with
 inputs already resident in HBM; `rtf` = per-stream real-time factor = step time / chunk duration.
+A plain run does only that; `--full` adds the latency sample, roofline / PMC figures, the other workloads and the baselines.
 """
 from __future__ import annotations
 
@@ -44,8 +45,15 @@ ENC_PARAMS, AR_PARAMS, VOC_PARAMS = 52.0e6, 129.77e6, 22.35e6
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=None, help="timed chunk-steps (default 200; with --config: the rest of the utterance)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the synchronous per-chunk latency sample, roofline + PMC passes, the semantic-head-on "
+                         "run, the 64-stream and re-prefill blocks, offline / prompt latencies, the CPU, eager-torch and torch.compile baselines "
+                         "(each can still be left out with its --no-* option).  Without it a run sets up, warms up, times --steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (rank 0): pcm [streams, samples] "
+                         "float32 and audio_codes [streams, 8, chunk] as float64")
     ap.add_argument("--streams", type=int, default=1, help="concurrent streams per GPU (B)")
     ap.add_argument("--chunk", type=int, default=1, help="decode_chunk_frames")
     ap.add_argument("--prompt-frames", type=int, default=107)
@@ -229,7 +237,7 @@ def pmc_traffic(B, chunk):
         for name, counters in (("RD", ["TCC_EA0_RDREQ_sum", "TCC_EA0_RDREQ_32B_sum"]), ("WR", ["WRITE_SIZE"])):
             d = os.path.join(tmp, name)
             cmd = ["rocprofv3", "--kernel-trace", "--pmc", *counters, "--output-format", "csv", "-d", d, "-o", "p", "--",
-                   sys.executable, os.path.abspath(__file__), "--steps", "24", "--warmup", "3", "--streams", str(B), "--chunk", str(chunk),
+                   sys.executable, os.path.abspath(__file__), "--full", "--steps", "24", "--warmup", "3", "--streams", str(B), "--chunk", str(chunk),
                    "--no-cpu-baseline", "--no-roofline", "--no-pipeline", "--no-batched", "--no-pmc", "--no-torch-gpu-baseline", "--no-offline", "--no-pin"]
             r = subprocess.run(cmd, env=env, cwd="/tmp", stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=200)
             files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
@@ -538,6 +546,13 @@ def main():
     args = parse()
     if args.compiled_baseline_worker:
         return compiled_baseline_worker(args)
+    if args.steps is None:
+        # 10 s = 215.3 frames; delay fill and warm-up come out of the utterance
+        args.steps = (216 if args.config == 4 else 54) - args.warmup - 4 if args.config else 200
+    if not args.full:
+        # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_roofline = args.no_batched = True
+        args.pmc = args.offline = args.torch_gpu_baseline = False
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args)
     rank = int(os.environ.get("RANK", "0"))
@@ -587,13 +602,12 @@ def main():
         args.streams, args.chunk = 64, 1
     elif args.config == 5:
         args.streams, args.chunk = 32, 4
-    if args.config and "--steps" not in sys.argv:
-        args.steps = (216 if args.config == 4 else 54) - args.warmup - 4          # 10 s = 215.3 frames; delay fill and warm-up come out of the utterance
     B, c = args.streams, args.chunk
     n = 2048 * c
     W = synth_weights.generate_all(0, specs.all_specs())
     eng = E.Engine(W, device=local_rank, ar_dtype=args.ar_dtype, mm_mode=args.mm_mode, voc_dtype=args.voc_dtype)
     pin_info = {}
+    outputs = {}                # --dump-outputs: the headline run's last timed step
     cpus_at_start = os.sched_getaffinity(0)
 
     def run_workload(B, steps, warmup, want_roofline, skip_semantic=None):
@@ -621,7 +635,7 @@ def main():
             batch.prefill_prompt(s_, cc, ac, style, timbre, noise_seed=1000 + u)
         batch.begin()
         n_delay = (2 + c - 1) // c              # chunks that only fill the delay (return zeros)
-        n_lat = 40                              # synchronous per-chunk latency sample after the timed region
+        n_lat = 40 if args.full else 0          # synchronous per-chunk latency sample after the timed region
         prime = max(0, 4 - warmup)              # GEMM autotuning + pipeline start-up need a few steady steps: never inside the timed region
         total_chunks = n_delay + prime + warmup + steps + n_lat + 20
         audio = np.stack([synth_utterance(1000 + u, n * total_chunks) for u in my_utts])     # [B, n*total]
@@ -637,6 +651,7 @@ def main():
             run(k); k += 1
         batch.sync()
         if args.pin and not pin_info:
+            k_pin = k
             # after the first steps (the runtime's helper threads exist and keep their placement): move this, the enqueueing,
             # thread to the core group with the cheapest kernel launches to this GPU -- kept only if enqueueing a real step
             # got cheaper (median of 5 steps into an idle queue), else the next-best group, else the original placement
@@ -669,6 +684,10 @@ def main():
             pin_info.update({"placed_on": best[0], "step_enqueue_ms": {t_[0]: round(t_[2], 3) for t_ in tried},
                              "probe_us_per_launch_best": round(min(table.values()), 2) if table else None,
                              "probe_us_per_launch_worst": round(max(table.values()), 2) if table else None})
+            # the probe ran 5, 10 or 15 steps: pad to 15 so that the timed steps see the same chunks and stream state every run
+            while k < k_pin + 15:
+                run(k); k += 1
+            batch.sync()
         torch.cuda.synchronize()
         if world > 1 or force_dist:
             dist.barrier()
@@ -681,21 +700,28 @@ def main():
         if world > 1 or force_dist:
             dist.barrier()
         dt = time.perf_counter() - t0
-        # per-chunk latency as a live caller sees it (enqueue + execute + sync per chunk; outside the timed region)
-        lat, enq = [], []
-        for _ in range(n_lat):
-            t1 = time.perf_counter()
-            run(k); k += 1
-            t2 = time.perf_counter()
-            batch.sync()
-            lat.append((time.perf_counter() - t1) * 1e3)
-            enq.append((t2 - t1) * 1e3)
+        if args.dump_outputs and not outputs:
+            # what the last timed step handed its caller: the converted chunk of every stream and the audio codes it decoded
+            rows = np.arange(B)
+            if B * n * 4 > 48 << 20:        # at most 64 MB in all: a fixed, seeded sample of the streams
+                rows = np.sort(np.random.default_rng(0).choice(B, (48 << 20) // (n * 4), replace=False))
+            outputs["pcm"] = d_out.cpu().numpy()[rows].astype(np.float32)
+            outputs["audio_codes"] = np.stack([batch.pred_codes(int(s_), c) for s_ in rows]).astype(np.float64)
+        extra = {"host_enqueue_ms_per_step": round(t_enq / steps * 1e3, 4)}          # back-to-back (includes queue back-pressure)
+        if n_lat:
+            # per-chunk latency as a live caller sees it (enqueue + execute + sync per chunk; outside the timed region)
+            lat, enq = [], []
+            for _ in range(n_lat):
+                t1 = time.perf_counter()
+                run(k); k += 1
+                t2 = time.perf_counter()
+                batch.sync()
+                lat.append((time.perf_counter() - t1) * 1e3)
+                enq.append((t2 - t1) * 1e3)
+            lat.sort(); enq.sort()
+            extra["host_enqueue_ms_idle_queue"] = round(enq[len(enq) // 2], 4)          # median with an empty queue: the pure host cost
+            extra["sync_latency_ms"] = {"p50": round(lat[len(lat) // 2], 4), "p99": round(lat[min(len(lat) - 1, int(0.99 * len(lat)))], 4), "n": n_lat}
         tm = batch.timings()          # of the last, individually synchronised step: its stages ran back to back, not overlapped
-        lat.sort(); enq.sort()
-        extra = {"host_enqueue_ms_per_step": round(t_enq / steps * 1e3, 4),          # back-to-back (includes queue back-pressure)
-                 "host_enqueue_ms_idle_queue": round(enq[len(enq) // 2], 4),          # median with an empty queue: the pure host cost
-                 "sync_latency_ms": {"p50": round(lat[len(lat) // 2], 4), "p99": round(lat[min(len(lat) - 1, int(0.99 * len(lat)))], 4),
-                                     "n": n_lat}}
         dt_rank = dt
         if world > 1 or force_dist:
             t = torch.tensor([dt], device="cuda", dtype=torch.float64)
@@ -842,11 +868,11 @@ def main():
                    "stage_pipelining": bool(args.pipeline) and not args.graph, "mm_mode": int(eng.cfg.mm_mode), "voc_dtype": int(eng.cfg.voc_dtype), "skip_semantic_head": bool(args.skip_semantic),
                    "enqueue_thread": pin_info or None},
         "rtf": round(ms * 1e-3 / (c * FRAME_S), 5), "x_realtime": round(fps * FRAME_S, 2),
-        # what a caller that waits for every chunk sees (the reference's process_one_chunk contract): median synchronous latency / chunk duration
-        "rtf_live": round(extra["sync_latency_ms"]["p50"] * 1e-3 / (c * FRAME_S), 5), "sync_latency_p50_ms": extra["sync_latency_ms"]["p50"],
-        "stage_ms_last_step": {k_: round(v, 4) for k_, v in tm.items()},
-        "gathered_utterances": n_gathered,
     }
+    if "sync_latency_ms" in extra:
+        # what a caller that waits for every chunk sees (the reference's process_one_chunk contract): median synchronous latency / chunk duration
+        out.update({"rtf_live": round(extra["sync_latency_ms"]["p50"] * 1e-3 / (c * FRAME_S), 5), "sync_latency_p50_ms": extra["sync_latency_ms"]["p50"]})
+    out.update({"stage_ms_last_step": {k_: round(v, 4) for k_, v in tm.items()}, "gathered_utterances": n_gathered})
     out.update(extra)
 
     def stage_rates(B_, ms_step, tm_, gflop_step, f32_only=True):
@@ -950,6 +976,10 @@ def main():
         dma = (r64.get("by_pipe") or {}).get("planes_dma_f16x2")
         if dma:          # the encoder's batch-scale GEMMs (persistent LDS-DMA planes kernel): algorithmic TF/s and fraction of the 833 TF/s three-product ceiling
             out["b64_planes_dma_tflops"], out["b64_planes_dma_frac"] = dma["achieved"], dma["frac"]
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     print(json.dumps(out))
     if world > 1 or force_dist:
         dist.destroy_process_group()

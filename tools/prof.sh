@@ -2,6 +2,7 @@
 # rocprofv3 kernel-trace stats of bench.py:  tools/prof.sh TAG [bench args...]
 TAG=$1; shift
 export TMPDIR=/tmp
+set -- --full "$@"        # the whole default run: 64-stream block, roofline step, semantic-head-on run
 rm -rf gpurun_out/prof_${TAG}
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${TAG} -o p -- python bench.py --no-cpu-baseline --no-pmc --no-torch-gpu-baseline --no-offline "$@" > gpurun_out/prof_${TAG}.log 2>&1
 tail -1 gpurun_out/prof_${TAG}.log | cut -c1-400

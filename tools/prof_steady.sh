@@ -4,6 +4,7 @@ TAG=$1; B=$2; K=${3:-100}
 export TMPDIR=/tmp
 rm -rf gpurun_out/prof_${TAG}
 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof_${TAG} -o p -- python bench.py --streams $B --steps $K --warmup 5 --no-pin \
+    --full \
     --no-cpu-baseline --no-batched --no-roofline --no-pmc --no-torch-gpu-baseline --no-offline > gpurun_out/prof_${TAG}.log 2>&1
 tail -1 gpurun_out/prof_${TAG}.log | cut -c1-300
 # 2 delay chunks + 5 warm-up steps precede the timed region

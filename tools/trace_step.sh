@@ -2,6 +2,7 @@
 # Timeline of ONE steady-state B=1 step from a rocprofv3 kernel trace: per-kernel duration and the gap to the previous
 # kernel on the same queue, aggregated per kernel name.  tools/trace_step.sh [bench args]
 export TMPDIR=/tmp
+set -- --full "$@"        # the step it reads is one of the synchronised latency-sample steps at the end of the run
 rm -rf gpurun_out/trace_step
 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/trace_step -o t -- python bench.py --no-cpu-baseline --no-pmc --no-torch-gpu-baseline --no-offline --no-batched --no-roofline --steps 12 --warmup 3 "$@" > gpurun_out/trace_step.log 2>&1
 python - <<'PY'
