@@ -299,6 +299,41 @@ int sva_test_prefill_attention(int device, int M, int H, int pos0, int S, const 
 int sva_test_pair_attention(int device, int M, int H, int pos0, int S, const float* q, const float* keys, const float* vals,
                                int half_kv, float* out_ref, float* out_mfma, int iters, float* us);
 
+/* Per-kernel hooks of the non-GEMM launchers (csrc/kernels.h), for tests/test_gpu_kernels.py: host arrays in, the production launcher with the
+ * caller's arguments, host arrays out.  Output arrays are uploaded before the launch, so a sentinel the caller wrote survives wherever the
+ * kernel writes nothing; every index a launch touches is checked against the array lengths first.
+ * Decode attention family over a cache [n_slots][2][H][S][64] (fp32 values; rounded to fp16 on upload and widened on return when half_kv) with
+ * caller-chosen slot[M] / pos[M].  variant 0: launch_ar_attention, 1: split-key launch_ar_attention (8 splits) merged by the GEMV (mode 4:
+ * out = x + W attention), 2: launch_ar_attention_pairs, 3: launch_ar_fast_attention (RoPE + cache write + attention, S <= 8), 4: GEMV mode 3
+ * (out = x + W attention over <= 8 keys), 5: launch_rope_kvwrite (qkv rotated in place, cache written), 6: GEMV mode 2 (qkv[:, :D] = RoPE(W q-rows
+ * RMSNorm(x)), k / v into the cache; W [3D][D]).  qkv [M][3 H 64] and cache are returned as the device left them; out [M][H 64]. */
+int sva_test_decode_attention(int device, int variant, int M, int H, int S, int n_slots, const int* slot, const int* pos, int half_kv, float* qkv,
+                              float* cache, const float* rope, int n_pos, const float* x, const float* W, const float* norm_w, float* out);
+/* launch_enc_attention: qkv [B][T][3 H 64], rope [T][32][2] -> out [B][T][H 64] (rows below row0 untouched), or, n_planes = 1 / 2, the fp16 hi
+ * (+ lo) planes uint16 [2][B T H 64] in the tensor's index space or K-blocked over B T rows (csrc/planes_split.h) */
+int sva_test_enc_attention(int device, int B, int T, int H, int row0, const float* qkv, const float* rope, int n_planes, int blocked, float* out,
+                           unsigned short* planes);
+/* kind 0: launch_dwconv7_ln (p0 = taps [7][C], p1 = bias, p2 / p3 = LayerNorm weight / bias), 1: launch_layernorm_rows (p0 / p1 = weight / bias,
+ * rows [skip_lo, skip_hi) of every item left alone), 2: launch_rmsnorm_rows (p0 = weight); x [x_len] and out [o_len] are whole arrays, the
+ * strides and offsets are the launcher's; planes uint16 [2][p_len] as in sva_test_enc_attention */
+int sva_test_rowop(int device, int kind, int B, int T, int C, const float* x, long x_len, long x_bstride, long x_off, int ldx, const float* p0,
+                   const float* p1, const float* p2, const float* p3, float eps, float* out, long o_len, long o_bstride, long o_off, int ldo, int skip_lo,
+                   int skip_hi, int n_planes, int blocked, unsigned short* planes, long p_len);
+/* launch_bsq: norm_w (or NULL) = fused RMSNorm, zn_out (or NULL) [z_len], idx_out int64 [idx_len], u_out (or NULL) [idx_len][nbits] */
+int sva_test_bsq(int device, int B, int T, int C, const float* z, long z_len, long z_bstride, long z_off, int ldz, const float* norm_w, float eps,
+                 float* zn_out, const float* W, const float* bias, int nbits, long long* idx_out, long idx_len, int idx_bstride, int idx_off, float* u_out);
+/* launch_stft_mag_ring (two = 0) / launch_stft_mag_ring2 over ring [B][N] with the engine's twiddle and window tables; step may be NULL;
+ * mag [B][mag_rows][ldm] */
+int sva_test_stft_ring(int device, int B, int N, const float* ring, const int* step, int n_chunk, int add, int m0, int nfr, int two, int m0b, int nfrb,
+                       int row_b0, float* mag, int mag_rows, int ldm);
+/* encode != 0: launch_fsq_encode (lat -> codes, Wt = project_in [G][4][gdim], bs [G][4]); else launch_fsq_decode (codes -> lat, Wt = project_out
+ * [G][gdim][4], bs [G][gdim]) */
+int sva_test_fsq(int device, int encode, int B, int T, int G, int gdim, float* lat, long l_len, long l_bstride, long l_off, int ld, const float* Wt,
+                 const float* bs, int* codes, long c_len, long c_bstride, long c_gstride);
+/* launch_conv_post_tanh: x rows [T + k - 1][C] per item -> pcm [T] per item */
+int sva_test_conv_post(int device, int B, int T, int C, int k, const float* x, long x_len, long x_bstride, long x_off, const float* w, const float* bias,
+                       float* pcm, long p_len, long p_bstride, long p_off);
+
 /* host cost (microseconds) of enqueueing one kernel from the calling thread, measured over `iters` launches of a one-element
  * kernel into an idle stream.  A synchronous single-stream step is ~170 launches (a pipelined one: four graph launches + the persistent
  * AR kernel), so the enqueueing thread's launch rate still matters for the synchronous mode

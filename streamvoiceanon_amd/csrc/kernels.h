@@ -34,7 +34,9 @@ int launch_rmsnorm_rows(const float* x, long x_bstride, long x_off, int ldx, int
 
 // causal self-attention of the BSQ pre-transformer: qkv [B, T, 3*D] -> out [B, T, D]; RoPE
 // (adjacent pairs, bf16-rounded table rope[T][hd/2][2]) applied to q and k on load.
-//   outp != null (T <= 128 only, enc_attention_can_write_planes): planes output as launch_dwconv7_ln
+//   rows row0 .. T-1 of every item are produced, rows below row0 are left alone (T - row0 <= 4 or a multiple of 4 outside the MFMA kernel);
+//   keys max(0, r - 511) .. r (the transformer's 512-key window)
+//   outp != null (T <= 128 only, enc_attention_can_write_planes): planes output as launch_dwconv7_ln, K-blocked only (op_rows = B * T > 0)
 bool enc_attention_can_write_planes(int T);
 int launch_enc_attention(const float* qkv, const float* rope, int B, int T, int H, int hd, float* out, int row0,
                          hipStream_t st, unsigned short* outp = nullptr, long op_pstride = 0, int op_planes = 0, long op_rows = 0);

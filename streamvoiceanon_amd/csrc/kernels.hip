@@ -491,6 +491,7 @@ __global__ __launch_bounds__(64 * NWV) void enc_attention_mfma_kernel(const floa
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float inv = 1.f / sum[r];
+            if (r0 + 4 * fk + r < row0) continue;          // row0 inside this 16-row tile: the rows below it belong to the caller
             if (outp) {          // the output projection takes its A operand as K-blocked planes (planes_split.h)
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
@@ -580,6 +581,8 @@ int launch_enc_attention(const float* qkv, const float* rope, int B, int T, int 
                          unsigned short* outp, long op_pstride, int op_planes, long op_rows) {
     SVA_CHECK(hd == 64 && T % 4 == 0, "enc_attention: head_dim must be 64 and T a multiple of 4");
     SVA_CHECK(!outp || enc_attention_can_write_planes(T), "enc_attention: planes output only from the <= 128-token MFMA kernel");
+    SVA_CHECK(!outp || (op_rows > 0 && (op_planes == 1 || op_planes == 2)), "enc_attention: planes output is K-blocked only (op_rows = B * T), 1 or 2 planes");
+    SVA_CHECK(row0 >= 0 && row0 < T, "enc_attention: row0 must be a row of the window");
     if (T % 16 == 0 && T <= 128) {
         const int tiles = T / 16 - row0 / 16;
         const int nwv = tiles > 4 ? 8 : 4;

@@ -98,147 +98,109 @@ extern "C" int sva_test_gemm_f16w(int device, int M, int N, int K, const float* 
     return 0;
 }
 
-// Prefill attention: M query rows at positions pos0 .. pos0 + M - 1 of one slot against a cache holding `keys` [pos0 + M][H*64] / `vals`
-// (fp32, or rounded to fp16 when half_kv): out_ref = the per-row kernel (ar_attention_kernel), out_mfma = the flash-style MFMA kernel
-// (ar_prefill_attention_kernel); us[0], us[1] = their average launch times over `iters`.
+// Device buffer of a test hook: freed when the hook returns, on every path
+namespace {
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes) { SVA_HIP(hipMalloc(&p, bytes ? bytes : 4)); return 0; }
+    int put(const void* host, size_t bytes) {
+        SVA_TRY(alloc(bytes));
+        if (bytes) SVA_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int get(void* host, size_t bytes) const {
+        if (bytes) SVA_HIP(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+std::vector<uint16_t> to_half_bits(const float* v, size_t n) {
+    std::vector<uint16_t> h(n);
+    for (size_t i = 0; i < n; ++i) { const _Float16 hv = (_Float16)v[i]; memcpy(&h[i], &hv, 2); }
+    return h;
+}
+}  // namespace
+
+// Prefill / pair attention hooks: M query rows at positions pos0 .. pos0 + M - 1 of slot 0 against a cache holding `keys` [pos0 + M][H*64] /
+// `vals` (fp32, or rounded to fp16 when half_kv): out_ref = the per-row kernel (ar_attention_kernel), out_b = kernel B -- the flash-style MFMA
+// kernel (ar_prefill_attention_kernel, pairs == 0) or the decode frame's PAIRED kernel (rows 2 i, 2 i + 1 = consecutive positions; M even);
+// us[0], us[1] = their average launch times over `iters`.
+static int test_attention_vs_per_row(int device, bool pairs, int M, int H, int pos0, int S, const float* q, const float* keys, const float* vals,
+                                     int half_kv, float* out_ref, float* out_b, int iters, float* us) {
+    SVA_HIP(hipSetDevice(device));
+    const int D = H * 64, L = pos0 + M;
+    SVA_CHECK(L <= S, "attention test hook: pos0 + M must fit the cache");
+    std::vector<float> qkv((size_t)M * 3 * D, 0.f);
+    for (int m = 0; m < M; ++m) memcpy(&qkv[(size_t)m * 3 * D], q + (size_t)m * D, sizeof(float) * D);
+    const size_t cache_elems = (size_t)2 * H * S * 64;
+    std::vector<float> cf(cache_elems, 0.f);
+    for (int j = 0; j < L; ++j)
+        for (int h = 0; h < H; ++h)
+            for (int dd = 0; dd < 64; ++dd) {
+                cf[((size_t)h * S + j) * 64 + dd] = keys[(size_t)j * D + h * 64 + dd];
+                cf[(size_t)H * S * 64 + ((size_t)h * S + j) * 64 + dd] = vals[(size_t)j * D + h * 64 + dd];
+            }
+    std::vector<int> slot(M, 0), pos(M);
+    for (int m = 0; m < M; ++m) pos[m] = pos0 + m;
+    DevBuf bq, bc, bo1, bo2, bs, bp, bch;
+    SVA_TRY(bq.put(qkv.data(), sizeof(float) * qkv.size()));
+    SVA_TRY(bc.put(cf.data(), sizeof(float) * cache_elems));
+    SVA_TRY(bo1.alloc(sizeof(float) * (size_t)M * D));
+    SVA_TRY(bo2.alloc(sizeof(float) * (size_t)M * D));
+    SVA_TRY(bs.put(slot.data(), sizeof(int) * M));
+    SVA_TRY(bp.put(pos.data(), sizeof(int) * M));
+    if (half_kv) {
+        const std::vector<uint16_t> ch = to_half_bits(cf.data(), cache_elems);
+        SVA_TRY(bch.put(ch.data(), 2 * cache_elems));
+    }
+    float *dq = bq.as<float>(), *dc = bc.as<float>(), *do1 = bo1.as<float>(), *do2 = bo2.as<float>();
+    const int *ds = bs.as<int>(), *dp = bp.as<int>();
+    const __half* c16 = bch.as<__half>();
+    const long slot_stride = (long)cache_elems;
+    auto run = [&](int which) -> int {
+        if (half_kv) {
+            if (!which) return launch_ar_attention<__half>(dq, M, H, 64, ds, dp, c16, slot_stride, S, do1, 0);
+            return pairs ? launch_ar_attention_pairs<__half>(dq, M, H, 64, ds, dp, c16, slot_stride, S, do2, 0)
+                         : launch_ar_prefill_attention<__half>(dq, M, H, 64, 0, pos0, c16, slot_stride, S, do2, 0);
+        }
+        if (!which) return launch_ar_attention<float>(dq, M, H, 64, ds, dp, dc, slot_stride, S, do1, 0);
+        return pairs ? launch_ar_attention_pairs<float>(dq, M, H, 64, ds, dp, dc, slot_stride, S, do2, 0)
+                     : launch_ar_prefill_attention<float>(dq, M, H, 64, 0, pos0, dc, slot_stride, S, do2, 0);
+    };
+    for (int which = 0; which < 2; ++which) {
+        if (run(which)) return -1;
+        SVA_HIP(hipDeviceSynchronize());
+        if (iters > 0 && us) {
+            hipEvent_t e0, e1;
+            SVA_HIP(hipEventCreate(&e0)); SVA_HIP(hipEventCreate(&e1));
+            SVA_HIP(hipEventRecord(e0, 0));
+            for (int i = 0; i < iters; ++i) if (run(which)) return -1;
+            SVA_HIP(hipEventRecord(e1, 0));
+            SVA_HIP(hipEventSynchronize(e1));
+            float ms = 0.f;
+            SVA_HIP(hipEventElapsedTime(&ms, e0, e1));
+            us[which] = ms * 1000.f / iters;
+            (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        }
+    }
+    SVA_TRY(bo1.get(out_ref, sizeof(float) * (size_t)M * D));
+    SVA_TRY(bo2.get(out_b, sizeof(float) * (size_t)M * D));
+    return 0;
+}
 extern "C" int sva_test_prefill_attention(int device, int M, int H, int pos0, int S, const float* q, const float* keys, const float* vals,
                                           int half_kv, float* out_ref, float* out_mfma, int iters, float* us) {
-    SVA_HIP(hipSetDevice(device));
-    const int D = H * 64, L = pos0 + M;
-    SVA_CHECK(L <= S, "sva_test_prefill_attention: pos0 + M must fit the cache");
-    std::vector<float> qkv((size_t)M * 3 * D, 0.f);
-    for (int m = 0; m < M; ++m) memcpy(&qkv[(size_t)m * 3 * D], q + (size_t)m * D, sizeof(float) * D);
-    const size_t cache_elems = (size_t)2 * H * S * 64;
-    std::vector<float> cf(cache_elems, 0.f);
-    for (int j = 0; j < L; ++j)
-        for (int h = 0; h < H; ++h)
-            for (int dd = 0; dd < 64; ++dd) {
-                cf[((size_t)h * S + j) * 64 + dd] = keys[(size_t)j * D + h * 64 + dd];
-                cf[(size_t)H * S * 64 + ((size_t)h * S + j) * 64 + dd] = vals[(size_t)j * D + h * 64 + dd];
-            }
-    std::vector<int> slot(M, 0), pos(M);
-    for (int m = 0; m < M; ++m) pos[m] = pos0 + m;
-    float *dq, *dc, *do1, *do2;
-    int *ds, *dp;
-    void* dch = nullptr;
-    SVA_HIP(hipMalloc(&dq, sizeof(float) * qkv.size()));
-    SVA_HIP(hipMalloc(&dc, sizeof(float) * cache_elems));
-    SVA_HIP(hipMalloc(&do1, sizeof(float) * (size_t)M * D));
-    SVA_HIP(hipMalloc(&do2, sizeof(float) * (size_t)M * D));
-    SVA_HIP(hipMalloc(&ds, sizeof(int) * M));
-    SVA_HIP(hipMalloc(&dp, sizeof(int) * M));
-    SVA_HIP(hipMemcpy(dq, qkv.data(), sizeof(float) * qkv.size(), hipMemcpyHostToDevice));
-    SVA_HIP(hipMemcpy(dc, cf.data(), sizeof(float) * cache_elems, hipMemcpyHostToDevice));
-    SVA_HIP(hipMemcpy(ds, slot.data(), sizeof(int) * M, hipMemcpyHostToDevice));
-    SVA_HIP(hipMemcpy(dp, pos.data(), sizeof(int) * M, hipMemcpyHostToDevice));
-    if (half_kv) {
-        std::vector<uint16_t> ch(cache_elems);
-        for (size_t i = 0; i < cache_elems; ++i) { const _Float16 hv = (_Float16)cf[i]; memcpy(&ch[i], &hv, 2); }
-        SVA_HIP(hipMalloc(&dch, 2 * cache_elems));
-        SVA_HIP(hipMemcpy(dch, ch.data(), 2 * cache_elems, hipMemcpyHostToDevice));
-    }
-    const long slot_stride = (long)cache_elems;
-    auto run = [&](int which) -> int {
-        if (half_kv) {
-            const __half* c16 = reinterpret_cast<const __half*>(dch);
-            return which ? launch_ar_prefill_attention<__half>(dq, M, H, 64, 0, pos0, c16, slot_stride, S, do2, 0)
-                         : launch_ar_attention<__half>(dq, M, H, 64, ds, dp, c16, slot_stride, S, do1, 0);
-        }
-        return which ? launch_ar_prefill_attention<float>(dq, M, H, 64, 0, pos0, dc, slot_stride, S, do2, 0)
-                     : launch_ar_attention<float>(dq, M, H, 64, ds, dp, dc, slot_stride, S, do1, 0);
-    };
-    for (int which = 0; which < 2; ++which) {
-        if (run(which)) return -1;
-        SVA_HIP(hipDeviceSynchronize());
-        if (iters > 0 && us) {
-            hipEvent_t e0, e1;
-            SVA_HIP(hipEventCreate(&e0)); SVA_HIP(hipEventCreate(&e1));
-            SVA_HIP(hipEventRecord(e0, 0));
-            for (int i = 0; i < iters; ++i) if (run(which)) return -1;
-            SVA_HIP(hipEventRecord(e1, 0));
-            SVA_HIP(hipEventSynchronize(e1));
-            float ms = 0.f;
-            SVA_HIP(hipEventElapsedTime(&ms, e0, e1));
-            us[which] = ms * 1000.f / iters;
-            (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        }
-    }
-    SVA_HIP(hipMemcpy(out_ref, do1, sizeof(float) * (size_t)M * D, hipMemcpyDeviceToHost));
-    SVA_HIP(hipMemcpy(out_mfma, do2, sizeof(float) * (size_t)M * D, hipMemcpyDeviceToHost));
-    (void)hipFree(dq); (void)hipFree(dc); (void)hipFree(do1); (void)hipFree(do2); (void)hipFree(ds); (void)hipFree(dp);
-    if (dch) (void)hipFree(dch);
-    return 0;
+    return test_attention_vs_per_row(device, false, M, H, pos0, S, q, keys, vals, half_kv, out_ref, out_mfma, iters, us);
+}
+extern "C" int sva_test_pair_attention(int device, int M, int H, int pos0, int S, const float* q, const float* keys, const float* vals,
+                                       int half_kv, float* out_ref, float* out_mfma, int iters, float* us) {
+    SVA_CHECK(M % 2 == 0, "sva_test_pair_attention: an even number of rows");
+    return test_attention_vs_per_row(device, true, M, H, pos0, S, q, keys, vals, half_kv, out_ref, out_mfma, iters, us);
 }
 
-// The same rows through the decode frame's PAIRED attention kernel (rows 2 i, 2 i + 1 = consecutive positions of one slot; M even): out_mfma = its result
-extern "C" int sva_test_pair_attention(int device, int M, int H, int pos0, int S, const float* q, const float* keys, const float* vals,
-                                          int half_kv, float* out_ref, float* out_mfma, int iters, float* us) {
-    SVA_HIP(hipSetDevice(device));
-    const int D = H * 64, L = pos0 + M;
-    SVA_CHECK(L <= S, "sva_test_pair_attention: pos0 + M must fit the cache");
-    std::vector<float> qkv((size_t)M * 3 * D, 0.f);
-    for (int m = 0; m < M; ++m) memcpy(&qkv[(size_t)m * 3 * D], q + (size_t)m * D, sizeof(float) * D);
-    const size_t cache_elems = (size_t)2 * H * S * 64;
-    std::vector<float> cf(cache_elems, 0.f);
-    for (int j = 0; j < L; ++j)
-        for (int h = 0; h < H; ++h)
-            for (int dd = 0; dd < 64; ++dd) {
-                cf[((size_t)h * S + j) * 64 + dd] = keys[(size_t)j * D + h * 64 + dd];
-                cf[(size_t)H * S * 64 + ((size_t)h * S + j) * 64 + dd] = vals[(size_t)j * D + h * 64 + dd];
-            }
-    std::vector<int> slot(M, 0), pos(M);
-    for (int m = 0; m < M; ++m) pos[m] = pos0 + m;
-    float *dq, *dc, *do1, *do2;
-    int *ds, *dp;
-    void* dch = nullptr;
-    SVA_HIP(hipMalloc(&dq, sizeof(float) * qkv.size()));
-    SVA_HIP(hipMalloc(&dc, sizeof(float) * cache_elems));
-    SVA_HIP(hipMalloc(&do1, sizeof(float) * (size_t)M * D));
-    SVA_HIP(hipMalloc(&do2, sizeof(float) * (size_t)M * D));
-    SVA_HIP(hipMalloc(&ds, sizeof(int) * M));
-    SVA_HIP(hipMalloc(&dp, sizeof(int) * M));
-    SVA_HIP(hipMemcpy(dq, qkv.data(), sizeof(float) * qkv.size(), hipMemcpyHostToDevice));
-    SVA_HIP(hipMemcpy(dc, cf.data(), sizeof(float) * cache_elems, hipMemcpyHostToDevice));
-    SVA_HIP(hipMemcpy(ds, slot.data(), sizeof(int) * M, hipMemcpyHostToDevice));
-    SVA_HIP(hipMemcpy(dp, pos.data(), sizeof(int) * M, hipMemcpyHostToDevice));
-    if (half_kv) {
-        std::vector<uint16_t> ch(cache_elems);
-        for (size_t i = 0; i < cache_elems; ++i) { const _Float16 hv = (_Float16)cf[i]; memcpy(&ch[i], &hv, 2); }
-        SVA_HIP(hipMalloc(&dch, 2 * cache_elems));
-        SVA_HIP(hipMemcpy(dch, ch.data(), 2 * cache_elems, hipMemcpyHostToDevice));
-    }
-    const long slot_stride = (long)cache_elems;
-    auto run = [&](int which) -> int {
-        if (half_kv) {
-            const __half* c16 = reinterpret_cast<const __half*>(dch);
-            return which ? launch_ar_attention_pairs<__half>(dq, M, H, 64, ds, dp, c16, slot_stride, S, do2, 0)
-                         : launch_ar_attention<__half>(dq, M, H, 64, ds, dp, c16, slot_stride, S, do1, 0);
-        }
-        return which ? launch_ar_attention_pairs<float>(dq, M, H, 64, ds, dp, dc, slot_stride, S, do2, 0)
-                     : launch_ar_attention<float>(dq, M, H, 64, ds, dp, dc, slot_stride, S, do1, 0);
-    };
-    for (int which = 0; which < 2; ++which) {
-        if (run(which)) return -1;
-        SVA_HIP(hipDeviceSynchronize());
-        if (iters > 0 && us) {
-            hipEvent_t e0, e1;
-            SVA_HIP(hipEventCreate(&e0)); SVA_HIP(hipEventCreate(&e1));
-            SVA_HIP(hipEventRecord(e0, 0));
-            for (int i = 0; i < iters; ++i) if (run(which)) return -1;
-            SVA_HIP(hipEventRecord(e1, 0));
-            SVA_HIP(hipEventSynchronize(e1));
-            float ms = 0.f;
-            SVA_HIP(hipEventElapsedTime(&ms, e0, e1));
-            us[which] = ms * 1000.f / iters;
-            (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        }
-    }
-    SVA_HIP(hipMemcpy(out_ref, do1, sizeof(float) * (size_t)M * D, hipMemcpyDeviceToHost));
-    SVA_HIP(hipMemcpy(out_mfma, do2, sizeof(float) * (size_t)M * D, hipMemcpyDeviceToHost));
-    (void)hipFree(dq); (void)hipFree(dc); (void)hipFree(do1); (void)hipFree(do2); (void)hipFree(ds); (void)hipFree(dp);
-    if (dch) (void)hipFree(dch);
-    return 0;
-}
 
 // microbenchmark of the conv-GEMM dispatcher on device-resident random data:
 //   out_us[0] = average microseconds per launch over `iters` back-to-back launches (hipEvents)
@@ -593,5 +555,251 @@ extern "C" int sva_test_gemm_planes(int device, int M, int N, int K, const float
     if (dCp) (void)hipFree(dCp);
     if (dG) (void)hipFree(dG);
     if (dR) (void)hipFree(dR);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Per-kernel hooks of the non-GEMM launchers (tests/test_gpu_kernels.py): each uploads the caller's arrays, calls the launcher the engine
+// calls with the caller's arguments, synchronises and downloads.  Output arrays are uploaded first, so whatever the caller pre-filled them
+// with (a sentinel) survives where the kernel writes nothing.  Every index the launch will touch is checked against the array lengths here.
+// ------------------------------------------------------------------------------------------------------------------------------------
+extern "C" int sva_test_decode_attention(int device, int variant, int M, int H, int S, int n_slots, const int* slot, const int* pos, int half_kv,
+                                         float* qkv, float* cache, const float* rope, int n_pos, const float* x, const float* W, const float* norm_w,
+                                         float* out) {
+    SVA_HIP(hipSetDevice(device));
+    SVA_CHECK(variant >= 0 && variant <= 6 && M >= 1 && H >= 1 && S >= 1 && n_slots >= 1, "sva_test_decode_attention: bad arguments");
+    SVA_CHECK(!half_kv || variant == 0 || variant == 2 || variant == 5, "sva_test_decode_attention: fp16 cache only for the per-row, pair and rope_kvwrite kernels");
+    const bool needs_rope = variant == 3 || variant == 5 || variant == 6;
+    for (int m = 0; m < M; ++m) {
+        SVA_CHECK(slot[m] >= 0 && slot[m] < n_slots && pos[m] >= 0 && pos[m] < S, "sva_test_decode_attention: slot / pos outside the cache");
+        SVA_CHECK(!needs_rope || pos[m] < n_pos, "sva_test_decode_attention: pos outside the RoPE table");
+    }
+    if (variant == 2) {
+        SVA_CHECK(M % 2 == 0, "sva_test_decode_attention: pairs need an even number of rows");
+        for (int m = 0; m < M; m += 2)
+            SVA_CHECK(slot[m + 1] == slot[m] && pos[m + 1] == pos[m] + 1, "sva_test_decode_attention: pair rows are positions (p, p + 1) of one slot");
+    }
+    SVA_CHECK(!needs_rope || rope, "sva_test_decode_attention: RoPE table missing");
+    SVA_CHECK((variant != 1 && variant != 4 && variant != 6) || (W && M <= 2), "sva_test_decode_attention: GEMV variants need W and M <= 2");
+    SVA_CHECK(variant != 6 || (x && norm_w), "sva_test_decode_attention: mode 2 needs x and norm_w");
+    const int D = H * 64, splits = 8;
+    const size_t slot_elems = (size_t)2 * H * S * 64, cache_elems = slot_elems * n_slots;
+    DevBuf bq, bc, bs, bp, br, bx, bw, bn, bo, bpart;
+    SVA_TRY(bq.put(qkv, sizeof(float) * (size_t)M * 3 * D));
+    if (half_kv) {
+        const std::vector<uint16_t> ch = to_half_bits(cache, cache_elems);
+        SVA_TRY(bc.put(ch.data(), 2 * cache_elems));
+    } else {
+        SVA_TRY(bc.put(cache, sizeof(float) * cache_elems));
+    }
+    SVA_TRY(bs.put(slot, sizeof(int) * M));
+    SVA_TRY(bp.put(pos, sizeof(int) * M));
+    if (rope) SVA_TRY(br.put(rope, sizeof(float) * (size_t)n_pos * 64));
+    if (x) SVA_TRY(bx.put(x, sizeof(float) * (size_t)M * D));
+    if (W) SVA_TRY(bw.put(W, sizeof(float) * (size_t)(variant == 6 ? 3 * D : D) * D));
+    if (norm_w) SVA_TRY(bn.put(norm_w, sizeof(float) * D));
+    SVA_TRY(bo.put(out, sizeof(float) * (size_t)M * D));
+    float *dq = bq.as<float>(), *dc = bc.as<float>(), *dout = bo.as<float>();
+    __half* dch = bc.as<__half>();
+    const int *ds = bs.as<int>(), *dp = bp.as<int>();
+    const long ss = (long)slot_elems;
+    Gemv g;
+    g.M = M; g.W = bw.as<float>(); g.K = D; g.slot = ds; g.pos = dp; g.H = H;
+    switch (variant) {
+        case 0:
+            SVA_TRY(half_kv ? launch_ar_attention<__half>(dq, M, H, 64, ds, dp, dch, ss, S, dout, 0) : launch_ar_attention<float>(dq, M, H, 64, ds, dp, dc, ss, S, dout, 0));
+            break;
+        case 1:         // slow AR at B <= 2: split-key attention, merged by the wo GEMV (+ residual)
+            SVA_TRY(bpart.alloc(sizeof(float) * (size_t)M * H * splits * 68));
+            SVA_TRY(launch_ar_attention<float>(dq, M, H, 64, ds, dp, dc, ss, S, nullptr, 0, bpart.as<float>(), splits));
+            g.X = bpart.as<float>(); g.ldx = 0; g.mode = 4; g.S = splits; g.N = D; g.res = bx.as<float>(); g.ldr = D; g.Y = dout; g.ldy = D;
+            SVA_TRY(launch_gemv(g, 0));
+            break;
+        case 2:
+            SVA_TRY(half_kv ? launch_ar_attention_pairs<__half>(dq, M, H, 64, ds, dp, dch, ss, S, dout, 0) : launch_ar_attention_pairs<float>(dq, M, H, 64, ds, dp, dc, ss, S, dout, 0));
+            break;
+        case 3:
+            SVA_TRY(launch_ar_fast_attention(dq, M, H, ds, dp, br.as<float>(), dc, ss, S, dout, 0));
+            break;
+        case 4:         // fast AR at B <= 2: attention over <= 8 cached keys inside the wo GEMV (+ residual)
+            g.X = dq; g.ldx = 3 * D; g.mode = 3; g.kv = dc; g.kv_slot_stride = ss; g.S = S; g.N = D; g.res = bx.as<float>(); g.ldr = D; g.Y = dout; g.ldy = D;
+            SVA_TRY(launch_gemv(g, 0));
+            break;
+        case 5:
+            SVA_TRY(half_kv ? launch_rope_kvwrite<__half>(dq, M, H, 64, ds, dp, br.as<float>(), dch, ss, S, 0) : launch_rope_kvwrite<float>(dq, M, H, 64, ds, dp, br.as<float>(), dc, ss, S, 0));
+            break;
+        default:        // 6: QKV GEMV with the RMSNorm prologue and the RoPE + KV-write epilogue
+            g.X = bx.as<float>(); g.ldx = D; g.N = 3 * D; g.norm_w = bn.as<float>(); g.eps = 1e-5f; g.Y = dq; g.ldy = 3 * D; g.mode = 2; g.rope = br.as<float>();
+            g.kv = dc; g.kv_slot_stride = ss; g.S = S;
+            SVA_TRY(launch_gemv(g, 0));
+            break;
+    }
+    SVA_HIP(hipDeviceSynchronize());
+    SVA_TRY(bq.get(qkv, sizeof(float) * (size_t)M * 3 * D));
+    SVA_TRY(bo.get(out, sizeof(float) * (size_t)M * D));
+    if (half_kv) {
+        std::vector<uint16_t> ch(cache_elems);
+        SVA_TRY(bc.get(ch.data(), 2 * cache_elems));
+        for (size_t i = 0; i < cache_elems; ++i) { _Float16 hv; memcpy(&hv, &ch[i], 2); cache[i] = (float)hv; }
+    } else {
+        SVA_TRY(bc.get(cache, sizeof(float) * cache_elems));
+    }
+    return 0;
+}
+
+// planes: uint16 [n_planes][rows * K] in the tensor's own index space (blocked == 0) or K-blocked over `rows` rows (planes_split.h)
+extern "C" int sva_test_enc_attention(int device, int B, int T, int H, int row0, const float* qkv, const float* rope, int n_planes, int blocked,
+                                      float* out, unsigned short* planes) {
+    SVA_HIP(hipSetDevice(device));
+    SVA_CHECK(B >= 1 && T >= 1 && H >= 1 && row0 >= 0 && row0 < T && n_planes >= 0 && n_planes <= 2, "sva_test_enc_attention: bad arguments");
+    const int D = H * 64;
+    const size_t n = (size_t)B * T * D;
+    DevBuf bq, br, bo, bpl;
+    SVA_TRY(bq.put(qkv, sizeof(float) * n * 3));
+    SVA_TRY(br.put(rope, sizeof(float) * (size_t)T * 64));
+    SVA_TRY(bo.put(out, sizeof(float) * n));
+    if (n_planes) SVA_TRY(bpl.put(planes, 2 * n * 2));
+    SVA_TRY(launch_enc_attention(bq.as<float>(), br.as<float>(), B, T, H, 64, bo.as<float>(), row0, 0, n_planes ? bpl.as<unsigned short>() : nullptr, (long)n,
+                                 n_planes, blocked ? (long)B * T : 0));
+    SVA_HIP(hipDeviceSynchronize());
+    SVA_TRY(bo.get(out, sizeof(float) * n));
+    if (n_planes) SVA_TRY(bpl.get(planes, 2 * n * 2));
+    return 0;
+}
+
+// kind 0: launch_dwconv7_ln (p0 = wT [7][C], p1 = bias, p2 = ln_w, p3 = ln_b; ldx = ldo = C), 1: launch_layernorm_rows (p0 = w, p1 = b),
+// 2: launch_rmsnorm_rows (p0 = w).  x [x_len], out [o_len] and planes uint16 [2][p_len] are whole arrays with the strides / offsets applied inside.
+extern "C" int sva_test_rowop(int device, int kind, int B, int T, int C, const float* x, long x_len, long x_bstride, long x_off, int ldx, const float* p0,
+                              const float* p1, const float* p2, const float* p3, float eps, float* out, long o_len, long o_bstride, long o_off, int ldo,
+                              int skip_lo, int skip_hi, int n_planes, int blocked, unsigned short* planes, long p_len) {
+    SVA_HIP(hipSetDevice(device));
+    SVA_CHECK(kind >= 0 && kind <= 2 && B >= 1 && T >= 1 && C >= 1 && n_planes >= 0 && n_planes <= 2, "sva_test_rowop: bad arguments");
+    if (kind == 0) SVA_CHECK(ldx == C && ldo == C && o_off == 0, "sva_test_rowop: dwconv7_ln rows are dense");
+    SVA_CHECK(kind != 1 || n_planes == 0, "sva_test_rowop: LayerNorm rows have no planes output");
+    const int in_rows = kind == 0 ? T + 6 : T;
+    SVA_CHECK(x_bstride >= 0 && x_off >= 0 && ldx >= C && (long)(B - 1) * x_bstride + x_off + (long)(in_rows - 1) * ldx + C <= x_len, "sva_test_rowop: input range outside x");
+    SVA_CHECK(o_bstride >= 0 && o_off >= 0 && ldo >= C && (long)(B - 1) * o_bstride + o_off + (long)(T - 1) * ldo + C <= o_len, "sva_test_rowop: output range outside out");
+    if (n_planes) {
+        if (blocked) SVA_CHECK(C % 32 == 0 && ldo == C && o_off == 0 && o_bstride == (long)T * C && (long)B * T * C <= p_len, "sva_test_rowop: K-blocked planes cover B * T dense rows");
+        else SVA_CHECK(o_len <= p_len, "sva_test_rowop: planes share the output's index space");
+    }
+    DevBuf bx, b0, b1, b2, b3, bo, bpl;
+    SVA_TRY(bx.put(x, sizeof(float) * (size_t)x_len));
+    SVA_TRY(b0.put(p0, sizeof(float) * (size_t)(kind == 0 ? 7 * C : C)));
+    if (p1) SVA_TRY(b1.put(p1, sizeof(float) * C));
+    if (p2) SVA_TRY(b2.put(p2, sizeof(float) * C));
+    if (p3) SVA_TRY(b3.put(p3, sizeof(float) * C));
+    SVA_CHECK(kind == 2 || p1, "sva_test_rowop: bias missing");
+    SVA_CHECK(kind != 0 || (p2 && p3), "sva_test_rowop: LayerNorm parameters missing");
+    SVA_TRY(bo.put(out, sizeof(float) * (size_t)o_len));
+    if (n_planes) SVA_TRY(bpl.put(planes, 2 * (size_t)p_len * 2));
+    unsigned short* dpl = n_planes ? bpl.as<unsigned short>() : nullptr;
+    const long op_rows = blocked ? (long)B * T : 0;
+    if (kind == 0)
+        SVA_TRY(launch_dwconv7_ln(bx.as<float>(), x_bstride, x_off, B, T, C, b0.as<float>(), b1.as<float>(), b2.as<float>(), b3.as<float>(), eps, bo.as<float>(), o_bstride, 0,
+                                  dpl, p_len, n_planes, op_rows));
+    else if (kind == 1)
+        SVA_TRY(launch_layernorm_rows(bx.as<float>(), x_bstride, x_off, ldx, B, T, C, b0.as<float>(), b1.as<float>(), eps, bo.as<float>(), o_bstride, o_off, ldo, 0, skip_lo, skip_hi));
+    else
+        SVA_TRY(launch_rmsnorm_rows(bx.as<float>(), x_bstride, x_off, ldx, B, T, C, b0.as<float>(), eps, bo.as<float>(), o_bstride, o_off, ldo, 0, dpl, p_len, n_planes, op_rows));
+    SVA_HIP(hipDeviceSynchronize());
+    SVA_TRY(bo.get(out, sizeof(float) * (size_t)o_len));
+    if (n_planes) SVA_TRY(bpl.get(planes, 2 * (size_t)p_len * 2));
+    return 0;
+}
+
+// launch_bsq: z [z_len] (rows b * z_bstride + z_off + t * ldz), zn_out (null or [z_len], same layout), idx_out int64 [idx_len] at b * idx_bstride + idx_off + t,
+// u_out (null or [idx_len][nbits])
+extern "C" int sva_test_bsq(int device, int B, int T, int C, const float* z, long z_len, long z_bstride, long z_off, int ldz, const float* norm_w, float eps,
+                            float* zn_out, const float* W, const float* bias, int nbits, long long* idx_out, long idx_len, int idx_bstride, int idx_off, float* u_out) {
+    SVA_HIP(hipSetDevice(device));
+    SVA_CHECK(B >= 1 && T >= 1 && C >= 1 && nbits >= 1 && nbits <= 62, "sva_test_bsq: bad arguments");
+    SVA_CHECK(z_bstride >= 0 && z_off >= 0 && ldz >= C && (long)(B - 1) * z_bstride + z_off + (long)(T - 1) * ldz + C <= z_len, "sva_test_bsq: input range outside z");
+    SVA_CHECK(idx_bstride >= 0 && idx_off >= 0 && (long)(B - 1) * idx_bstride + idx_off + T <= idx_len, "sva_test_bsq: index range outside idx_out");
+    DevBuf bz, bn, bzn, bw, bb, bi, bu;
+    SVA_TRY(bz.put(z, sizeof(float) * (size_t)z_len));
+    if (norm_w) SVA_TRY(bn.put(norm_w, sizeof(float) * C));
+    if (zn_out) SVA_TRY(bzn.put(zn_out, sizeof(float) * (size_t)z_len));
+    SVA_TRY(bw.put(W, sizeof(float) * (size_t)nbits * C));
+    SVA_TRY(bb.put(bias, sizeof(float) * nbits));
+    SVA_TRY(bi.put(idx_out, sizeof(long long) * (size_t)idx_len));
+    if (u_out) SVA_TRY(bu.put(u_out, sizeof(float) * (size_t)idx_len * nbits));
+    SVA_TRY(launch_bsq(bz.as<float>(), z_bstride, z_off, ldz, B, T, C, norm_w ? bn.as<float>() : nullptr, eps, zn_out ? bzn.as<float>() : nullptr, bw.as<float>(), bb.as<float>(),
+                       nbits, bi.as<long long>(), idx_bstride, idx_off, u_out ? bu.as<float>() : nullptr, 0));
+    SVA_HIP(hipDeviceSynchronize());
+    if (zn_out) SVA_TRY(bzn.get(zn_out, sizeof(float) * (size_t)z_len));
+    SVA_TRY(bi.get(idx_out, sizeof(long long) * (size_t)idx_len));
+    if (u_out) SVA_TRY(bu.get(u_out, sizeof(float) * (size_t)idx_len * nbits));
+    return 0;
+}
+
+// ring [B][N]; step == null -> the launcher's nullptr; two != 0: launch_stft_mag_ring2.  mag [B][mag_rows][ldm] (batch stride mag_rows * ldm).
+// The twiddle and window tables are the engine's (packer.hip).
+extern "C" int sva_test_stft_ring(int device, int B, int N, const float* ring, const int* step, int n_chunk, int add, int m0, int nfr, int two, int m0b, int nfrb,
+                                  int row_b0, float* mag, int mag_rows, int ldm) {
+    SVA_HIP(hipSetDevice(device));
+    SVA_CHECK(B >= 1 && N >= 512 && nfr >= 1 && nfr <= mag_rows && n_chunk >= 0, "sva_test_stft_ring: bad arguments");
+    SVA_CHECK(!step || (long)*step + add >= 0, "sva_test_stft_ring: negative ring origin");
+    SVA_CHECK(!two || (nfrb >= 1 && row_b0 >= nfr && row_b0 + nfrb <= mag_rows), "sva_test_stft_ring: second range outside mag");
+    std::vector<float> hann(2048), tw(2048);
+    for (int i = 0; i < 2048; ++i) hann[i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * i / 2048.0));
+    for (int k = 0; k < 1024; ++k) {
+        tw[2 * k] = (float)cos(2.0 * M_PI * k / 2048.0);
+        tw[2 * k + 1] = (float)(-sin(2.0 * M_PI * k / 2048.0));
+    }
+    const size_t mag_n = (size_t)B * mag_rows * ldm;
+    DevBuf br, bs, bh, bt, bm;
+    SVA_TRY(br.put(ring, sizeof(float) * (size_t)B * N));
+    if (step) SVA_TRY(bs.put(step, sizeof(int)));
+    SVA_TRY(bh.put(hann.data(), sizeof(float) * 2048));
+    SVA_TRY(bt.put(tw.data(), sizeof(float) * 2048));
+    SVA_TRY(bm.put(mag, sizeof(float) * mag_n));
+    const int* dstep = step ? bs.as<int>() : nullptr;
+    if (two)
+        SVA_TRY(launch_stft_mag_ring2(br.as<float>(), dstep, n_chunk, add, B, N, bt.as<float2>(), bh.as<float>(), bm.as<float>(), ldm, (long)mag_rows * ldm, m0, nfr, m0b, nfrb,
+                                      row_b0, 0));
+    else
+        SVA_TRY(launch_stft_mag_ring(br.as<float>(), dstep, n_chunk, add, B, N, bt.as<float2>(), bh.as<float>(), bm.as<float>(), ldm, (long)mag_rows * ldm, m0, nfr, 0));
+    SVA_HIP(hipDeviceSynchronize());
+    SVA_TRY(bm.get(mag, sizeof(float) * mag_n));
+    return 0;
+}
+
+// encode != 0: launch_fsq_encode (lat = x in, Wt = Win [G][4][gdim], bs = bin [G][4], codes out); else launch_fsq_decode (codes in, Wt = Wout [G][gdim][4],
+// bs = bout [G][gdim], lat = out).  lat element (b, t, c) at b * l_bstride + l_off + t * ld + c; codes element (b, g, t) at b * c_bstride + g * c_gstride + t.
+extern "C" int sva_test_fsq(int device, int encode, int B, int T, int G, int gdim, float* lat, long l_len, long l_bstride, long l_off, int ld, const float* Wt,
+                            const float* bs, int* codes, long c_len, long c_bstride, long c_gstride) {
+    SVA_HIP(hipSetDevice(device));
+    SVA_CHECK(B >= 1 && T >= 1 && G >= 1 && gdim >= 1, "sva_test_fsq: bad arguments");
+    SVA_CHECK(l_bstride >= 0 && l_off >= 0 && ld >= G * gdim && (long)(B - 1) * l_bstride + l_off + (long)(T - 1) * ld + (long)G * gdim <= l_len, "sva_test_fsq: latent range outside lat");
+    SVA_CHECK(c_bstride >= 0 && c_gstride >= 0 && (long)(B - 1) * c_bstride + (long)(G - 1) * c_gstride + T <= c_len, "sva_test_fsq: code range outside codes");
+    DevBuf bl, bw, bb, bc;
+    SVA_TRY(bl.put(lat, sizeof(float) * (size_t)l_len));
+    SVA_TRY(bw.put(Wt, sizeof(float) * (size_t)G * gdim * 4));
+    SVA_TRY(bb.put(bs, sizeof(float) * (size_t)(encode ? G * 4 : G * gdim)));
+    SVA_TRY(bc.put(codes, sizeof(int) * (size_t)c_len));
+    if (encode) SVA_TRY(launch_fsq_encode(bl.as<float>(), l_bstride, l_off, ld, B, T, G, gdim, bw.as<float>(), bb.as<float>(), bc.as<int>(), c_bstride, c_gstride, 0));
+    else SVA_TRY(launch_fsq_decode(bc.as<int>(), c_bstride, c_gstride, B, T, G, gdim, bw.as<float>(), bb.as<float>(), bl.as<float>(), l_bstride, l_off, ld, 0));
+    SVA_HIP(hipDeviceSynchronize());
+    SVA_TRY(bl.get(lat, sizeof(float) * (size_t)l_len));
+    SVA_TRY(bc.get(codes, sizeof(int) * (size_t)c_len));
+    return 0;
+}
+
+// launch_conv_post_tanh: x element (b, r, c) at b * x_bstride + x_off + r * C + c (rows 0 .. T + k - 2), pcm (b, t) at b * p_bstride + p_off + t
+extern "C" int sva_test_conv_post(int device, int B, int T, int C, int k, const float* x, long x_len, long x_bstride, long x_off, const float* w, const float* bias,
+                                  float* pcm, long p_len, long p_bstride, long p_off) {
+    SVA_HIP(hipSetDevice(device));
+    SVA_CHECK(B >= 1 && T >= 1 && C >= 1 && k >= 1, "sva_test_conv_post: bad arguments");
+    SVA_CHECK(x_bstride >= 0 && x_off >= 0 && (long)(B - 1) * x_bstride + x_off + (long)(T + k - 1) * C <= x_len, "sva_test_conv_post: input range outside x");
+    SVA_CHECK(p_bstride >= 0 && p_off >= 0 && (long)(B - 1) * p_bstride + p_off + T <= p_len, "sva_test_conv_post: output range outside pcm");
+    DevBuf bx, bw, bb, bp;
+    SVA_TRY(bx.put(x, sizeof(float) * (size_t)x_len));
+    SVA_TRY(bw.put(w, sizeof(float) * (size_t)k * C));
+    SVA_TRY(bb.put(bias, sizeof(float)));
+    SVA_TRY(bp.put(pcm, sizeof(float) * (size_t)p_len));
+    SVA_TRY(launch_conv_post_tanh(bx.as<float>(), x_bstride, x_off, B, T, C, k, bw.as<float>(), bb.as<float>(), bp.as<float>(), p_bstride, p_off, 0));
+    SVA_HIP(hipDeviceSynchronize());
+    SVA_TRY(bp.get(pcm, sizeof(float) * (size_t)p_len));
     return 0;
 }

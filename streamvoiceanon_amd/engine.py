@@ -107,6 +107,14 @@ def load_library():
     lib.sva_set_sampler_edits.argtypes = [vp, vp, i32, C.c_float, vp, i32]
     lib.sva_test_prefill_attention.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp]
     lib.sva_test_pair_attention.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp]
+    i64 = C.c_long
+    lib.sva_test_decode_attention.argtypes = [i32] * 6 + [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.sva_test_enc_attention.argtypes = [i32] * 5 + [vp, vp, i32, i32, vp, vp]
+    lib.sva_test_rowop.argtypes = [i32] * 5 + [vp, i64, i64, i64, i32, vp, vp, vp, vp, C.c_float, vp, i64, i64, i64, i32, i32, i32, i32, i32, vp, i64]
+    lib.sva_test_bsq.argtypes = [i32] * 4 + [vp, i64, i64, i64, i32, vp, C.c_float, vp, vp, vp, i32, vp, i64, i32, i32, vp]
+    lib.sva_test_stft_ring.argtypes = [i32] * 3 + [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32]
+    lib.sva_test_fsq.argtypes = [i32] * 6 + [vp, i64, i64, i64, i32, vp, vp, vp, i64, i64, i64]
+    lib.sva_test_conv_post.argtypes = [i32] * 5 + [vp, i64, i64, i64, vp, vp, vp, i64, i64, i64]
     lib.sva_test_gemm_f16w.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp]
     lib.sva_test_gemm_planes.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.sva_host_launch_cost.argtypes = [i32, i32, f32p]
@@ -123,7 +131,7 @@ EXPORTED_SYMBOLS = [
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
     "sva_op_geglu", "sva_op_l2norm", "sva_ops_capture_begin", "sva_ops_capture_end", "sva_ops_graph_launch", "sva_ops_graph_free",
-    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
+    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
 ]
 
 
@@ -552,6 +560,103 @@ def test_pair_attention(q, keys, vals, pos0=0, S=2048, half_kv=False, iters=0, d
     _check(lib.sva_test_pair_attention(device, M, D // 64, int(pos0), int(S), _ptr(q), _ptr(keys), _ptr(vals), int(bool(half_kv)), _ptr(o1), _ptr(o2),
                                        int(iters), _ptr(us)), "sva_test_pair_attention")
     return o1, o2, (float(us[0]), float(us[1]))
+
+
+# ---- per-kernel hooks of the non-GEMM launchers (include/sva.h); tests/test_gpu_kernels.py compares them with fp64 references ----
+def _f32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def test_decode_attention(variant, qkv, cache, slot, pos, rope=None, x=None, W=None, norm_w=None, half_kv=False, out_fill=0.0, device=0):
+    """qkv [M, 3 H 64], cache [n_slots, 2, H, S, 64] -> (out [M, H 64], qkv after the launch, cache after the launch); variants in include/sva.h"""
+    lib = load_library()
+    qkv, cache = np.array(qkv, dtype=np.float32, order="C"), np.array(cache, dtype=np.float32, order="C")
+    slot, pos = np.ascontiguousarray(slot, dtype=np.int32), np.ascontiguousarray(pos, dtype=np.int32)
+    n_slots, _, H, S, _ = cache.shape
+    M = qkv.shape[0]
+    assert qkv.shape == (M, 3 * H * 64) and cache.shape == (n_slots, 2, H, S, 64) and slot.shape == (M,) and pos.shape == (M,)
+    rope, x, W, norm_w = _f32(rope), _f32(x), _f32(W), _f32(norm_w)
+    assert x is None or x.shape == (M, H * 64)
+    assert W is None or W.shape == ((3 if variant == 6 else 1) * H * 64, H * 64)
+    out = np.full((M, H * 64), out_fill, np.float32)
+    _check(lib.sva_test_decode_attention(device, int(variant), M, H, S, n_slots, _ptr(slot), _ptr(pos), int(bool(half_kv)), _ptr(qkv), _ptr(cache), _ptr(rope),
+                                         0 if rope is None else rope.shape[0], _ptr(x), _ptr(W), _ptr(norm_w), _ptr(out)), "sva_test_decode_attention")
+    return out, qkv, cache
+
+
+def test_enc_attention(qkv, rope, H, row0=0, n_planes=0, blocked=False, fill=0.0, device=0):
+    """qkv [B, T, 3 H 64] -> (out [B, T, H 64] pre-filled with `fill`, planes uint16 [2, B T H 64] pre-filled with 0xFFFF or None)"""
+    lib = load_library()
+    qkv, rope = _f32(qkv), _f32(rope)
+    B, T, _ = qkv.shape
+    assert qkv.shape == (B, T, 3 * H * 64) and rope.shape == (T, 32, 2)
+    out = np.full((B, T, H * 64), fill, np.float32)
+    planes = np.full((2, B * T * H * 64), 0xFFFF, np.uint16) if n_planes else None
+    _check(lib.sva_test_enc_attention(device, B, T, H, int(row0), _ptr(qkv), _ptr(rope), int(n_planes), int(bool(blocked)), _ptr(out), _ptr(planes)),
+           "sva_test_enc_attention")
+    return out, planes
+
+
+def test_rowop(kind, x, B, T, C, params, eps, out, x_bstride, x_off=0, ldx=None, o_bstride=None, o_off=0, ldo=None, skip=(0, 0), n_planes=0, blocked=False,
+               device=0):
+    """kind 0 dwconv7 + LayerNorm, 1 LayerNorm rows, 2 RMSNorm rows over the flat arrays x / out (out is updated in place and returned with the
+    planes uint16 [2, len(out)], pre-filled with 0xFFFF, or None)"""
+    lib = load_library()
+    x = _f32(x).reshape(-1)
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.ndim == 1
+    p = [_f32(a) for a in params] + [None] * (4 - len(params))
+    planes = np.full((2, out.size), 0xFFFF, np.uint16) if n_planes else None
+    _check(lib.sva_test_rowop(device, int(kind), B, T, C, _ptr(x), x.size, int(x_bstride), int(x_off), int(C if ldx is None else ldx), _ptr(p[0]), _ptr(p[1]),
+                              _ptr(p[2]), _ptr(p[3]), float(eps), _ptr(out), out.size, int(T * C if o_bstride is None else o_bstride), int(o_off),
+                              int(C if ldo is None else ldo), int(skip[0]), int(skip[1]), int(n_planes), int(bool(blocked)), _ptr(planes), out.size),
+           "sva_test_rowop")
+    return out, planes
+
+
+def test_bsq(z, B, T, W, bias, idx_out, z_bstride, z_off=0, ldz=None, norm_w=None, eps=1e-5, zn_out=None, idx_bstride=None, idx_off=0, u_out=None, device=0):
+    """launch_bsq over the flat array z; idx_out int64 [n], zn_out (flat, like z) and u_out [n, nbits] are updated in place"""
+    lib = load_library()
+    z, W, bias, norm_w = _f32(z).reshape(-1), _f32(W), _f32(bias), _f32(norm_w)
+    nbits, Cc = W.shape
+    assert idx_out.dtype == np.int64 and idx_out.flags.c_contiguous
+    assert zn_out is None or (zn_out.dtype == np.float32 and zn_out.size == z.size and zn_out.flags.c_contiguous)
+    assert u_out is None or (u_out.dtype == np.float32 and u_out.shape == (idx_out.size, nbits) and u_out.flags.c_contiguous)
+    _check(lib.sva_test_bsq(device, B, T, Cc, _ptr(z), z.size, int(z_bstride), int(z_off), int(Cc if ldz is None else ldz), _ptr(norm_w), float(eps), _ptr(zn_out),
+                            _ptr(W), _ptr(bias), nbits, _ptr(idx_out), idx_out.size, int(T if idx_bstride is None else idx_bstride), int(idx_off), _ptr(u_out)),
+           "sva_test_bsq")
+    return idx_out, u_out, zn_out
+
+
+def test_stft_ring(ring, mag, step=None, n_chunk=0, add=0, m0=0, nfr=1, second=None, device=0):
+    """ring [B, N], mag [B, rows, ldm] (updated in place); second = (m0b, nfrb, row_b0) selects the two-range launch"""
+    lib = load_library()
+    ring = _f32(ring)
+    B, N = ring.shape
+    assert mag.dtype == np.float32 and mag.flags.c_contiguous and mag.shape[0] == B
+    st = None if step is None else np.array([step], np.int32)
+    m0b, nfrb, row_b0 = second if second is not None else (0, 0, 0)
+    _check(lib.sva_test_stft_ring(device, B, N, _ptr(ring), _ptr(st), int(n_chunk), int(add), int(m0), int(nfr), int(second is not None), int(m0b), int(nfrb),
+                                  int(row_b0), _ptr(mag), mag.shape[1], mag.shape[2]), "sva_test_stft_ring")
+    return mag
+
+
+def test_fsq(encode, lat, codes, B, T, G, gdim, Wt, bs, l_bstride, l_off, ld, c_bstride, c_gstride, device=0):
+    """flat lat (float32) and codes (int32), updated in place: encode lat -> codes, else codes -> lat"""
+    lib = load_library()
+    assert lat.dtype == np.float32 and codes.dtype == np.int32 and lat.flags.c_contiguous and codes.flags.c_contiguous
+    Wt, bs = _f32(Wt), _f32(bs)
+    _check(lib.sva_test_fsq(device, int(bool(encode)), B, T, G, gdim, _ptr(lat), lat.size, int(l_bstride), int(l_off), int(ld), _ptr(Wt), _ptr(bs), _ptr(codes),
+                            codes.size, int(c_bstride), int(c_gstride)), "sva_test_fsq")
+    return lat, codes
+
+
+def test_conv_post(x, pcm, B, T, Cc, k, w, bias, x_bstride, x_off, p_bstride, p_off, device=0):
+    lib = load_library()
+    x, w, bias = _f32(x).reshape(-1), _f32(w), _f32(bias)
+    assert pcm.dtype == np.float32 and pcm.flags.c_contiguous
+    _check(lib.sva_test_conv_post(device, B, T, Cc, k, _ptr(x), x.size, int(x_bstride), int(x_off), _ptr(w), _ptr(bias), _ptr(pcm), pcm.size, int(p_bstride),
+                                  int(p_off)), "sva_test_conv_post")
+    return pcm
 
 
 def test_gemm_choice(A, W, choice, bias=None, device=0):

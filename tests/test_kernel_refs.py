@@ -1,0 +1,255 @@
+"""The float64 references of tests/kernel_refs.py against the oracle's own (fp32 torch) functions on the same inputs: the oracle is pinned
+to the reference project's fixtures (test_oracle_golden.py), so this pins the per-kernel references to the same thing.  The two cannot be
+equal (fp32 vs fp64); the oracle's rms_norm at 170 x 512 sits 8e-8 (relative) from its own float64 evaluation, so
+max |ref64 - oracle32| <= 1e-5 max |ref64| leaves two orders of room for rounding and none for a wrong formula."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import sva_oracle as O
+import kernel_refs as R
+
+torch.set_grad_enabled(False)
+
+
+def _close(ref64, oracle32, what):
+    ref64 = np.asarray(ref64, np.float64)
+    got = np.asarray(oracle32, np.float64)
+    assert ref64.shape == got.shape, (what, ref64.shape, got.shape)
+    err, scale = np.abs(ref64 - got).max(), np.abs(ref64).max()
+    print(what, "max err", err, "scale", scale, "ratio", err / (1e-5 * scale))
+    assert err <= 1e-5 * scale, (what, err, scale)
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+
+
+def test_rms_norm_matches_oracle():
+    rng = np.random.default_rng(1)
+    x = rng.standard_normal((170, 512)).astype(np.float32) * 3 + 0.5
+    w = rng.uniform(0.5, 1.5, 512).astype(np.float32)
+    _close(R.rms_norm(x, w, 1e-5), O.rms_norm(_t(x), _t(w)).numpy(), "rms_norm")
+    # the float32 restatement is the same formula: it lands within the same distance
+    _close(R.rms_norm(x, w, 1e-5), R.rms_norm(x, w, 1e-5, np.float32), "rms_norm f32 restatement")
+
+
+def test_layer_norm_matches_oracle():
+    rng = np.random.default_rng(2)
+    x = rng.standard_normal((2, 384, 43)).astype(np.float32) * 2 - 1          # channel-first like the oracle
+    w = rng.uniform(0.5, 1.5, 384).astype(np.float32)
+    b = rng.standard_normal(384).astype(np.float32)
+    want = O.layer_norm_c(_t(x), _t(w), _t(b)).numpy().transpose(0, 2, 1)
+    _close(R.layer_norm(x.transpose(0, 2, 1), w, b, 1e-6), want, "layer_norm")
+
+
+@pytest.mark.parametrize("C,T", [(128, 10), (512, 43)])
+def test_dwconv7_ln_matches_convnext_block_prologue(C, T):
+    rng = np.random.default_rng(C + T)
+    x = rng.standard_normal((2, C, T)).astype(np.float32)
+    w = rng.standard_normal((C, 1, 7)).astype(np.float32) * 0.4
+    b, lw, lb = (rng.standard_normal(C).astype(np.float32) for _ in range(3))
+    y = O.causal_conv1d(_t(x), _t(w), _t(b), groups=C).transpose(1, 2)
+    want = torch.nn.functional.layer_norm(y, (C,), _t(lw), _t(lb), 1e-6).numpy()
+    xin = np.concatenate([np.zeros((2, 6, C), np.float32), x.transpose(0, 2, 1)], 1)       # the causal left pad as 6 history rows
+    _close(R.dwconv7_ln(xin, w[:, 0, :].T, b, lw, lb, 1e-6), want, "dwconv7_ln")
+
+
+@pytest.mark.parametrize("kind", ["noise", "silence", "impulse"])
+def test_stft_mag_matches_oracle(kind):
+    rng = np.random.default_rng(3)
+    N = 8 * 512
+    a = np.zeros((2, N), np.float32)
+    if kind == "noise":
+        a = rng.standard_normal((2, N)).astype(np.float32)
+    elif kind == "impulse":
+        a[0, 1700] = 1.0
+        a[1, 5] = -1.0
+    want = O.stft_magnitude(_t(a)).numpy().transpose(0, 2, 1)
+    got = R.stft_mag(a)
+    _close(got, want, "stft_mag " + kind)
+    if kind == "silence":
+        assert np.abs(got - 1e-3).max() < 1e-12          # sqrt(1e-6), not 0
+
+
+def _bsq_weights(rng, C=512):
+    return {"w": rng.standard_normal((13, C)).astype(np.float32) / np.sqrt(C), "b": rng.standard_normal(13).astype(np.float32) * 0.1}
+
+
+def test_bsq_matches_oracle_tail():
+    """the tail of bsq_encode (Linear 512 -> 13, L2 normalise, sign bits MSB first) and the final RMSNorm of its pre_module"""
+    rng = np.random.default_rng(4)
+    z = rng.standard_normal((40, 512)).astype(np.float32) * 2
+    nw = rng.uniform(0.5, 1.5, 512).astype(np.float32)
+    P = _bsq_weights(rng)
+    zn = O.rms_norm(_t(z), _t(nw))
+    u = torch.nn.functional.normalize(torch.nn.functional.linear(zn, _t(P["w"]), _t(P["b"])).float(), dim=-1)
+    idx = ((u > 0).long() * 2 ** torch.arange(12, -1, -1)).sum(-1)
+    zn64, u64, raw64, idx64 = R.bsq(z, nw, 1e-5, P["w"], P["b"])
+    _close(zn64, zn.numpy(), "bsq zn")
+    _close(u64, u.numpy(), "bsq u")
+    assert np.abs(u64).min() >= 1e-4 and np.array_equal(idx64, idx.numpy())
+
+
+def test_bsq_matches_oracle_bsq_encode(weights1):
+    """through the oracle's own entry point: bsq_encode(return_u=True) on tokenizer weights; the reference consumes the oracle's last
+    pre-norm activation, so only the fused RMSNorm + projection + normalise + bits are compared"""
+    W, p = weights1, "tok.quantizer."
+    rng = np.random.default_rng(5)
+    feat = _t(rng.standard_normal((1, 512, 16)))
+    captured = {}
+    orig = O.rms_norm
+
+    def spy(x, w, eps=1e-5):
+        if w is W[p + "pre_module.norm.weight"]:
+            captured["x"] = x.clone()
+        return orig(x, w, eps)
+
+    O.rms_norm = spy
+    try:
+        idx, u = O.bsq_encode(feat, W, return_u=True)
+    finally:
+        O.rms_norm = orig
+    z = captured["x"][0].numpy()
+    _, u64, _, idx64 = R.bsq(z, W[p + "pre_module.norm.weight"].numpy(), 1e-5, W[p + "residual_bsq.rvqs.0.project_in.weight"].numpy(),
+                             W[p + "residual_bsq.rvqs.0.project_in.bias"].numpy())
+    _close(u64, u[0].numpy(), "bsq_encode u")
+    safe = np.abs(u64).min(-1) >= 1e-4
+    assert safe.any() and np.array_equal(idx64[safe], idx[0].numpy()[safe])
+
+
+def _fsq_weights(rng, G=8, gd=64):
+    W = {}
+    for g in range(G):
+        W[f"voc.quantizer.residual_fsq.rvqs.{g}.project_in.weight"] = _t(rng.standard_normal((4, gd)) / np.sqrt(gd))
+        W[f"voc.quantizer.residual_fsq.rvqs.{g}.project_in.bias"] = _t(rng.standard_normal(4) * 0.1)
+        W[f"voc.quantizer.residual_fsq.rvqs.{g}.project_out.weight"] = _t(rng.standard_normal((gd, 4)))
+        W[f"voc.quantizer.residual_fsq.rvqs.{g}.project_out.bias"] = _t(rng.standard_normal(gd) * 0.1)
+    return W
+
+
+def test_fsq_encode_decode_match_oracle():
+    rng = np.random.default_rng(6)
+    W = _fsq_weights(rng)
+    Win = np.stack([W[f"voc.quantizer.residual_fsq.rvqs.{g}.project_in.weight"].numpy() for g in range(8)])
+    bin_ = np.stack([W[f"voc.quantizer.residual_fsq.rvqs.{g}.project_in.bias"].numpy() for g in range(8)])
+    Wout = np.stack([W[f"voc.quantizer.residual_fsq.rvqs.{g}.project_out.weight"].numpy() for g in range(8)])
+    bout = np.stack([W[f"voc.quantizer.residual_fsq.rvqs.{g}.project_out.bias"].numpy() for g in range(8)])
+    z = rng.standard_normal((2, 512, 43)).astype(np.float32) * 2
+    idx, margin = O.fsq_encode(_t(z), W, return_margin=True)
+    codes64, margin64 = R.fsq_encode(z.transpose(0, 2, 1), Win, bin_)
+    safe = margin64 >= 1e-4
+    assert safe.mean() > 0.99 and np.array_equal(codes64[safe], idx.numpy()[safe])
+    assert np.abs(margin64 - margin.numpy()).max() <= 1e-5
+    codes = rng.integers(0, 1000, (2, 8, 43)).astype(np.int32)
+    _close(R.fsq_decode(codes, Wout, bout), O.fsq_decode(torch.from_numpy(codes), W).numpy().transpose(0, 2, 1), "fsq_decode")
+
+
+def test_conv_post_tanh_matches_oracle_tail():
+    """hifigan's tail: silu -> causal conv (C -> 1, k = 7) -> tanh"""
+    rng = np.random.default_rng(7)
+    C, T, k = 16, 43, 7
+    x = rng.standard_normal((2, C, T)).astype(np.float32) * 2
+    w = rng.standard_normal((1, C, k)).astype(np.float32) * 0.2
+    b = np.array([0.05], np.float32)
+    want = torch.tanh(O.causal_conv1d(torch.nn.functional.silu(_t(x)), _t(w), _t(b)))[:, 0].numpy()
+    xin = np.concatenate([np.zeros((2, k - 1, C), np.float32), x.transpose(0, 2, 1)], 1)
+    _close(R.conv_post_tanh(xin, w[0].T, b), want, "conv_post_tanh")
+
+
+@pytest.mark.parametrize("T", [48, 520])
+def test_enc_attention_matches_one_window_transformer_layer(T):
+    """one layer of the oracle's window_transformer (T = 520 crosses the 512-key window) against the same layer assembled in float64
+    from the references: rms_norm -> wqkv -> enc_attention -> wo (gamma) -> SwiGLU (gamma) -> final rms_norm"""
+    rng = np.random.default_rng(T)
+    H, C, I = 2, 128, 256
+    p, q = "t.", "t.layers.0."
+    g = lambda *s: (rng.standard_normal(s) / np.sqrt(s[-1])).astype(np.float32)
+    Wn = {q + "attention_norm.weight": rng.uniform(0.5, 1.5, C).astype(np.float32), q + "attention.wqkv.weight": g(3 * C, C) * 3,
+          q + "attention.wo.weight": g(C, C), q + "attention_layer_scale.gamma": rng.uniform(0.5, 1.0, C).astype(np.float32),
+          q + "ffn_norm.weight": rng.uniform(0.5, 1.5, C).astype(np.float32), q + "feed_forward.w1.weight": g(I, C),
+          q + "feed_forward.w3.weight": g(I, C), q + "feed_forward.w2.weight": g(C, I),
+          q + "ffn_layer_scale.gamma": rng.uniform(0.5, 1.0, C).astype(np.float32), p + "norm.weight": rng.uniform(0.5, 1.5, C).astype(np.float32)}
+    x = rng.standard_normal((2, C, T)).astype(np.float32)
+    want = O.window_transformer(_t(x), {k: _t(v) for k, v in Wn.items()}, p, n_layer=1, n_head=H).numpy().transpose(0, 2, 1)
+    W = {k: v.astype(np.float64) for k, v in Wn.items()}
+    xr = x.transpose(0, 2, 1).astype(np.float64)
+    qkv = R.rms_norm(xr, W[q + "attention_norm.weight"], 1e-5) @ W[q + "attention.wqkv.weight"].T
+    att = R.enc_attention(qkv, R.rope_table(T), H)
+    xr = xr + (att @ W[q + "attention.wo.weight"].T) * W[q + "attention_layer_scale.gamma"]
+    h = R.rms_norm(xr, W[q + "ffn_norm.weight"], 1e-5)
+    a = h @ W[q + "feed_forward.w1.weight"].T
+    f = ((a / (1 + np.exp(-a))) * (h @ W[q + "feed_forward.w3.weight"].T)) @ W[q + "feed_forward.w2.weight"].T
+    xr = R.rms_norm(xr + f * W[q + "ffn_layer_scale.gamma"], W[p + "norm.weight"], 1e-5)
+    _close(xr, want, f"window_transformer layer T={T}")
+    if T > 512:        # the window binds: plain causal attention must NOT reproduce the oracle
+        att_c = R.enc_attention(qkv, R.rope_table(T), H, window=T)
+        assert np.abs(att_c - att).max() > 1e-3 * np.abs(att).max()
+
+
+def test_decode_attention_and_rope_kvwrite_match_dual_ar_block():
+    """DualAR._block (RMSNorm, wqkv, RoPE, cache write at pos, attention over 0 .. pos, wo + residual, SwiGLU) for rows at ragged positions
+    of one stream's cache against the same block assembled in float64 from rope_kvwrite + decode_attention"""
+    rng = np.random.default_rng(8)
+    H, hd, S, M = 3, 64, 96, 4
+    D, I = H * hd, 256
+    p = "l."
+    g = lambda *s: (rng.standard_normal(s) / np.sqrt(s[-1])).astype(np.float32)
+    Wn = {p + "attention_norm.weight": rng.uniform(0.5, 1.5, D).astype(np.float32), p + "attention.wqkv.weight": g(3 * D, D) * 3,
+          p + "attention.wo.weight": g(D, D), p + "ffn_norm.weight": rng.uniform(0.5, 1.5, D).astype(np.float32),
+          p + "feed_forward.w1.weight": g(I, D), p + "feed_forward.w3.weight": g(I, D), p + "feed_forward.w2.weight": g(D, I)}
+    pos = np.array([0, 63, 64, 95])
+    kc0 = rng.standard_normal((H, S, hd)).astype(np.float32)
+    vc0 = rng.standard_normal((H, S, hd)).astype(np.float32)
+    x = rng.standard_normal((M, D)).astype(np.float32)
+    me = types.SimpleNamespace(W={k: _t(v) for k, v in Wn.items()}, cfg=types.SimpleNamespace(n_head=H), hd=hd)
+    kc, vc = _t(kc0).clone(), _t(vc0).clone()
+    want = O.DualAR._block(me, _t(x), p, O.rope_table(S, hd), kc, vc, torch.from_numpy(pos)).numpy()
+    W = {k: v.astype(np.float64) for k, v in Wn.items()}
+    x64 = x.astype(np.float64)
+    qkv = R.rms_norm(x64, W[p + "attention_norm.weight"], 1e-5) @ W[p + "attention.wqkv.weight"].T
+    cache = np.stack([kc0, vc0])[None]                                    # [1 slot, 2, H, S, hd]
+    slot = np.zeros(M, np.int64)
+    qkv_r, cache_r = R.rope_kvwrite(qkv, cache, slot, pos, R.rope_table(S), H)
+    # the oracle writes all M rows, then masks by position: row m sees the rows written at positions <= pos[m] -- the same cache
+    att = R.decode_attention(qkv_r[:, :D], cache_r, slot, pos, H)
+    x64 = x64 + att @ W[p + "attention.wo.weight"].T
+    h = R.rms_norm(x64, W[p + "ffn_norm.weight"], 1e-5)
+    a = h @ W[p + "feed_forward.w1.weight"].T
+    x64 = x64 + ((a / (1 + np.exp(-a))) * (h @ W[p + "feed_forward.w3.weight"].T)) @ W[p + "feed_forward.w2.weight"].T
+    _close(x64, want, "DualAR._block")
+    _close(cache_r[0, 0], kc.numpy(), "k cache")
+    _close(cache_r[0, 1], vc.numpy(), "v cache")
+    untouched = np.ones(S, bool)
+    untouched[pos] = False
+    assert np.array_equal(cache_r[0][:, :, untouched], np.stack([kc0, vc0])[:, :, untouched].astype(np.float64))
+
+
+def test_float32_restatements_stay_close():
+    """bound() needs the float32 restatement to be the SAME formula: each lands within 1e-4 (relative) of its float64 twin"""
+    rng = np.random.default_rng(9)
+    H, T = 2, 80
+    qkv = rng.standard_normal((1, T, 3 * H * 64)).astype(np.float32)
+    tab = R.rope_table(T)
+    a64, a32 = R.enc_attention(qkv, tab, H), R.enc_attention(qkv, tab, H, dt=np.float32)
+    assert np.abs(a64 - a32).max() <= 1e-4 * np.abs(a64).max() and a32.dtype == np.float32
+    w = rng.standard_normal((1, 4096)).astype(np.float32)
+    s64, s32 = R.stft_mag(w), R.stft_mag(w, dt=np.float32)
+    assert np.abs(s64 - s32).max() <= 1e-4 * np.abs(s64).max() and s32.dtype == np.float32
+    e32 = R.e32_of(a32, a64)
+    assert R.bound(e32, a64) >= 4 * e32 > 0
+
+
+def test_planes_decode_layouts():
+    rng = np.random.default_rng(10)
+    rows, K = 6, 64
+    x = rng.standard_normal((rows, K)).astype(np.float32)
+    hi = x.astype(np.float16)
+    lo = (x - hi.astype(np.float32)).astype(np.float16)
+    rm = np.stack([hi.reshape(-1), lo.reshape(-1)]).view(np.uint16)
+    assert np.abs(R.planes_decode(rm, 2, rows, K, False) - x).max() <= 2.0 ** -21 * np.abs(x).max()
+    blk = np.stack([a.reshape(rows, K // 32, 32).transpose(1, 0, 2).reshape(-1) for a in (hi, lo)]).view(np.uint16)
+    assert np.array_equal(R.planes_decode(blk, 2, rows, K, True), R.planes_decode(rm, 2, rows, K, False))
+    assert np.array_equal(R.planes_decode(blk, 1, rows, K, True), hi.astype(np.float64))
