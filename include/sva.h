@@ -63,6 +63,10 @@ typedef struct sva_config {
                             * has fp16's RANGE: an operand beyond +-65504 raises an error at the next sva_step* / sva_sync naming mm_mode = 0 */
     int voc_dtype;         /* 0: vocoder (firefly.decode) GEMMs in the mm_mode grade; 1: fp16 operands, fp32 accumulate -- the reference's
                             * own precision for this stage (torch.autocast(fp16) around code2wav_fn, infer_arvc.py:493, 571-590) */
+    int enc_dtype;         /* 0 (default): content encoder in fp32 grade, BSQ indices bit-equal to the fp32 oracle; 1: every groups = 1 conv / Linear of the
+                            * tokenizer's content encoder takes both operands rounded once (nearest even) to fp16, exact products, fp32 accumulation; the A
+                            * operand is the activation as its producer stores it (fp16(RMSNorm(x) w), ...); mel, depthwise convs, norms, attention, residuals and
+                            * BSQ stay fp32.  NOT parity-preserving: a code bit may flip where its pre-sign value is near zero.  fp16 RANGE, reported as mm_mode's */
 } sva_config;
 
 /* evaluations/infer_arvc.py setup_stream_caches (:443-460) + stream_infer defaults (:598-613) */
@@ -282,6 +286,13 @@ int sva_test_gemm_choice(int device, int M, int N, int K, const float* A, const 
  * iters > 0 also returns the average microseconds per launch. */
 int sva_test_gemm_f16w(int device, int M, int N, int K, const float* A, const float* W, const float* bias, const float* rms_w,
                        const float* res, int mode, float* C, int iters, float* out_us);
+/* The fp16-operand weight-streaming conv-GEMM of an enc_dtype = 1 encoder below batch scale (csrc/gemm_stream_h.hip) through its production
+ * launcher.  Dense host arrays: A [B][(T - 1) stride + (taps - 1) dil + 1][Cin], W [N][taps * Cin], bias [N] or null, gamma [N] / res [B][T][N]
+ * (mode bit 2), C [B][T][N, or N / 2 with SwiGLU] in and out.  mode bits: 1 = GELU, 2 = gamma + residual, 4 = rows [T / 4, T / 2) of every item
+ * skipped, 8 = SwiGLU, 16 = padded item strides and offsets on the device, 32 = range check (a non-finite output fails the call).  (mt, nt, kw) =
+ * 16-row tiles, 16-column tiles, K-split waves per workgroup; mt = 0: the heuristic's.  iters > 0 also returns microseconds per launch. */
+int sva_test_gemm_h16(int device, int B, int T, int N, int Cin, int taps, int dil, int stride, const float* A, const float* W, const float* bias,
+                      const float* gamma, const float* res, int mode, int mt, int nt, int kw, float* C, int iters, float* out_us);
 /* conv-GEMM fed from pre-split 16-bit operand planes (csrc/gemm_planes.hip; the Linear layers of firefly.py:421-440 and
  * windowed_transformer.py:134-143 at batch scale): mode 0 = three bf16 planes / six products (fp32-grade), 1 = two fp16 planes /
  * three products (fp32-grade inside the fp16 range), 2 = one fp16 plane (torch.autocast(fp16), evaluations/infer_arvc.py:493);

@@ -41,6 +41,7 @@ struct Lin {
     float* W = nullptr;
     float* Wk = nullptr;         // the same values in the fragment-major packing of gemm_stream.hip (K % 16 == 0)
     void* Wh = nullptr;          // fp16 copy in the same [N][K] layout (AR layers of an ar_dtype = 1 engine)
+    void* Wkh = nullptr;         // fp16 fragment-major packing of gemm_stream_h.hip (K % 32 == 0; the content encoder's layers of an enc_dtype = 1 engine)
     float* b = nullptr;
     int N = 0, K = 0;
     unsigned short* Wp = nullptr;    // pre-split 16-bit planes [planes][N][K] of W * 2^e (gemm_planes.hip), wp_inv = 2^-e, pmode = their PlanesMode

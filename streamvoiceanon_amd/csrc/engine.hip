@@ -505,7 +505,7 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
         if (!b->d_ar_fail) SVA_TRY(dev_alloc(A, &b->d_ar_fail, 1));
         if (debug_options().ar_timing && !b->d_ar_dbg) SVA_TRY(dev_alloc(A, &b->d_ar_dbg, 1024));
     }
-    if (c.mm_mode == 1 || c.voc_dtype == 1) {       // fp16 operand planes: their range check reports here (checked by sva_sync)
+    if (c.mm_mode == 1 || c.voc_dtype == 1 || c.enc_dtype == 1) {       // fp16 operands: their range check reports here (checked by sva_sync)
         SVA_HIP(hipHostMalloc((void**)&b->h_mm_ovf, sizeof(int), hipHostMallocMapped));
         *b->h_mm_ovf = 0;
         SVA_HIP(hipHostGetDevicePointer((void**)&b->d_mm_ovf, b->h_mm_ovf, 0));
@@ -940,6 +940,10 @@ namespace {
 int check_mm_overflow(sva_batch* b) {
     if (b->h_mm_ovf && *reinterpret_cast<volatile int*>(b->h_mm_ovf) != 0) {
         *b->h_mm_ovf = 0;
+        if (b->e->cfg.enc_dtype == 1)
+            SVA_CHECK(false, "a GEMM on fp16 operands produced a non-finite output: an activation or weight is outside the fp16 range (as it would be for "
+                             "the reference under torch.autocast(fp16)); create the engine with sva_config.enc_dtype = 0 (and mm_mode = 0, voc_dtype = 0) for "
+                             "the range-safe kernels -- the results since the last synchronisation are invalid");
         SVA_CHECK(false, "a batch-scale GEMM on fp16 operand planes produced a non-finite output: an activation or weight is outside the fp16 range "
                          "(as it would be for the reference under torch.autocast(fp16)); create the engine with sva_config.mm_mode = 0 (and voc_dtype = 0) "
                          "for the range-safe bf16 kernels -- the results since the last synchronisation are invalid");

@@ -921,6 +921,25 @@ static int launch_conv_gemm_impl(const ConvGemm& g, hipStream_t st, int group_n)
     if (g.rms_w) SVA_CHECK(g.taps == 1 && !g.a_silu && conv_gemm_can_fuse_rms(g.M, g.N), "conv_gemm: fused RMSNorm needs taps == 1 on the small-M path");
     if (g.dw_wT) SVA_CHECK(g.taps == 1 && g.M <= 16 && g.Cin <= 512 && !g.a_silu && !g.rms_w && !g.w13 && group_n == 1 && g.dw_b && g.ln_w && g.ln_b,
                            "conv_gemm: the fused ConvNeXt prologue needs taps == 1, M <= 16, Cin <= 512");
+    // A layer that carries the fp16 fragment-major packing (the content encoder of an enc_dtype = 1 engine) runs on fp16 operands only: the planes
+    // kernel in H1 under its existing rule (operands handed over as planes, or >= 1024 rows), the fp16 weight-streaming kernel otherwise --
+    // never an fp32 kind; no table, no timed search
+    if (g.Wkh) {
+        SVA_CHECK(group_n == 1 && !t_group, "conv_gemm: fp16-operand layers take single problems");
+        const bool want = g.Ap || g.Cp || (g.pmode == PLANES_H1 && g.M >= 1024 && g.N >= 32);
+        if (want && c_vec && g.pmode == PLANES_H1 && planes_gemm_supported(g)) {
+            t_planes_mode = -1;
+            SVA_TRY_RC(launch_choice(g, st, Choice{4, 8 + planes_variant(g, 1), 0, 0}));
+            t_last_kind = 6 + t_planes_mode;
+        } else {
+            SVA_CHECK(!g.Ap && !g.Cp, "conv_gemm: operand planes handed to a problem the planes kernel does not take");
+            SVA_CHECK(stream_h_gemm_supported(g), "conv_gemm: an fp16-operand layer that neither the planes kernel nor the fp16 weight-streaming kernel takes");
+            SVA_TRY_RC(launch_stream_h_gemm(g, 0, 0, 0, st));
+            t_last_kind = 11;
+        }
+        SVA_HIP(hipGetLastError());
+        return 0;
+    }
     Choice ch = heuristic_choice(g, c_vec);
     const unsigned long long key_flags = (unsigned long long)(g.a_silu ? 1 : 0) | (g.rms_w ? 2 : 0) | (g.w13 ? 4 : 0) | (c_vec ? 8 : 0) | (g.accumulate ? 16 : 0) |
                                          (group_n > 1 ? 32 : 0) | (g.dw_wT ? 64 : 0);

@@ -15,7 +15,7 @@ extern "C" int sva_config_default(sva_config* c) {
     c->tr_layers = 8; c->tr_heads = 8; c->tr_dim = 512; c->tr_inter = 1536; c->bsq_bits = 13;
     c->ar_dim = 768; c->ar_heads = 12; c->ar_layers = 12; c->ar_fast_layers = 4; c->ar_inter = 2304;
     c->ar_vocab = 8192; c->codebook_size = 1000; c->num_codebooks = 8; c->max_delay = 8; c->max_seq_len = 2048;
-    c->timbre_dim = 128; c->timbre_tokens = 32; c->style_dim = 192; c->voc_dim = 512; c->ar_dtype = 0; c->mm_mode = 1; c->voc_dtype = 0;
+    c->timbre_dim = 128; c->timbre_tokens = 32; c->style_dim = 192; c->voc_dim = 512; c->ar_dtype = 0; c->mm_mode = 1; c->voc_dtype = 0; c->enc_dtype = 0;
     return 0;
 }
 extern "C" int sva_stream_params_default(sva_stream_params* p) {
@@ -35,6 +35,7 @@ extern "C" int sva_engine_create(const sva_config* cfg, int device, sva_engine**
     SVA_CHECK(cfg->tr_dim == cfg->enc_dims[3] && cfg->voc_dim == 512, "unsupported dims");
     SVA_CHECK(cfg->ar_dim / cfg->ar_heads == 64 && cfg->tr_dim / cfg->tr_heads == 64, "head_dim must be 64");
     SVA_CHECK(cfg->ar_dtype == 0 || cfg->ar_dtype == 1, "ar_dtype must be 0 (fp32 weights / fp32 KV) or 1 (fp16 weights / fp16 slow KV)");
+    SVA_CHECK(cfg->enc_dtype == 0 || cfg->enc_dtype == 1, "enc_dtype must be 0 (fp32-grade content encoder) or 1 (fp16 operands, fp32 accumulate)");
     int ndev = 0;
     SVA_HIP(hipGetDeviceCount(&ndev));
     SVA_CHECK(ndev > 0 && device < ndev, "no such HIP device (the product path has no CPU fallback)");
@@ -467,6 +468,9 @@ extern "C" int sva_engine_finalize(sva_engine* e) {
     {
         const int enc_mode = c.mm_mode == 1 ? PLANES_H3 : -1;
         const int voc_mode = c.voc_dtype == 1 ? PLANES_H1 : enc_mode;
+        // enc_dtype = 1: the tokenizer's content encoder (front-end + pre_module transformer) on fp16 operands -- one plane at batch scale, the fp16
+        // fragment-major packing of gemm_stream_h.hip below it.  Only then, and only for those layers (no second copy for anyone else)
+        const int tok_mode = c.enc_dtype == 1 ? PLANES_H1 : enc_mode;
         SVA_CHECK((c.mm_mode == 0 || c.mm_mode == 1) && (c.voc_dtype == 0 || c.voc_dtype == 1),
                   "bad mm_mode / voc_dtype (mm_mode = 2, pre-split bf16 planes, was measured slower than mm_mode = 0 and removed in round 5)");
         std::vector<float> host;
@@ -482,14 +486,32 @@ extern "C" int sva_engine_finalize(sva_engine* e) {
             l.pmode = mode;
             return 0;
         };
-        auto front = [&](EncFront& F, int mode) -> int {
+        auto frag_h = [&](Lin& l) -> int {
+            if (!l.W) return 0;
+            SVA_CHECK(l.K % 32 == 0 && l.N >= 16, "enc_dtype = 1: an encoder layer whose K is not a multiple of 32");
+            const long n = (long)l.N * l.K;
+            host.resize(n);
+            SVA_HIP(hipMemcpy(host.data(), l.W, sizeof(float) * n, hipMemcpyDeviceToHost));
+            std::vector<uint16_t> p;
+            stream_h_pack_weights(host.data(), l.N, l.K, p);
+            uint16_t* d = nullptr;
+            SVA_TRY(dev_alloc(e->allocs, &d, p.size(), false));
+            SVA_HIP(hipMemcpy(d, p.data(), p.size() * 2, hipMemcpyHostToDevice));
+            l.Wkh = d;
+            return 0;
+        };
+        auto enc_lin = [&](Lin& l, int mode, bool h16) -> int {
+            SVA_TRY(planes(l, mode));
+            return h16 ? frag_h(l) : 0;
+        };
+        auto front = [&](EncFront& F, int mode, bool h16 = false) -> int {
             if (!F.loaded) return 0;
-            SVA_TRY(planes(F.stem, mode));
+            SVA_TRY(enc_lin(F.stem, mode, h16));
             for (int i = 0; i < 4; ++i) {
-                SVA_TRY(planes(F.trans[i], mode));
-                for (auto& cx : F.stages[i]) { SVA_TRY(planes(cx.pw1, mode)); SVA_TRY(planes(cx.pw2, mode)); }
+                SVA_TRY(enc_lin(F.trans[i], mode, h16));
+                for (auto& cx : F.stages[i]) { SVA_TRY(enc_lin(cx.pw1, mode, h16)); SVA_TRY(enc_lin(cx.pw2, mode, h16)); }
             }
-            for (int i = 0; i < 2; ++i) { SVA_TRY(planes(F.ds_conv[i], mode)); SVA_TRY(planes(F.ds_cnx[i].pw1, mode)); SVA_TRY(planes(F.ds_cnx[i].pw2, mode)); }
+            for (int i = 0; i < 2; ++i) { SVA_TRY(enc_lin(F.ds_conv[i], mode, h16)); SVA_TRY(enc_lin(F.ds_cnx[i].pw1, mode, h16)); SVA_TRY(enc_lin(F.ds_cnx[i].pw2, mode, h16)); }
             return 0;
         };
         // (narrow levels: K = k * C padded with zero columns to whole 32-k blocks)
@@ -513,9 +535,12 @@ extern "C" int sva_engine_finalize(sva_engine* e) {
             (void)hipFree(tmp);
             return rc;
         };
-        SVA_TRY(front(e->tokf, enc_mode));
+        SVA_TRY(front(e->tokf, tok_mode, c.enc_dtype == 1));
         SVA_TRY(front(e->vocf, enc_mode));           // firefly.encode of the prompt produces FSQ indices: encoder grade
-        for (auto& L : e->tr) { SVA_TRY(planes(L.wqkv, enc_mode)); SVA_TRY(planes(L.wo, enc_mode)); SVA_TRY(planes(L.w13, enc_mode)); SVA_TRY(planes(L.w2, enc_mode)); }
+        for (auto& L : e->tr) {
+            const bool h16 = c.enc_dtype == 1;
+            SVA_TRY(enc_lin(L.wqkv, tok_mode, h16)); SVA_TRY(enc_lin(L.wo, tok_mode, h16)); SVA_TRY(enc_lin(L.w13, tok_mode, h16)); SVA_TRY(enc_lin(L.w2, tok_mode, h16));
+        }
         for (int i = 0; i < 2; ++i) { SVA_TRY(planes(e->up_conv[i], voc_mode)); SVA_TRY(planes(e->up_cnx[i].pw1, voc_mode)); SVA_TRY(planes(e->up_cnx[i].pw2, voc_mode)); }
         SVA_TRY(planes(e->conv_pre, voc_mode));
         for (int i = 0; i < 5; ++i) {

@@ -16,7 +16,7 @@ int gemm_call(sva_batch* b, const float* A, long a_bstride, long a_off, int lda,
     ConvGemm g = proto;
     g.A = A; g.a_bstride = a_bstride; g.a_off = a_off; g.lda = lda;
     g.T = T; g.M = nb * T; g.stride = stride; g.dil = dil; g.taps = taps; g.Cin = Cin;
-    g.W = w.W; g.Wk = w.Wk; g.Wh = w.Wh; g.N = w.N; g.bias = w.b;
+    g.W = w.W; g.Wk = w.Wk; g.Wh = w.Wh; g.Wkh = w.Wkh; g.N = w.N; g.bias = w.b;
     g.Wp = w.Wp; g.wp_pstride = (long)w.N * w.K; g.wp_inv = w.wp_inv; g.pmode = w.pmode; g.ovf = b->d_mm_ovf;
     g.cu_limit = b->enc_cus;        // (the encoder / vocoder streams' CU mask when the batch runs its AR chain on a partition of its own)
     g.C = C; g.c_bstride = c_bstride; g.c_off = c_off; g.ldc = ldc;
@@ -194,7 +194,7 @@ int cnx_block_t(sva_batch* b, const CNX& c, Act& x, int T, float* h1, long h1_bs
         p1.Cp = reinterpret_cast<unsigned short*>(h2); p1.cp_pstride = h2_bs * b->B; p1.cp_rows = rows;
         p2.Ap = p1.Cp; p2.ap_pstride = p1.cp_pstride; p2.ap_rows = rows;
     }
-    if (b->B * T <= 16 && C <= 512) {
+    if (b->B * T <= 16 && C <= 512 && !c.pw1.Wkh) {        // (enc_dtype = 1: the GEMM's A operand is fp16 of the STORED LayerNorm output -- no fused prologue)
         // a handful of rows (streaming pass, upsampler at small B): depthwise conv + LayerNorm happen in the prologue of the
         // pointwise GEMM (every column block recomputes them -- a few thousand FMAs -- instead of a launch of their own)
         p1.dw_wT = c.dwT; p1.dw_b = c.dwb; p1.ln_w = c.lnw; p1.ln_b = c.lnb; p1.ln_eps = 1e-6f;
@@ -452,7 +452,8 @@ int enc_transformer(sva_batch* b, const Act& xin, int need_rows, int part) {
         const int Tr = tail ? need_rows : T2;             // rows of this layer's output that are needed
         const int r0 = T2 - Tr;
         // RMSNorm folded into the projection when the small-M kernel runs it (few streams); a separate pass otherwise
-        if (conv_gemm_can_fuse_rms(B * T2, 3 * D)) {
+        // (enc_dtype = 1: never folded -- the fp16 operand is the normalised row itself, fp16(RMSNorm(x) w), not x w rounded ahead of the row statistic)
+        if (conv_gemm_can_fuse_rms(B * T2, 3 * D) && !L.wqkv.Wkh) {
             ConvGemm pn;
             pn.rms_w = L.attn_norm; pn.rms_eps = 1e-5f;
             SVA_TRY(gemm_call(b, xr, xr_bs, xr_off, D, B, T2, 1, 1, 1, D, L.wqkv, b->tr_qkv, (long)T2 * 3 * D, 0, 3 * D, pn));
@@ -486,7 +487,7 @@ int enc_transformer(sva_batch* b, const Act& xin, int need_rows, int part) {
             pg.Cp = reinterpret_cast<unsigned short*>(b->tr_g); pg.cp_pstride = (long)B * T2 * I; pg.cp_rows = (long)B * T2;
             pd.Ap = pg.Cp; pd.ap_pstride = pg.cp_pstride; pd.ap_rows = pg.cp_rows;
         }
-        if (conv_gemm_can_fuse_rms(B * Tr, 2 * I)) {
+        if (conv_gemm_can_fuse_rms(B * Tr, 2 * I) && !L.w13.Wkh) {
             pg.rms_w = L.ffn_norm; pg.rms_eps = 1e-5f;
             SVA_TRY(gemm_call(b, xw, xw_bs, (long)r0 * D, D, B, Tr, 1, 1, 1, D, L.w13, b->tr_g, (long)T2 * I, (long)r0 * I, I, pg));
         } else {

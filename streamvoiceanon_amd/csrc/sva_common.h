@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <atomic>
 #include <string>
+#include <vector>
 
 namespace sva {
 
@@ -107,6 +108,8 @@ struct ConvGemm {
     const float* W = nullptr;   // [N][taps*Cin], K contiguous
     const float* Wk = nullptr;  // optional fragment-major packing of W ([N / 16][K / 16][64 lanes][4]: gemm_stream.hip reads one contiguous KiB per wave-instruction)
     const void* Wh = nullptr;   // optional fp16 copy of W (ar_dtype = 1 AR layers): decode-sized problems stream it instead (gemm_f16w.hip)
+    const void* Wkh = nullptr;  // optional fp16 fragment-major packing of W ([N / 16][K / 32][64 lanes][8 halves]; the encoder's layers of an enc_dtype = 1 engine):
+                                //   the problem then runs on fp16 operands ONLY -- gemm_stream_h.hip, or the planes kernel in H1 -- never on an fp32 kind
     int N = 0;
     const float* bias = nullptr;    // [N]
     const float* gamma = nullptr;   // [N]  (ConvNeXt gamma / LayerScale)
@@ -246,8 +249,14 @@ int launch_f16w_gemm(const ConvGemm& g, hipStream_t st);
 // bit 1 = Wsrc is the fragment-major packing of g.W ([N / 16][K / 16][64][4]); probe != 0: timing diagnostics
 bool stream_gemm_supported(const ConvGemm& g);
 int launch_stream_gemm(const ConvGemm& g, const float* Wsrc, int mt, int nt, int kw, int wmode, int probe, hipStream_t st);
+// gemm_stream_h.hip: its fp16-operand sibling (v_mfma_f32_16x16x32_f16 on g.Wkh, activations converted in registers, round to nearest even); the
+// encoder's GEMMs below the planes kernel's scale when sva_config.enc_dtype = 1.  mt = 0: (mt, nt, kw) from stream_h_config
+bool stream_h_gemm_supported(const ConvGemm& g);
+void stream_h_config(const ConvGemm& g, int* mt, int* nt, int* kw);
+int launch_stream_h_gemm(const ConvGemm& g, int mt, int nt, int kw, hipStream_t st);
+void stream_h_pack_weights(const float* W, int N, int K, std::vector<uint16_t>& out);
 int launch_conv_gemm(const ConvGemm& g, hipStream_t st);
-int conv_gemm_last_kind();          // kernel family the calling thread's latest launch_conv_gemm[_group] picked: 0 small-M, 1 tiled, 2 pipelined, 6 weight-streaming (f32 MFMA), 4 split-bf16, 5 fp16 weights (f16 MFMA), 7 / 8 planes H3 / H1, 9 / 10 their LDS-DMA form
+int conv_gemm_last_kind();          // kernel family the calling thread's latest launch_conv_gemm[_group] picked: 0 small-M, 1 tiled, 2 pipelined, 6 weight-streaming (f32 MFMA), 4 split-bf16, 5 fp16 weights (f16 MFMA), 7 / 8 planes H3 / H1, 9 / 10 their LDS-DMA form, 11 fp16-operand weight-streaming (gemm_stream_h.hip)
 int launch_conv_gemm_group(const ConvGemm* gs, int n, hipStream_t st);
 // true when launch_conv_gemm would route this (M, N) problem to the K-split small-M kernel, which can normalise its A rows
 bool conv_gemm_can_fuse_rms(int M, int N);

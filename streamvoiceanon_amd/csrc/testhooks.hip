@@ -558,6 +558,108 @@ extern "C" int sva_test_gemm_planes(int device, int M, int N, int K, const float
     return 0;
 }
 
+// The fp16-operand weight-streaming conv-GEMM (gemm_stream_h.hip) through its production launcher: the caller's tile configuration (mt = 0:
+// the heuristic's), weights packed as sva_engine_finalize packs them.  Host arrays, all dense: A [B][(T - 1) stride + (taps - 1) dil + 1][Cin],
+// W [N][taps * Cin], bias [N] or null, gamma [N] and res [B][T][N] (mode bit 2), C [B][T][N or N / 2] -- uploaded first, so what the caller
+// pre-filled survives where the kernel stores nothing.  mode bits: 1 = GELU, 2 = gamma + residual, 4 = rows t in [T / 4, T / 2) of every item are
+// computed but not stored (skip_lo / skip_hi), 8 = SwiGLU over 16-row interleaved (gate, up) weights, 16 = on the device the items sit at padded
+// strides behind non-zero offsets (the padding is checked to come back untouched), 32 = range check (a non-finite output fails the call).
+// Every index the launch will touch is checked against the device arrays' lengths before the launch.  iters > 0 also times it.
+extern "C" int sva_test_gemm_h16(int device, int B, int T, int N, int Cin, int taps, int dil, int stride, const float* A, const float* W,
+                                 const float* bias, const float* gamma, const float* res, int mode, int mt, int nt, int kw, float* C, int iters,
+                                 float* out_us) {
+    SVA_HIP(hipSetDevice(device));
+    SVA_CHECK(B >= 1 && T >= 1 && N >= 1 && Cin >= 32 && Cin % 32 == 0 && taps >= 1 && dil >= 1 && stride >= 1 && A && W && C, "test_gemm_h16: bad arguments");
+    SVA_CHECK(!(mode & 2) || (gamma && res), "test_gemm_h16: mode bit 2 needs gamma and res");
+    SVA_CHECK(!(mode & 8) || (N % 32 == 0 && !(mode & 3) && !bias), "test_gemm_h16: SwiGLU takes N % 32 == 0 and no other epilogue");
+    const long K = (long)taps * Cin, rows_in = (long)(T - 1) * stride + (long)(taps - 1) * dil + 1;
+    const int Nout = (mode & 8) ? N / 2 : N;
+    const bool pad = (mode & 16) != 0;
+    const long a_bs = rows_in * Cin + (pad ? 8 : 0), a_off = pad ? 4 : 0;
+    const long c_bs = (long)T * Nout + (pad ? 5 : 0), c_off = pad ? 3 : 0;
+    const long r_bs = (long)T * N + (pad ? 7 : 0), r_off = pad ? 1 : 0;
+    const size_t lenA = (size_t)B * a_bs + a_off, lenC = (size_t)B * c_bs + c_off, lenR = (size_t)B * r_bs + r_off;
+    const float marker = -12345.f;
+    std::vector<float> hA(lenA, 0.f), hC(lenC, marker), hR;
+    for (int b = 0; b < B; ++b) {
+        memcpy(&hA[(size_t)b * a_bs + a_off], A + (size_t)b * rows_in * Cin, sizeof(float) * rows_in * Cin);
+        memcpy(&hC[(size_t)b * c_bs + c_off], C + (size_t)b * T * Nout, sizeof(float) * (size_t)T * Nout);
+    }
+    std::vector<uint16_t> hW;
+    stream_h_pack_weights(W, N, (int)K, hW);
+    DevBuf dA, dW, dB, dG, dR, dC;
+    SVA_TRY(dA.put(hA.data(), sizeof(float) * lenA));
+    SVA_TRY(dW.put(hW.data(), 2 * hW.size()));
+    SVA_TRY(dC.put(hC.data(), sizeof(float) * lenC));
+    if (bias) SVA_TRY(dB.put(bias, sizeof(float) * N));
+    ConvGemm g;
+    g.A = dA.as<float>(); g.a_bstride = a_bs; g.a_off = a_off; g.lda = Cin; g.T = T; g.M = B * T; g.stride = stride; g.dil = dil; g.taps = taps; g.Cin = Cin;
+    g.Wkh = dW.p; g.N = N; g.bias = bias ? dB.as<float>() : nullptr;
+    g.C = dC.as<float>(); g.c_bstride = c_bs; g.c_off = c_off; g.ldc = Nout;
+    if (mode & 1) g.act = ACT_GELU;
+    if (mode & 2) {
+        hR.assign(lenR, 0.f);
+        for (int b = 0; b < B; ++b) memcpy(&hR[(size_t)b * r_bs + r_off], res + (size_t)b * T * N, sizeof(float) * (size_t)T * N);
+        SVA_TRY(dG.put(gamma, sizeof(float) * N));
+        SVA_TRY(dR.put(hR.data(), sizeof(float) * lenR));
+        g.gamma = dG.as<float>(); g.res = dR.as<float>(); g.r_bstride = r_bs; g.r_off = r_off; g.ldr = N;
+    }
+    if (mode & 4) { g.skip_lo = T / 4; g.skip_hi = T / 2; }
+    if (mode & 8) g.w13 = 1;
+    // the largest index of every array the launch touches
+    SVA_CHECK((size_t)((long)(B - 1) * g.a_bstride + g.a_off + ((long)(T - 1) * stride + (long)(taps - 1) * dil) * g.lda + Cin - 1) < lenA, "test_gemm_h16: A index out of range");
+    SVA_CHECK((size_t)((long)(B - 1) * g.c_bstride + g.c_off + (long)(T - 1) * g.ldc + Nout - 1) < lenC, "test_gemm_h16: C index out of range");
+    SVA_CHECK(!g.res || (size_t)((long)(B - 1) * g.r_bstride + g.r_off + (long)(T - 1) * g.ldr + N - 1) < lenR, "test_gemm_h16: res index out of range");
+    SVA_CHECK((size_t)((N + 15) / 16) * (K / 32) * 512 == hW.size(), "test_gemm_h16: weight packing size");
+    SVA_CHECK(stream_h_gemm_supported(g), "test_gemm_h16: unsupported problem");
+    if (mt == 0) stream_h_config(g, &mt, &nt, &kw);
+    SVA_CHECK((mt == 1 || mt == 2 || mt == 4) && (nt == 1 || nt == 2) && (kw == 4 || kw == 8 || (kw == 16 && mt * nt <= 2)) && !(g.w13 && nt != 2),
+              "test_gemm_h16: bad tile configuration");
+    int* h_ovf = nullptr;
+    if (mode & 32) {
+        SVA_HIP(hipHostMalloc((void**)&h_ovf, sizeof(int), hipHostMallocMapped));
+        *h_ovf = 0;
+        SVA_HIP(hipHostGetDevicePointer((void**)&g.ovf, h_ovf, 0));
+    }
+    int rc = launch_stream_h_gemm(g, mt, nt, kw, 0);
+    if (!rc && hipGetLastError() != hipSuccess) { set_error("test_gemm_h16: launch failed"); rc = -2; }
+    const hipError_t se = hipDeviceSynchronize();
+    if (h_ovf) {
+        const int o = *reinterpret_cast<volatile int*>(h_ovf);
+        (void)hipHostFree(h_ovf);
+        g.ovf = nullptr;
+        if (!rc && se == hipSuccess && o) {
+            set_error("fp16-operand GEMM: non-finite output (an operand outside the fp16 range); sva_config.enc_dtype = 0 keeps the encoder on the fp32-grade kernels");
+            return -3;
+        }
+    }
+    if (rc) return rc;
+    SVA_HIP(se);
+    SVA_TRY(dC.get(hC.data(), sizeof(float) * lenC));
+    for (int b = 0; b < B; ++b) memcpy(C + (size_t)b * T * Nout, &hC[(size_t)b * c_bs + c_off], sizeof(float) * (size_t)T * Nout);
+    if (pad) {
+        bool clean = true;
+        for (long i = 0; i < c_off; ++i) clean = clean && hC[i] == marker;
+        for (int b = 0; b < B; ++b)
+            for (long i = (long)T * Nout; i < c_bs; ++i) clean = clean && hC[(size_t)b * c_bs + c_off + i] == marker;
+        SVA_CHECK(clean, "test_gemm_h16: the kernel stored between the items");
+    }
+    if (iters > 0 && out_us) {
+        hipEvent_t e0, e1;
+        SVA_HIP(hipEventCreate(&e0));
+        SVA_HIP(hipEventCreate(&e1));
+        SVA_HIP(hipEventRecord(e0, 0));
+        for (int i = 0; i < iters; ++i) SVA_TRY(launch_stream_h_gemm(g, mt, nt, kw, 0));
+        SVA_HIP(hipEventRecord(e1, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        float ms = 0;
+        SVA_HIP(hipEventElapsedTime(&ms, e0, e1));
+        out_us[0] = ms * 1e3f / iters;
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------
 // Per-kernel hooks of the non-GEMM launchers (tests/test_gpu_kernels.py): each uploads the caller's arrays, calls the launcher the engine
 // calls with the caller's arguments, synchronises and downloads.  Output arrays are uploaded first, so whatever the caller pre-filled them

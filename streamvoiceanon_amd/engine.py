@@ -31,7 +31,7 @@ class SvaConfig(C.Structure):
         ("ar_dim", C.c_int), ("ar_heads", C.c_int), ("ar_layers", C.c_int), ("ar_fast_layers", C.c_int), ("ar_inter", C.c_int),
         ("ar_vocab", C.c_int), ("codebook_size", C.c_int), ("num_codebooks", C.c_int), ("max_delay", C.c_int),
         ("max_seq_len", C.c_int), ("timbre_dim", C.c_int), ("timbre_tokens", C.c_int), ("style_dim", C.c_int),
-        ("voc_dim", C.c_int), ("ar_dtype", C.c_int), ("mm_mode", C.c_int), ("voc_dtype", C.c_int),
+        ("voc_dim", C.c_int), ("ar_dtype", C.c_int), ("mm_mode", C.c_int), ("voc_dtype", C.c_int), ("enc_dtype", C.c_int),
     ]
 
 
@@ -117,6 +117,7 @@ def load_library():
     lib.sva_test_conv_post.argtypes = [i32] * 5 + [vp, i64, i64, i64, vp, vp, vp, i64, i64, i64]
     lib.sva_test_gemm_f16w.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp]
     lib.sva_test_gemm_planes.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.sva_test_gemm_h16.argtypes = [i32] * 8 + [vp] * 5 + [i32] * 4 + [vp, i32, vp]
     lib.sva_host_launch_cost.argtypes = [i32, i32, f32p]
     lib.sva_test_sampler.argtypes = [i32, i32, i32, i32, vp, vp, C.c_float, C.c_float, vp, i32, f32p]
     _lib = lib
@@ -131,7 +132,7 @@ EXPORTED_SYMBOLS = [
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
     "sva_op_geglu", "sva_op_l2norm", "sva_ops_capture_begin", "sva_ops_capture_end", "sva_ops_graph_launch", "sva_ops_graph_free",
-    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
+    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
 ]
 
 
@@ -205,9 +206,10 @@ class Engine:
     """Weights on one MI355X.  `weights`: dict name -> array-like (numpy / torch CPU tensor) keyed by the
     reference state-dict names prefixed with 'arvc.' / 'tok.' / 'voc.'."""
 
-    def __init__(self, weights: dict, device: int = 0, ar_dtype: int = 0, mm_mode: int = None, voc_dtype: int = None):
+    def __init__(self, weights: dict, device: int = 0, ar_dtype: int = 0, mm_mode: int = None, voc_dtype: int = None, enc_dtype: int = None):
         """mm_mode / voc_dtype: sva_config fields of the same names (None = the library's default): precision format of the batch-scale
-        encoder / vocoder GEMMs (csrc/gemm_planes.hip) and the reference-precision (fp16 operand) vocoder."""
+        encoder / vocoder GEMMs (csrc/gemm_planes.hip) and the reference-precision (fp16 operand) vocoder.  enc_dtype = 1: the tokenizer's
+        content encoder on fp16 operands with fp32 accumulation (include/sva.h; content codes are no longer bit-equal to the fp32 oracle)."""
         self.lib = load_library()
         self.cfg = SvaConfig()
         _check(self.lib.sva_config_default(C.byref(self.cfg)), "sva_config_default")
@@ -216,6 +218,8 @@ class Engine:
             self.cfg.mm_mode = mm_mode
         if voc_dtype is not None:
             self.cfg.voc_dtype = voc_dtype
+        if enc_dtype is not None:
+            self.cfg.enc_dtype = enc_dtype
         self.h = C.c_void_p()
         _check(self.lib.sva_engine_create(C.byref(self.cfg), device, C.byref(self.h)), "sva_engine_create")
         self.device = device
@@ -530,6 +534,31 @@ def test_gemm_planes(A, W, bias=None, mode=1, variant=0, a_planes=False, c_plane
     _check(lib.sva_test_gemm_planes(device, M, N, K, _ptr(A), _ptr(W), _ptr(b), _ptr(out), int(mode), int(variant), flags, int(iters), _ptr(us)),
            "sva_test_gemm_planes")
     return out, float(us[0])
+
+
+def test_gemm_h16(A, W, B, T, taps=1, dil=1, stride=1, bias=None, gamma=None, res=None, gelu=False, swiglu=False, skip_rows=False, padded=False,
+                  range_check=False, config=(0, 0, 0), out=None, iters=0, device=0):
+    """The fp16-operand weight-streaming conv-GEMM (csrc/gemm_stream_h.hip) through its production launcher.  A [B, (T - 1) stride +
+    (taps - 1) dil + 1, Cin], W [N, taps * Cin] fp32 (rounded to fp16 by the kernel / the packing); config = (mt, nt, kw), (0, 0, 0) = the
+    heuristic's; `out` [B, T, N or N / 2] is uploaded first (skip_rows: rows [T / 4, T / 2) of every item keep it).  -> (C, us per launch)."""
+    lib = load_library()
+    A = np.ascontiguousarray(A, dtype=np.float32)
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    Cin = A.shape[-1]
+    N = W.shape[0]
+    assert A.shape == (B, (T - 1) * stride + (taps - 1) * dil + 1, Cin) and W.shape == (N, taps * Cin)
+    Nout = N // 2 if swiglu else N
+    b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32).reshape(N)
+    gm = None if gamma is None else np.ascontiguousarray(gamma, dtype=np.float32).reshape(N)
+    r = None if res is None else np.ascontiguousarray(res, dtype=np.float32).reshape(B, T, N)
+    assert (gm is None) == (r is None)
+    Cout = np.zeros((B, T, Nout), dtype=np.float32) if out is None else np.ascontiguousarray(out, dtype=np.float32).reshape(B, T, Nout).copy()
+    us = np.zeros(1, dtype=np.float32)
+    mode = ((1 if gelu else 0) | (2 if gm is not None else 0) | (4 if skip_rows else 0) | (8 if swiglu else 0) | (16 if padded else 0) |
+            (32 if range_check else 0))
+    _check(lib.sva_test_gemm_h16(device, B, T, N, Cin, taps, dil, stride, _ptr(A), _ptr(W), _ptr(b), _ptr(gm), _ptr(r), mode, int(config[0]),
+                                 int(config[1]), int(config[2]), _ptr(Cout), int(iters), _ptr(us)), "sva_test_gemm_h16")
+    return Cout, float(us[0])
 
 
 def test_prefill_attention(q, keys, vals, pos0=0, S=2048, half_kv=False, iters=0, device=0):

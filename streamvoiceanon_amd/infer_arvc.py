@@ -134,15 +134,17 @@ class InferenceWrapper:
     MEL_BINS = 80
 
     def __init__(self, config_path=None, checkpoint_path=None, compile_encoder=False, compile_decoder=False, compile_ar=False,
-                 fp16=False, weights: dict | None = None, device: int = 0):
+                 fp16=False, weights: dict | None = None, device: int = 0, enc_dtype: int = 0):
         """Same signature as the reference (:33) plus ``weights``: a dict of state-dict tensors keyed
-        'arvc.*' / 'tok.*' / 'voc.*' (real checkpoints are loaded with load_checkpoints())."""
+        'arvc.*' / 'tok.*' / 'voc.*' (real checkpoints are loaded with load_checkpoints()) and ``enc_dtype``: 1 runs the content encoder's
+        GEMMs on fp16 operands with fp32 accumulation, as the reference does under its torch.autocast(fp16) (:493) -- sva_config.enc_dtype;
+        content codes are then no longer bit-equal to the fp32 oracle's."""
         if weights is None:
             weights = self.load_checkpoints(config_path, checkpoint_path)
         self.sr = 44100
         self.device = f"cuda:{device}"
         # fp16: the reference's `self.model.half()` (:62-63) -> fp16 AR weights + fp16 KV cache (sva_config.ar_dtype = 1)
-        self.engine = E.Engine(weights, device=device, ar_dtype=1 if fp16 else 0)
+        self.engine = E.Engine(weights, device=device, ar_dtype=1 if fp16 else 0, enc_dtype=enc_dtype)
         self.use_graph = bool(compile_ar or compile_decoder or compile_encoder)   # the reference's --compile
         self.batch = None
         self._win_batch = None            # (Wp, Batch) of the last whole-utterance encode: see _window_batch
@@ -511,11 +513,12 @@ def main(argv=None, weights=None, style_vectors=None, timbre_latents=None):
     parser.add_argument("--max_seq_frames", type=int, default=768, help="Maximum sequence length in frames")
     parser.add_argument("--buffer_frames", type=int, default=32, help="Buffer frames when refilling prompt")
     parser.add_argument("--decode_chunk_frames", type=int, default=1, help="Decode chunk size in frames")
+    parser.add_argument("--enc-fp16", action="store_true", help="content encoder GEMMs on fp16 operands, fp32 accumulate (sva_config.enc_dtype = 1; not in the reference's command line)")
     args = parser.parse_args(argv)
     infer_wrapper = InferenceWrapper(
         args.config_path, args.checkpoint_path, compile_ar=args.compile,
         compile_decoder=args.compile if args.simulate_streaming else False,
-        compile_encoder=args.compile if args.simulate_streaming else False, weights=weights)
+        compile_encoder=args.compile if args.simulate_streaming else False, weights=weights, enc_dtype=1 if args.enc_fp16 else 0)
     ref_path = args.ref_path if isinstance(args.ref_path, list) and len(args.ref_path) > 1 else args.ref_path[0] if isinstance(args.ref_path, list) else args.ref_path
     Path(args.out_dir).mkdir(parents=True, exist_ok=True)
     extra = {k: v for k, v in (("style_vectors", style_vectors), ("timbre_latents", timbre_latents)) if v is not None}

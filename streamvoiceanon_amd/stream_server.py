@@ -156,8 +156,9 @@ def main(argv=None):
     ap.add_argument("--host", type=str, default="127.0.0.1")
     ap.add_argument("--port", type=int, default=5577)
     ap.add_argument("--fp16", action="store_true", help="fp16 AR weights + KV cache (the reference's InferenceWrapper(fp16=True))")
+    ap.add_argument("--enc-fp16", action="store_true", help="content encoder GEMMs on fp16 operands, fp32 accumulate (sva_config.enc_dtype = 1)")
     args = ap.parse_args(argv)
-    model_set = InferenceWrapper(args.config_path, args.checkpoint_path, fp16=args.fp16)
+    model_set = InferenceWrapper(args.config_path, args.checkpoint_path, fp16=args.fp16, enc_dtype=1 if args.enc_fp16 else 0)
     print(f"listening on {args.host}:{args.port}", flush=True)
     serve(model_set, args.host, args.port)
 
