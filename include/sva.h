@@ -164,6 +164,26 @@ int sva_vocoder_head(sva_batch* b, const float* z, int T, float* pcm_out);
 int sva_vocode_stream(sva_batch* b, const int32_t* codes, int T, float* pcm_out);
 int sva_vocode_reset(sva_batch* b);
 
+/* ---- single streams inside a running batch ---------------------------------------------------------------------------------
+ * Replace the stream in `slot` of a begun batch by a new utterance.  Same operands as sva_prefill_prompt.  From the next step on the slot
+ * behaves exactly like a slot of a fresh batch after sva_prefill_prompt + sva_streams_begin: zero audio window, silence-steady encoder
+ * state, ceil(delay / chunk) steps of zero output while its own delay fills, then decoding from frame 0 with noise keyed by noise_seed.
+ * Every other slot is unaffected: all its later outputs are bit-identical to a run without the call.  Drains the batch's streams.
+ * The step in which the slot's delay fills also prefills its prompt and primes its vocoder with the prompt's tail (a whole-batch vocoder
+ * run of decode_window_frames - 1 frames): that step stalls every stream of the batch ("Restarting single streams").
+ * Fails, changing nothing, before sva_streams_begin, for a slot out of range, for R <= delay (or a prompt that does not fit the KV cache /
+ * is shorter than the vocoder's 16-frame receptive field), and in the configurations that cannot fill one slot's encoder state:
+ *   - encode_window_frames <= 40 + chunk_frames: the batch runs the full-window encoder, which keeps no cached silence state;
+ *   - a batch whose persistent AR decode kernel has timed out (sva_streams_begin restarts all its streams). */
+int sva_stream_restart(sva_batch* b, int slot, const int64_t* ref_content_codes, const int32_t* ref_audio_codes, int R,
+                       const float* style, const float* timbre, uint64_t noise_seed);
+/* Idle a slot: its input is no longer read (it counts as zeros, so the caller may leave anything there, NaN included), its output is zeros,
+ * and it never raises an error of its own (re-prefill, range flag).  Only sva_stream_restart brings it back.  Fails before
+ * sva_streams_begin and for a slot out of range.  Drains the batch's streams. */
+int sva_stream_retire(sva_batch* b, int slot);
+/* phase: 0 retired, 1 delay filling, 2 decoding; frames = frames decoded since the slot's stream began (0 unless decoding) */
+int sva_stream_state(sva_batch* b, int slot, int* phase, long* frames);
+
 /* AR seams with caller-supplied content codes (chunk_frames == 1):
  *   ARVCWrapper.prefill_src_condition4delay (modules/arvc_wrapper.py:114-119): codes int64[B][delay]
  *   ARVCWrapper.decode_one (:121-126 -> dual_ar_stream.py:817-837): code int64[B] -> codes_out int32[B][8],

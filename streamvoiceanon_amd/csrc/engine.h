@@ -320,11 +320,32 @@ struct sva_batch {
 
     // host mirrors of the deterministic per-slot state
     std::vector<int> h_last_pos, h_nframes;
-    int h_ncontent = 0;                    // content codes seen (lock step)
+    std::vector<int> h_ncontent;           // [B] content codes seen (a restarted slot counts from its own start)
     int h_step = 0;
     bool delay_filled = false;
     bool begun = false;
     std::vector<char> prefilled;
+    // ---- per-slot stream phases (sva_stream_restart / sva_stream_retire) ----
+    // 0 retired, 1 delay filling, 2 decoding.  The slots begun together by sva_streams_begin move 1 -> 2 in lock step (delay_filled above);
+    // a restarted slot carries its new prompt in `pending` while its own delay fills and is activated -- prefill, delay fill, vocoder
+    // priming, in the order a fresh stream sees them -- at the end of the step in which its content count reaches the delay.
+    struct PendingPrompt {
+        std::vector<int64_t> cc;
+        std::vector<int32_t> ac;
+        std::vector<float> style, timbre;
+        int R = 0;
+        unsigned long long seed = 0;
+    };
+    std::vector<char> h_phase;             // [B]
+    std::vector<char> restarted;           // [B] 1: `pending` holds the prompt of a restart that has not been activated yet
+    std::vector<PendingPrompt> pending;    // [B]
+    int* d_slot_flag = nullptr;            // [B] kSlotInputMuted | kSlotOutputMuted (kernels.h), read by the ring write and by conv_post
+    std::vector<int> h_slot_flag;          // its host mirror
+    // one-slot vocoder priming: the history rows of every ShiftDesc of the vocoder, saved around a whole-batch priming run
+    float* voc_save = nullptr;             // [B][voc_save_bstride]
+    long voc_save_bstride = 0;
+    long* d_voc_save_offs = nullptr;       // [shift_host.size()] offset of each desc's rows inside a slot's block
+    float* prime_pcm = nullptr;            // [B][2048 * chunk] PCM sink of the priming run (the step's own PCM stays where it is)
 
     // ---- vocoder workspace ----
     int Tv = 0;                            // max code frames per call

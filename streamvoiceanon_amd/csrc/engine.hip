@@ -309,6 +309,7 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
     SVA_TRY(dev_alloc(A, &b->d_ncontent, B));
     SVA_TRY(dev_alloc(A, &b->d_seed, B));
     SVA_TRY(dev_alloc(A, &b->d_use_forced, 1));
+    SVA_TRY(dev_alloc(A, &b->d_slot_flag, B));
     // encoder
     b->We = p->encode_window_frames;
     b->N = b->We * 2048;
@@ -540,6 +541,7 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
     SVA_TRY(dev_alloc(A, &b->d_prompt_ac, (size_t)ncb * b->Pmax));
     b->ref_content.resize(B); b->ref_audio.resize(B); b->ref_len.assign(B, 0);
     b->h_last_pos.assign(B, -1); b->h_nframes.assign(B, 0); b->prefilled.assign(B, 0);
+    b->h_ncontent.assign(B, 0); b->h_phase.assign(B, 1); b->restarted.assign(B, 0); b->pending.resize(B); b->h_slot_flag.assign(B, 0);
     // vocoder
     const int Tv = b->Tv = b->p.voc_max_frames;
     const int V = c.voc_dim;
@@ -708,13 +710,9 @@ int stage_prompt(sva_batch* b, const std::vector<int64_t>& cc, const std::vector
 }
 }  // namespace
 
-extern "C" int sva_prefill_prompt(sva_batch* b, int slot, const int64_t* ref_content_codes, const int32_t* ref_audio_codes, int R,
-                                  const float* style, const float* timbre, uint64_t noise_seed) {
-    SVA_CHECK(b && slot >= 0 && slot < b->B && ref_content_codes && ref_audio_codes && style && timbre, "bad argument");
-    SVA_HIP(hipSetDevice(b->e->device));
-    (void)hipGetLastError();
-    SVA_TRY(quiesce(b));
-    SVA_TRY(recover_ar_failure(b));
+// the prompt of one slot on a drained batch: speaker operands, noise key, KV prefill, the stored (truncated) prompt
+static int prefill_slot_impl(sva_batch* b, int slot, const int64_t* ref_content_codes, const int32_t* ref_audio_codes, int R, const float* style,
+                             const float* timbre, uint64_t noise_seed, bool tap_logits) {
     const sva_config& c = b->e->cfg;
     const int ncb = c.num_codebooks;
     std::vector<int64_t> cc(ref_content_codes, ref_content_codes + R);
@@ -725,7 +723,7 @@ extern "C" int sva_prefill_prompt(sva_batch* b, int slot, const int64_t* ref_con
     SVA_TRY(h2d(b, b->d_seed + slot, &sd, sizeof(sd)));
     // quirk (iv): the KV prefill uses the UNTRUNCATED prompt (infer_arvc.py:484-489) ...
     SVA_TRY(stage_prompt(b, cc, ac, R));
-    SVA_TRY(ar_prefill_slot(b, slot, R, true));
+    SVA_TRY(ar_prefill_slot(b, slot, R, tap_logits));
     // ... while the stored prompt (re-prefill, vocoder fill) is truncated to max_prompt_frames (:469-470)
     const int Rt = std::min(R, b->p.max_prompt_frames);
     b->ref_content[slot].assign(cc.begin(), cc.begin() + Rt);
@@ -743,6 +741,16 @@ extern "C" int sva_prefill_prompt(sva_batch* b, int slot, const int64_t* ref_con
     }
     b->prefilled[slot] = 1;
     return 0;
+}
+
+extern "C" int sva_prefill_prompt(sva_batch* b, int slot, const int64_t* ref_content_codes, const int32_t* ref_audio_codes, int R,
+                                  const float* style, const float* timbre, uint64_t noise_seed) {
+    SVA_CHECK(b && slot >= 0 && slot < b->B && ref_content_codes && ref_audio_codes && style && timbre, "bad argument");
+    SVA_HIP(hipSetDevice(b->e->device));
+    (void)hipGetLastError();
+    SVA_TRY(quiesce(b));
+    SVA_TRY(recover_ar_failure(b));
+    return prefill_slot_impl(b, slot, ref_content_codes, ref_audio_codes, R, style, timbre, noise_seed, true);
 }
 
 extern "C" int sva_vocode_reset(sva_batch* b) {
@@ -854,7 +862,12 @@ extern "C" int sva_streams_begin(sva_batch* b) {
     SVA_HIP(hipMemsetAsync(b->d_step, 0, sizeof(int), b->stream));
     SVA_HIP(hipMemsetAsync(b->d_nframes, 0, sizeof(int) * B, b->stream));
     SVA_HIP(hipMemsetAsync(b->d_ncontent, 0, sizeof(int) * B, b->stream));
-    b->h_step = 0; b->h_ncontent = 0; b->delay_filled = false;
+    b->h_step = 0; b->delay_filled = false;
+    std::fill(b->h_ncontent.begin(), b->h_ncontent.end(), 0);
+    std::fill(b->h_phase.begin(), b->h_phase.end(), 1);          // every slot starts in lock step: no restart pending, nothing muted
+    std::fill(b->restarted.begin(), b->restarted.end(), 0);
+    std::fill(b->h_slot_flag.begin(), b->h_slot_flag.end(), 0);
+    SVA_HIP(hipMemsetAsync(b->d_slot_flag, 0, sizeof(int) * B, b->stream));
     std::fill(b->h_nframes.begin(), b->h_nframes.end(), 0);
     if (b->enc_incremental) {
         // The reference's window starts as all-zero audio (:451): initialise the per-layer histories and the steady
@@ -963,10 +976,10 @@ int reprefill_slots(sva_batch* b, const std::vector<int>& due) {
         a.row_off[0] = 0;
         for (int i = 0; i < a.n; ++i) {
             const int slot = due[lo + i];
-            const int nf = b->h_nframes[slot], ncon = b->h_ncontent;
+            const int nf = b->h_nframes[slot], ncon = b->h_ncontent[slot];
             const int na = std::min(bf, nf);
             SVA_CHECK(na == std::max(0, (ncon - d) - std::max(0, ncon - bf - d)) && na >= d, "re-prefill: content/audio history length mismatch");
-            a.slot[i] = slot; a.Rt[i] = b->ref_len[slot]; a.nf[i] = nf; a.na[i] = na;
+            a.slot[i] = slot; a.Rt[i] = b->ref_len[slot]; a.nf[i] = nf; a.na[i] = na; a.ncon[i] = ncon;
             a.row_off[i + 1] = a.row_off[i] + 2 * na;
             // BEFORE anything is enqueued: rows past the slot's cache would land in the next slot's
             SVA_CHECK(nspk + 2 * (a.Rt[i] + na) + 2 * d <= c.max_seq_len, "re-prefill: prompt too long for the KV cache");
@@ -974,7 +987,7 @@ int reprefill_slots(sva_batch* b, const std::vector<int>& due) {
         const int M = a.row_off[a.n];
         SVA_CHECK(M <= b->Mmax, "re-prefill: more rows than the AR scratch holds");
         hipLaunchKernelGGL(build_reprefill_kernel, dim3(M), dim3(256), 0, st, a, e->content_emb, e->codebook_emb, b->d_content_hist, b->d_pred_hist,
-                           b->hist_cap, b->h_ncontent, b->d_ref_tail, c.max_delay, d, ncb, c.codebook_size, D, nspk, b->ax, b->d_slot, b->d_pos);
+                           b->hist_cap, b->d_ref_tail, c.max_delay, d, ncb, c.codebook_size, D, nspk, b->ax, b->d_slot, b->d_pos);
         SVA_TRY(ar_layers_pass(b, e->ar_layers, M, b->d_slot, b->d_pos, e->rope_ar, (float*)b->kv_slow, b->kv_slow_layer, b->kv_slow_slot,
                                c.max_seq_len, b->ax));
         hipLaunchKernelGGL(finish_reprefill_kernel, dim3(a.n * d), dim3(256), 0, st, a, e->codebook_emb, b->d_pred_hist, b->hist_cap, b->d_ref_tail,
@@ -991,7 +1004,7 @@ int reprefill_slot(sva_batch* b, int slot) {
     const sva_config& c = b->e->cfg;
     const int ncb = c.num_codebooks, d = b->p.delay, bf = b->p.buffer_frames;
     const int R = b->ref_len[slot];
-    const int nf = b->h_nframes[slot], ncon = b->h_ncontent;
+    const int nf = b->h_nframes[slot], ncon = b->h_ncontent[slot];
     const int na = std::min(bf, nf);                   // pred_codes[..., -bf:]
     const int c_hi = ncon - d, c_lo = std::max(0, ncon - bf - d);
     const int nc = std::max(0, c_hi - c_lo);
@@ -1030,7 +1043,7 @@ int steady_launches(sva_batch* b, bool timing_events) {
     const int B = b->B, chunk = b->p.chunk_frames, n = 2048 * chunk, ncb = c.num_codebooks;
     hipStream_t st = b->stream;
     if (timing_events) SVA_HIP(hipEventRecord(b->ev[0], st));
-    SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, st));
+    SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, st, b->d_slot_flag));
     SVA_TRY(b->enc_incremental ? encode_incremental(b, b->d_step, n, 1) : encode(b, b->d_step, n, 1));
     hipLaunchKernelGGL(append_content_kernel, dim3((B + 63) / 64), dim3(64), 0, st, b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap,
                        b->d_ncontent, b->d_step_content, B, b->d_step);
@@ -1136,7 +1149,7 @@ int steady_pipelined(sva_batch* b) {
                 if (b->pipe_evFeat[par]) SVA_HIP(hipStreamWaitEvent(se, b->pipe_evFeat[par], 0));
                 SVA_TRY(stage_graph(b, &b->gEm[par], se, [&]() -> int {
                     b->stream = se;
-                    SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se));
+                    SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se, b->d_slot_flag));
                     b->step_bump = b->d_step;              // the history shift that ends the chain also advances the chunk counter
                     const int frc = enc_frontend_merged(b, b->d_step, n, 1, 3, par);
                     b->step_bump = nullptr;
@@ -1159,7 +1172,7 @@ int steady_pipelined(sva_batch* b) {
             // shift): only they wait for transformer(n-1)'s first layer -- the front-end of step n itself starts at once
             SVA_TRY(stage_graph(b, &b->gE, se, [&]() -> int {
                 b->stream = se;
-                SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se));
+                SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se, b->d_slot_flag));
                 return enc_frontend_merged(b, b->d_step, n, 1, 1);
             }));
             if (b->pipe_evD2C) SVA_HIP(hipStreamWaitEvent(se, b->pipe_evD2C, 0));
@@ -1195,7 +1208,7 @@ int steady_pipelined(sva_batch* b) {
             if (stage_ev) SVA_HIP(hipEventRecord(b->ev[1], sx));
             SVA_TRY(mark(4, sx));
         } else {
-        SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se));
+        SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se, b->d_slot_flag));
         SVA_TRY(launch_shift_history(b->d_shift_d2c, 1, B, se, 16));                       // steady tokens slide down by c
         int erc = 0;
         if (b->stream_cut > 0) {          // the first stages of the streaming pass run on main (its chunk counter), the rest on sx
@@ -1243,7 +1256,7 @@ int steady_pipelined(sva_batch* b) {
         if (b->pipe_evR) { SVA_HIP(hipStreamWaitEvent(se, b->pipe_evR, 0)); b->pipe_evR = nullptr; }
         b->stream = se;
         if (stage_ev) SVA_HIP(hipEventRecord(b->ev[0], se));
-        SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se));
+        SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se, b->d_slot_flag));
         SVA_TRY(b->enc_incremental ? encode_incremental(b, b->d_step, n, 1) : encode(b, b->d_step, n, 1));
         hipLaunchKernelGGL(append_content_kernel, dim3((B + 63) / 64), dim3(64), 0, se, b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap,
                            b->d_ncontent, b->d_step_content, B, b->d_step);
@@ -1340,6 +1353,135 @@ int quiesce(sva_batch* b) {
     return 0;
 }
 
+// ---- per-slot restart (sva_stream_restart / sva_stream_retire) ----
+// A parked slot (retired, or filling its own delay) still rides through the AR launches and decodes throw-away frames.  Whenever it would
+// become due for a re-prefill, and when it is restarted, its position goes back to where its last stored prompt ends: every K / V row
+// up to there was written by that prompt's prefill, so the slot decodes on valid state and never runs past its cache.
+int parked_position(const sva_batch* b, int slot) { return b->e->cfg.timbre_tokens + 2 * b->ref_len[slot]; }
+
+// the slots that sva_streams_begin started together leave their delay phase together
+void lockstep_slots_decode(sva_batch* b) {
+    for (int i = 0; i < b->B; ++i)
+        if (b->h_phase[i] == 1 && !b->restarted[i]) b->h_phase[i] = 2;
+}
+
+int set_slot_flag(sva_batch* b, int slot, int flag) {
+    b->h_slot_flag[slot] = flag;
+    SVA_HIP(hipMemcpyAsync(b->d_slot_flag + slot, &b->h_slot_flag[slot], sizeof(int), hipMemcpyHostToDevice, b->stream));
+    SVA_HIP(hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+// The restarted slot's front-end as sva_streams_begin leaves every slot: an all-zero audio window (origin-free: the ring position stays
+// the batch's), every history row and every cached token at the network's steady response to silence, no content codes seen.
+int restart_encoder_state(sva_batch* b, int slot) {
+    sva_engine* e = b->e;
+    hipStream_t st = b->stream;
+    const auto it = e->silence.find(std::make_pair(b->B, b->p.chunk_frames));
+    SVA_CHECK(b->enc_incremental && b->enc_merged && it != e->silence.end(), "restart: no cached silence state for this encoder mode");
+    const sva_engine::SilenceState& ss = it->second;
+    EncMerged& M = b->em;
+    std::vector<ShiftDesc> sd(M.n_shift);
+    SVA_HIP(hipMemcpy(sd.data(), M.d_shift, sizeof(ShiftDesc) * M.n_shift, hipMemcpyDeviceToHost));
+    SVA_CHECK(ss.rows.size() == sd.size(), "restart: silence state does not match the encoder's history buffers");
+    SVA_HIP(hipMemsetAsync(b->ring + (long)slot * b->N, 0, sizeof(float) * (size_t)b->N, st));
+    for (size_t i = 0; i < sd.size(); ++i) {
+        const ShiftDesc& d = sd[i];
+        hipLaunchKernelGGL(fill_rows_kernel, dim3(d.H, 1), dim3(128), 0, st, d.ptr + (long)slot * d.bstride, d.bstride, d.C, ss.rows[i]);
+    }
+    hipLaunchKernelGGL(fill_rows_kernel, dim3(b->T2, 1), dim3(128), 0, st, b->d2c.p + (long)slot * b->d2c.bstride, b->d2c.bstride, e->cfg.tr_dim, ss.tok);
+    SVA_HIP(hipGetLastError());
+    SVA_HIP(hipMemsetAsync(b->d_ncontent + slot, 0, sizeof(int), st));
+    b->h_ncontent[slot] = 0;
+    return 0;
+}
+
+// vocoder frames a fresh stream is primed with (sva_streams_begin), for a stored prompt of Rt frames
+int priming_frames(const sva_batch* b, int Rt) {
+    const int c = b->p.chunk_frames;
+    return (std::min(b->p.decode_window_frames - 1, Rt) / c) * c;
+}
+
+// The slot's streaming vocoder state becomes "zero state, then the last P frames of its prompt streamed in chunk-sized calls", as
+// sva_streams_begin leaves every slot, through the production launches: save every slot's history rows, reset and prime the WHOLE batch
+// with this slot's prompt tail, keep the slot's rows of the result and put everybody else's back.  Stalls all streams for P / chunk
+// vocoder steps (tools/stream_restart_report.py measures it).
+int prime_vocoder_slot(sva_batch* b, int slot) {
+    const int B = b->B, c = b->p.chunk_frames, ncb = b->e->cfg.num_codebooks;
+    const int nd = (int)b->shift_host.size();
+    hipStream_t st = b->stream;
+    if (!b->voc_save) {
+        std::vector<long> offs(nd);
+        long tot = 0;
+        for (int i = 0; i < nd; ++i) { offs[i] = tot; tot += (long)b->shift_host[i].H * b->shift_host[i].C; }
+        b->voc_save_bstride = tot;
+        SVA_TRY(dev_alloc(b->allocs, &b->d_voc_save_offs, (size_t)nd));
+        SVA_HIP(hipMemcpy(b->d_voc_save_offs, offs.data(), sizeof(long) * nd, hipMemcpyHostToDevice));
+        SVA_TRY(dev_alloc(b->allocs, &b->prime_pcm, (size_t)B * 2048 * c));
+        SVA_TRY(dev_alloc(b->allocs, &b->voc_save, (size_t)B * tot));
+    }
+    const int R = b->ref_len[slot], P = priming_frames(b, R);
+    int frames_kept = 0;
+    SVA_HIP(hipMemcpy(&frames_kept, b->d_voc_frames, sizeof(int), hipMemcpyDeviceToHost));
+    if (nd) hipLaunchKernelGGL(history_rows_copy_kernel, dim3(nd, B), dim3(256), 0, st, b->d_shift, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, 0, 0);
+    SVA_HIP(hipGetLastError());
+    SVA_TRY(sva_vocode_reset(b));
+    // the step that activates the slot may hold its PCM in d_pcm or in the caller's buffer: the priming run writes its own sink
+    struct Keep {
+        sva_batch* b; float* dst; long bs; bool done; double fl, by; long ln;
+        ~Keep() { b->pcm_dst = dst; b->pcm_dst_bstride = bs; b->pcm_direct_done = done; b->gemm_flops = fl; b->gemm_bytes = by; b->gemm_launches = ln; }
+    } keep{b, b->pcm_dst, b->pcm_dst_bstride, b->pcm_direct_done, b->gemm_flops, b->gemm_bytes, b->gemm_launches};
+    b->pcm_dst = b->prime_pcm; b->pcm_dst_bstride = 2048L * c;
+    std::vector<int32_t> codes((size_t)(P / c) * B * ncb * c);       // (alive until the copies have landed)
+    for (int f = 0; f < P; f += c) {
+        int32_t* cf = codes.data() + (size_t)(f / c) * B * ncb * c;
+        for (int i = 0; i < B; ++i)
+            for (int q = 0; q < ncb; ++q)
+                for (int k = 0; k < c; ++k) cf[((size_t)i * ncb + q) * c + k] = b->ref_audio[slot][(size_t)q * R + (R - P + f + k)];
+        SVA_TRY(upload_vcodes(b, cf, c));
+        SVA_TRY(vocode(b, c, true));
+    }
+    if (nd) {
+        hipLaunchKernelGGL(history_rows_copy_kernel, dim3(nd, 1), dim3(256), 0, st, b->d_shift, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, slot, 0);
+        hipLaunchKernelGGL(history_rows_copy_kernel, dim3(nd, B), dim3(256), 0, st, b->d_shift, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, 0, 1);
+    }
+    SVA_HIP(hipGetLastError());
+    SVA_HIP(hipMemcpyAsync(b->d_voc_frames, &frames_kept, sizeof(int), hipMemcpyHostToDevice, st));
+    SVA_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+// A restarted slot whose content count has reached the delay becomes a decoding stream: everything a parked step may have clobbered is
+// rebuilt in the order a fresh stream sees it (sva_prefill_prompt, the delay fill of sva_streams_begin's first steps, the vocoder priming).
+// Runs on drained streams.
+int activate_slot(sva_batch* b, int slot) {
+    sva_batch::PendingPrompt& P = b->pending[slot];
+    struct Keep { sva_batch* b; const float* src; ~Keep() { b->step_src = src; } } keep{b, b->step_src};
+    b->step_src = nullptr;
+    SVA_TRY(prefill_slot_impl(b, slot, P.cc.data(), P.ac.data(), P.R, P.style.data(), P.timbre.data(), P.seed, false));
+    SVA_HIP(hipMemsetAsync(b->d_nframes + slot, 0, sizeof(int), b->stream));
+    b->h_nframes[slot] = 0;
+    SVA_TRY(ar_delay_fill(b, std::vector<int>{slot}));
+    SVA_TRY(prime_vocoder_slot(b, slot));
+    b->h_phase[slot] = 2;
+    b->restarted[slot] = 0;
+    P = sva_batch::PendingPrompt();
+    return set_slot_flag(b, slot, 0);
+}
+
+int activate_due_slots(sva_batch* b) {
+    std::vector<int> due;
+    for (int i = 0; i < b->B; ++i)
+        if (b->restarted[i] && b->h_phase[i] == 1 && b->h_ncontent[i] >= b->p.delay) due.push_back(i);
+    if (due.empty()) return 0;
+    // rare: drain the stage streams of the pipelined mode and work on the main stream, as a re-prefill behind a host synchronisation does
+    SVA_TRY(quiesce(b));
+    b->stream = b->main_stream;
+    SVA_HIP(hipStreamSynchronize(b->stream));
+    for (int s_ : due) SVA_TRY(activate_slot(b, s_));
+    return 0;
+}
+
 int step_body(sva_batch* b) {
     sva_engine* e = b->e;
     (void)e;
@@ -1349,7 +1491,7 @@ int step_body(sva_batch* b) {
     SVA_TRY(check_mm_overflow(b));
     const int B = b->B, chunk = b->p.chunk_frames, d = b->p.delay, n = 2048 * chunk;
     hipStream_t st = b->stream;
-    const bool steady = b->delay_filled && (b->h_ncontent + chunk >= d);
+    const bool steady = b->delay_filled;          // (set once the lock-step slots hold `delay` content codes; a restarted slot rides along parked)
     if (steady) {
         const bool graph_ok = b->p.use_graph && b->noise_on_device && !b->forced_now && !b->prof_on;
         const bool pipe_ok = b->p.pipeline && b->sa && b->allow_pipe && b->noise_on_device && !b->forced_now && !b->prof_on && !b->p.use_graph &&
@@ -1387,16 +1529,25 @@ int step_body(sva_batch* b) {
             b->graph_step = false;
         }
         b->h_step += 1;
-        b->h_ncontent += chunk;
-        for (int i = 0; i < B; ++i) { b->h_last_pos[i] += 2 * chunk; b->h_nframes[i] += chunk; }
+        for (int i = 0; i < B; ++i) {
+            b->h_ncontent[i] += chunk;
+            b->h_last_pos[i] += 2 * chunk;
+            if (b->h_phase[i] == 2) b->h_nframes[i] += chunk;      // (a parked slot -- retired, or filling its own delay -- decodes throw-away frames)
+        }
         // re-prefill when current_pos // 2 >= max_seq_frames (:547-564).  Positions are deterministic, so the host
         // mirror decides without a device round trip; doing it after the vocoder instead of before (as the reference
         // does) changes nothing: the vocoder consumes the codes just decoded, the re-prefill only rewrites KV state.
         std::vector<int> redo;
         if (b->pipe_dirty) b->stream = b->sa;  // pipelined: the KV rewrite belongs to the AR stream (it already waited for E of this step)
         int rrc = 0;
-        for (int i = 0; i < B; ++i)
-            if (b->h_last_pos[i] / 2 >= b->p.max_seq_frames) redo.push_back(i);
+        for (int i = 0; i < B; ++i) {
+            if (b->h_last_pos[i] / 2 < b->p.max_seq_frames) continue;
+            if (b->h_phase[i] == 2) { redo.push_back(i); continue; }
+            // a parked slot never becomes due: its position goes back to the end of its last stored prompt, over K / V rows that stay valid
+            const int lp = parked_position(b, i);
+            hipLaunchKernelGGL(set_slot_i32_kernel, dim3(1), dim3(64), 0, b->stream, b->d_last_pos, i, lp);
+            b->h_last_pos[i] = lp;
+        }
         if (!redo.empty()) {
             // one pass for all due slots against the cached prompt prefix (reprefill_slots); SVA_DEBUG reprefill=0: the round-3 path, one
             // whole-prompt prefill per slot behind a host synchronisation (A/B, parity of the two)
@@ -1414,32 +1565,105 @@ int step_body(sva_batch* b) {
                 SVA_HIP(hipEventRecord(b->pipe_evR, b->sa));
             }
         }
+        if (!rrc) rrc = activate_due_slots(b);
         return rrc;
     }
     b->graph_step = false;
     SVA_TRY(quiesce(b));
     SVA_HIP(hipEventRecord(b->ev[0], st));
     // E0: shift window / append chunk (:495-496), then E1..E8
-    SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, st));
+    SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, st, b->d_slot_flag));
     SVA_TRY(b->enc_incremental ? encode_incremental(b, b->d_step, n, 1) : encode(b, b->d_step, n, 1));
     hipLaunchKernelGGL(append_content_kernel, dim3((B + 63) / 64), dim3(64), 0, st, b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap,
                        b->d_ncontent, b->d_step_content, B, b->d_step);
     b->h_step += 1;
-    b->h_ncontent += chunk;
+    for (int& nc : b->h_ncontent) nc += chunk;
     SVA_HIP(hipEventRecord(b->ev[1], st));
-    if (b->h_ncontent >= d && !b->delay_filled) {
+    int lock = -1;                                      // a slot of the batch-wide start (they share one count)
+    for (int i = 0; i < B && lock < 0; ++i)
+        if (b->h_phase[i] == 1 && !b->restarted[i]) lock = i;
+    if (lock < 0) {                                     // every slot retired or restarted since sva_streams_begin: nothing left to fill in lock step
+        b->delay_filled = true;
+    } else if (b->h_ncontent[lock] >= d) {
         SVA_TRY(ar_delay_fill(b));                      // :521-525 -> zeros
         b->delay_filled = true;
+        lockstep_slots_decode(b);
     }                                                   // else :519-520 -> zeros
     SVA_HIP(hipEventRecord(b->ev[2], st));
     SVA_HIP(hipMemsetAsync(b->d_pcm, 0, sizeof(float) * (size_t)B * 2048 * b->Tv, st));
     SVA_HIP(hipEventRecord(b->ev[3], st));
-    return 0;
+    return activate_due_slots(b);
 }
 
 }  // namespace
 
 static int check_ar_fail(sva_batch* b);
+
+// drained streams, main stream current: what the slot calls below change is read by the next step's launches
+static int drain_for_slot_call(sva_batch* b) {
+    SVA_HIP(hipSetDevice(b->e->device));
+    (void)hipGetLastError();
+    SVA_TRY(quiesce(b));
+    b->stream = b->main_stream;
+    SVA_HIP(hipStreamSynchronize(b->stream));
+    return 0;
+}
+static int park_slot(sva_batch* b, int slot) {
+    const int lp = parked_position(b, slot);
+    SVA_HIP(hipMemcpyAsync(b->d_last_pos + slot, &lp, sizeof(int), hipMemcpyHostToDevice, b->stream));
+    SVA_HIP(hipStreamSynchronize(b->stream));
+    b->h_last_pos[slot] = lp;
+    return 0;
+}
+
+extern "C" int sva_stream_restart(sva_batch* b, int slot, const int64_t* ref_content_codes, const int32_t* ref_audio_codes, int R, const float* style,
+                                  const float* timbre, uint64_t noise_seed) {
+    SVA_CHECK(b && ref_content_codes && ref_audio_codes && style && timbre, "sva_stream_restart: null argument");
+    SVA_CHECK(b->begun, "sva_stream_restart: the batch has not begun (sva_prefill_prompt + sva_streams_begin start its first streams)");
+    SVA_CHECK(slot >= 0 && slot < b->B, "sva_stream_restart: slot out of range");
+    const sva_config& c = b->e->cfg;
+    const int ncb = c.num_codebooks, nspk = c.timbre_tokens + 1;
+    SVA_CHECK(R > b->p.delay, "sva_stream_restart: the prompt must be longer than the delay");
+    SVA_CHECK(R <= b->Pmax && nspk + 2 * R <= b->Mmax && nspk + 2 * R <= c.max_seq_len, "sva_stream_restart: prompt too long for the KV cache");
+    const int P = priming_frames(b, std::min(R, b->p.max_prompt_frames));
+    SVA_CHECK(P >= 16 || P == b->p.decode_window_frames - 1, "sva_stream_restart: prompt shorter than the vocoder receptive field (16 frames)");
+    SVA_CHECK(b->enc_incremental && b->enc_merged,
+              "sva_stream_restart: this batch runs the full-window encoder (encode_window_frames <= 40 + chunk_frames), which has no cached "
+              "silence state to fill one slot from");
+    SVA_CHECK(!b->ar_failed && !(b->h_ar_fail && *reinterpret_cast<volatile int*>(b->h_ar_fail) != 0),
+              "sva_stream_restart: this batch's persistent AR decode kernel timed out: sva_streams_begin restarts its streams");
+    SVA_TRY(drain_for_slot_call(b));
+    SVA_TRY(restart_encoder_state(b, slot));           // (its own refusal -- no silence state -- comes before its first write)
+    sva_batch::PendingPrompt& P_ = b->pending[slot];
+    P_.cc.assign(ref_content_codes, ref_content_codes + R);
+    P_.ac.assign(ref_audio_codes, ref_audio_codes + (size_t)ncb * R);
+    P_.style.assign(style, style + c.style_dim);
+    P_.timbre.assign(timbre, timbre + (size_t)c.timbre_tokens * c.timbre_dim);
+    P_.R = R; P_.seed = noise_seed;
+    b->restarted[slot] = 1;
+    b->h_phase[slot] = 1;
+    SVA_TRY(park_slot(b, slot));
+    return set_slot_flag(b, slot, kSlotOutputMuted);
+}
+
+extern "C" int sva_stream_retire(sva_batch* b, int slot) {
+    SVA_CHECK(b, "sva_stream_retire: null batch");
+    SVA_CHECK(b->begun, "sva_stream_retire: the batch has not begun");
+    SVA_CHECK(slot >= 0 && slot < b->B, "sva_stream_retire: slot out of range");
+    SVA_TRY(drain_for_slot_call(b));
+    b->restarted[slot] = 0;
+    b->pending[slot] = sva_batch::PendingPrompt();
+    b->h_phase[slot] = 0;              // (its position is rewound when it would become due for a re-prefill: step_body)
+    return set_slot_flag(b, slot, kSlotInputMuted | kSlotOutputMuted);
+}
+
+extern "C" int sva_stream_state(sva_batch* b, int slot, int* phase, long* frames) {
+    SVA_CHECK(b && b->begun, "sva_stream_state: the batch has not begun");
+    SVA_CHECK(slot >= 0 && slot < b->B, "sva_stream_state: slot out of range");
+    if (phase) *phase = b->h_phase[slot];
+    if (frames) *frames = b->h_phase[slot] == 2 ? b->h_nframes[slot] : 0;
+    return 0;
+}
 
 extern "C" int sva_step(sva_batch* b, const float* pcm_in, float* pcm_out, const float* noise, const int32_t* forced_codes) {
     SVA_CHECK(b && pcm_in && pcm_out && b->begun, "sva_step: bad argument or sva_streams_begin not called");
@@ -1680,9 +1904,10 @@ extern "C" int sva_ar_delay_fill(sva_batch* b, const int64_t* codes) {
     SVA_TRY(h2d(b, tmp, codes, sizeof(int64_t) * (size_t)B * d));
     hipLaunchKernelGGL(put_codes_kernel, dim3((B + 63) / 64), dim3(64), 0, b->stream, tmp, d, b->d_codes, b->T2, b->d_content_hist, b->hist_cap,
                        b->d_ncontent, B);
-    b->h_ncontent += d;
+    for (int& nc : b->h_ncontent) nc += d;
     SVA_TRY(ar_delay_fill(b));
     b->delay_filled = true;
+    lockstep_slots_decode(b);
     SVA_HIP(hipStreamSynchronize(b->stream));
     return 0;
 }
@@ -1700,7 +1925,7 @@ extern "C" int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float*
     SVA_TRY(h2d(b, tmp, code, sizeof(int64_t) * (size_t)B));
     hipLaunchKernelGGL(put_codes_kernel, dim3((B + 63) / 64), dim3(64), 0, st, tmp, 1, b->d_codes, b->T2, b->d_content_hist, b->hist_cap,
                        b->d_ncontent, B);
-    b->h_ncontent += 1;
+    for (int& nc : b->h_ncontent) nc += 1;
     b->noise_on_device = (noise == nullptr);
     if (noise) SVA_TRY(h2d(b, b->d_noise, noise, sizeof(float) * (size_t)B * (c.ar_vocab + ncb * c.codebook_size)));
     const int uf = forced ? 1 : 0;

@@ -156,7 +156,7 @@ __global__ void build_delayfill_kernel(const float* __restrict__ content_emb, co
 //   position 33 + 2 i = content_emb[content_hist[c_lo + i - Rt]],  34 + 2 i = audio_embed(ac'[:, i - d]),
 //   ac'[:, j] = ref_audio[:, j] for j < Rt (the last d reference frames: ref_tail) and pred_hist[nf - na + j - Rt] beyond.
 __global__ void build_reprefill_kernel(const ReprefillArgs a, const float* __restrict__ content_emb, const float* __restrict__ codebook_emb,
-                                       const int* __restrict__ content_hist, const int* __restrict__ pred_hist, int hist_cap, int ncontent,
+                                       const int* __restrict__ content_hist, const int* __restrict__ pred_hist, int hist_cap,
                                        const int* __restrict__ ref_tail, int max_delay, int d, int ncb, int cbsize, int D, int nspk,
                                        float* __restrict__ x, int* __restrict__ slot_out, int* __restrict__ pos_out) {
     const int row = blockIdx.x;
@@ -167,7 +167,7 @@ __global__ void build_reprefill_kernel(const ReprefillArgs a, const float* __res
     float* o = x + (long)row * D;
     const int mask = hist_cap - 1;
     if ((r & 1) == 0) {
-        const int c_lo = ncontent - d - na;                      // src_content_codes[-buffer-d:-d]
+        const int c_lo = a.ncon[li] - d - na;                      // src_content_codes[-buffer-d:-d]
         const int code = content_hist[(long)b * hist_cap + ((c_lo + (i - Rt)) & mask)];
         for (int k = threadIdx.x; k < D; k += blockDim.x) o[k] = content_emb[(long)code * D + k];
     } else {
@@ -215,4 +215,21 @@ __global__ void add_vec_kernel(int* p, int n, int v) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] += v;
 }
+__global__ void set_slot_i32_kernel(int* p, int slot, int v) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) p[slot] = v;
+}
 
+// The streaming state of the vocoder is the H history rows in front of every tensor of its ShiftDesc table: desc blockIdx.x, slot slot_lo +
+// blockIdx.y, H * C floats at ptr + slot * bstride <-> save + slot * save_bstride + offs[desc].  The K-blocked operand planes are in that
+// table as one desc per (plane, 32-k block) -- [k / 32][B rows][32], plane_off_blocked of planes_split.h -- so a slot's rows of such a
+// plane are reached through the same (ptr, bstride) pairs that shift them, never through one pointer offset into the plane.
+__global__ __launch_bounds__(256) void history_rows_copy_kernel(const sva::ShiftDesc* __restrict__ descs, const long* __restrict__ offs,
+                                                                float* __restrict__ save, long save_bstride, int slot_lo, int to_live) {
+    const sva::ShiftDesc d = descs[blockIdx.x];
+    const int slot = slot_lo + blockIdx.y;
+    float* live = d.ptr + (long)slot * d.bstride;
+    float* sv = save + (long)slot * save_bstride + offs[blockIdx.x];
+    const long n = (long)d.H * d.C;
+    if (to_live) for (long i = threadIdx.x; i < n; i += blockDim.x) live[i] = sv[i];
+    else for (long i = threadIdx.x; i < n; i += blockDim.x) sv[i] = live[i];
+}

@@ -104,7 +104,7 @@ int launch_fsq_encode(const float* x, long x_bstride, long x_off, int ldx, int B
 // conv_post (C -> 1, k taps) on silu(x) + tanh: x (b, r, c) at x[b*x_bstride + x_off + r*C + c]; row t reads t..t+k-1
 int launch_conv_post_tanh(const float* x, long x_bstride, long x_off, int B, int T, int C, int k,
                           const float* w /*[k][C]*/, const float* bias, float* pcm, long p_bstride, long p_off,
-                          hipStream_t st);
+                          hipStream_t st, const int* slot_flag = nullptr);
 
 struct ShiftDesc {      // one history buffer: rows [T, T+H) move to [0, H) after a step
     float* ptr;
@@ -117,7 +117,10 @@ int launch_shift_history(const ShiftDesc* descs_dev, int n_desc, int B, hipStrea
 // small helpers
 int launch_fill_i32(int* p, int n, int v, hipStream_t st);
 int launch_add_i32(int* p, int v, hipStream_t st);
-int launch_ring_write(float* ring, int* step, int B, int N, const float* chunk, int n, hipStream_t st);
+int launch_ring_write(float* ring, int* step, int B, int N, const float* chunk, int n, hipStream_t st, const int* slot_flag = nullptr);
+// per-slot flag word of a batch (sva_batch::d_slot_flag, [B], all zero by default): what launch_ring_write / launch_conv_post_tanh read
+constexpr int kSlotInputMuted = 1;      // retired slot: its chunk is written as zeros, the caller's memory is not read
+constexpr int kSlotOutputMuted = 2;     // retired slot, or a restarted one while its delay fills: its PCM rows are written as zeros
 
 }  // namespace sva
 

@@ -15,18 +15,20 @@ __device__ __forceinline__ float silu_acc(float x) { return x / (1.f + expf(-x))
 // appends the new chunk (evaluations/infer_arvc.py:495-496); here the window is a ring whose
 // oldest sample sits at ((step + add) * n) % N, `step` being the device-side chunk counter.
 // ------------------------------------------------------------------------------------------
-__global__ void ring_write_kernel(float* ring, const int* step, int N, const float* chunk, int n) {
+// slot_flag (may be null) [B]: bit 0 set = the slot's input is muted -- its chunk counts as zeros and the caller's memory is not read
+__global__ void ring_write_kernel(float* ring, const int* step, int N, const float* chunk, int n, const int* __restrict__ slot_flag) {
     const int b = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int start = (int)(((long)(*step) * n) % N);
     int idx = start + i;
     if (idx >= N) idx -= N;
-    ring[(long)b * N + idx] = chunk[(long)b * n + i];
+    const bool muted = slot_flag && (slot_flag[b] & kSlotInputMuted);
+    ring[(long)b * N + idx] = muted ? 0.f : chunk[(long)b * n + i];
 }
-int launch_ring_write(float* ring, int* step, int B, int N, const float* chunk, int n, hipStream_t st) {
+int launch_ring_write(float* ring, int* step, int B, int N, const float* chunk, int n, hipStream_t st, const int* slot_flag) {
     dim3 grid((n + 255) / 256, B);
-    hipLaunchKernelGGL(ring_write_kernel, grid, dim3(256), 0, st, ring, step, N, chunk, n);
+    hipLaunchKernelGGL(ring_write_kernel, grid, dim3(256), 0, st, ring, step, N, chunk, n, slot_flag);
     SVA_HIP(hipGetLastError());
     return 0;
 }
@@ -1929,9 +1931,13 @@ int launch_fsq_decode(const int* codes, long c_bstride, long c_gstride, int B, i
 __global__ __launch_bounds__(256) void conv_post_tanh_kernel(const float* __restrict__ x, long x_bstride, long x_off, int T,
                                                              int C, int k, const float* __restrict__ w,
                                                              const float* __restrict__ bias, float* __restrict__ pcm,
-                                                             long p_bstride, long p_off) {
+                                                             long p_bstride, long p_off, const int* __restrict__ slot_flag) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int b = blockIdx.y, t0 = blockIdx.x * 256, tid = threadIdx.x;
+    if (slot_flag && (slot_flag[b] & kSlotOutputMuted)) {      // (uniform over the workgroup) a retired or delay-filling slot: its PCM rows are zeros
+        if (t0 + tid < T) pcm[(long)b * p_bstride + p_off + t0 + tid] = 0.f;
+        return;
+    }
     const int nrows = min(256, T - t0) + k - 1;
     const int LD = C + 1;                // odd row stride: thread t reads row t + j, so a stride of C = 16 would put 64 lanes on 2 banks
     const float* xb = x + (long)b * x_bstride + x_off + (long)t0 * C;
@@ -1950,11 +1956,11 @@ __global__ __launch_bounds__(256) void conv_post_tanh_kernel(const float* __rest
     }
 }
 int launch_conv_post_tanh(const float* x, long x_bstride, long x_off, int B, int T, int C, int k, const float* w,
-                          const float* bias, float* pcm, long p_bstride, long p_off, hipStream_t st) {
+                          const float* bias, float* pcm, long p_bstride, long p_off, hipStream_t st, const int* slot_flag) {
     const size_t smem = ((size_t)(256 + k - 1) * (C + 1) + (size_t)k * C) * sizeof(float);
     SVA_CHECK(smem <= 64 * 1024, "conv_post: tile too large");
     hipLaunchKernelGGL(conv_post_tanh_kernel, dim3((T + 255) / 256, B), dim3(256), smem, st, x, x_bstride, x_off, T, C, k, w,
-                       bias, pcm, p_bstride, p_off);
+                       bias, pcm, p_bstride, p_off, slot_flag);
     SVA_HIP(hipGetLastError());
     return 0;
 }

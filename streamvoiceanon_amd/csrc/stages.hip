@@ -1165,7 +1165,7 @@ int vocode(sva_batch* b, int T, bool shift, int part) {
         if (par) SVA_TRY(stream_fork(b, b->aux[1], st));      // join: branch 2's last conv is ordered after 0 and 1
     }
     SVA_TRY(launch_conv_post_tanh(b->S[5].p, b->S[5].bstride, (long)(b->S[5].H - (e->post_k - 1)) * b->S[5].C, B, (int)Tl, b->S[5].C, e->post_k,
-                                  e->post_w, e->post_b, b->pcm_dst ? b->pcm_dst : b->d_pcm, b->pcm_dst ? b->pcm_dst_bstride : 2048L * b->Tv, 0, st));
+                                  e->post_w, e->post_b, b->pcm_dst ? b->pcm_dst : b->d_pcm, b->pcm_dst ? b->pcm_dst_bstride : 2048L * b->Tv, 0, st, b->d_slot_flag));
     if (b->pcm_dst) b->pcm_direct_done = true;
     if (shift) {
         // update T in the descriptors if it changed (host table re-uploaded; rare)

@@ -71,6 +71,9 @@ def load_library():
     lib.sva_batch_destroy.restype = None
     lib.sva_prefill_prompt.argtypes = [vp, i32, vp, vp, i32, vp, vp, C.c_uint64]
     lib.sva_streams_begin.argtypes = [vp]
+    lib.sva_stream_restart.argtypes = [vp, i32, vp, vp, i32, vp, vp, C.c_uint64]
+    lib.sva_stream_retire.argtypes = [vp, i32]
+    lib.sva_stream_state.argtypes = [vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_long)]
     lib.sva_step.argtypes = [vp, vp, vp, vp, vp]
     lib.sva_step_device.argtypes = [vp, vp, vp]
     lib.sva_step_device_on.argtypes = [vp, vp, vp, vp, C.c_int]
@@ -127,7 +130,7 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "sva_last_error", "sva_config_default", "sva_stream_params_default", "sva_engine_create",
     "sva_engine_load_weight", "sva_engine_finalize", "sva_engine_destroy", "sva_batch_create", "sva_batch_destroy",
-    "sva_prefill_prompt", "sva_streams_begin", "sva_step", "sva_step_device", "sva_step_device_on", "sva_join_stream", "sva_batch_uses_persistent_decode", "sva_test_force_ar_timeout", "sva_debug_configure", "sva_sync", "sva_stream_chunks", "sva_encode_window", "sva_firefly_encode",
+    "sva_prefill_prompt", "sva_streams_begin", "sva_stream_restart", "sva_stream_retire", "sva_stream_state", "sva_step", "sva_step_device", "sva_step_device_on", "sva_join_stream", "sva_batch_uses_persistent_decode", "sva_test_force_ar_timeout", "sva_debug_configure", "sva_sync", "sva_stream_chunks", "sva_encode_window", "sva_firefly_encode",
     "sva_vocode_window", "sva_vocode_stream", "sva_vocode_reset", "sva_quantizer_decode", "sva_vocoder_head", "sva_ar_delay_fill", "sva_ar_decode_one", "sva_generate", "sva_get_tap", "sva_get_timings",
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
@@ -294,6 +297,27 @@ class Batch:
 
     def begin(self):
         _check(self.lib.sva_streams_begin(self.h), "sva_streams_begin")
+
+    def restart(self, slot, ref_content_codes, ref_audio_codes, style, timbre, noise_seed=0):
+        """sva_stream_restart: a new utterance in `slot` of a begun batch (operands as prefill_prompt).  From the next step on the slot
+        behaves like a slot of a fresh batch -- `delay` chunks of zeros, then frame 0 -- and every other slot is unaffected."""
+        cc = np.ascontiguousarray(ref_content_codes, dtype=np.int64).reshape(-1)
+        ac = np.ascontiguousarray(ref_audio_codes, dtype=np.int32).reshape(8, -1)
+        assert ac.shape[1] == cc.shape[0]
+        st = np.ascontiguousarray(style, dtype=np.float32).reshape(-1)
+        tm = np.ascontiguousarray(timbre, dtype=np.float32)
+        _check(self.lib.sva_stream_restart(self.h, int(slot), _ptr(cc), _ptr(ac), cc.shape[0], _ptr(st), _ptr(tm), int(noise_seed)),
+               "sva_stream_restart")
+
+    def retire(self, slot):
+        """sva_stream_retire: the slot's input is no longer read and its output is zeros until restart()."""
+        _check(self.lib.sva_stream_retire(self.h, int(slot)), "sva_stream_retire")
+
+    def stream_state(self, slot):
+        """-> (phase, frames): phase 0 retired, 1 delay filling, 2 decoding; frames decoded since the slot's stream began."""
+        ph, fr = C.c_int(), C.c_long()
+        _check(self.lib.sva_stream_state(self.h, int(slot), C.byref(ph), C.byref(fr)), "sva_stream_state")
+        return int(ph.value), int(fr.value)
 
     def step(self, pcm_in, noise=None, forced_codes=None):
         x = np.ascontiguousarray(pcm_in, dtype=np.float32).reshape(self.B, 2048 * self.chunk)

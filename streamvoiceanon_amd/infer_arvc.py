@@ -490,6 +490,43 @@ class InferenceWrapper:
         return pred
 
 
+    def stream_infer_many(self, sources, refs, n_slots, encode_window_frames=128, decode_window_frames=64, max_prompt_frames=256,
+                          max_seq_frames=768, buffer_frames=32, decode_chunk_frames=1, delay=None, noise_seeds=None, on_step=None):
+        """stream_infer over a queue of utterances of unequal length on ONE batch of `n_slots` streams (continuous batching): the first
+        n_slots utterances start together, a slot takes the next utterance of the queue in the step after its own ends
+        (Batch.restart), and slots are retired when the queue is empty.  sources[i]: wav path or float array at 44.1 kHz; refs[i]: the
+        prompt of utterance i as (ref_audio_codes, ref_content_codes, style_vectors, timbre_latents) -- calculate_prompt(...)[:4] --
+        or a reference wav path / array to compute it from.  -> list of per-utterance PCM, each padded and trimmed exactly as
+        stream_infer returns it (the leading zero chunks of the delay stay)."""
+        from . import stream_pool
+
+        assert len(sources) == len(refs) and len(sources) >= 1
+        n = self.SAMPLES_PER_FRAME * decode_chunk_frames
+        srcs, prompts = [], []
+        for src, ref in zip(sources, refs):
+            wav = self._load_src(src)[0]
+            pad = n - (wav.shape[0] % n)          # as stream_infer (:648-649)
+            srcs.append(np.concatenate([np.zeros(pad, np.float32), np.asarray(wav, np.float32).reshape(-1)]))
+            if not (isinstance(ref, (tuple, list)) and len(ref) >= 4):
+                ref = self.calculate_prompt(self.load_and_crop_references(*self.process_ref_paths(ref, None)))
+            ac, cc, st, tm = (np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x) for x in ref[:4])
+            prompts.append((ac.reshape(8, -1), cc.reshape(-1), st.reshape(-1), tm.reshape(32, -1)))
+        n_slots = min(int(n_slots), len(srcs))      # a batch begins with a stream in every slot
+        seeds = list(noise_seeds) if noise_seeds is not None else [0] * len(srcs)
+        self.delay = 2 if delay is None else int(delay)
+        if self.batch is not None:
+            self.batch.close()
+        self.decode_chunk_frames = decode_chunk_frames
+        self.batch = E.Batch(self.engine, n_streams=n_slots, encode_window_frames=encode_window_frames,
+                             decode_window_frames=decode_window_frames, chunk_frames=decode_chunk_frames, delay=self.delay,
+                             max_seq_frames=max_seq_frames, buffer_frames=buffer_frames, max_prompt_frames=max_prompt_frames)
+        for s in range(n_slots):
+            ac, cc, st, tm = prompts[s]
+            self.batch.prefill_prompt(s, cc, ac, st, tm, noise_seed=seeds[s])
+        self.batch.begin()
+        return stream_pool.run_pool(self.batch, srcs, prompts, n_slots, n, noise_seeds=seeds, on_step=on_step)
+
+
 def main(argv=None, weights=None, style_vectors=None, timbre_latents=None):
     """The reference's command line (evaluations/infer_arvc.py:691-743), flag for flag.  `weights` / `style_vectors` /
     `timbre_latents` exist for tests and for deployments without the speaker-encoder checkpoints."""
