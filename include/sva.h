@@ -280,6 +280,11 @@ int sva_batch_uses_persistent_decode(sva_batch* b);
 int sva_debug_configure(const char* kv);
 /* test hook: set the persistent kernel's device-side timeout word, as a launch with non-resident workgroups would */
 int sva_test_force_ar_timeout(sva_batch* b);
+/* test hook: do the four chain streams of a pipelined batch -- main, encoder side, AR, vocoder -- run concurrently, i.e. sit on four
+ * hardware queues?  pair_ok[6], pairs in the order (main, side) (main, AR) (main, vocoder) (side, AR) (side, vocoder) (AR, vocoder):
+ * 1 = a kernel on the second stream ran while one on the first was still running, 0 = the two streams serialise.  Each pair costs at
+ * most 2 ms (the waiting kernel gives up by the clock); synchronises the device. */
+int sva_test_stream_overlap(sva_batch* b, int* pair_ok);
 
 /* The optional sampler edits of decode_one_token_ar (modules/dual_ar_stream.py:1175-1213 -> logits_to_probs :1099-1117):
  *   previous_tokens [1 + num_codebooks][W] int32 (row 0 edits the token head, row cb + 1 codebook cb; negative entries are

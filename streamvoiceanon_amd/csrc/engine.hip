@@ -61,6 +61,7 @@ static void parse_debug(DebugOptions& o, const char* env) {
             else if (k == "f16_weights") o.f16_weights = atoi(v.c_str());
             else if (k == "cu_partition") o.cu_partition = atoi(v.c_str());
             else if (k == "cu_ar") o.cu_ar = atoi(v.c_str());
+            else if (k == "stream_queues") o.stream_queues = atoi(v.c_str());
             else if (k == "pipe_skip") o.pipe_skip = atoi(v.c_str());
             else if (k == "tune_dump") o.tune_dump = v;
             else fprintf(stderr, "[sva] debug option '%s' unknown, ignored\n", k.c_str());
@@ -115,6 +116,29 @@ std::map<int, StreamSet> g_streams;          // per device, process lifetime
 // short dependent kernels that each leave most of the chip idle, yet when they share CUs the AR chain's kernels queue behind
 // the encoder's and vocoder's workgroups.  The gain shrinks with the batch (and wants a smaller AR share as it grows) and turns
 // into a loss beyond 32 streams, where the GEMMs want the whole chip.  SVA_DEBUG=cu_partition=0|1[,cu_ar=N] overrides for A/B runs.
+//
+// Hardware queues.  The runtime multiplexes plain streams onto a pool of hardware queues (4 unless the process environment said
+// otherwise before the runtime started -- which a library loaded into a host application cannot count on), the host application's
+// streams included, and two streams on one hardware queue serialise.  The four chains of the pipelined step must not: with a pool
+// of 4 and four plain streams the single-stream step ran at 630 frames/s against 1070 with a pool of 8, 64 streams at 7880 against
+// 8580 (profiles/hw_queues_report.txt).  So the unpartitioned set (variant 0) is provisioned by construction:
+//   SQ_PRIO  (the default) the AR and the vocoder stream at the highest stream priority, main and the encoder side stream at normal
+//            priority, all hipStreamNonBlocking.  The runtime keeps one pool PER priority level and hands a new stream the entry with
+//            the fewest users, so the two pairs cannot meet and two streams of a pair share an entry only when the host application
+//            itself keeps more than pool - 2 streams at that level.  Measured at a pool of 4 under torch: all six pairs concurrent
+//            (tests/test_gpu_stream_queues.py), 1065-1074 frames/s at one stream, 8550-8720 at 64.
+//   SQ_MASK  CU-masked streams with every CU enabled: a queue each outside the pool (what the partitioned variants get anyway).  Same
+//            throughput (1070 / 8690), but the runtime creates a CU-masked stream with the DEFAULT flags: it synchronises with the
+//            legacy null stream, i.e. with a host application's torch work, and costs four more hardware queues.  Not the default.
+//   SQ_PLAIN four plain non-blocking streams (the behaviour before; each stream's fallback when the chosen call fails).
+// SVA_DEBUG=stream_queues=0|1|2 picks plain / mask / prio for A/B runs (tools/hwq_ab.sh; tools/micro/stream_queues.hip is the
+// stand-alone probe of the three).  ops_stream, aux1 and the test hooks' streams stay plain.
+// Hardware queues a process can end up with: the pools (4 entries per priority level in use: normal + highest = 8, shared with the
+// host application) + 4 dedicated ones per LIVE partitioned variant (the policy uses the 1-stream split and 64 / 96 / 128 AR CUs: 16
+// if one process ever creates all four, 4 in a process that serves one partitioned batch size) = 8 to 12 as a rule, 24 at the very
+// most, under the 32 the runtime allows a process; SQ_MASK would add 4.
+enum { SQ_PLAIN = 0, SQ_MASK = 1, SQ_PRIO = 2 };
+constexpr int kStreamQueues = SQ_PRIO;
 int get_streams(int device, bool need_aux1, int n_streams_if_pipelined, StreamSet* out, int ar_cus = 96) {
     std::lock_guard<std::mutex> lk(g_streams_mu);
     // variant 1 (one stream): AR 96 CUs | encoder 128 | vocoder 32 (12 / 16 / 4 per XCD) -- 2.11 -> 1.75 ms per step, 1.60 with the
@@ -130,28 +154,38 @@ int get_streams(int device, bool need_aux1, int n_streams_if_pipelined, StreamSe
         part[1] = n; part[2] = part[4] = n; part[3] = part[5] = 256 - n;
         variant = n;
     }
-    if (partitioned) {
-        hipDeviceProp_t prop;
-        SVA_HIP(hipGetDeviceProperties(&prop, device));
-        if (prop.multiProcessorCount != 256) partitioned = false;         // the ranges are sized for the 256 CUs of an MI355X
-    }
+    int cus = 0;
+    SVA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (partitioned && cus != 256) partitioned = false;         // the ranges are sized for the 256 CUs of an MI355X
     if (!partitioned) variant = 0;
     StreamSet& s = g_streams[device * 256 + variant];
     if (!s.main) {
-        auto make = [&](hipStream_t* st, int lo, int n) -> int {
-            if (!partitioned || n <= 0 || n >= 256) { SVA_HIP(hipStreamCreateWithFlags(st, hipStreamNonBlocking)); return 0; }
-            uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int i = lo; i < lo + n && i < 256; ++i) mask[i >> 5] |= 1u << (i & 31);
-            if (hipExtStreamCreateWithCUMask(st, 8, mask) != hipSuccess) {      // (a runtime without CU masking: plain stream, no partition)
+        const int sq = debug_options().stream_queues >= 0 ? debug_options().stream_queues : kStreamQueues;
+        int prio_least = 0, prio_greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) { (void)hipGetLastError(); prio_least = prio_greatest = 0; }
+        // a failed call of either kind: clear the error, plain non-blocking stream (no partition / the shared pool)
+        auto make = [&](hipStream_t* st, int lo, int n, bool high) -> int {
+            *st = nullptr;
+            if (!partitioned && sq == SQ_PRIO && prio_greatest < prio_least) {
+                if (hipStreamCreateWithPriority(st, hipStreamNonBlocking, high ? prio_greatest : 0) == hipSuccess) return 0;
                 (void)hipGetLastError();
-                SVA_HIP(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+                *st = nullptr;
             }
+            if (!partitioned && sq == SQ_MASK) { lo = 0; n = cus; }        // every CU: only the queue of its own is wanted
+            if ((partitioned && n > 0 && n < 256) || (!partitioned && sq == SQ_MASK && n > 0 && n <= 256)) {
+                uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                for (int i = lo; i < lo + n && i < 256; ++i) mask[i >> 5] |= 1u << (i & 31);
+                if (hipExtStreamCreateWithCUMask(st, partitioned ? 8 : (uint32_t)((n + 31) / 32), mask) == hipSuccess) return 0;
+                (void)hipGetLastError();
+                *st = nullptr;
+            }
+            SVA_HIP(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
             return 0;
         };
-        SVA_TRY(make(&s.main, part[2], part[3]));
-        SVA_TRY(make(&s.aux0, part[2], part[3]));
-        SVA_TRY(make(&s.sa, part[0], part[1]));
-        SVA_TRY(make(&s.sv, part[4], part[5]));
+        SVA_TRY(make(&s.main, part[2], part[3], false));
+        SVA_TRY(make(&s.aux0, part[2], part[3], false));
+        SVA_TRY(make(&s.sa, part[0], part[1], true));
+        SVA_TRY(make(&s.sv, part[4], part[5], true));
     }
     if (need_aux1 && !s.aux1) SVA_HIP(hipStreamCreateWithFlags(&s.aux1, hipStreamNonBlocking));     // legacy three-stream vocoder only
     *out = s;
@@ -230,11 +264,12 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
     SVA_CHECK(p->encode_window_frames % 1 == 0 && p->encode_window_frames >= p->chunk_frames, "bad encode window");
     if (b->p.voc_max_frames < p->chunk_frames) b->p.voc_max_frames = p->chunk_frames;
     // Streams come from a process-wide set per device, created once in a fixed order (main, encoder side stream, AR,
-    // vocoder) and shared by every batch: the runtime multiplexes streams onto a few hardware queues (4 by default) in
-    // creation order, two streams on one hardware queue serialise (a stream stuck behind another one's event wait blocks
+    // vocoder) and shared by every batch: the runtime multiplexes streams onto a few hardware queues (4 by default),
+    // two streams on one hardware queue serialise (a stream stuck behind another one's event wait blocks
     // its queue mates), and streams created after others were destroyed land on unlucky queues -- measured: the pipelined
     // mode gains 16 % at 64 streams in a fresh process and nothing after one create / destroy cycle.  Batches that are
-    // alive at the same time therefore share the streams (in-order, so still correct).
+    // alive at the same time therefore share the streams (in-order, so still correct), and get_streams keeps the four
+    // chains on four hardware queues whatever the size of that pool.
     if (b->p.pipeline) SVA_CHECK(b->voc_grouped, "stage pipelining needs the grouped vocoder launches");
     {
         StreamSet ss;

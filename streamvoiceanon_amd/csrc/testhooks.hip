@@ -1,6 +1,8 @@
 // Kernel unit-test hooks exported through the C ABI (include/sva.h: sva_test_*).
 #include "../../include/sva.h"
 #include "kernels.h"
+#include "engine.h"
+#include "stream_overlap.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -903,5 +905,20 @@ extern "C" int sva_test_conv_post(int device, int B, int T, int C, int k, const 
     SVA_TRY(launch_conv_post_tanh(bx.as<float>(), x_bstride, x_off, B, T, C, k, bw.as<float>(), bb.as<float>(), bp.as<float>(), p_bstride, p_off, 0));
     SVA_HIP(hipDeviceSynchronize());
     SVA_TRY(bp.get(pcm, sizeof(float) * (size_t)p_len));
+    return 0;
+}
+
+// Do the four chain streams of a pipelined batch (main, encoder side stream, AR, vocoder) each have a hardware queue of their own?  For
+// every unordered pair (X, Y), in the order (main, aux0) (main, sa) (main, sv) (aux0, sa) (aux0, sv) (sa, sv): a bounded waiter kernel on
+// X and, enqueued after it, a setter kernel on Y (stream_overlap.h); pair_ok[k] = 1 when the waiter saw the setter's store, 0 when it ran
+// into its 2 ms limit -- the two streams share a hardware queue.  Synchronises the device; the batch's own state is not touched.
+extern "C" int sva_test_stream_overlap(sva_batch* b, int* pair_ok) {
+    SVA_CHECK(b && pair_ok, "sva_test_stream_overlap: a batch and an output array of 6 ints");
+    SVA_CHECK(b->main_stream && b->aux[0] && b->sa && b->sv, "sva_test_stream_overlap: the batch is not pipelined (no AR / vocoder streams)");
+    SVA_HIP(hipSetDevice(b->e->device));
+    DevBuf words;
+    SVA_TRY(words.alloc(2 * sizeof(int)));
+    const hipStream_t st[4] = {b->main_stream, b->aux[0], b->sa, b->sv};
+    SVA_HIP(sva_overlap::pairs_of_four(st, words.as<int>(), pair_ok));
     return 0;
 }

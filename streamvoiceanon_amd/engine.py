@@ -16,9 +16,11 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # The engine overlaps its stages on four HIP streams (plus the process's default stream).  The runtime multiplexes streams
-# onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue serialise; a host application that wants
-# the pipelined throughput mode at its best exports GPU_MAX_HW_QUEUES=8 BEFORE the HIP runtime starts (bench.py does; see
-# INTEGRATION.md).  This module does not touch the process environment.  Measured: 382 -> 465 frames/s single-stream.
+# onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue serialise; the library gives its four
+# streams a hardware queue each by construction (two stream-priority levels: csrc/engine.hip get_streams), at any pool size:
+# 630 -> 1070 frames/s single-stream at the default pool of 4 (profiles/hw_queues_report.txt).  Exporting GPU_MAX_HW_QUEUES=8
+# BEFORE the HIP runtime starts (bench.py asks for it where the variable is unset) is harmless and no longer
+# needed; the name stays for callers that read it.  This module does not touch the process environment.
 RECOMMENDED_ENV = {"GPU_MAX_HW_QUEUES": "8"}
 
 LIB_PATH = os.environ.get("SVA_LIB_PATH") or os.path.join(_HERE, "libsva_hip.so")      # override: A/B builds of the kernels
@@ -80,6 +82,7 @@ def load_library():
     lib.sva_join_stream.argtypes = [vp, vp]
     lib.sva_batch_uses_persistent_decode.argtypes = [vp]
     lib.sva_test_force_ar_timeout.argtypes = [vp]
+    lib.sva_test_stream_overlap.argtypes = [vp, C.POINTER(C.c_int)]
     lib.sva_debug_configure.argtypes = [C.c_char_p]
     lib.sva_sync.argtypes = [vp]
     lib.sva_encode_window.argtypes = [vp, vp, vp, vp]
@@ -130,7 +133,7 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "sva_last_error", "sva_config_default", "sva_stream_params_default", "sva_engine_create",
     "sva_engine_load_weight", "sva_engine_finalize", "sva_engine_destroy", "sva_batch_create", "sva_batch_destroy",
-    "sva_prefill_prompt", "sva_streams_begin", "sva_stream_restart", "sva_stream_retire", "sva_stream_state", "sva_step", "sva_step_device", "sva_step_device_on", "sva_join_stream", "sva_batch_uses_persistent_decode", "sva_test_force_ar_timeout", "sva_debug_configure", "sva_sync", "sva_stream_chunks", "sva_encode_window", "sva_firefly_encode",
+    "sva_prefill_prompt", "sva_streams_begin", "sva_stream_restart", "sva_stream_retire", "sva_stream_state", "sva_step", "sva_step_device", "sva_step_device_on", "sva_join_stream", "sva_batch_uses_persistent_decode", "sva_test_force_ar_timeout", "sva_test_stream_overlap", "sva_debug_configure", "sva_sync", "sva_stream_chunks", "sva_encode_window", "sva_firefly_encode",
     "sva_vocode_window", "sva_vocode_stream", "sva_vocode_reset", "sva_quantizer_decode", "sva_vocoder_head", "sva_ar_delay_fill", "sva_ar_decode_one", "sva_generate", "sva_get_tap", "sva_get_timings",
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
@@ -463,6 +466,14 @@ class Batch:
 
     def uses_persistent_decode(self):
         return self.decode_path() != 0
+
+    STREAM_PAIRS = ("main|aux0", "main|sa", "main|sv", "aux0|sa", "aux0|sv", "sa|sv")
+
+    def stream_overlap(self):
+        """{pair: bool} for the six pairs of the pipelined batch's chain streams: True = the two run concurrently (a hardware queue each)."""
+        ok = (C.c_int * 6)()
+        _check(self.lib.sva_test_stream_overlap(self.h, ok), "sva_test_stream_overlap")
+        return {n: bool(v) for n, v in zip(self.STREAM_PAIRS, ok)}
 
     def join_stream(self, stream=None):
         if stream is None:
