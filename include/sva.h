@@ -299,13 +299,19 @@ int sva_set_sampler_edits(sva_batch* b, const int32_t* previous_tokens, int W, f
 /* kernel unit-test hook: C = A[M,K] * W[N,K]^T (+bias) through the conv-GEMM kernel (host arrays) */
 int sva_test_gemm(int device, int M, int N, int K, const float* A, const float* W, const float* bias, float* C);
 
-/* same through one specific dispatch choice of the GEMM dispatcher (kind 0: small-M K-split kernel, a = 16-row tiles per
- * workgroup, b = K-split waves, c = 16-column tiles per wave; kind 1: LDS-tiled f32-MFMA kernel, a = tile variant 0..7; kind 2: the
- * small-M kernel with its K axis also split over c >> 4 workgroups (fence-free tagged hand-off), c & 15 = column tiles, launched
- * twice; kind 3: the register-staged pipelined f32-MFMA kernel (gemm_pipe.hip), a = tile variant 0..6, needs K % 64 == 0; kind 4: the
- * six-product split-bf16 kernel (gemm_split.hip), a = tile variant 0..4, needs 16-byte aligned operands) */
+/* same through one given plan instead of the dispatcher's: kind 0 / 1 / 3 / 4 / 7 = GemmFamily SmallM / Tiled / Ring / Split / Stream
+ * (csrc/sva_common.h, where the parameters a, b, c of each family are documented); kind 2: SmallM with its K axis also split over c >> 4
+ * workgroups, c & 15 = column tiles, launched twice; kind 6: Planes / PlanesDma, a = tile variant */
 int sva_test_gemm_choice(int device, int M, int N, int K, const float* A, const float* W, const float* bias, float* C, int kind,
                          int a, int b, int c);
+/* The dispatcher's decision for a problem, without launching it and without a GPU.  desc: n = 1..3 group members x 12 ints
+ *   {B, T, N, Cin, taps, stride, dil, flags, operands, pmode, misaligned, 0}
+ *   flags bits: 1 bias, 2 gamma, 4 residual, 8 GELU, 16 a_silu, 32 w13, 64 accumulate, 128 rms_w, 256 dw_wT (+ dw_b, ln_w, ln_b), 512 cp_silu
+ *   operands bits: 1 Wk, 2 Wh, 4 Wkh, 8 Wp, 16 Ap, 32 Cp (planes over the tensor's dense rows); pmode: -1, 1 = H3, 2 = H1
+ *   misaligned bits: 1 A (a_off), 2 C (ldc), 4 residual (ldr) not a multiple of 4 floats
+ * out[6] = {family (GemmFamily of csrc/sva_common.h), a, b, c, z, family number of the profiling tables}; an error (sva_last_error) where the
+ * dispatcher refuses the problem. */
+int sva_test_gemm_plan(const int* desc, int n, int* out);
 /* fp16-weight GEMM of the batched fp16 AR decode (csrc/gemm_f16w.hip; the reference's autocast(fp16) linear layers,
  * modules/dual_ar_stream.py:1168-1219): C = epi(A x fp16(W)^T), mode bits 1 = RMSNorm prologue, 2 = residual, 4 = SwiGLU pairs;
  * iters > 0 also returns the average microseconds per launch. */
@@ -385,9 +391,9 @@ int sva_test_sampler(int device, int variant, int rows, int V, const float* logi
 /* microbenchmark of the conv-GEMM dispatcher: conv over [B][(taps-1)*dil + T][Cin] -> [B][T][N]; mode bits:
  * 1 GELU, 2 gamma+residual, 4 SiLU-on-load, 8 SwiGLU (w13); returns avg microseconds per launch in out_us[0] */
 int sva_bench_gemm(int device, int B, int T, int N, int Cin, int taps, int dil, int mode, int iters, float* out_us);
-/* One dispatch choice of the same kernel family on device-resident random data with `nrot` rotating weight copies (cold weights); kind -1 = the
-   dispatcher, 0 / 1 / 2 / 4 / 6 = small-M / tiled / pipelined / split-bf16 / weight-streaming kernel with parameters (a, b, c) as in
-   csrc/testhooks.hip.  out[0] = us per launch eager, out[1] = replayed as one graph, out[2] = max |C - C_dispatcher|, out[3] = max |C_dispatcher|. */
+/* One given plan of the same dispatcher on device-resident random data with `nrot` rotating weight copies (cold weights); kind -1 = the
+   dispatcher, 0 / 1 / 2 / 4 = GemmFamily SmallM / Tiled / Ring / Split (csrc/sva_common.h), 6 = the weight-streaming kernel; parameters (a, b, c) as
+   in csrc/testhooks.hip.  out[0] = us per launch eager, out[1] = replayed as one graph, out[2] = max |C - C_dispatcher|, out[3] = max |C_dispatcher|. */
 int sva_bench_gemm_choice(int device, int B, int T, int N, int Cin, int taps, int dil, int mode, int kind, int a, int b, int c, int nrot, int iters,
                           float* out);
 

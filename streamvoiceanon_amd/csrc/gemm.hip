@@ -10,24 +10,12 @@
 // next tile's global loads are issued before the current tile's MFMAs and written to the other
 // LDS buffer after them (one barrier per K tile).
 #include "sva_common.h"
-#include <array>
-#include <map>
 #include <mutex>
 #include <unordered_map>
-#include <utility>
-#include <vector>
-#include <stdlib.h>
-#include <stdio.h>
 
 namespace sva {
 
 constexpr int KS_ERR_WORD = (1 << 16) - 1;      // last word of a stream's split-K arrival counters: set when a partial never arrived
-
-#define SVA_TRY_RC(expr)     \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -529,10 +517,6 @@ __global__ __launch_bounds__(64 * KW) void skinny_gemm_kernel(const ConvGemmGrou
     }
 }
 
-// set by launch_conv_gemm_group around the dispatch: the launchers then send the whole group (grid.z = members)
-static thread_local const ConvGemmGroup* t_group = nullptr;
-// grid-level K split requested by the dispatch choice for the next small-M launch
-static thread_local int t_ksplit = 1;
 // split-K scratch (partial tiles + arrival counters), one per stream: launches on one stream are ordered, so they can
 // share it; concurrent streams must not
 struct KsScratch { float* ws = nullptr; unsigned* cnt = nullptr; };
@@ -587,13 +571,13 @@ int conv_gemm_prepare_stream(hipStream_t st) {
 }
 
 template <int MT, int NT, int KW, int D, int AOP>
-static int launch_skinny_op(const ConvGemm& g, hipStream_t st) {
+static int launch_skinny_op(const ConvGemmGroup& gin, int z, hipStream_t st) {
+    const ConvGemm& g = gin.g[0];
     const size_t smem = ((size_t)KW * MT * NT * 256 + (AOP == 2 ? KW * MT * 16 : 0) + (AOP == 3 ? (size_t)16 * MT * (g.Cin + 4) : 0)) * sizeof(float);
-    ConvGemmGroup gg;
-    if (t_group) gg = *t_group; else gg.g[0] = g;
+    ConvGemmGroup gg = gin;
     dim3 grid((g.N + 16 * NT - 1) / (16 * NT), (g.M + 16 * MT - 1) / (16 * MT), gg.n);
     if (gg.n == 1) {
-        int Z = AOP == 2 ? 1 : t_ksplit;                  // (the fused RMSNorm needs the whole row in one workgroup)
+        int Z = AOP == 2 ? 1 : z;                         // grid-level K split of the plan (the fused RMSNorm needs the whole row in one workgroup)
         const long nkb = (long)g.taps * g.Cin / 16;
         if (Z > nkb) Z = (int)nkb;
         const size_t tiles = (size_t)grid.x * grid.y;
@@ -612,14 +596,15 @@ static int launch_skinny_op(const ConvGemm& g, hipStream_t st) {
     return 0;
 }
 template <int MT, int NT, int KW, int D>
-static int launch_skinny(const ConvGemm& g, hipStream_t st) {
+static int launch_skinny(const ConvGemmGroup& gg, int z, hipStream_t st) {
+    const ConvGemm& g = gg.g[0];
     if (g.dw_wT) {
-        if constexpr (MT == 1 && NT == 1) return launch_skinny_op<MT, NT, KW, D, 3>(g, st);
+        if constexpr (MT == 1 && NT == 1) return launch_skinny_op<MT, NT, KW, D, 3>(gg, z, st);
         else { set_error("conv_gemm: the fused ConvNeXt prologue runs on one 16-row tile"); return -1; }
     }
-    if (g.rms_w) return launch_skinny_op<MT, NT, KW, D, 2>(g, st);
-    if (g.a_silu) return launch_skinny_op<MT, NT, KW, D, 1>(g, st);
-    return launch_skinny_op<MT, NT, KW, D, 0>(g, st);
+    if (g.rms_w) return launch_skinny_op<MT, NT, KW, D, 2>(gg, z, st);
+    if (g.a_silu) return launch_skinny_op<MT, NT, KW, D, 1>(gg, z, st);
+    return launch_skinny_op<MT, NT, KW, D, 0>(gg, z, st);
 }
 
 #ifndef SVA_D18
@@ -632,51 +617,34 @@ static int launch_skinny(const ConvGemm& g, hipStream_t st) {
 #define SVA_D44 4
 #endif
 template <int NT>
-static int launch_cfg(const ConvGemm& g, hipStream_t st, int mt, int kw) {
+static int launch_cfg(const ConvGemmGroup& gg, int mt, int kw, int z, hipStream_t st) {
     if constexpr (NT == 4) {      // 64-column workgroups: rows x K-split waves in {16, 32, 64} x {4, 8}
         switch (mt) {
-            case 1: return kw == 8 ? launch_skinny<1, 4, 8, 4>(g, st) : launch_skinny<1, 4, 4, 4>(g, st);
-            case 2: return kw == 8 ? launch_skinny<2, 4, 8, 3>(g, st) : launch_skinny<2, 4, 4, 3>(g, st);
-            default: return kw == 8 ? launch_skinny<4, 4, 8, 2>(g, st) : launch_skinny<4, 4, 4, 2>(g, st);
+            case 1: return kw == 8 ? launch_skinny<1, 4, 8, 4>(gg, z, st) : launch_skinny<1, 4, 4, 4>(gg, z, st);
+            case 2: return kw == 8 ? launch_skinny<2, 4, 8, 3>(gg, z, st) : launch_skinny<2, 4, 4, 3>(gg, z, st);
+            default: return kw == 8 ? launch_skinny<4, 4, 8, 2>(gg, z, st) : launch_skinny<4, 4, 4, 2>(gg, z, st);
         }
     }
     switch (mt) {
         case 1:
-            if (kw == 16) return launch_skinny<1, NT, 16, SVA_D116>(g, st);
-            if (kw == 8) return launch_skinny<1, NT, 8, SVA_D18>(g, st);
-            return launch_skinny<1, NT, 4, SVA_D14>(g, st);
+            if (kw == 16) return launch_skinny<1, NT, 16, SVA_D116>(gg, z, st);
+            if (kw == 8) return launch_skinny<1, NT, 8, SVA_D18>(gg, z, st);
+            return launch_skinny<1, NT, 4, SVA_D14>(gg, z, st);
         case 2:
-            if (kw == 8) return launch_skinny<2, NT, 8, SVA_D28>(g, st);
-            return launch_skinny<2, NT, 4, SVA_D24>(g, st);
+            if (kw == 8) return launch_skinny<2, NT, 8, SVA_D28>(gg, z, st);
+            return launch_skinny<2, NT, 4, SVA_D24>(gg, z, st);
         case 3:
-            if (kw == 8) return launch_skinny<3, NT, 8, SVA_D28>(g, st);
-            return launch_skinny<3, NT, 4, SVA_D44>(g, st);
+            if (kw == 8) return launch_skinny<3, NT, 8, SVA_D28>(gg, z, st);
+            return launch_skinny<3, NT, 4, SVA_D44>(gg, z, st);
         default:
-            if (kw == 8) return launch_skinny<4, NT, 8, SVA_D48>(g, st);
-            return launch_skinny<4, NT, 4, SVA_D44>(g, st);
+            if (kw == 8) return launch_skinny<4, NT, 8, SVA_D48>(gg, z, st);
+            return launch_skinny<4, NT, 4, SVA_D44>(gg, z, st);
     }
-}
-// Heuristic choice of (rows per workgroup = 16*MT, K-split waves KW) for the small-M kernel.
-static void skinny_heuristic(const ConvGemm& g, int NT, int* mt_out, int* kw_out) {
-    const int mt_total = (g.M + 15) / 16;
-    const long nk = (long)g.taps * g.Cin / 16;
-    const long cols = (g.N + 16 * NT - 1) / (16 * NT);
-    int mt = mt_total < 4 ? mt_total : 4;
-    auto blocks = [&](int m) { return cols * ((mt_total + m - 1) / m); };
-    // Every row tile of a column block re-reads that block's weights.  Weight-heavy problems (AR layers at M = 64..128:
-    // the panel comes from HBM) keep the tallest workgroup; light ones (encoder at M = 128..160: the panel sits in L2)
-    // trade re-reads for >= ~1.5 workgroups per CU.  Tuned with tools/gemm_sweep4.py.
-    const bool heavy = (long)g.N * g.taps * g.Cin * 4 > (8L << 20);
-    if (heavy) { while (mt > 1 && blocks(mt) * 4 < 512) mt = mt > 2 ? 2 : 1; }
-    else       { while (mt > 1 && blocks(mt) < 384) mt = mt > 2 ? 2 : 1; }
-    int kw = 4;
-    while (kw < 8 && blocks(mt) * kw < 2048 && nk / (2 * kw) >= 2) kw *= 2;
-    if (kw == 8 && blocks(mt) * 8 < 512 && nk / 32 >= 2 && mt == 1) kw = 16;     // a handful of column blocks: split K deeper
-    *mt_out = mt; *kw_out = kw;
 }
 
 template <int BM, int BN, int WM, int WN, int BK>
-static int launch_t(const ConvGemm& g, hipStream_t st) {
+static int launch_t(const ConvGemmGroup& gin, hipStream_t st) {
+    const ConvGemm& g = gin.g[0];
     constexpr size_t smem_ab = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float);
     constexpr size_t smem_c = (size_t)BM * (BN + 4) * sizeof(float);          // epilogue staging tile reuses the buffers
     constexpr size_t smem = smem_ab > smem_c ? smem_ab : smem_c;
@@ -685,508 +653,36 @@ static int launch_t(const ConvGemm& g, hipStream_t st) {
         SVA_HIP(hipFuncSetAttribute((const void*)conv_gemm_kernel<BM, BN, WM, WN, BK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set.done();
     }
-    ConvGemmGroup gg;
-    if (t_group) gg = *t_group; else gg.g[0] = g;
+    ConvGemmGroup gg = gin;
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, gg.n);
     gg.xcd_swz = xcd_swizzle_for(grid.x, grid.y);
     hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BK>), grid, dim3(64 * WM * WN), smem, st, gg);
     return 0;
 }
 
-// One dispatch decision: kind 0 = small-M K-split kernel (a = rows/16 per workgroup, b = K-split waves, c = 16-column
-// tiles per wave); kind 1 = LDS-tiled kernel (a: 0 = 64x64, 1 = 128x128, 2 = 128x32, 3 = 256x16, 4 = 128x64, 5 = 64x128,
-// 6 = 256x64, 7 = 256x128 on 8 waves; 4..7 are reached through the autotuner only); kind 6 = weight-streaming kernel (gemm_stream.hip:
-// a = 16-row tiles, b = K-split waves, c = 16-column tiles per workgroup; reads the fragment-major weight copy when the problem carries one).
-struct Choice { int kind, a, b, c; int z = 1; };      // z: grid-level K split of the small-M kernel
-static thread_local int t_planes_mode = -1;              // set by launch_choice when the planes kernel took a kind-4 choice
-static thread_local int t_last_kind = -1;                // kernel family of this thread's latest dispatch (bench.py: per-pipe roofline)
-
-// Tile variant of the planes kernel (gemm_planes.hip) for a problem.  The candidates that ever win on the encoder's / vocoder's shapes
-// (tools/planes_bench.py, profiles/r04_planes_bench.txt) are 128 x 128 (two workgroups per CU) and 256 x 128 (eight waves, one per CU,
-// two thirds of the operand traffic); which one is a matter of how the tile count quantises over the 256 CUs.  In units of the time
-// T a CU needs for one 128 x 128 tile's worth of work when it is full: a round of 512 small tiles costs 2 T, a last round of <= 256
-// of them (one per CU) 1.3 T, a round of 256 large tiles 1.7 T.  The rule reproduces the measured winner of the two on all ten shapes.
-struct PlanesRow { int M, N, K, variant; };
-static const PlanesRow g_planes_table[] = {
-#include "planes_table.inc"
-};
-static int planes_variant(const ConvGemm& g, int group_n) {
-    // conv taps over A planes (the HiFiGAN levels' ResBlock convs, three branches per launch): only the LDS-DMA form reads them; its tile by
-    // the output width and by whether 128 x 128 tiles would fill the chip
-    if (g.Ap && (g.taps > 1 || group_n > 1 || g.cp_silu) && debug_options().planes_dma != 0) {
-        bool ok = planes_dma_conv_supported(g);
-        if (t_group) for (int i = 0; i < t_group->n; ++i) ok = ok && planes_dma_conv_supported(t_group->g[i]);
-        if (ok) {
-            const int dv = debug_options().voc_dma_variant;
-            if (g.N % 128 == 0 && (long)((g.M + 127) / 128) * (g.N / 128) * group_n >= 192) return dv >= 9 && dv <= 14 && dv != 12 ? dv : 11;       // (its loader-wave form: 66 / 61 -> 60 / 55 us per launch at C = 128, 64 streams)
-            return g.N == 64 && g.M * (long)group_n >= 3 * 8192 ? 13 : 14;
-        }
-    }
-    bool dma_ok = planes_dma_gemm_supported(g) && debug_options().planes_dma != 0;
-    if (group_n > 1) dma_ok = false;
-    // measured winners for the encoder's shapes (tools/planes_tune.py -> planes_table.inc; every variant computes the same accumulation per
-    // output, so the table is a speed choice only): the row with this (N, K) whose M is nearest, if within a quarter of it
-    if (group_n == 1 && g.taps == 1) {
-        const PlanesRow* best = nullptr;
-        for (const PlanesRow& r : g_planes_table)
-            if (r.N == g.N && r.K == g.Cin && (r.variant < 8 || dma_ok) &&
-                (!best || std::abs(r.M - g.M) < std::abs(best->M - g.M))) best = &r;
-        if (best && std::abs(best->M - g.M) * 4 <= g.M && (best->variant != 6 || g.M >= 256) &&
-            (g.M >= 128 || best->variant == 2 || best->variant == 3 || best->variant >= 9))
-            return best->variant >= 11 && debug_options().planes_lw == 0 ? 10 : best->variant;       // (A/B: the loader-wave forms off)
-    }
-    // both operands as planes, whole 128-column tiles, a shape outside the table: the persistent LDS-DMA form with 128 x 128 tiles and TWO
-    // workgroups per CU (variant 10: one workgroup's epilogue runs under the other's K steps) -- it wins or ties on every encoder shape at 64
-    // streams with the real epilogues (profiles/r05_planes_dma_bench.txt); 256 x 128 (8) never wins.  (Table vs this rule for the shapes
-    // the table holds: encoder stage 4.41 / 5.13 / 8.50 ms against 4.67 / 5.28 / 8.68 at 48 / 64 / 128 streams, pipelined frames/s equal.)
-    if (dma_ok && (long)((g.M + 127) / 128) * (g.N / 128) >= 64) return 10;
-    if (g.N < 128) return g.M >= 128 ? 1 : 3;
-    if (g.M < 128) return 2;
-    const long wg0 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * group_n, wg6 = (long)((g.M + 255) / 256) * ((g.N + 127) / 128) * group_n;
-    if (wg0 < 224) return 3;                // too few 128 x 128 tiles for the chip: 64 x 64 (the mid-size shapes of profiles/r04_planes_bench_small.txt)
-    if (g.M < 256) return 0;
-    const long rem = wg0 % 512;
-    const double t0 = (double)(wg0 / 512) * 2.0 + (rem == 0 ? 0.0 : rem <= 256 ? 1.3 : 2.0);
-    const double t6 = (double)((wg6 + 255) / 256) * 1.7;
-    if (t6 < t0) return 6;
-    return wg0 <= 768 ? 7 : 0;              // up to a round and a half of tiles: the 8-wave form of the same tile (four waves per SIMD overlap its phases better)
+// The two entry points of this file for the dispatcher (gemm_dispatch.hip); a single problem is a group of one.
+// small-M kernel: mt = rows / 16 per workgroup, kw = K-split waves, nt = 16-column tiles per wave, z = grid-level K split
+int launch_small_m_gemm(const ConvGemmGroup& gg, int mt, int kw, int nt, int z, hipStream_t st) {
+    return nt == 4 ? launch_cfg<4>(gg, mt, kw, z, st) : nt == 2 ? launch_cfg<2>(gg, mt, kw, z, st) : launch_cfg<1>(gg, mt, kw, z, st);
 }
-
-static int launch_choice(const ConvGemm& g, hipStream_t st, const Choice& ch) {
-    if (ch.kind == 4) {                 // fp32 on the bf16 matrix pipes, six-product split (gemm_split.hip), a = tile variant
-        ConvGemmGroup gg;
-        if (t_group) gg = *t_group; else gg.g[0] = g;
-        if (ch.a >= 8) {                // the kernel fed from pre-split operand planes (gemm_planes.hip), its tile variant a - 8
-            t_planes_mode = g.pmode + (ch.a - 8 >= 8 ? 2 : 0);          // (+ 2: its persistent LDS-DMA form)
-            return launch_planes_gemm(gg, ch.a - 8, st);
-        }
-        SVA_CHECK(!g.Ap && !g.Cp, "conv_gemm: operand planes need the planes kernel");
-        return launch_split_gemm(gg, ch.a, st);
-    }
-    if (ch.kind == 6) {                 // weight-streaming kernel (gemm_stream.hip): a = row tiles, b = K-split waves, c = column tiles per workgroup
-        SVA_CHECK(!t_group && stream_gemm_supported(g), "conv_gemm: the weight-streaming kernel takes single problems");
-        return launch_stream_gemm(g, g.Wk ? g.Wk : g.W, ch.a, ch.c, ch.b, g.Wk ? 2 : 0, 0, st);
-    }
-    if (ch.kind == 2) {                 // LDS-DMA ring kernel (gemm_pipe.hip), a = tile variant
-        ConvGemmGroup gg;
-        if (t_group) gg = *t_group; else gg.g[0] = g;
-        return launch_pipe_gemm(gg, ch.a, st);
-    }
-    if (ch.kind == 0) {
-        t_ksplit = ch.z;
-        const int rc = ch.c == 4 ? launch_cfg<4>(g, st, ch.a, ch.b) : ch.c == 2 ? launch_cfg<2>(g, st, ch.a, ch.b) : launch_cfg<1>(g, st, ch.a, ch.b);
-        t_ksplit = 1;
-        return rc;
-    }
-    const int bk = g.Cin % 64 == 0 ? 64 : (g.Cin % 32 == 0 ? 32 : 16);
-    switch (ch.a) {
-        case 3: return launch_t<256, 16, 4, 1, 16>(g, st);
-        case 2: return bk >= 32 ? launch_t<128, 32, 4, 1, 32>(g, st) : launch_t<128, 32, 4, 1, 16>(g, st);
-        case 1: return bk >= 32 ? launch_t<128, 128, 2, 2, 32>(g, st) : launch_t<128, 128, 2, 2, 16>(g, st);
-        case 4: return bk >= 32 ? launch_t<128, 64, 2, 2, 32>(g, st) : launch_t<128, 64, 2, 2, 16>(g, st);
-        case 5: return bk >= 32 ? launch_t<64, 128, 2, 2, 32>(g, st) : launch_t<64, 128, 2, 2, 16>(g, st);
-        case 6: return bk >= 32 ? launch_t<256, 64, 4, 1, 32>(g, st) : launch_t<256, 64, 4, 1, 16>(g, st);
-        case 7: return bk >= 32 ? launch_t<256, 128, 4, 2, 32>(g, st) : launch_t<256, 128, 4, 2, 16>(g, st);       // 8 waves, 64x64 per wave
+// LDS-tiled kernel: variant 0 = 64x64, 1 = 128x128, 2 = 128x32, 3 = 256x16, 4 = 128x64, 5 = 64x128, 6 = 256x64, 7 = 256x128 on 8 waves (4..7 are
+// reached through the autotuner only); the K tile is as deep as Cin allows
+int launch_tiled_gemm(const ConvGemmGroup& gg, int variant, hipStream_t st) {
+    const int Cin = gg.g[0].Cin;
+    const int bk = Cin % 64 == 0 ? 64 : (Cin % 32 == 0 ? 32 : 16);
+    switch (variant) {
+        case 3: return launch_t<256, 16, 4, 1, 16>(gg, st);
+        case 2: return bk >= 32 ? launch_t<128, 32, 4, 1, 32>(gg, st) : launch_t<128, 32, 4, 1, 16>(gg, st);
+        case 1: return bk >= 32 ? launch_t<128, 128, 2, 2, 32>(gg, st) : launch_t<128, 128, 2, 2, 16>(gg, st);
+        case 4: return bk >= 32 ? launch_t<128, 64, 2, 2, 32>(gg, st) : launch_t<128, 64, 2, 2, 16>(gg, st);
+        case 5: return bk >= 32 ? launch_t<64, 128, 2, 2, 32>(gg, st) : launch_t<64, 128, 2, 2, 16>(gg, st);
+        case 6: return bk >= 32 ? launch_t<256, 64, 4, 1, 32>(gg, st) : launch_t<256, 64, 4, 1, 16>(gg, st);
+        case 7: return bk >= 32 ? launch_t<256, 128, 4, 2, 32>(gg, st) : launch_t<256, 128, 4, 2, 16>(gg, st);       // 8 waves, 64x64 per wave
         default:
-            if (bk == 64) return launch_t<64, 64, 2, 2, 64>(g, st);
-            if (bk == 32) return launch_t<64, 64, 2, 2, 32>(g, st);
-            return launch_t<64, 64, 2, 2, 16>(g, st);
+            if (bk == 64) return launch_t<64, 64, 2, 2, 64>(gg, st);
+            if (bk == 32) return launch_t<64, 64, 2, 2, 32>(gg, st);
+            return launch_t<64, 64, 2, 2, 16>(gg, st);
     }
-}
-
-// tile variant of the ring kernel for an under-filled grid: the largest tile that still gives every CU of a partition work
-static int pipe_variant(const ConvGemm& g) {
-    auto tiles = [&](int bm, int bn) { return (long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn); };
-    if (tiles(128, 64) >= 192) return 2;
-    if (tiles(64, 64) >= 160) return 1;
-    if (tiles(32, 64) >= 96 || g.N % 64 == 0) return 0;
-    return 6;
-}
-
-static Choice heuristic_choice(const ConvGemm& g, bool c_vec) {
-    // MFMA-bound problems outside the tuned table (batch sizes the tuning runs did not visit): the split-bf16 kernel, tile shape by
-    // the rule the table shows -- wave-specialised 128x128 for narrow outputs with a long K, plain 128x128 otherwise, 64x64 for N < 128
-    if (c_vec && split_gemm_supported(g) && g.M >= 2048 && g.N >= 64) {
-        if (g.N < 128) return Choice{4, 3, 0, 0};
-        const long K = (long)g.taps * g.Cin;
-        return Choice{4, (g.N <= 512 && K >= 1024) ? 4 : 0, 0, 0};
-    }
-    {
-        const long t64 = (long)((g.M + 63) / 64) * ((g.N + 63) / 64);
-        if (c_vec && pipe_gemm_supported(g) && g.M >= 32 && g.N >= 32 && t64 < 1024) return Choice{2, pipe_variant(g), 0, 0};
-    }
-    // the K tile is as deep as Cin allows (bytes in flight per workgroup hide the L2/HBM latency of the register-staged
-    // pipeline); 128x128 tiles only when they still fill the 256 CUs
-    const long big = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
-    // under-filled grids (fewer than ~1 tiled workgroup per CU): the barrier-free K-split kernel keeps far more
-    // loads in flight per CU than the LDS-staged one and pays for it with extra L2 reads, which are cheap there
-    const long tiles64 = (long)((g.M + 63) / 64) * ((g.N + 63) / 64);
-    if (g.M <= 64 || (tiles64 < 256 && g.N >= 64) || !c_vec) {      // (the tiled epilogue needs 16-byte aligned C rows)
-        // two 16-column tiles per wave halve the A re-reads; worth it once the A panel dominates the L2 traffic
-        const bool nt2 = g.w13 || (g.N % 32 == 0 && g.M >= 512 && (long)g.M * g.N >= 256L * 1024);
-        Choice ch{0, 1, 4, nt2 ? 2 : 1};
-        skinny_heuristic(g, ch.c, &ch.a, &ch.b);
-        // A workgroup ingests 16*(MT + NT) rows of K floats and a CU sustains only ~40 GB/s of loads (tools/gemm_kscale.py:
-        // time grows with K alone), so when the tiles do not cover the 256 CUs the K axis is split over more workgroups
-        const long wgs = (long)((g.N + 16 * ch.c - 1) / (16 * ch.c)) * (((g.M + 15) / 16 + ch.a - 1) / ch.a);
-        const long nkb = (long)g.taps * g.Cin / 16;
-        while (ch.z < 8 && wgs * ch.z * 2 <= 256 && nkb / (2L * ch.z * ch.b) >= 2) ch.z *= 2;
-        return ch;
-    }
-    if (g.N <= 16 && !g.w13) return Choice{1, 3, 0, 0};
-    if (g.N <= 32) return Choice{1, 2, 0, 0};
-    // 128x128 tiles only when their last (partial) round over the 256 CUs does not cost more than the lower operand
-    // reuse of 64x64 tiles (e.g. 320 big tiles = 2 rounds for 1.25 rounds of work)
-    if (big >= 256 && ((big + 255) / 256) * 4.0 <= ((tiles64 + 255) / 256) * 1.25) return Choice{1, 1, 0, 0};
-    return Choice{1, 0, 0, 0};
-}
-
-static std::mutex g_tune_mu;
-static std::map<std::array<int, 6>, Choice> g_tune;      // (M, N, K, taps, epilogue / prologue flags, stride)
-// compiled-in per-shape choices: the outcome of an offline tuning run (tools/make_tune_table.py -> tune_table.inc), so the
-// default dispatch is a pure function of the problem shape
-struct TuneRow { int key[6]; int kind, a, b, c, z; };
-static const TuneRow kTuneTable[] = {
-#include "tune_table.inc"
-    {{0, 0, 0, 0, 0, 0}, -1, 0, 0, 0, 1}};
-static const std::map<std::array<int, 6>, Choice>& static_table() {
-    static const std::map<std::array<int, 6>, Choice> m = [] {
-        std::map<std::array<int, 6>, Choice> t;
-        if (!debug_options().tune_table) return t;
-        for (const TuneRow& r : kTuneTable) {
-            if (r.kind < 0 || !((debug_options().tune_kinds >> r.kind) & 1)) continue;
-            Choice c{r.kind, r.a, r.b, r.c};
-            c.z = r.z;
-            t[{r.key[0], r.key[1], r.key[2], r.key[3], r.key[4], r.key[5]}] = c;
-        }
-        return t;
-    }();
-    return m;
-}
-// SVA_DEBUG=tune_dump=<file>: the shapes tuned by this process (autotune=1) are appended as table rows when the library unloads
-static void dump_tune_table() {
-    if (debug_options().tune_dump.empty()) return;
-    FILE* f = fopen(debug_options().tune_dump.c_str(), "a");
-    if (!f) return;
-    for (const auto& kv : g_tune)
-        fprintf(f, "{{%d, %d, %d, %d, %d, %d}, %d, %d, %d, %d, %d},\n", kv.first[0], kv.first[1], kv.first[2], kv.first[3], kv.first[4], kv.first[5],
-                kv.second.kind, kv.second.a, kv.second.b, kv.second.c, kv.second.z);
-    fclose(f);
-}
-static const int g_tune_dump_registered = (atexit(dump_tune_table), 0);
-static float* g_tune_c = nullptr;
-static size_t g_tune_elems = 0;
-
-static int launch_conv_gemm_impl(const ConvGemm& g, hipStream_t st, int group_n);
-int launch_conv_gemm(const ConvGemm& g, hipStream_t st) { return launch_conv_gemm_impl(g, st, 1); }
-
-int launch_conv_gemm_group(const ConvGemm* gs, int n, hipStream_t st) {
-    SVA_CHECK(n >= 1 && n <= 3, "conv_gemm_group: 1..3 members");
-    if (n == 1) return launch_conv_gemm_impl(gs[0], st, 1);
-    ConvGemmGroup gg;
-    gg.n = n;
-    int lead = 0;
-    for (int i = 0; i < n; ++i) {
-        const ConvGemm& a = gs[i];
-        const ConvGemm& r = gs[0];
-        SVA_CHECK(a.M == r.M && a.T == r.T && a.N == r.N && a.Cin == r.Cin && a.stride == r.stride && a.a_silu == r.a_silu && a.w13 == r.w13 &&
-                  a.act == r.act && a.accumulate == r.accumulate && !a.rms_w && a.ldc % 4 == r.ldc % 4 && (a.res != nullptr) == (r.res != nullptr) &&
-                  (a.gamma != nullptr) == (r.gamma != nullptr) && (a.bias != nullptr) == (r.bias != nullptr),
-                  "conv_gemm_group: members must share shape and epilogue");
-        SVA_CHECK(a.lda % 4 == 0 && a.a_off % 4 == 0 && a.a_bstride % 4 == 0 && a.c_off % 4 == r.c_off % 4 && a.c_bstride % 4 == r.c_bstride % 4 &&
-                  (!a.res || (a.ldr % 4 == r.ldr % 4 && a.r_off % 4 == r.r_off % 4 && a.r_bstride % 4 == r.r_bstride % 4)),
-                  "conv_gemm_group: alignment classes must match");
-        gg.g[i] = a;
-        if (a.taps > gs[lead].taps) lead = i;
-    }
-    t_group = &gg;                       // the dispatch decision is taken for (and timed on) the member with the longest K
-    const int rc = launch_conv_gemm_impl(gs[lead], st, n);
-    t_group = nullptr;
-    return rc;
-}
-
-static int launch_conv_gemm_impl(const ConvGemm& g, hipStream_t st, int group_n) {
-    SVA_CHECK(g.Cin % 16 == 0 && g.Cin > 0, "conv_gemm: Cin must be a multiple of 16");
-    // decode-sized linear layers of an fp16-weight AR: stream the fp16 weights (half the bytes of the fp32 copy) through the f16 pipes
-    if (g.Wh && group_n == 1 && g.M <= 256 && debug_options().f16_weights && (f16w_gemm_validated_compiler() || debug_options().f16_weights == 2) &&
-        f16w_gemm_supported(g)) {
-        t_last_kind = 5;
-        return launch_f16w_gemm(g, st);
-    }
-    SVA_CHECK(g.lda % 4 == 0 && (g.a_off % 4) == 0 && (g.a_bstride % 4) == 0, "conv_gemm: A must be float4-aligned");
-    const bool c_vec = g.N % 4 == 0 && g.ldc % 4 == 0 && g.c_off % 4 == 0 && g.c_bstride % 4 == 0 &&
-                       (!g.res || (g.ldr % 4 == 0 && g.r_off % 4 == 0 && g.r_bstride % 4 == 0));
-    SVA_CHECK(g.M > 0 && g.N > 0 && g.T > 0, "conv_gemm: empty problem");
-    if (g.w13) SVA_CHECK(g.N % 32 == 0, "conv_gemm: w13 needs N % 32 == 0");
-    if (g.rms_w) SVA_CHECK(g.taps == 1 && !g.a_silu && conv_gemm_can_fuse_rms(g.M, g.N), "conv_gemm: fused RMSNorm needs taps == 1 on the small-M path");
-    if (g.dw_wT) SVA_CHECK(g.taps == 1 && g.M <= 16 && g.Cin <= 512 && !g.a_silu && !g.rms_w && !g.w13 && group_n == 1 && g.dw_b && g.ln_w && g.ln_b,
-                           "conv_gemm: the fused ConvNeXt prologue needs taps == 1, M <= 16, Cin <= 512");
-    // A layer that carries the fp16 fragment-major packing (the content encoder of an enc_dtype = 1 engine) runs on fp16 operands only: the planes
-    // kernel in H1 under its existing rule (operands handed over as planes, or >= 1024 rows), the fp16 weight-streaming kernel otherwise --
-    // never an fp32 kind; no table, no timed search
-    if (g.Wkh) {
-        SVA_CHECK(group_n == 1 && !t_group, "conv_gemm: fp16-operand layers take single problems");
-        const bool want = g.Ap || g.Cp || (g.pmode == PLANES_H1 && g.M >= 1024 && g.N >= 32);
-        if (want && c_vec && g.pmode == PLANES_H1 && planes_gemm_supported(g)) {
-            t_planes_mode = -1;
-            SVA_TRY_RC(launch_choice(g, st, Choice{4, 8 + planes_variant(g, 1), 0, 0}));
-            t_last_kind = 6 + t_planes_mode;
-        } else {
-            SVA_CHECK(!g.Ap && !g.Cp, "conv_gemm: operand planes handed to a problem the planes kernel does not take");
-            SVA_CHECK(stream_h_gemm_supported(g), "conv_gemm: an fp16-operand layer that neither the planes kernel nor the fp16 weight-streaming kernel takes");
-            SVA_TRY_RC(launch_stream_h_gemm(g, 0, 0, 0, st));
-            t_last_kind = 11;
-        }
-        SVA_HIP(hipGetLastError());
-        return 0;
-    }
-    Choice ch = heuristic_choice(g, c_vec);
-    const unsigned long long key_flags = (unsigned long long)(g.a_silu ? 1 : 0) | (g.rms_w ? 2 : 0) | (g.w13 ? 4 : 0) | (c_vec ? 8 : 0) | (g.accumulate ? 16 : 0) |
-                                         (group_n > 1 ? 32 : 0) | (g.dw_wT ? 64 : 0);
-    {
-        const auto& tab = static_table();
-        auto it = tab.find({g.M, g.N, g.taps * g.Cin, g.taps, (int)key_flags, g.stride});
-        // a decode-sized row count between two tabulated ones (40 or 44 streams: the table holds 36 and 48) takes the choice of the next larger one within
-        // 1.5 x -- every kernel handles partial row tiles, and the heuristic's pick there measured 20 % slower (AR stage 4.7 ms at 40 / 44 streams, 3.8 at 48)
-        // (the scan is memoised per shape -- ADVICE r05: an untabulated shape paid up to M / 2 map look-ups on every launch)
-        if (it == tab.end() && g.M >= 8 && g.M <= 512) {
-            static std::mutex memo_mu;
-            static std::map<std::array<int, 6>, int> memo;            // shape -> the tabulated row count it borrows (0: none)
-            const std::array<int, 6> key{g.M, g.N, g.taps * g.Cin, g.taps, (int)key_flags, g.stride};
-            int borrowed = -1;
-            {
-                std::lock_guard<std::mutex> lk(memo_mu);
-                auto mi = memo.find(key);
-                if (mi != memo.end()) borrowed = mi->second;
-            }
-            if (borrowed < 0) {
-                borrowed = 0;
-                for (int m = g.M + 1; m <= g.M + g.M / 2; ++m)
-                    if (tab.find({m, g.N, g.taps * g.Cin, g.taps, (int)key_flags, g.stride}) != tab.end()) { borrowed = m; break; }
-                std::lock_guard<std::mutex> lk(memo_mu);
-                memo[key] = borrowed;
-            }
-            if (borrowed > 0) it = tab.find({borrowed, g.N, g.taps * g.Cin, g.taps, (int)key_flags, g.stride});
-        }
-        if (it != tab.end()) {
-            // the table is keyed by shape only; the pipelined / split kernels also need aligned operands (a seam such as sva_op_conv can
-            // present a tuned shape with other strides): keep the tuned choice only if its kernel accepts THIS problem
-            const Choice& tc = it->second;
-            const bool ok = (tc.kind == 2) ? (c_vec && pipe_gemm_supported(g)) : (tc.kind == 4) ? (c_vec && split_gemm_supported(g)) :
-                            (tc.kind == 6) ? (group_n == 1 && stream_gemm_supported(g) && (g.M + 16 * tc.a - 1) / (16 * tc.a) * (long)((g.N + 16 * tc.c - 1) / (16 * tc.c)) < 65536) :
-                            (tc.kind == 1 ? c_vec || tc.a == 0 : true);
-            if (ok) ch = tc;
-        }
-    }
-    // Deterministic by default: the kernel / configuration of a problem shape comes from the compiled-in table (tune_table.inc,
-    // generated offline from a logged tuning run) or the heuristic -- never from wall-clock measurements of this process, so two
-    // processes, ranks or runs sum in the same order.  SVA_DEBUG=autotune=1 re-enables the timed search (tools/make_tune_table.py uses it).
-    static const bool tune = debug_options().autotune != 0;
-    if (tune && !g.Ap && !g.Cp) {          // (a problem whose operands are planes has one kernel family: its variant comes from planes_table.inc)
-        // Shape-keyed autotune: the first eager launch of a problem shape times the candidate kernels / configurations on
-        // the real operands with the output redirected to scratch, and keeps a candidate only if it beats the heuristic
-        // by > 7 %.  Launches inside a stream capture (and shapes first seen there) use the heuristic.
-        const unsigned long long flags = (unsigned long long)(g.a_silu ? 1 : 0) | (g.rms_w ? 2 : 0) | (g.w13 ? 4 : 0) | (c_vec ? 8 : 0) | (g.accumulate ? 16 : 0) |
-                                         (group_n > 1 ? 32 : 0) | (g.dw_wT ? 64 : 0);
-        const std::array<int, 6> key = {g.M, g.N, g.taps * g.Cin, g.taps, (int)flags, g.stride};
-        std::lock_guard<std::mutex> lk(g_tune_mu);
-        auto it = g_tune.find(key);
-        if (it != g_tune.end()) ch = it->second;
-        else {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
-                const int ldc = g.w13 ? g.N / 2 : g.N;
-                const size_t need = (size_t)g.M * ldc * (size_t)group_n;
-                if (need > g_tune_elems) {
-                    if (g_tune_c) (void)hipFree(g_tune_c);
-                    SVA_HIP(hipMalloc((void**)&g_tune_c, need * sizeof(float)));
-                    g_tune_elems = need;
-                }
-                ConvGemm t = g;
-                t.C = g_tune_c; t.c_bstride = (long)g.T * ldc; t.c_off = 0; t.ldc = ldc;
-                // a group is timed as a group, every member's output redirected to its own scratch slab
-                const ConvGemmGroup* real_group = t_group;
-                ConvGemmGroup tg;
-                if (real_group) {
-                    tg = *real_group;
-                    for (int i = 0; i < tg.n; ++i) {
-                        tg.g[i].C = g_tune_c + (size_t)i * g.M * ldc; tg.g[i].c_bstride = (long)g.T * ldc; tg.g[i].c_off = 0; tg.g[i].ldc = ldc;
-                    }
-                    t_group = &tg;
-                }
-                hipEvent_t e0, e1;
-                SVA_HIP(hipEventCreate(&e0)); SVA_HIP(hipEventCreate(&e1));
-                // measured alone on the device (other streams drained first) and as the better of two batches: the pick should
-                // not depend on what happened to run beside the probe
-                SVA_HIP(hipDeviceSynchronize());
-                auto time_choice = [&](const Choice& c, float* ms) -> int {
-                    SVA_TRY_RC(launch_choice(t, st, c));
-                    float best_ms = 1e30f;
-                    for (int rep = 0; rep < 2; ++rep) {
-                        SVA_HIP(hipEventRecord(e0, st));
-                        for (int r = 0; r < 5; ++r) SVA_TRY_RC(launch_choice(t, st, c));
-                        SVA_HIP(hipEventRecord(e1, st));
-                        SVA_HIP(hipEventSynchronize(e1));
-                        float m = 0.f;
-                        SVA_HIP(hipEventElapsedTime(&m, e0, e1));
-                        if (m < best_ms) best_ms = m;
-                    }
-                    *ms = best_ms;
-                    return 0;
-                };
-                std::vector<Choice> cand;
-                const long tiles64 = (long)((g.M + 63) / 64) * ((g.N + 63) / 64);
-                const bool must_skinny = g.rms_w || g.dw_wT || !c_vec;
-                if (must_skinny || tiles64 < 1024) {
-                    const int mt_total = (g.M + 15) / 16;
-                    const long nk = (long)g.taps * g.Cin / 16;
-                    for (int nt = 1; nt <= 4; nt *= 2) {
-                        if (g.w13 && nt == 1) continue;
-                        if (nt == 2 && (g.N % 32 != 0 || g.dw_wT)) continue;
-                        if (nt == 4 && (g.N % 64 != 0 || g.dw_wT || g.M < 32)) continue;       // 64-column workgroups: a third of the operand reads per output
-                        const int mts[3] = {1, 2, 4}, kws[3] = {4, 8, 16};
-                        for (int a = 0; a < 3; ++a)
-                            for (int b2 = 0; b2 < 3; ++b2) {
-                                if (mts[a] > mt_total || (mts[a] >= 2 && kws[b2] == 16) || nk / kws[b2] < 1) continue;
-                                if (nt == 4 && kws[b2] == 16) continue;
-                                cand.push_back(Choice{0, mts[a], kws[b2], nt});
-                                if (g.rms_w || group_n > 1) continue;
-                                const long wgs = (long)((g.N + 16 * nt - 1) / (16 * nt)) * ((mt_total + mts[a] - 1) / mts[a]);
-                                for (int z = 2; z <= 8; z *= 2)
-                                    if (wgs * z <= 512 && nk / ((long)z * kws[b2]) >= 1) cand.push_back(Choice{0, mts[a], kws[b2], nt, z});
-                            }
-                    }
-                }
-                if (!must_skinny) {
-                    if (g.N > 32) cand.push_back(Choice{1, 0, 0, 0});
-                    if (g.M >= 128 && g.N >= 128) cand.push_back(Choice{1, 1, 0, 0});
-                    if (g.M >= 128 && g.N >= 64) cand.push_back(Choice{1, 4, 0, 0});
-                    if (g.M >= 64 && g.N >= 128) cand.push_back(Choice{1, 5, 0, 0});
-                    if (g.M >= 256 && g.N >= 64) cand.push_back(Choice{1, 6, 0, 0});
-                    if (g.M >= 256 && g.N >= 128) cand.push_back(Choice{1, 7, 0, 0});
-                    if (g.N <= 64) cand.push_back(Choice{1, 2, 0, 0});
-                    if (g.N <= 16 && !g.w13) cand.push_back(Choice{1, 3, 0, 0});
-                }
-                if (group_n == 1 && stream_gemm_supported(g) && g.M <= 512 && !g.dw_wT && g.N >= 16) {
-                    // weight-streaming kernel: (row tiles, column tiles, K-split waves) per workgroup
-                    const int mt_total = (g.M + 15) / 16;
-                    const int cfgs[15][3] = {{1, 1, 4}, {1, 1, 8}, {1, 1, 16}, {2, 1, 4}, {2, 1, 8}, {2, 1, 16}, {4, 1, 4}, {4, 1, 8},
-                                             {1, 2, 4}, {1, 2, 8}, {1, 2, 16}, {2, 2, 4}, {2, 2, 8}, {4, 2, 4}, {4, 2, 8}};
-                    for (const auto& cf : cfgs) {
-                        if (cf[0] > mt_total || (g.w13 && cf[1] != 2) || (cf[1] == 2 && g.N % 32 != 0)) continue;
-                        cand.push_back(Choice{6, cf[0], cf[2], cf[1]});
-                    }
-                }
-                if (c_vec && pipe_gemm_supported(g) && g.M >= 32 && g.N >= 32)
-                    for (int v = 0; v <= 6; ++v) {
-                        if (v == 4 && (g.M < 128 || g.N < 128)) continue;
-                        if ((v == 2 && g.M < 128) || ((v == 3 || v == 5) && g.N < 128)) continue;
-                        cand.push_back(Choice{2, v, 0, 0});
-                    }
-                if (c_vec && split_gemm_supported(g) && g.M >= 64 && g.N >= 64)
-                    for (int v = 0; v <= 4; ++v) {
-                        if ((v == 0 || v == 1 || v == 4) && g.M < 128) continue;
-                        if ((v == 0 || v == 2 || v == 4) && g.N < 128) continue;
-                        cand.push_back(Choice{4, v, 0, 0});
-                    }
-                float base = 0.f;
-                SVA_TRY_RC(time_choice(ch, &base));
-                float best = base * 0.93f;
-                for (const Choice& c : cand) {
-                    if (c.kind == ch.kind && c.a == ch.a && c.b == ch.b && c.c == ch.c && c.z == ch.z) continue;
-                    float ms = 0.f;
-                    SVA_TRY_RC(time_choice(c, &ms));
-                    if (ms < best) { best = ms; ch = c; }
-                }
-                (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-                t_group = real_group;
-                static const bool tlog = debug_options().tune_log != 0;
-                if (tlog)
-                    fprintf(stderr, "[sva tune] M=%d N=%d K=%d taps=%d flags=%llu: heuristic %.1f us -> kind %d (%d,%d,%d) z%d %.1f us\n", g.M, g.N,
-                            g.taps * g.Cin, g.taps, flags, base * 200.f, ch.kind, ch.a, ch.b, ch.c, ch.z, (best < base * 0.93f ? best : base) * 200.f);
-                g_tune[key] = ch;
-            }
-        }
-    }
-    // Weights that carry pre-split planes (gemm_planes.hip).  fp16 x 1 (a voc_dtype = 1 vocoder): one product per block instead of the
-    // six or eight of any fp32-grade kernel -- every problem with enough rows to fill its tiles.  fp32-grade planes (fp16 x 2, bf16 x 3):
-    // where the split kernels are the choice anyway and the batch is large enough for the 128-row tiles to fill the chip (measured:
-    // with its tile variant from the measured table it beats the tuned in-loop split kernels on 38 of 40 mid-size shapes, by 5-60 %:
-    // profiles/r04_old_vs_planes.txt (full chip); from 3072 rows = 24 streams -- below that the pipelined mode runs the encoder on a CU partition the old table was tuned for: 16 streams -2.6 %, 24 / 32 / 48 streams +1 / +1 / +8 %).  A
-    // problem whose operands only exist as planes has no other kernel.
-    {
-        bool planes = c_vec;
-        if (t_group) { for (int i = 0; i < t_group->n; ++i) planes = planes && planes_gemm_supported(t_group->g[i]); }
-        else planes = planes && planes_gemm_supported(g);
-        // (and the few 2048+-row problems of a 64-stream batch that the table gives to the f32-MFMA kernels: the C = 256 HiFiGAN level's
-        // grouped convs -- 5.6 GFLOP per launch at ~60 TF/s there)
-        const double gflop = 2e-9 * g.M * (double)g.N * g.taps * g.Cin * group_n;
-        const bool want = g.Ap || g.Cp ||
-                          (g.pmode == PLANES_H1 ? g.M >= 1024 && g.N >= 32 : g.N < 64 ? false : ((ch.kind == 4 && g.M >= 3072) || (ch.kind != 4 && g.M >= 2048 && g.N >= 128 && gflop >= 2.0)));
-        if (planes && want) ch = Choice{4, 8 + planes_variant(g, group_n), 0, 0};
-        else SVA_CHECK(!g.Ap && !g.Cp, "conv_gemm: operand planes handed to a problem the planes kernel does not take");
-    }
-    t_planes_mode = -1;
-    SVA_TRY_RC(launch_choice(g, st, ch));
-    t_last_kind = t_planes_mode >= 0 ? 6 + t_planes_mode : ch.kind;       // 7 / 8: planes kernel in H3 / H1, 9 / 10: its LDS-DMA form
-    SVA_HIP(hipGetLastError());
-    return 0;
-}
-
-int conv_gemm_last_kind() { return t_last_kind; }
-
-// test hook: run one specific dispatch choice (kind 0: a = rows/16, b = K split, c = column tiles; kind 1: a = tile variant)
-int launch_conv_gemm_choice(const ConvGemm& g, hipStream_t st, int kind, int a, int b, int c) {
-    SVA_CHECK(g.Cin % 16 == 0 && g.lda % 4 == 0, "conv_gemm_choice: alignment");
-    if (kind == 2) {
-        SVA_CHECK(pipe_gemm_supported(g) && a >= 0 && a <= 6, "conv_gemm_choice: the pipelined kernel needs Cin % 64 == 0 and 16-byte aligned operands");
-        SVA_TRY_RC(launch_choice(g, st, Choice{2, a, 0, 0}));
-        SVA_HIP(hipGetLastError());
-        return 0;
-    }
-    if (kind == 6) {                    // the planes kernel (gemm_planes.hip), a = its tile variant
-        SVA_CHECK(planes_gemm_supported(g) && a >= 0 && a <= 12 && a != 8 && (a < 8 || planes_dma_gemm_supported(g)) && g.N % 4 == 0 && g.ldc % 4 == 0, "conv_gemm_choice: the planes kernel needs weight planes, Cin % 32 == 0 and 16-byte aligned C rows");
-        SVA_TRY_RC(launch_choice(g, st, Choice{4, 8 + a, 0, 0}));
-        SVA_HIP(hipGetLastError());
-        return 0;
-    }
-    if (kind == 4) {
-        SVA_CHECK(split_gemm_supported(g) && a >= 0 && a <= 4 && g.N % 4 == 0 && g.ldc % 4 == 0, "conv_gemm_choice: the split-bf16 kernel needs Cin % 32 == 0 and 16-byte aligned C rows");
-        SVA_TRY_RC(launch_choice(g, st, Choice{4, a, 0, 0}));
-        SVA_HIP(hipGetLastError());
-        return 0;
-    }
-    if (kind == 7) {                    // the weight-streaming kernel (gemm_stream.hip): a = row tiles, b = K-split waves, c = column tiles
-        SVA_CHECK(stream_gemm_supported(g) && (a == 1 || a == 2 || a == 4) && (c == 1 || c == 2) && (b == 4 || b == 8 || (b == 16 && a * c <= 2)) && !(g.w13 && c != 2),
-                  "conv_gemm_choice: bad weight-streaming configuration");
-        SVA_TRY_RC(launch_choice(g, st, Choice{6, a, b, c}));
-        SVA_HIP(hipGetLastError());
-        return 0;
-    }
-    SVA_CHECK(kind == 0 || kind == 1, "conv_gemm_choice: kind");
-    if (kind == 0) SVA_CHECK((a == 1 || a == 2 || a == 3 || a == 4) && (b == 4 || b == 8 || (b == 16 && a == 1)) &&
-                                 (c == 1 || (c == 2 && g.N % 32 == 0) || (c == 4 && g.N % 64 == 0 && a != 3 && b != 16)),
-                             "conv_gemm_choice: bad small-M configuration");
-    else SVA_CHECK(a >= 0 && a <= 7 && g.N % 4 == 0 && g.ldc % 4 == 0, "conv_gemm_choice: bad tile variant");
-    SVA_TRY_RC(launch_choice(g, st, Choice{kind, a, b, c}));
-    SVA_HIP(hipGetLastError());
-    return 0;
-}
-int launch_conv_gemm_choice_z(const ConvGemm& g, hipStream_t st, int a, int b, int c, int z) {
-    SVA_CHECK(g.Cin % 16 == 0 && g.lda % 4 == 0, "conv_gemm_choice: alignment");
-    SVA_CHECK((a == 1 || a == 2 || a == 3 || a == 4) && (b == 4 || b == 8 || (b == 16 && a == 1)) &&
-                  (c == 1 || (c == 2 && g.N % 32 == 0) || (c == 4 && g.N % 64 == 0 && a != 3 && b != 16)) && z >= 1 && z <= 8,
-              "conv_gemm_choice: bad small-M configuration");
-    Choice ch{0, a, b, c};
-    ch.z = z;
-    SVA_TRY_RC(launch_choice(g, st, ch));
-    SVA_HIP(hipGetLastError());
-    return 0;
-}
-
-bool conv_gemm_can_fuse_rms(int M, int N) {
-    const long tiles64 = (long)((M + 63) / 64) * ((N + 63) / 64);
-    return M <= 64 || (tiles64 < 256 && N >= 64);
 }
 
 }  // namespace sva

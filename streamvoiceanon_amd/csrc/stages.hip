@@ -36,9 +36,10 @@ int gemm_call(sva_batch* b, const float* A, long a_bstride, long a_off, int lda,
         }
         b->prof_shapes.push_back({g.M, g.N, w.K, taps, g.w13 * 8 + g.a_silu * 4 + (g.res ? 2 : 0) + (g.act == ACT_GELU ? 1 : 0)});
         SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n], b->stream));
-        int rc = launch_conv_gemm(g, b->stream);
+        int kind = -1;
+        int rc = launch_conv_gemm(g, b->stream, &kind);
         SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n + 1], b->stream));
-        b->prof_shapes.back()[4] += 256 * (conv_gemm_last_kind() + 1);        // kernel family of the launch, for the per-pipe roofline
+        b->prof_shapes.back()[4] += 256 * (kind + 1);        // kernel family of the launch (plan_report_kind), for the per-pipe roofline
         b->prof_n += 2;
         return rc;
     }
@@ -99,9 +100,10 @@ int gemm_group_call(sva_batch* b, const ConvGemm* gs, int n) {
         for (int i = 0; i < n; ++i) ksum += gs[i].taps * gs[i].Cin;
         b->prof_shapes.push_back({gs[0].M, gs[0].N, ksum, tmax, 16 + gs[0].a_silu * 4 + (gs[0].res ? 2 : 0)});
         SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n], b->stream));
-        int rc = launch_conv_gemm_group(gs, n, b->stream);
+        int kind = -1;
+        int rc = launch_conv_gemm_group(gs, n, b->stream, &kind);
         SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n + 1], b->stream));
-        b->prof_shapes.back()[4] += 256 * (conv_gemm_last_kind() + 1);
+        b->prof_shapes.back()[4] += 256 * (kind + 1);
         b->prof_n += 2;
         return rc;
     }

@@ -77,6 +77,12 @@ struct DeviceOnce {
         }                                                                                    \
     } while (0)
 
+#define SVA_TRY_RC(expr)     \
+    do {                     \
+        int _rc = (expr);    \
+        if (_rc) return _rc; \
+    } while (0)
+
 #define SVA_CHECK(cond, msg)                                                       \
     do {                                                                           \
         if (!(cond)) {                                                             \
@@ -257,12 +263,37 @@ bool stream_h_gemm_supported(const ConvGemm& g);
 void stream_h_config(const ConvGemm& g, int* mt, int* nt, int* kw);
 int launch_stream_h_gemm(const ConvGemm& g, int mt, int nt, int kw, hipStream_t st);
 void stream_h_pack_weights(const float* W, int N, int K, std::vector<uint16_t>& out);
-int launch_conv_gemm(const ConvGemm& g, hipStream_t st);
-int conv_gemm_last_kind();          // kernel family the calling thread's latest launch_conv_gemm[_group] picked: 0 small-M, 1 tiled, 2 pipelined, 6 weight-streaming (f32 MFMA), 4 split-bf16, 5 fp16 weights (f16 MFMA), 7 / 8 planes H3 / H1, 9 / 10 their LDS-DMA form, 11 fp16-operand weight-streaming (gemm_stream_h.hip)
-int launch_conv_gemm_group(const ConvGemm* gs, int n, hipStream_t st);
-// true when launch_conv_gemm would route this (M, N) problem to the K-split small-M kernel, which can normalise its A rows
+// gemm.hip: the f32-MFMA kernels.  Small-M K-split kernel: mt = rows / 16 per workgroup, kw = K-split waves, nt = 16-column tiles per wave,
+// z = grid-level K split (single problems); LDS-tiled kernel: see launch_tiled_gemm for its tile variants
+int launch_small_m_gemm(const ConvGemmGroup& gg, int mt, int kw, int nt, int z, hipStream_t st);
+int launch_tiled_gemm(const ConvGemmGroup& gg, int variant, hipStream_t st);
+
+// gemm_dispatch.hip: which family runs a problem.  The meaning of a plan's parameters, per family (z = 1 unless stated):
+enum class GemmFamily : int {
+    SmallM,         // gemm.hip K-split kernel: a = rows / 16 per workgroup, b = K-split waves, c = 16-column tiles per wave, z = grid-level K split
+    Tiled,          // gemm.hip LDS-tiled kernel: a = tile variant (launch_tiled_gemm)
+    Ring,           // gemm_pipe.hip LDS-DMA ring kernel: a = tile variant (launch_pipe_gemm)
+    Split,          // gemm_split.hip fp32 on the bf16 pipes, six part products: a = tile variant (launch_split_gemm)
+    F16W,           // gemm_f16w.hip fp16 weights on the f16 pipes (ar_dtype = 1 decode); no parameters
+    Stream,         // gemm_stream.hip weight-streaming f32-MFMA kernel: a = 16-row tiles, b = K-split waves, c = 16-column tiles per workgroup
+    Planes,         // gemm_planes.hip operands as pre-split planes, register-staged tiles: a = tile variant 0 .. 7 (launch_planes_gemm)
+    PlanesDma,      // its persistent LDS-DMA form: a = tile variant 9 .. 14 (launch_planes_gemm)
+    StreamH,        // gemm_stream_h.hip fp16-operand weight-streaming kernel (enc_dtype = 1); configuration from stream_h_config
+};
+struct GemmPlan { GemmFamily family = GemmFamily::SmallM; int a = 0, b = 0, c = 0, z = 1; };
+// members checked and copied into a group; lead = the member the decision is taken for
+int conv_gemm_group_of(const ConvGemm* gs, int n, ConvGemmGroup* gg, int* lead);
+// the decision: a pure host function (no HIP call); an error where the dispatcher refuses the problem
+int plan_conv_gemm(const ConvGemmGroup& gg, int lead, GemmPlan* out);
+// the family number of a plan in the profiling tables (the only numbering of the families outside the enum); the five families of the timed
+// search carry the same number in tune_table.inc: a table row as a plan (false: no such kind)
+int plan_report_kind(const GemmPlan& p, int pmode);
+bool plan_from_table_kind(int kind, int a, int b, int c, int z, GemmPlan* out);
+// plan + launch; kind_out (optional): plan_report_kind of what ran
+int launch_conv_gemm(const ConvGemm& g, hipStream_t st, int* kind_out = nullptr);
+int launch_conv_gemm_group(const ConvGemm* gs, int n, hipStream_t st, int* kind_out = nullptr);
+// true when the planner routes an (M, N) problem to the K-split small-M kernel, which can normalise its A rows
 bool conv_gemm_can_fuse_rms(int M, int N);
-int launch_conv_gemm_choice(const ConvGemm& g, hipStream_t st, int kind, int a, int b, int c);   // unit-test hook
-int launch_conv_gemm_choice_z(const ConvGemm& g, hipStream_t st, int a, int b, int c, int z);        // small-M kernel with a grid-level K split
+int launch_conv_gemm_plan(const ConvGemm& g, const GemmPlan& p, hipStream_t st);        // test / bench hooks: one given plan, checked against the problem
 
 }  // namespace sva

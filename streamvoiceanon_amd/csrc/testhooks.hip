@@ -20,6 +20,14 @@ using namespace sva;
     } while (0)
 
 static int test_gemm_impl(int device, int M, int N, int K, const float* A, const float* W, const float* bias, float* C, const int* choice);
+// The kind numbers of sva_test_gemm_choice (include/sva.h) as plans.  The planes kernel's variants 0 .. 7 / 9 .. 14 are two families (GemmFamily).
+static GemmPlan test_choice_plan(int kind, int a, int b, int c) {
+    static const GemmFamily fam[8] = {GemmFamily::SmallM, GemmFamily::Tiled, GemmFamily::SmallM, GemmFamily::Ring, GemmFamily::Split, GemmFamily::SmallM,
+                                      GemmFamily::Planes, GemmFamily::Stream};
+    if (kind < 0 || kind > 7 || kind == 5) return GemmPlan{GemmFamily::SmallM, -1, 0, 0, 1};      // (no plan takes a = -1: refused)
+    if (kind == 2) return GemmPlan{GemmFamily::SmallM, a, b, c & 15, c >> 4};
+    return GemmPlan{kind == 6 && a >= 8 ? GemmFamily::PlanesDma : fam[kind], a, b, c, 1};
+}
 extern "C" int sva_test_gemm(int device, int M, int N, int K, const float* A, const float* W, const float* bias, float* C) {
     return test_gemm_impl(device, M, N, K, A, W, bias, C, nullptr);
 }
@@ -43,13 +51,9 @@ static int test_gemm_impl(int device, int M, int N, int K, const float* A, const
     ConvGemm g;
     g.A = dA; g.a_bstride = (long)M * K; g.lda = K; g.T = M; g.M = M; g.Cin = K; g.taps = 1;
     g.W = dW; g.N = N; g.bias = dB; g.C = dC; g.c_bstride = (long)M * N; g.ldc = N;
-    // kind 2: small-M kernel with a grid-level K split, c = column tiles + 16 * splits
-    int rc = !choice ? launch_conv_gemm(g, 0)
-             : choice[0] == 3 ? launch_conv_gemm_choice(g, 0, 2, choice[1], 0, 0)       // the register-staged pipelined kernel (gemm_pipe.hip), tile variant choice[1]
-             : choice[0] == 4 ? launch_conv_gemm_choice(g, 0, 4, choice[1], 0, 0)       // the split-bf16 kernel, tile variant choice[1]
-             : choice[0] == 2 ? launch_conv_gemm_choice_z(g, 0, choice[1], choice[2], choice[3] & 15, choice[3] >> 4)
-                              : launch_conv_gemm_choice(g, 0, choice[0], choice[1], choice[2], choice[3]);
-    if (!rc && choice && choice[0] == 2) rc = launch_conv_gemm_choice_z(g, 0, choice[1], choice[2], choice[3] & 15, choice[3] >> 4);   // twice: the counters re-arm
+    const GemmPlan p = choice ? test_choice_plan(choice[0], choice[1], choice[2], choice[3]) : GemmPlan();
+    int rc = !choice ? launch_conv_gemm(g, 0) : launch_conv_gemm_plan(g, p, 0);
+    if (!rc && choice && p.z > 1) rc = launch_conv_gemm_plan(g, p, 0);   // a grid-level K split twice: the counters re-arm
     if (rc) return rc;
     SVA_HIP(hipDeviceSynchronize());
     SVA_HIP(hipMemcpy(C, dC, sizeof(float) * (size_t)M * N, hipMemcpyDeviceToHost));
@@ -254,11 +258,18 @@ extern "C" int sva_bench_gemm(int device, int B, int T, int N, int Cin, int taps
 
 // One dispatch choice of the conv-GEMM family timed on device-resident random data, `nrot` weight copies rotated launch by launch (large nrot:
 // every launch streams its weights from HBM, as inside a step that touches 0.8 GB of weights; 1: the weights stay in L2 / MALL).
-//   kind -1 = the dispatcher; 0 = small-M kernel (a = rows / 16, b = K-split waves, c = column tiles + 16 * grid-level K split); 1 tiled (a);
-//   2 = pipelined (a); 4 = split-bf16 (a); 6 = weight-streaming kernel (gemm_stream.hip: a = mt + 16 * nt, b = kw, c = wmode + 16 * probe)
+//   kind -1 = the dispatcher; 0 / 1 / 2 / 4 = GemmFamily SmallM (c = column tiles + 16 * grid-level K split) / Tiled / Ring / Split with its parameters
+//   (sva_common.h); 6 = the weight-streaming kernel launched directly (gemm_stream.hip: a = mt + 16 * nt, b = kw, c = wmode + 16 * probe)
 //   mode bits: 1 GELU, 2 residual + gamma, 4 SiLU on load, 8 SwiGLU (w13), 16 fused RMSNorm of the rows
 //   out[0] = microseconds per launch, eager back-to-back; out[1] = the same launches replayed as one hipGraph; out[2] = max |C - C_dispatcher|;
 //   out[3] = max |C_dispatcher|
+// its kind numbers are the tuned table's (kind 6, the weight-streaming kernel with its weight mode and probes, is launched directly below)
+static GemmPlan bench_choice_plan(int kind, int a, int b, int c) {
+    GemmPlan p;
+    if (kind == 7) return GemmPlan{GemmFamily::Stream, a, b, c & 15, 1};       // (row-major weights, through the plan check)
+    if (kind == 6 || !plan_from_table_kind(kind, a, b, c & 15, kind == 0 && (c >> 4) > 1 ? c >> 4 : 1, &p)) p.a = -1;      // (no plan takes a = -1: refused)
+    return p;
+}
 extern "C" int sva_bench_gemm_choice(int device, int B, int T, int N, int Cin, int taps, int dil, int mode, int kind, int a, int b, int c, int nrot,
                                      int iters, float* out) {
     SVA_HIP(hipSetDevice(device));
@@ -324,8 +335,7 @@ extern "C" int sva_bench_gemm_choice(int device, int B, int T, int N, int Cin, i
         q.W = dW[r];
         if (kind < 0) return launch_conv_gemm(q, st);
         if (kind == 6) return launch_stream_gemm(q, packed ? dWp[r] : dW[r], a & 15, a >> 4, b, c & 15, c >> 4, st);
-        if (kind == 0 && (c >> 4) > 1) return launch_conv_gemm_choice_z(q, st, a, b, c & 15, c >> 4);
-        return launch_conv_gemm_choice(q, st, kind, a, b, c & 15);
+        return launch_conv_gemm_plan(q, bench_choice_plan(kind, a, b, c), st);
     };
     // reference result: the dispatcher's own choice
     {
@@ -514,7 +524,7 @@ extern "C" int sva_test_gemm_planes(int device, int M, int N, int K, const float
         *h_ovf = 0;
         SVA_HIP(hipHostGetDevicePointer((void**)&g.ovf, h_ovf, 0));
     }
-    SVA_TRY(launch_conv_gemm_choice(g, 0, 6, variant, 0, 0));
+    SVA_TRY(launch_conv_gemm_plan(g, test_choice_plan(6, variant, 0, 0), 0));
     SVA_HIP(hipDeviceSynchronize());
     if (h_ovf) {
         const int o = *reinterpret_cast<volatile int*>(h_ovf);
@@ -543,7 +553,7 @@ extern "C" int sva_test_gemm_planes(int device, int M, int N, int K, const float
         SVA_HIP(hipEventCreate(&e0));
         SVA_HIP(hipEventCreate(&e1));
         SVA_HIP(hipEventRecord(e0, 0));
-        for (int i = 0; i < iters; ++i) SVA_TRY(launch_conv_gemm_choice(g, 0, 6, variant, 0, 0));
+        for (int i = 0; i < iters; ++i) SVA_TRY(launch_conv_gemm_plan(g, test_choice_plan(6, variant, 0, 0), 0));
         SVA_HIP(hipEventRecord(e1, 0));
         SVA_HIP(hipDeviceSynchronize());
         float ms = 0;
@@ -920,5 +930,51 @@ extern "C" int sva_test_stream_overlap(sva_batch* b, int* pair_ok) {
     SVA_TRY(words.alloc(2 * sizeof(int)));
     const hipStream_t st[4] = {b->main_stream, b->aux[0], b->sa, b->sv};
     SVA_HIP(sva_overlap::pairs_of_four(st, words.as<int>(), pair_ok));
+    return 0;
+}
+
+// The dispatcher's decision for a described problem, without a GPU (include/sva.h).  Pointers are fabricated: nothing dereferences them.
+static void plan_hook_problem(const int* d, ConvGemm* g) {
+    alignas(16) static float mem[4];                                    // a 16-byte aligned address that stands for every operand
+    float* const P = mem;
+    const int B = d[0], T = d[1], N = d[2], Cin = d[3], taps = d[4], stride = d[5], dil = d[6], fl = d[7], op = d[8], mis = d[10];
+    const int Nout = (fl & 32) ? N / 2 : N;
+    const long H = (long)(taps - 1) * dil, rows = H + (long)T * stride;
+    g->A = P; g->lda = Cin; g->a_bstride = rows * Cin; g->a_off = (mis & 1) ? 2 : 0;
+    g->T = T; g->M = B * T; g->stride = stride; g->dil = dil; g->taps = taps; g->Cin = Cin;
+    g->W = P; g->N = N;
+    g->C = P; g->ldc = Nout + ((mis & 2) ? 1 : 0); g->c_bstride = (long)T * g->ldc; g->c_off = 0;
+    if (fl & 1) g->bias = P;
+    if (fl & 2) g->gamma = P;
+    if (fl & 4) { g->res = P; g->ldr = Nout + ((mis & 4) ? 1 : 0); g->r_bstride = (long)T * g->ldr; g->r_off = 0; }
+    if (fl & 8) g->act = ACT_GELU;
+    g->a_silu = (fl >> 4) & 1; g->w13 = (fl >> 5) & 1; g->accumulate = (fl >> 6) & 1;
+    if (fl & 128) g->rms_w = P;
+    if (fl & 256) { g->dw_wT = P; g->dw_b = P; g->ln_w = P; g->ln_b = P; }
+    g->cp_silu = (fl >> 9) & 1;
+    if (op & 1) g->Wk = P;
+    if (op & 2) g->Wh = P;
+    if (op & 4) g->Wkh = P;
+    if (op & 8) { g->Wp = reinterpret_cast<const unsigned short*>(P); g->wp_pstride = (long)N * taps * Cin; }
+    g->pmode = d[9];
+    if (op & 16) {          // A as planes over the dense rows of the tensor: (b, t) -> b * rows + t
+        g->Ap = reinterpret_cast<const unsigned short*>(P); g->A = nullptr;
+        g->ap_rows = (long)B * rows; g->ap_pstride = g->ap_rows * Cin;
+    }
+    if (op & 32) {
+        g->Cp = reinterpret_cast<unsigned short*>(P); g->C = nullptr;
+        g->cp_rows = (long)B * T; g->cp_pstride = g->cp_rows * Nout;
+    }
+}
+extern "C" int sva_test_gemm_plan(const int* desc, int n, int* out) {
+    SVA_CHECK(desc && out && n >= 1 && n <= 3, "test_gemm_plan: 1..3 members");
+    ConvGemm gs[3];
+    for (int i = 0; i < n; ++i) plan_hook_problem(desc + 12 * i, &gs[i]);
+    ConvGemmGroup gg;
+    int lead = 0;
+    GemmPlan p;
+    SVA_TRY(conv_gemm_group_of(gs, n, &gg, &lead));
+    SVA_TRY(plan_conv_gemm(gg, lead, &p));
+    out[0] = (int)p.family; out[1] = p.a; out[2] = p.b; out[3] = p.c; out[4] = p.z; out[5] = plan_report_kind(p, gg.g[lead].pmode);
     return 0;
 }

@@ -929,6 +929,55 @@ def test_every_gemm_dispatch_choice_vs_fp64():
             assert err <= tol * np.abs(ref).max(), (M, N, K, ch, err)
 
 
+# (engine options, streams): the sizes at which the dispatch policy changes branch -- one stream: the weight-streaming and small-M kernels (and
+# the tiled one for the vocoder's long levels); 12: past planes_min_streams = 10; 64: the encoder on the LDS-DMA planes kernel, the vocoder on
+# conv-form planes and grouped launches
+DISPATCH_CONFIGS = [("fp32", {}, 1), ("fp32", {}, 12), ("fp32", {}, 64), ("ar16_voc16", {"ar_dtype": 1, "voc_dtype": 1}, 12),
+                    ("enc16", {"enc_dtype": 1}, 1), ("enc16", {"enc_dtype": 1}, 64)]
+
+
+def dispatch_sequence(E, e, B):
+    """(M, N, K, taps, mode) of every conv-GEMM launch of one profiled serial step (the third of a B-stream batch), in launch order;
+    mode carries the kernel family of the launch in its high bits (256 * (plan_report_kind + 1))"""
+    from streamvoiceanon_amd.synth_audio import synth_prompt, synth_utterance
+
+    b = E.Batch(e, n_streams=B)
+    for s in range(B):
+        ac, cc, style, timbre = synth_prompt(2000 + s % 5, 60 + 7 * (s % 5))
+        b.prefill_prompt(s, cc, ac, style, timbre, noise_seed=1000 + s)
+    b.begin()
+    src = np.stack([synth_utterance(1000 + s % 7, 2048 * 3) for s in range(B)])
+    for i in range(3):
+        if i == 2:
+            b.profile_gemm(True)
+        b.step(src[:, i * 2048:(i + 1) * 2048])
+    tab = b.gemm_profile_table()
+    b.profile_gemm(False)
+    b.close()
+    assert 0 < len(tab) < 4096
+    return np.ascontiguousarray(tab[:, :5]).astype(np.int32)
+
+
+@pytest.mark.parametrize("name,opts,B", DISPATCH_CONFIGS, ids=[f"{n}-{B}" for n, _, B in DISPATCH_CONFIGS])
+def test_step_dispatch_sequence_is_pinned(eng, weights0, name, opts, B):
+    """What a real step dispatches: the ordered (shape, kernel family) sequence of its conv-GEMM launches equals the one recorded on the GPU
+    before the dispatch decision became a function of its own (tests/golden/gemm_dispatch_steps.npz; times are ignored)."""
+    import os
+    from streamvoiceanon_amd import engine as E
+
+    assert "SVA_DEBUG" not in os.environ, "the pinned sequences are the default policy's"
+    e = eng if not opts else E.Engine(weights0, **opts)
+    try:
+        got = dispatch_sequence(E, e, B)
+    finally:
+        if opts:
+            e.close()
+    want = load_golden("gemm_dispatch_steps")[f"{name}_{B}"]
+    assert got.shape == want.shape, (got.shape, want.shape)
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert len(bad) == 0, [(int(i), got[i].tolist(), want[i].tolist()) for i in bad[:8]]
+
+
 def test_stream_gemm_packed_weights_and_epilogues_vs_dispatcher():
     """gemm_stream.hip through its product form -- the fragment-major weight copy -- with every prologue / epilogue it serves (fused RMSNorm,
     SiLU on load, bias, GELU, gamma + residual, SwiGLU, conv taps over shifted rows), ragged rows / columns (N = 1000: a partial column tile),
