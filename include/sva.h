@@ -87,6 +87,16 @@ typedef struct sva_stream_params {
     int pipeline;              /* sva_step_device only: run encoder / AR / vocoder of consecutive chunk-steps on three streams
                                 * (E(n+1) || A(n) || V(n-1)); same results, higher throughput for simulated streaming; a caller that
                                 * synchronises per chunk sees the unpipelined latency */
+    int slot_priming;          /* 0 (default): the step that activates a restarted slot primes its vocoder in a whole-batch run (below,
+                                * sva_stream_restart).  1: slot-local activation -- the batch owns a one-stream vocoder workspace of
+                                * ((decode_window_frames - 1) / chunk) * chunk code frames (allocated by sva_batch_create; measured
+                                * at the default window: 624 / 766 / 1280 MiB of device memory beside a 2 / 8 / 64-stream batch); the slot's
+                                * state is primed there in ONE pass over the prompt tail and moved into the slot.  Measured stall of the
+                                * activating step: 5.0 / 5.1 / 4.1 ms at 2 / 8 / 64 streams against 38.5 / 61.8 / 100.3 ms with 0
+                                * (profiles/slot_priming_report.txt).  Contract: codes, positions and frame
+                                * counts of every slot are identical to slot_priming = 0; every OTHER slot is bit-identical; the restarted
+                                * slot's PCM is within the vocoder tolerance of a fresh slot, not bit-identical to it (its state comes from a
+                                * T = P pass instead of P / chunk chunk-sized passes: other GEMM tilings).  Inert until a restart. */
 } sva_stream_params;
 
 const char* sva_last_error(void);
@@ -169,8 +179,10 @@ int sva_vocode_reset(sva_batch* b);
  * behaves exactly like a slot of a fresh batch after sva_prefill_prompt + sva_streams_begin: zero audio window, silence-steady encoder
  * state, ceil(delay / chunk) steps of zero output while its own delay fills, then decoding from frame 0 with noise keyed by noise_seed.
  * Every other slot is unaffected: all its later outputs are bit-identical to a run without the call.  Drains the batch's streams.
- * The step in which the slot's delay fills also prefills its prompt and primes its vocoder with the prompt's tail (a whole-batch vocoder
- * run of decode_window_frames - 1 frames): that step stalls every stream of the batch ("Restarting single streams").
+ * The step in which the slot's delay fills also prefills its prompt and primes its vocoder with the prompt's tail: that step stalls every
+ * stream of the batch ("Restarting single streams").  With slot_priming = 0 the priming is a whole-batch vocoder run of
+ * decode_window_frames - 1 frames in chunk-sized steps, and the stall grows with the batch; with slot_priming = 1 it is one pass over a
+ * one-stream workspace plus a copy of the slot's history rows (sva_stream_params.slot_priming states what stays identical).
  * Fails, changing nothing, before sva_streams_begin, for a slot out of range, for R <= delay (or a prompt that does not fit the KV cache /
  * is shorter than the vocoder's 16-frame receptive field), and in the configurations that cannot fill one slot's encoder state:
  *   - encode_window_frames <= 40 + chunk_frames: the batch runs the full-window encoder, which keeps no cached silence state;
@@ -183,6 +195,9 @@ int sva_stream_restart(sva_batch* b, int slot, const int64_t* ref_content_codes,
 int sva_stream_retire(sva_batch* b, int slot);
 /* phase: 0 retired, 1 delay filling, 2 decoding; frames = frames decoded since the slot's stream began (0 unless decoding) */
 int sva_stream_state(sva_batch* b, int slot, int* phase, long* frames);
+/* activations since the batch was created: counts[0] slot-local ones (slot_priming = 1), counts[1] whole-batch ones; last_ms (may be NULL):
+ * host wall time of the last activation -- prompt prefill, delay fill, vocoder priming -- taken after its final synchronise (0 before the first) */
+int sva_stream_activations(sva_batch* b, long counts[2], float* last_ms);
 
 /* AR seams with caller-supplied content codes (chunk_frames == 1):
  *   ARVCWrapper.prefill_src_condition4delay (modules/arvc_wrapper.py:114-119): codes int64[B][delay]

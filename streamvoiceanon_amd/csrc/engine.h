@@ -346,6 +346,13 @@ struct sva_batch {
     long voc_save_bstride = 0;
     long* d_voc_save_offs = nullptr;       // [shift_host.size()] offset of each desc's rows inside a slot's block
     float* prime_pcm = nullptr;            // [B][2048 * chunk] PCM sink of the priming run (the step's own PCM stays where it is)
+    // slot-local priming (p.slot_priming): a one-stream, vocoder-only workspace owned by this batch.  Only the fields vocode() reads are
+    // set up in it; every level keeps the form of this batch, so its ShiftDesc table is parallel to this one's (same count, same H / C
+    // per entry) and one kernel moves slot 0 of it into a slot of this batch.  Not a stream batch: no encoder, AR or KV memory, not
+    // counted in persistent_batches.
+    sva_batch* prime_ws = nullptr;
+    long n_act_local = 0, n_act_whole = 0; // activations primed through the workspace / through the whole-batch run
+    float last_act_ms = 0.f;               // host wall time of the last activate_slot, taken after its final synchronise
 
     // ---- vocoder workspace ----
     int Tv = 0;                            // max code frames per call

@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 
 namespace sva {
 
@@ -230,6 +231,146 @@ static bool abatch_serves(int B, int ar_dtype, bool pipelined, int chunk) {
     if (!pipelined) return B <= 32;           // a caller that synchronises every chunk: one launch per frame from 5 streams (profiles/r04_small_batch_ab.txt)
     const PolicyRow* r = policy_row(B, ar_dtype, chunk);
     return r ? r->decode == 2 : B <= 32;
+}
+
+// The vocoder workspace of a batch: activations with their history rows, operand planes, the ShiftDesc table, code and PCM buffers for up to
+// Tv code frames per call.  The FORM of every HiFiGAN level -- fp32 rows, the fused C = 16 level, K-blocked planes, row-major planes -- is a
+// static choice per batch, derived here from its streams and Tv (forms == nullptr), or taken over from the batch `forms` that owns this one as
+// its priming workspace: the history rows of the two must be the same rows in the same layout, whatever B = 1 and its Tv would have chosen.
+static int alloc_vocoder(sva_batch* b, int Tv, const sva_batch* forms) {
+    sva_engine* e = b->e;
+    const sva_config& c = e->cfg;
+    auto& A = b->allocs;
+    const int B = b->B, V = c.voc_dim, ncb = c.num_codebooks;
+    b->Tv = Tv;
+    if (forms) {
+        b->voc_fused = forms->voc_fused;
+        b->voc_fused_mask = (voc_level_is_fused(forms, 16) ? 1 : 0) | (voc_level_is_fused(forms, 32) ? 2 : 0);
+    } else if (debug_options().voc_fused_mask >= 0) b->voc_fused_mask = debug_options().voc_fused_mask;
+    SVA_TRY(dev_alloc(A, &b->d_voc_frames, 1));
+    SVA_HIP(hipMemset(b->d_voc_frames, 0, sizeof(int)));
+    SVA_TRY(alloc_act(A, b->zq, B, 0, Tv, V));
+    SVA_TRY(alloc_act(A, b->u0, B, 6, 2L * Tv, V));
+    SVA_TRY(alloc_act(A, b->v0, B, 0, 2L * Tv, V));
+    SVA_TRY(alloc_act(A, b->u1, B, 6, 4L * Tv, V));
+    SVA_TRY(alloc_act(A, b->pin, B, e->pre_k - 1, 4L * Tv, V));
+    SVA_TRY(dev_alloc(A, &b->vh1, (size_t)B * 4 * Tv * V));
+    SVA_TRY(dev_alloc(A, &b->vh2, (size_t)B * 4 * Tv * 4 * V));
+    SVA_TRY(alloc_act(A, b->S[0], B, 1, 4L * Tv, V));
+    SVA_TRY(register_shift(b, b->u0, 2));
+    SVA_TRY(register_shift(b, b->u1, 4));
+    SVA_TRY(register_shift(b, b->pin, 4));
+    SVA_TRY(register_shift(b, b->S[0], 4));
+    long rows = 4L * Tv;
+    int rpf = 4;
+    int ch = V;
+    for (int i = 0; i < 5; ++i) {
+        rows *= e->ups_s[i];
+        rpf *= e->ups_s[i];
+        ch /= 2;
+        b->voc_rpf[i] = rpf;
+        const bool fused_level = voc_level_is_fused(b, ch);
+        // Every level of a batch with enough rows per step: the 18 ResBlock convs on operand planes, three branches per launch (C >= 64: the LDS-DMA
+        // planes kernel's conv form; C = 16 / 32: voc_conv_kernel), the activations between them as planes (history included).  A static choice per
+        // batch -- the history lives in one form.  From 10 code frames per step over the batch (streams x voc_max_frames): +4.7 / +5.7 / +6.7 / +5.2 /
+        // +3.9 % frames/s at 16 / 24 / 32 / 48 / 128 streams, +2 % and a 6 % shorter synchronous step at 10 / 12, even at 8 (profiles/r05_voc_dma_sweep.txt)
+        const int voc_pm = c.voc_dtype == 1 ? PLANES_H1 : (c.mm_mode == 1 ? PLANES_H3 : -1);
+        bool dma_level = forms ? forms->voc_dma[i] != 0
+                               : !fused_level && ch % 16 == 0 && voc_pm >= 0 && debug_options().planes_dma != 0 && debug_options().voc_dma != 0 &&
+                                     (debug_options().voc_dma == 1 || (long)B * Tv >= 10);
+        // C = 16 / 32: row-major planes + voc_conv_kernel (the input rows of a tile and the branch's whole weight resident in LDS); wider: K-blocked planes +
+        // the LDS-DMA GEMM's conv form
+        const bool halo_level = forms ? forms->voc_dma[i] == 2 : dma_level && ch <= 32 && voc_conv_supported(ch, rpf, voc_pm);
+        for (int br = 0; br < 3 && dma_level && !forms; ++br)
+            for (int j = 0; j < 3; ++j) {
+                const ResConv& rcv = e->res[i][br][j];
+                if (halo_level) dma_level = dma_level && rcv.q1 && rcv.q2;
+                else dma_level = dma_level && ch % 64 == 0 && rcv.c1.Wp && rcv.c2.Wp && rcv.c1.pmode == voc_pm && rcv.c2.pmode == voc_pm;
+            }
+        if (dma_level) b->voc_pmode = voc_pm;
+        b->voc_dma[i] = dma_level ? (halo_level ? 2 : 1) : 0;
+        auto alloc_planes = [&](const Act& a, unsigned short** P) -> int {
+            const int npl = planes_count(b->voc_pmode);
+            const size_t n = (size_t)npl * B * a.bstride;
+            SVA_TRY(dev_alloc(A, P, n));
+            if (a.H == 0) return 0;
+            for (int p = 0; p < npl; ++p) {
+                if (halo_level) {       // row-major plane: a [B][rows][C / 2 floats] tensor
+                    ShiftDesc d;
+                    d.ptr = reinterpret_cast<float*>(*P + (size_t)p * B * a.bstride);
+                    d.bstride = a.rows * (a.C / 2); d.H = a.H; d.T = 0; d.C = a.C / 2; d.pad = rpf;
+                    b->shift_host.push_back(d);
+                    continue;
+                }
+                // K-blocked: the history rows of every (plane, 32-channel block) shift like a [B][rows][16 floats] tensor of its own
+                for (int kb = 0; kb < a.C / 32; ++kb) {
+                    ShiftDesc d;
+                    d.ptr = reinterpret_cast<float*>(*P + (size_t)p * B * a.bstride + (size_t)kb * B * a.rows * 32);
+                    d.bstride = a.rows * 16; d.H = a.H; d.T = 0; d.C = 16; d.pad = rpf;
+                    b->shift_host.push_back(d);
+                }
+            }
+            return 0;
+        };
+        // fused levels keep the receptive field of the whole six-conv chain as input history (their only streaming state)
+        SVA_TRY(alloc_act(A, b->X[i], B, fused_level ? (kResK[2] - 1) * 2 * (kResD[0] + kResD[1] + kResD[2]) : (kResK[2] - 1) * kResD[0], rows, ch));
+        if (dma_level) SVA_TRY(alloc_planes(b->X[i], &b->XP[i]));        // (the fp32 tensors of such a level are read as residuals only: current rows)
+        else SVA_TRY(register_shift(b, b->X[i], rpf));
+        for (int br = 0; br < 3; ++br)
+            for (int j = 0; j < 3; ++j) {
+                SVA_TRY(alloc_act(A, b->tb[i][br][j], B, (kResK[br] - 1) * kResD[j], rows, ch));
+                if (dma_level) SVA_TRY(alloc_planes(b->tb[i][br][j], &b->tbP[i][br][j]));
+                else SVA_TRY(register_shift(b, b->tb[i][br][j], rpf));
+                if (j < 2) {
+                    SVA_TRY(alloc_act(A, b->yb[i][br][j], B, (kResK[br] - 1) * kResD[j + 1], rows, ch));
+                    if (dma_level) SVA_TRY(alloc_planes(b->yb[i][br][j], &b->ybP[i][br][j]));
+                    else SVA_TRY(register_shift(b, b->yb[i][br][j], rpf));
+                }
+            }
+        for (int br = 0; br < 3; ++br) SVA_TRY(alloc_act(A, b->y3[i][br], B, 0, rows, ch));
+        SVA_TRY(alloc_act(A, b->S[i + 1], B, i < 4 ? 1 : e->post_k - 1, rows, ch));
+        SVA_TRY(register_shift(b, b->S[i + 1], rpf));
+    }
+    SVA_TRY(dev_alloc(A, &b->d_pcm, (size_t)B * 2048 * Tv));
+    SVA_TRY(dev_alloc(A, &b->d_vcodes, (size_t)B * ncb * Tv));
+    SVA_TRY(dev_alloc(A, &b->d_shift, b->shift_host.size()));
+    return 0;
+}
+
+// Slot-local activation (sva_stream_params.slot_priming): the one-stream vocoder workspace a restarted slot's state is primed in.  An internal
+// sva_batch on which only what vocode() reads is set up; it runs on the owner's stream with the owner's CU limit and reports fp16-range
+// overflows through the owner's flag.  Allocated with the owner so that no activating step allocates; freed by sva_batch_destroy(owner).
+static int create_priming_workspace(sva_batch* b) {
+    const int chunk = b->p.chunk_frames;
+    const int Tv = ((b->p.decode_window_frames - 1) / chunk) * chunk;
+    SVA_CHECK(b->p.slot_priming == 1, "slot_priming must be 0 or 1");
+    SVA_CHECK(Tv >= 1, "slot_priming: decode_window_frames - 1 holds no whole chunk to prime with");
+    sva_batch* w = new sva_batch();
+    for (auto& ev : w->evpool) ev = nullptr;
+    for (auto& ev : w->ev) ev = nullptr;
+    b->prime_ws = w;                        // (owned from here on: a failure below is cleaned up with the owner)
+    w->e = b->e;
+    w->p = b->p;
+    w->p.n_streams = 1; w->p.slot_priming = 0; w->p.voc_max_frames = Tv; w->p.pipeline = 0; w->p.use_graph = 0;
+    w->B = 1;
+    w->stream = w->main_stream = w->out_stream = b->main_stream;
+    w->aux[0] = b->aux[0]; w->aux[1] = b->aux[1];
+    w->concurrency = b->concurrency;
+    w->voc_grouped = b->voc_grouped;
+    w->enc_cus = b->enc_cus;
+    w->d_mm_ovf = b->d_mm_ovf;              // (h_mm_ovf stays null here: the owner polls and frees the flag)
+    for (int i = 0; i < 64; ++i) SVA_HIP(hipEventCreateWithFlags(&w->evpool[i], hipEventDisableTiming));
+    SVA_TRY(alloc_vocoder(w, Tv, b));
+    // the move kernel walks the two tables in parallel: refuse anything else here, not in an activating step
+    bool parallel = w->shift_host.size() == b->shift_host.size() && w->voc_pmode == b->voc_pmode;
+    for (size_t i = 0; parallel && i < w->shift_host.size(); ++i) {
+        const ShiftDesc &x = w->shift_host[i], &y = b->shift_host[i];
+        parallel = x.H == y.H && x.C == y.C && x.pad == y.pad && (long)y.H * y.C <= y.bstride && (long)x.H * x.C <= x.bstride;
+    }
+    for (int i = 0; i < 5; ++i) parallel = parallel && w->voc_dma[i] == b->voc_dma[i] && w->voc_rpf[i] == b->voc_rpf[i];
+    SVA_CHECK(parallel, "slot_priming: the priming workspace's vocoder state is not in the form of the batch's (history descriptors differ)");
+    SVA_HIP(hipMemcpy(w->d_shift, w->shift_host.data(), sizeof(ShiftDesc) * w->shift_host.size(), hipMemcpyHostToDevice));
+    return 0;
 }
 
 static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batch* b);
@@ -578,95 +719,8 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
     b->h_last_pos.assign(B, -1); b->h_nframes.assign(B, 0); b->prefilled.assign(B, 0);
     b->h_ncontent.assign(B, 0); b->h_phase.assign(B, 1); b->restarted.assign(B, 0); b->pending.resize(B); b->h_slot_flag.assign(B, 0);
     // vocoder
-    const int Tv = b->Tv = b->p.voc_max_frames;
-    const int V = c.voc_dim;
-    if (debug_options().voc_fused_mask >= 0) b->voc_fused_mask = debug_options().voc_fused_mask;
-    SVA_TRY(dev_alloc(A, &b->d_voc_frames, 1));
-    SVA_HIP(hipMemset(b->d_voc_frames, 0, sizeof(int)));
-    SVA_TRY(alloc_act(A, b->zq, B, 0, Tv, V));
-    SVA_TRY(alloc_act(A, b->u0, B, 6, 2L * Tv, V));
-    SVA_TRY(alloc_act(A, b->v0, B, 0, 2L * Tv, V));
-    SVA_TRY(alloc_act(A, b->u1, B, 6, 4L * Tv, V));
-    SVA_TRY(alloc_act(A, b->pin, B, e->pre_k - 1, 4L * Tv, V));
-    SVA_TRY(dev_alloc(A, &b->vh1, (size_t)B * 4 * Tv * V));
-    SVA_TRY(dev_alloc(A, &b->vh2, (size_t)B * 4 * Tv * 4 * V));
-    SVA_TRY(alloc_act(A, b->S[0], B, 1, 4L * Tv, V));
-    SVA_TRY(register_shift(b, b->u0, 2));
-    SVA_TRY(register_shift(b, b->u1, 4));
-    SVA_TRY(register_shift(b, b->pin, 4));
-    SVA_TRY(register_shift(b, b->S[0], 4));
-    long rows = 4L * Tv;
-    int rpf = 4;
-    int ch = V;
-    for (int i = 0; i < 5; ++i) {
-        rows *= e->ups_s[i];
-        rpf *= e->ups_s[i];
-        ch /= 2;
-        b->voc_rpf[i] = rpf;
-        const bool fused_level = voc_level_is_fused(b, ch);
-        // Every level of a batch with enough rows per step: the 18 ResBlock convs on operand planes, three branches per launch (C >= 64: the LDS-DMA
-        // planes kernel's conv form; C = 16 / 32: voc_conv_kernel), the activations between them as planes (history included).  A static choice per
-        // batch -- the history lives in one form.  From 10 code frames per step over the batch (streams x voc_max_frames): +4.7 / +5.7 / +6.7 / +5.2 /
-        // +3.9 % frames/s at 16 / 24 / 32 / 48 / 128 streams, +2 % and a 6 % shorter synchronous step at 10 / 12, even at 8 (profiles/r05_voc_dma_sweep.txt)
-        const int voc_pm = c.voc_dtype == 1 ? PLANES_H1 : (c.mm_mode == 1 ? PLANES_H3 : -1);
-        bool dma_level = !fused_level && ch % 16 == 0 && voc_pm >= 0 && debug_options().planes_dma != 0 && debug_options().voc_dma != 0 &&
-                         (debug_options().voc_dma == 1 || (long)B * Tv >= 10);
-        // C = 16 / 32: row-major planes + voc_conv_kernel (the input rows of a tile and the branch's whole weight resident in LDS); wider: K-blocked planes +
-        // the LDS-DMA GEMM's conv form
-        const bool halo_level = dma_level && ch <= 32 && voc_conv_supported(ch, rpf, voc_pm);
-        for (int br = 0; br < 3 && dma_level; ++br)
-            for (int j = 0; j < 3; ++j) {
-                const ResConv& rcv = e->res[i][br][j];
-                if (halo_level) dma_level = dma_level && rcv.q1 && rcv.q2;
-                else dma_level = dma_level && ch % 64 == 0 && rcv.c1.Wp && rcv.c2.Wp && rcv.c1.pmode == voc_pm && rcv.c2.pmode == voc_pm;
-            }
-        if (dma_level) b->voc_pmode = voc_pm;
-        b->voc_dma[i] = dma_level ? (halo_level ? 2 : 1) : 0;
-        auto alloc_planes = [&](const Act& a, unsigned short** P) -> int {
-            const int npl = planes_count(b->voc_pmode);
-            const size_t n = (size_t)npl * B * a.bstride;
-            SVA_TRY(dev_alloc(A, P, n));
-            if (a.H == 0) return 0;
-            for (int p = 0; p < npl; ++p) {
-                if (halo_level) {       // row-major plane: a [B][rows][C / 2 floats] tensor
-                    ShiftDesc d;
-                    d.ptr = reinterpret_cast<float*>(*P + (size_t)p * B * a.bstride);
-                    d.bstride = a.rows * (a.C / 2); d.H = a.H; d.T = 0; d.C = a.C / 2; d.pad = rpf;
-                    b->shift_host.push_back(d);
-                    continue;
-                }
-                // K-blocked: the history rows of every (plane, 32-channel block) shift like a [B][rows][16 floats] tensor of its own
-                for (int kb = 0; kb < a.C / 32; ++kb) {
-                    ShiftDesc d;
-                    d.ptr = reinterpret_cast<float*>(*P + (size_t)p * B * a.bstride + (size_t)kb * B * a.rows * 32);
-                    d.bstride = a.rows * 16; d.H = a.H; d.T = 0; d.C = 16; d.pad = rpf;
-                    b->shift_host.push_back(d);
-                }
-            }
-            return 0;
-        };
-        // fused levels keep the receptive field of the whole six-conv chain as input history (their only streaming state)
-        SVA_TRY(alloc_act(A, b->X[i], B, fused_level ? (kResK[2] - 1) * 2 * (kResD[0] + kResD[1] + kResD[2]) : (kResK[2] - 1) * kResD[0], rows, ch));
-        if (dma_level) SVA_TRY(alloc_planes(b->X[i], &b->XP[i]));        // (the fp32 tensors of such a level are read as residuals only: current rows)
-        else SVA_TRY(register_shift(b, b->X[i], rpf));
-        for (int br = 0; br < 3; ++br)
-            for (int j = 0; j < 3; ++j) {
-                SVA_TRY(alloc_act(A, b->tb[i][br][j], B, (kResK[br] - 1) * kResD[j], rows, ch));
-                if (dma_level) SVA_TRY(alloc_planes(b->tb[i][br][j], &b->tbP[i][br][j]));
-                else SVA_TRY(register_shift(b, b->tb[i][br][j], rpf));
-                if (j < 2) {
-                    SVA_TRY(alloc_act(A, b->yb[i][br][j], B, (kResK[br] - 1) * kResD[j + 1], rows, ch));
-                    if (dma_level) SVA_TRY(alloc_planes(b->yb[i][br][j], &b->ybP[i][br][j]));
-                    else SVA_TRY(register_shift(b, b->yb[i][br][j], rpf));
-                }
-            }
-        for (int br = 0; br < 3; ++br) SVA_TRY(alloc_act(A, b->y3[i][br], B, 0, rows, ch));
-        SVA_TRY(alloc_act(A, b->S[i + 1], B, i < 4 ? 1 : e->post_k - 1, rows, ch));
-        SVA_TRY(register_shift(b, b->S[i + 1], rpf));
-    }
-    SVA_TRY(dev_alloc(A, &b->d_pcm, (size_t)B * 2048 * Tv));
-    SVA_TRY(dev_alloc(A, &b->d_vcodes, (size_t)B * ncb * Tv));
-    SVA_TRY(dev_alloc(A, &b->d_shift, b->shift_host.size()));
+    SVA_TRY(alloc_vocoder(b, b->p.voc_max_frames, nullptr));
+    if (b->p.slot_priming) SVA_TRY(create_priming_workspace(b));
     SVA_HIP(hipHostMalloc((void**)&b->hp_in, sizeof(float) * (size_t)B * 2048 * chunk));
     SVA_HIP(hipHostMalloc((void**)&b->hp_out, sizeof(float) * (size_t)B * 2048 * chunk));
     for (int i = 0; i < 5; ++i) SVA_HIP(hipEventCreate(&b->ev[i]));
@@ -709,6 +763,12 @@ extern "C" void sva_batch_destroy(sva_batch* b) {
     for (auto& ge : b->pipe_graph_a) if (ge) (void)hipGraphExecDestroy(ge);
     for (hipGraphExec_t ge : {b->gEm[0], b->gEm[1], b->gEs[0], b->gEs[1], b->gE, b->gE2, b->gT0, b->gT1[0], b->gT1[1], b->gV}) if (ge) (void)hipGraphExecDestroy(ge);
     for (void* p : b->allocs.chunks) (void)hipFree(p);
+    if (sva_batch* w = b->prime_ws) {        // the priming workspace: arena chunks and its event pool (streams and the overflow flag are the owner's)
+        for (void* p : w->allocs.chunks) (void)hipFree(p);
+        for (int i = 0; i < 64; ++i) if (w->evpool[i]) (void)hipEventDestroy(w->evpool[i]);
+        delete w;
+        b->prime_ws = nullptr;
+    }
     if (b->h_ar_fail) (void)hipHostFree(b->h_ar_fail);
     if (b->h_mm_ovf) (void)hipHostFree(b->h_mm_ovf);
     if (b->hp_in) (void)hipHostFree(b->hp_in);
@@ -1486,10 +1546,38 @@ int prime_vocoder_slot(sva_batch* b, int slot) {
     return 0;
 }
 
+// Slot-local form of the above (sva_stream_params.slot_priming): the same state -- zero state, then the last P frames of the prompt -- built in
+// the batch's one-stream workspace in ONE T = P pass, then moved into the slot by one kernel.  Nothing of the batch but the slot's history rows
+// is written (d_voc_frames, the other slots, the PCM sinks and the GEMM counters stay), and the cost does not depend on the batch size.  The
+// rows differ from the chunk-by-chunk ones by the rounding of other GEMM tilings only.  Runs on the batch's drained stream, never beside its steps.
+int prime_vocoder_slot_local(sva_batch* b, int slot) {
+    sva_batch* w = b->prime_ws;
+    SVA_CHECK(w, "slot-local priming without a workspace");
+    const int ncb = b->e->cfg.num_codebooks, nd = (int)b->shift_host.size();
+    const int R = b->ref_len[slot], P = priming_frames(b, R);
+    SVA_CHECK(slot >= 0 && slot < b->B, "slot-local priming: slot out of range");
+    SVA_CHECK(P <= w->Tv, "slot-local priming: prompt tail longer than the workspace");
+    hipStream_t st = b->stream;
+    w->stream = st;
+    SVA_TRY(sva_vocode_reset(w));
+    std::vector<int32_t> codes((size_t)ncb * std::max(P, 1));        // [1][8][P] (alive until the synchronisation below)
+    for (int q = 0; q < ncb; ++q)
+        for (int k = 0; k < P; ++k) codes[(size_t)q * P + k] = b->ref_audio[slot][(size_t)q * R + (R - P + k)];
+    if (P > 0) {
+        SVA_TRY(upload_vcodes(w, codes.data(), P));
+        SVA_TRY(vocode(w, P, true));
+    }
+    if (nd) hipLaunchKernelGGL(history_rows_move_kernel, dim3(nd), dim3(256), 0, st, w->d_shift, b->d_shift, slot);
+    SVA_HIP(hipGetLastError());
+    SVA_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 // A restarted slot whose content count has reached the delay becomes a decoding stream: everything a parked step may have clobbered is
 // rebuilt in the order a fresh stream sees it (sva_prefill_prompt, the delay fill of sva_streams_begin's first steps, the vocoder priming).
 // Runs on drained streams.
 int activate_slot(sva_batch* b, int slot) {
+    const auto t0 = std::chrono::steady_clock::now();
     sva_batch::PendingPrompt& P = b->pending[slot];
     struct Keep { sva_batch* b; const float* src; ~Keep() { b->step_src = src; } } keep{b, b->step_src};
     b->step_src = nullptr;
@@ -1497,11 +1585,14 @@ int activate_slot(sva_batch* b, int slot) {
     SVA_HIP(hipMemsetAsync(b->d_nframes + slot, 0, sizeof(int), b->stream));
     b->h_nframes[slot] = 0;
     SVA_TRY(ar_delay_fill(b, std::vector<int>{slot}));
-    SVA_TRY(prime_vocoder_slot(b, slot));
+    SVA_TRY(b->prime_ws ? prime_vocoder_slot_local(b, slot) : prime_vocoder_slot(b, slot));
     b->h_phase[slot] = 2;
     b->restarted[slot] = 0;
     P = sva_batch::PendingPrompt();
-    return set_slot_flag(b, slot, 0);
+    SVA_TRY(set_slot_flag(b, slot, 0));
+    (b->prime_ws ? b->n_act_local : b->n_act_whole) += 1;
+    b->last_act_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
 }
 
 int activate_due_slots(sva_batch* b) {
@@ -1697,6 +1788,14 @@ extern "C" int sva_stream_state(sva_batch* b, int slot, int* phase, long* frames
     SVA_CHECK(slot >= 0 && slot < b->B, "sva_stream_state: slot out of range");
     if (phase) *phase = b->h_phase[slot];
     if (frames) *frames = b->h_phase[slot] == 2 ? b->h_nframes[slot] : 0;
+    return 0;
+}
+
+extern "C" int sva_stream_activations(sva_batch* b, long counts[2], float* last_ms) {
+    SVA_CHECK(b && counts, "sva_stream_activations: null argument");
+    counts[0] = b->n_act_local;
+    counts[1] = b->n_act_whole;
+    if (last_ms) *last_ms = b->last_act_ms;
     return 0;
 }
 

@@ -25,3 +25,4 @@ __global__ void add_list_kernel(int* p, const int* list, int n, int v);
 __global__ void add_vec_kernel(int* p, int n, int v);
 __global__ void set_slot_i32_kernel(int* p, int slot, int v);
 __global__ void history_rows_copy_kernel(const sva::ShiftDesc* descs, const long* offs, float* save, long save_bstride, int slot_lo, int to_live);
+__global__ void history_rows_move_kernel(const sva::ShiftDesc* src_descs, const sva::ShiftDesc* dst_descs, int slot);

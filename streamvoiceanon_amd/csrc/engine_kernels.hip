@@ -233,3 +233,22 @@ __global__ __launch_bounds__(256) void history_rows_copy_kernel(const sva::Shift
     if (to_live) for (long i = threadIdx.x; i < n; i += blockDim.x) live[i] = sv[i];
     else for (long i = threadIdx.x; i < n; i += blockDim.x) sv[i] = live[i];
 }
+
+// Slot-local activation: the H history rows of every desc, from slot 0 of a one-stream workspace's table into slot `slot` of the batch's
+// table.  The two tables are parallel (same count, same H and C per entry: checked when the workspace is created), so desc blockIdx.x of
+// one is desc blockIdx.x of the other and the K-blocked planes are reached per (plane, 32-k block) as above.  Writes the target slot's
+// rows only.  float4 lanes where the block's length and both addresses allow.
+__global__ __launch_bounds__(256) void history_rows_move_kernel(const sva::ShiftDesc* __restrict__ src_descs, const sva::ShiftDesc* __restrict__ dst_descs,
+                                                                int slot) {
+    const sva::ShiftDesc s = src_descs[blockIdx.x], d = dst_descs[blockIdx.x];
+    const float* from = s.ptr;
+    float* to = d.ptr + (long)slot * d.bstride;
+    const long n = (long)d.H * d.C;
+    if (n % 4 == 0 && ((reinterpret_cast<uintptr_t>(from) | reinterpret_cast<uintptr_t>(to)) & 15) == 0) {
+        const float4* f4 = reinterpret_cast<const float4*>(from);
+        float4* t4 = reinterpret_cast<float4*>(to);
+        for (long i = threadIdx.x; i < n / 4; i += blockDim.x) t4[i] = f4[i];
+    } else {
+        for (long i = threadIdx.x; i < n; i += blockDim.x) to[i] = from[i];
+    }
+}

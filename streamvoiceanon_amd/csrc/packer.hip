@@ -24,6 +24,7 @@ extern "C" int sva_stream_params_default(sva_stream_params* p) {
     p->n_streams = 1; p->encode_window_frames = 128; p->decode_window_frames = 64; p->chunk_frames = 1;
     p->delay = 2; p->max_seq_frames = 768; p->buffer_frames = 32; p->max_prompt_frames = 256;
     p->temperature = 0.7f; p->top_p = 0.7f; p->voc_max_frames = 1; p->use_graph = 0; p->skip_semantic = 0;
+    p->slot_priming = 0;
     return 0;
 }
 

@@ -43,6 +43,7 @@ class SvaStreamParams(C.Structure):
         ("chunk_frames", C.c_int), ("delay", C.c_int), ("max_seq_frames", C.c_int), ("buffer_frames", C.c_int),
         ("max_prompt_frames", C.c_int), ("temperature", C.c_float), ("top_p", C.c_float),
         ("voc_max_frames", C.c_int), ("use_graph", C.c_int), ("skip_semantic", C.c_int), ("pipeline", C.c_int),
+        ("slot_priming", C.c_int),
     ]
 
 
@@ -76,6 +77,7 @@ def load_library():
     lib.sva_stream_restart.argtypes = [vp, i32, vp, vp, i32, vp, vp, C.c_uint64]
     lib.sva_stream_retire.argtypes = [vp, i32]
     lib.sva_stream_state.argtypes = [vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_long)]
+    lib.sva_stream_activations.argtypes = [vp, C.POINTER(C.c_long), f32p]
     lib.sva_step.argtypes = [vp, vp, vp, vp, vp]
     lib.sva_step_device.argtypes = [vp, vp, vp]
     lib.sva_step_device_on.argtypes = [vp, vp, vp, vp, C.c_int]
@@ -134,7 +136,7 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "sva_last_error", "sva_config_default", "sva_stream_params_default", "sva_engine_create",
     "sva_engine_load_weight", "sva_engine_finalize", "sva_engine_destroy", "sva_batch_create", "sva_batch_destroy",
-    "sva_prefill_prompt", "sva_streams_begin", "sva_stream_restart", "sva_stream_retire", "sva_stream_state", "sva_step", "sva_step_device", "sva_step_device_on", "sva_join_stream", "sva_batch_uses_persistent_decode", "sva_test_force_ar_timeout", "sva_test_stream_overlap", "sva_debug_configure", "sva_sync", "sva_stream_chunks", "sva_encode_window", "sva_firefly_encode",
+    "sva_prefill_prompt", "sva_streams_begin", "sva_stream_restart", "sva_stream_retire", "sva_stream_state", "sva_stream_activations", "sva_step", "sva_step_device", "sva_step_device_on", "sva_join_stream", "sva_batch_uses_persistent_decode", "sva_test_force_ar_timeout", "sva_test_stream_overlap", "sva_debug_configure", "sva_sync", "sva_stream_chunks", "sva_encode_window", "sva_firefly_encode",
     "sva_vocode_window", "sva_vocode_stream", "sva_vocode_reset", "sva_quantizer_decode", "sva_vocoder_head", "sva_ar_delay_fill", "sva_ar_decode_one", "sva_generate", "sva_get_tap", "sva_get_timings",
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
@@ -260,7 +262,7 @@ class Batch:
 
     def __init__(self, engine: Engine, n_streams=1, encode_window_frames=128, decode_window_frames=64, chunk_frames=1,
                  delay=2, max_seq_frames=768, buffer_frames=32, max_prompt_frames=256, temperature=0.7, top_p=0.7,
-                 voc_max_frames=None, use_graph=False, skip_semantic=False, pipeline=False):
+                 voc_max_frames=None, use_graph=False, skip_semantic=False, pipeline=False, slot_priming=False):
         self.engine = engine
         self.lib = engine.lib
         p = SvaStreamParams()
@@ -271,6 +273,7 @@ class Batch:
         p.voc_max_frames = voc_max_frames or chunk_frames
         p.use_graph, p.skip_semantic = int(use_graph), int(skip_semantic)
         p.pipeline = int(pipeline)
+        p.slot_priming = int(slot_priming)
         self.p = p
         self.B, self.chunk = n_streams, chunk_frames
         self.h = C.c_void_p()
@@ -322,6 +325,13 @@ class Batch:
         ph, fr = C.c_int(), C.c_long()
         _check(self.lib.sva_stream_state(self.h, int(slot), C.byref(ph), C.byref(fr)), "sva_stream_state")
         return int(ph.value), int(fr.value)
+
+    def activations(self):
+        """sva_stream_activations -> (n_local, n_whole, last_ms): restarted slots activated through the one-stream priming workspace
+        (slot_priming=True) / through a whole-batch priming run, and the host wall time of the last activation."""
+        counts, ms = (C.c_long * 2)(), C.c_float()
+        _check(self.lib.sva_stream_activations(self.h, counts, C.byref(ms)), "sva_stream_activations")
+        return int(counts[0]), int(counts[1]), float(ms.value)
 
     def step(self, pcm_in, noise=None, forced_codes=None):
         x = np.ascontiguousarray(pcm_in, dtype=np.float32).reshape(self.B, 2048 * self.chunk)
