@@ -327,6 +327,18 @@ int sva_test_gemm_choice(int device, int M, int N, int K, const float* A, const 
  * out[6] = {family (GemmFamily of csrc/sva_common.h), a, b, c, z, family number of the profiling tables}; an error (sva_last_error) where the
  * dispatcher refuses the problem. */
 int sva_test_gemm_plan(const int* desc, int n, int* out);
+/* The host-side book of the per-slot stream state (csrc/slot_book.h: phases, KV positions, frame and content counters, what a step plans),
+ * scripted without a batch and without a GPU.  cfg[7] = {B, chunk_frames, delay, max_seq_frames, buffer_frames, decode_window_frames,
+ * speaker prefix rows (timbre tokens + 1)}; ops: n_ops x 3 ints {op, slot, R} with op 0 = begin, 1 = prefilled(slot, R frames),
+ * 2 = one chunk step, 3 = restart(slot, R frames), 4 = retire(slot); prompts are stored untruncated.  trace: n_ops rows of 8 B + 6 ints, the
+ * state after the op:  B x {phase, last_pos, nframes, ncontent} | delay_filled | one-pass re-prefill possible (-1: none planned) |
+ * n_redo, redo[B] | n_rewind, rewind[B] x {slot, position} | n_activated, activated[B] | vocoder priming frames (begin: of the batch; a step:
+ * of its first activated slot; else -1).  Unused list entries are -1; the lists are what the step planned before it carried them out. */
+int sva_test_slot_book(const int* cfg, const int* ops, int n_ops, int* trace);
+/* The book's stored prompt: a prompt of R frames (content code i at frame i, audio code 1000 q + i in codebook q) stored truncated to Rt
+ * frames; out [ncb][n] = frames [first, first + n) of the last P stored frames (what primes a vocoder), stored[4] = {ref_len, content codes
+ * kept, audio codes kept, last content code kept}. */
+int sva_test_slot_prompt_tail(int R, int Rt, int ncb, int P, int first, int n, int* out, int* stored);
 /* fp16-weight GEMM of the batched fp16 AR decode (csrc/gemm_f16w.hip; the reference's autocast(fp16) linear layers,
  * modules/dual_ar_stream.py:1168-1219): C = epi(A x fp16(W)^T), mode bits 1 = RMSNorm prologue, 2 = residual, 4 = SwiGLU pairs;
  * iters > 0 also returns the average microseconds per launch. */

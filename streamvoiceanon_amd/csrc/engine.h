@@ -4,6 +4,7 @@
 #include "kernels.h"
 #include "ar_decode.h"
 #include "ar_batch.h"
+#include "slot_book.h"
 
 #include <array>
 #include <map>
@@ -75,20 +76,6 @@ struct Act {
     int H = 0, C = 0;
     long rows = 0;       // H + Tmax
     long bstride = 0;    // rows * C
-};
-
-// per-layer streaming state of the exact-incremental encoder (newest 4c mel frames per step)
-struct EncStream {
-    float* mag = nullptr;                  // [B][nm][1088]
-    Act mel;                               // [B][6+nm][160]
-    Act tmp0;                              // stem conv output [B][nm][128]
-    std::vector<std::vector<Act>> x;       // x[i][j] = input of block j of stage i  [B][6+nm][C_i]
-    Act xout[4];                           // output of the last block of stage i    [B][nm][C_i]
-    Act feat;                              // [B][nm][512]
-    Act d1, d1o, d2;                       // [B][6+nm/2][512], [B][nm/2][512], [B][6+nm/4][512]
-    float *h1 = nullptr, *h2 = nullptr;    // ConvNeXt scratch
-    ShiftDesc* d_shift = nullptr;
-    int n_shift = 0;
 };
 
 // Merged incremental front-end pass: the newest 4c mel frames ride in the SAME launches as the head pass (they use the same
@@ -197,13 +184,9 @@ struct sva_batch {
     int B = 0;
     hipStream_t stream = nullptr;          // current launch stream (== main except inside a forked branch)
     hipStream_t main_stream = nullptr;
-    hipStream_t aux[2] = {nullptr, nullptr};   // side streams for independent sub-chains (fork / join by events)
+    hipStream_t aux0 = nullptr;            // side stream: the encoder's second chain (the transformer in the pipelined regime; fork / join by events)
     // stage pipelining over consecutive chunk-steps (sva_step_device, p.pipeline): AR and vocoder streams, hand-off events
     hipStream_t sa = nullptr, sv = nullptr;
-    hipEvent_t pipe_evD2C = nullptr;       // recorded once the transformer of a step no longer reads the token cache
-    hipEvent_t tr_l0_event = nullptr;      // enc_transformer records this after its first layer's output projection
-    int stream_cut = 1;                    // pipelined encoder: stages of the streaming pass that run on the main stream (0..3)
-    int pipe_split_e = 1;                  // 0: encoder as one in-order stage
     std::vector<hipEvent_t> trace_ev;     // SVA_PIPE_TRACE=N: timestamps of the stage chains of the last N pipelined steps (debug)
     long trace_steps = 0;
     int trace_n = 0;
@@ -217,7 +200,6 @@ struct sva_batch {
     hipEvent_t evpool[64];
     int evi = 0;
     bool concurrency = true;
-    bool fused_decode = true;              // B <= 2: GEMV path with fused norm / RoPE / KV-write / SwiGLU
     bool ar_failed = false;                // a persistent launch timed out: every step fails until sva_streams_begin, which falls back to the multi-launch decode
     bool use_mega = false;                 // B == 1: one persistent kernel per decoded frame (ar_decode.hip)
     int mega_per_launch = 1;               // streams per persistent launch (2 when 192 workgroups find a CU each)
@@ -270,9 +252,7 @@ struct sva_batch {
     float *tr_hn = nullptr, *tr_qkv = nullptr, *tr_att = nullptr, *tr_g = nullptr, *tr_z = nullptr;
     float* tr_x = nullptr;                 // [B][T2][512] transformer work copy
     sva::Act d2c;                          // [B][T2][512] steady token cache of the exact-incremental encoder
-    sva::EncStream es;
     sva::EncMerged em;
-    bool enc_merged = true;                // new frames folded into the head-pass launches (SVA_ENC_MERGED=0: separate streaming pass)
     sva::ShiftDesc* d_shift_d2c = nullptr;
     int Ht = 40;                           // head tokens recomputed every chunk (receptive field 38.25 tokens)
     bool enc_incremental = true;
@@ -310,37 +290,14 @@ struct sva_batch {
     int* d_pred_hist = nullptr;            // [B][8][hist_cap]
     int* d_step_content = nullptr;         // [B][chunk] content codes of this step (int32)
     int* d_step_audio = nullptr;           // [B][8][chunk]
-    // prompt (truncated to max_prompt_frames) kept for re-prefill / vocoder priming
-    std::vector<std::vector<int64_t>> ref_content;   // [B][R']
-    std::vector<std::vector<int32_t>> ref_audio;     // [B][8*R']
-    std::vector<int> ref_len;
     int* d_prompt_cc = nullptr;            // [Pmax] scratch prompt content codes (int32)
     int* d_prompt_ac = nullptr;            // [8][Pmax]
     int Pmax = 0;
 
-    // host mirrors of the deterministic per-slot state
-    std::vector<int> h_last_pos, h_nframes;
-    std::vector<int> h_ncontent;           // [B] content codes seen (a restarted slot counts from its own start)
-    int h_step = 0;
-    bool delay_filled = false;
+    // host mirrors of the deterministic per-slot state: phases, positions, counters, stored and pending prompts (slot_book.h)
+    sva::SlotBook slots;
     bool begun = false;
-    std::vector<char> prefilled;
-    // ---- per-slot stream phases (sva_stream_restart / sva_stream_retire) ----
-    // 0 retired, 1 delay filling, 2 decoding.  The slots begun together by sva_streams_begin move 1 -> 2 in lock step (delay_filled above);
-    // a restarted slot carries its new prompt in `pending` while its own delay fills and is activated -- prefill, delay fill, vocoder
-    // priming, in the order a fresh stream sees them -- at the end of the step in which its content count reaches the delay.
-    struct PendingPrompt {
-        std::vector<int64_t> cc;
-        std::vector<int32_t> ac;
-        std::vector<float> style, timbre;
-        int R = 0;
-        unsigned long long seed = 0;
-    };
-    std::vector<char> h_phase;             // [B]
-    std::vector<char> restarted;           // [B] 1: `pending` holds the prompt of a restart that has not been activated yet
-    std::vector<PendingPrompt> pending;    // [B]
     int* d_slot_flag = nullptr;            // [B] kSlotInputMuted | kSlotOutputMuted (kernels.h), read by the ring write and by conv_post
-    std::vector<int> h_slot_flag;          // its host mirror
     // one-slot vocoder priming: the history rows of every ShiftDesc of the vocoder, saved around a whole-batch priming run
     float* voc_save = nullptr;             // [B][voc_save_bstride]
     long voc_save_bstride = 0;
@@ -371,7 +328,6 @@ struct sva_batch {
     unsigned short* XP[5] = {};
     unsigned short* tbP[5][3][3] = {};
     unsigned short* ybP[5][3][2] = {};
-    bool voc_grouped = true;               // the three ResBlock branches of a level share one launch per conv stage
     float* d_pcm = nullptr;                // [B][2048*Tv]
     // per-step redirections of the device-buffer step (no staging copies): chunk source, PCM destination, codes source
     const float* step_src = nullptr;       // ring_write reads the caller's chunk directly
@@ -403,19 +359,18 @@ struct sva_batch {
     hipGraphExec_t graph_exec = nullptr;
     hipGraphExec_t pipe_graph_a[2] = {nullptr, nullptr};     // pipelined mode: the AR stage of a step, one per code-buffer parity
     int pipe_graph_mode = 1;                                 // 0: AR stage enqueued kernel by kernel
-    // pipelined mode: the front-end chain, the transformer (cut after its first layer, where it releases the token cache) and the
+    // pipelined mode: the front-end chain, the transformer (gT0 = its first layer, gT1 = the rest) and the
     // vocoder (behind the FSQ decode, where it releases the step's codes) replayed as hipGraphs: ~135 launches per step off the
     // enqueueing thread, which is otherwise the bound once the GPU side of a single-stream step drops to ~1 ms
     bool stage_graphs = true;
     hipGraphExec_t gEm[2] = {nullptr, nullptr}, gEs[2] = {nullptr, nullptr};      // front-end cut behind the backbone: main part / side part, per parity
     hipEvent_t pipe_evFeat[2] = {nullptr, nullptr};
-    int enc_cut = 1;
     int* step_bump = nullptr;              // set around a front-end call whose last kernel should also advance this counter
     int voc_fused_mask = -1;               // -1: default policy; else bit 0: the C = 16 level, bit 1: the C = 32 level
     bool voc_fused = true;                 // narrow vocoder levels (C <= 32) as one fused launch (voc_fused.hip)
     int* d_voc_frames = nullptr;           // code frames the streaming vocoder has consumed since its last reset
     int voc_rpf[5] = {0, 0, 0, 0, 0};      // rows of level i per code frame
-    hipGraphExec_t gE = nullptr, gE2 = nullptr, gT0 = nullptr, gT1[2] = {nullptr, nullptr}, gV = nullptr;
+    hipGraphExec_t gT0 = nullptr, gT1[2] = {nullptr, nullptr}, gV = nullptr;
     bool graph_ready = false;
     bool graph_step = false;       // last step ran through the graph (no per-stage events)
     bool forced_now = false;

@@ -92,7 +92,7 @@ static int recover_ar_failure(sva_batch* b) {
     b->use_abatch = false;
     for (auto& ge : b->pipe_graph_a) if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
     if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
-    std::fill(b->prefilled.begin(), b->prefilled.end(), 0);
+    b->slots.forget_prompts();
     b->begun = false;
     b->ar_failed = false;
     return 0;
@@ -109,7 +109,7 @@ extern "C" const char* sva_last_error(void) { return g_err.c_str(); }
 // ============================================================================================
 
 namespace {
-struct StreamSet { hipStream_t main = nullptr, aux0 = nullptr, sa = nullptr, sv = nullptr, aux1 = nullptr; };
+struct StreamSet { hipStream_t main = nullptr, aux0 = nullptr, sa = nullptr, sv = nullptr; };
 std::mutex g_streams_mu;
 std::map<int, StreamSet> g_streams;          // per device, process lifetime
 // `partitioned`: the AR stream and the encoder / vocoder streams get disjoint compute-unit masks (hipExtStreamCreateWithCUMask;
@@ -133,14 +133,14 @@ std::map<int, StreamSet> g_streams;          // per device, process lifetime
 //            legacy null stream, i.e. with a host application's torch work, and costs four more hardware queues.  Not the default.
 //   SQ_PLAIN four plain non-blocking streams (the behaviour before; each stream's fallback when the chosen call fails).
 // SVA_DEBUG=stream_queues=0|1|2 picks plain / mask / prio for A/B runs (tools/hwq_ab.sh; tools/micro/stream_queues.hip is the
-// stand-alone probe of the three).  ops_stream, aux1 and the test hooks' streams stay plain.
+// stand-alone probe of the three).  ops_stream and the test hooks' streams stay plain.
 // Hardware queues a process can end up with: the pools (4 entries per priority level in use: normal + highest = 8, shared with the
 // host application) + 4 dedicated ones per LIVE partitioned variant (the policy uses the 1-stream split and 64 / 96 / 128 AR CUs: 16
 // if one process ever creates all four, 4 in a process that serves one partitioned batch size) = 8 to 12 as a rule, 24 at the very
 // most, under the 32 the runtime allows a process; SQ_MASK would add 4.
 enum { SQ_PLAIN = 0, SQ_MASK = 1, SQ_PRIO = 2 };
 constexpr int kStreamQueues = SQ_PRIO;
-int get_streams(int device, bool need_aux1, int n_streams_if_pipelined, StreamSet* out, int ar_cus = 96) {
+int get_streams(int device, int n_streams_if_pipelined, StreamSet* out, int ar_cus = 96) {
     std::lock_guard<std::mutex> lk(g_streams_mu);
     // variant 1 (one stream): AR 96 CUs | encoder 128 | vocoder 32 (12 / 16 / 4 per XCD) -- 2.11 -> 1.75 ms per step, 1.60 with the
     // encoder split; 96/136/24 measures the same but leaves the vocoder no slack (96/138/22 and 92/140/24 lose the whole gain:
@@ -188,7 +188,6 @@ int get_streams(int device, bool need_aux1, int n_streams_if_pipelined, StreamSe
         SVA_TRY(make(&s.sa, part[0], part[1], true));
         SVA_TRY(make(&s.sv, part[4], part[5], true));
     }
-    if (need_aux1 && !s.aux1) SVA_HIP(hipStreamCreateWithFlags(&s.aux1, hipStreamNonBlocking));     // legacy three-stream vocoder only
     *out = s;
     return 0;
 }
@@ -354,9 +353,8 @@ static int create_priming_workspace(sva_batch* b) {
     w->p.n_streams = 1; w->p.slot_priming = 0; w->p.voc_max_frames = Tv; w->p.pipeline = 0; w->p.use_graph = 0;
     w->B = 1;
     w->stream = w->main_stream = w->out_stream = b->main_stream;
-    w->aux[0] = b->aux[0]; w->aux[1] = b->aux[1];
+    w->aux0 = b->aux0;
     w->concurrency = b->concurrency;
-    w->voc_grouped = b->voc_grouped;
     w->enc_cus = b->enc_cus;
     w->d_mm_ovf = b->d_mm_ovf;              // (h_mm_ovf stays null here: the owner polls and frees the flag)
     for (int i = 0; i < 64; ++i) SVA_HIP(hipEventCreateWithFlags(&w->evpool[i], hipEventDisableTiming));
@@ -411,7 +409,6 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
     // mode gains 16 % at 64 streams in a fresh process and nothing after one create / destroy cycle.  Batches that are
     // alive at the same time therefore share the streams (in-order, so still correct), and get_streams keeps the four
     // chains on four hardware queues whatever the size of that pool.
-    if (b->p.pipeline) SVA_CHECK(b->voc_grouped, "stage pipelining needs the grouped vocoder launches");
     {
         StreamSet ss;
         // one stream with the persistent AR decode kernel: no CU partition -- that kernel is a single launch of 96 workgroups that
@@ -447,7 +444,7 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
         }
         if (debug_options().cu_partition == 0) part_streams = 0;
         else if (debug_options().cu_partition == 1 && b->p.pipeline) { part_streams = B; if (debug_options().cu_ar > 0) ar_cus = debug_options().cu_ar; }
-        SVA_TRY(get_streams(e->device, !b->voc_grouped, part_streams, &ss, ar_cus));
+        SVA_TRY(get_streams(e->device, part_streams, &ss, ar_cus));
         b->ar_cus = part_streams >= 1 ? ar_cus : 0;
         b->ar_partitioned = part_streams >= 1;
         if (b->ar_partitioned) {
@@ -456,12 +453,11 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
             b->enc_cus = std::max(8, cus - ar_cus);
         }
         b->stream = b->main_stream = ss.main;
-        b->aux[0] = ss.aux0;
-        b->aux[1] = b->voc_grouped ? nullptr : ss.aux1;
+        b->aux0 = ss.aux0;
         if (b->p.pipeline) { b->sa = ss.sa; b->sv = ss.sv; }
         // split-K scratch per stream, now: a launch inside a stream capture must not allocate (and must not fall back to an
         // unsplit launch, which sums in a different order than the eager launch of the same shape)
-        for (hipStream_t s_ : {ss.main, ss.aux0, ss.aux1, ss.sa, ss.sv})
+        for (hipStream_t s_ : {ss.main, ss.aux0, ss.sa, ss.sv})
             if (s_) SVA_TRY(conv_gemm_prepare_stream(s_));
     }
     b->out_stream = b->stream;
@@ -514,47 +510,13 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
     SVA_TRY(alloc_act(A, b->d2c, B, 0, T2, Dm));
     b->Ht = 40;
     b->enc_incremental = T2 > b->Ht + p->chunk_frames;
-    {   // streaming state of the exact-incremental encoder
-        EncStream& S = b->es;
-        const int nm = 4 * chunk;
-        std::vector<ShiftDesc> sd;
-        auto reg = [&](Act& a, int rows_per_step) {
-            if (a.H == 0) return;
-            ShiftDesc d;
-            d.ptr = a.p; d.bstride = a.bstride; d.H = a.H; d.T = rows_per_step; d.C = a.C; d.pad = 0;
-            sd.push_back(d);
-        };
-        SVA_TRY(dev_alloc(A, &S.mag, (size_t)B * nm * 1088));
-        SVA_TRY(alloc_act(A, S.mel, B, 6, nm, c.n_mels));
-        reg(S.mel, nm);
-        SVA_TRY(alloc_act(A, S.tmp0, B, 0, nm, c.enc_dims[0]));
-        S.x.resize(4);
-        for (int i = 0; i < 4; ++i) {
-            S.x[i].resize(c.enc_depths[i]);
-            for (int j = 0; j < c.enc_depths[i]; ++j) {
-                SVA_TRY(alloc_act(A, S.x[i][j], B, 6, nm, c.enc_dims[i]));
-                reg(S.x[i][j], nm);
-            }
-            SVA_TRY(alloc_act(A, S.xout[i], B, 0, nm, c.enc_dims[i]));
-        }
-        SVA_TRY(alloc_act(A, S.feat, B, 0, nm, Dm));
-        SVA_TRY(alloc_act(A, S.d1, B, 6, nm / 2, Dm));
-        reg(S.d1, nm / 2);
-        SVA_TRY(alloc_act(A, S.d1o, B, 0, nm / 2, Dm));
-        SVA_TRY(alloc_act(A, S.d2, B, 6, nm / 4, Dm));
-        reg(S.d2, nm / 4);
-        SVA_TRY(dev_alloc(A, &S.h1, (size_t)B * nm * Dm));
-        SVA_TRY(dev_alloc(A, &S.h2, (size_t)B * nm * 4 * Dm));
-        S.n_shift = (int)sd.size();
-        SVA_TRY(dev_alloc(A, &S.d_shift, sd.size()));
-        SVA_HIP(hipMemcpy(S.d_shift, sd.data(), sizeof(ShiftDesc) * sd.size(), hipMemcpyHostToDevice));
-        // steady token cache: rows [Ht + c, T2) slide to [Ht, T2 - c) every step
+    {   // steady token cache of the exact-incremental encoder: rows [Ht + c, T2) slide to [Ht, T2 - c) every step
         ShiftDesc dc;
         dc.ptr = b->d2c.p + (long)b->Ht * Dm; dc.bstride = b->d2c.bstride; dc.H = std::max(0, T2 - b->Ht - chunk); dc.T = chunk; dc.C = Dm; dc.pad = 0;
         SVA_TRY(dev_alloc(A, &b->d_shift_d2c, 1));
         SVA_HIP(hipMemcpy(b->d_shift_d2c, &dc, sizeof(ShiftDesc), hipMemcpyHostToDevice));
     }
-    if (b->enc_incremental && b->enc_merged) {
+    if (b->enc_incremental) {
         EncMerged& M = b->em;
         M.Hh = 4 * b->Ht; M.nm = 4 * chunk;
         const int Hh = M.Hh, nm = M.nm, R0 = Hh + 6 + nm, R1 = Hh / 2 + 6 + nm / 2, R2 = Hh / 4 + 6 + nm / 4;
@@ -638,7 +600,7 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
     // persistent batch-1 decode kernel (ar_decode.hip): granule buffers, tag epoch, timeout word, fast K/V scratch
     // up to mega_max_b streams decode in ONE launch of it (96 workgroups per stream, each stream's group talks only to itself); the
     // multi-launch chain of the batched path (~200 dependent launches, 2.4-3.3 ms per frame at 2-8 streams) takes over above that
-    b->use_mega = B <= b->mega_max && e->mega_ok && b->fused_decode && debug_options().ar_persistent != 0 && debug_options().ar_batch != 2;
+    b->use_mega = B <= b->mega_max && e->mega_ok && debug_options().ar_persistent != 0 && debug_options().ar_batch != 2;
     if (b->use_mega) {
         // every workgroup of a persistent launch must be resident at once: check the launch geometry against the occupancy query and
         // the CUs the AR stream may use, never assume it.  One workgroup per CU is what the kernel is sized for (256 registers, 4 waves);
@@ -715,9 +677,7 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
     b->Pmax = S;
     SVA_TRY(dev_alloc(A, &b->d_prompt_cc, b->Pmax));
     SVA_TRY(dev_alloc(A, &b->d_prompt_ac, (size_t)ncb * b->Pmax));
-    b->ref_content.resize(B); b->ref_audio.resize(B); b->ref_len.assign(B, 0);
-    b->h_last_pos.assign(B, -1); b->h_nframes.assign(B, 0); b->prefilled.assign(B, 0);
-    b->h_ncontent.assign(B, 0); b->h_phase.assign(B, 1); b->restarted.assign(B, 0); b->pending.resize(B); b->h_slot_flag.assign(B, 0);
+    b->slots.reset(B);
     // vocoder
     SVA_TRY(alloc_vocoder(b, b->p.voc_max_frames, nullptr));
     if (b->p.slot_priming) SVA_TRY(create_priming_workspace(b));
@@ -744,7 +704,7 @@ extern "C" void sva_batch_destroy(sva_batch* b) {
         if (b->counted_persistent) { b->e->persistent_batches -= 1; b->counted_persistent = false; }
     }
     if (b->main_stream) (void)hipStreamSynchronize(b->main_stream);
-    for (int i = 0; i < 2; ++i) if (b->aux[i]) (void)hipStreamSynchronize(b->aux[i]);
+    if (b->aux0) (void)hipStreamSynchronize(b->aux0);
     if (b->sa) (void)hipStreamSynchronize(b->sa);
     if (b->sv) (void)hipStreamSynchronize(b->sv);
     if (b->trace_n && b->trace_steps >= b->trace_n) {       // SVA_PIPE_TRACE: when each chain of the last steps could start / ended (us)
@@ -761,7 +721,7 @@ extern "C" void sva_batch_destroy(sva_batch* b) {
     for (auto& t : b->trace_ev) (void)hipEventDestroy(t);
     if (b->graph_exec) (void)hipGraphExecDestroy(b->graph_exec);
     for (auto& ge : b->pipe_graph_a) if (ge) (void)hipGraphExecDestroy(ge);
-    for (hipGraphExec_t ge : {b->gEm[0], b->gEm[1], b->gEs[0], b->gEs[1], b->gE, b->gE2, b->gT0, b->gT1[0], b->gT1[1], b->gV}) if (ge) (void)hipGraphExecDestroy(ge);
+    for (hipGraphExec_t ge : {b->gEm[0], b->gEm[1], b->gEs[0], b->gEs[1], b->gT0, b->gT1[0], b->gT1[1], b->gV}) if (ge) (void)hipGraphExecDestroy(ge);
     for (void* p : b->allocs.chunks) (void)hipFree(p);
     if (sva_batch* w = b->prime_ws) {        // the priming workspace: arena chunks and its event pool (streams and the overflow flag are the owner's)
         for (void* p : w->allocs.chunks) (void)hipFree(p);
@@ -821,11 +781,6 @@ static int prefill_slot_impl(sva_batch* b, int slot, const int64_t* ref_content_
     SVA_TRY(ar_prefill_slot(b, slot, R, tap_logits));
     // ... while the stored prompt (re-prefill, vocoder fill) is truncated to max_prompt_frames (:469-470)
     const int Rt = std::min(R, b->p.max_prompt_frames);
-    b->ref_content[slot].assign(cc.begin(), cc.begin() + Rt);
-    b->ref_audio[slot].resize((size_t)ncb * Rt);
-    for (int q = 0; q < ncb; ++q)
-        for (int i = 0; i < Rt; ++i) b->ref_audio[slot][(size_t)q * Rt + i] = ac[(size_t)q * R + i];
-    b->ref_len[slot] = Rt;
     {   // the last max_delay frames of the stored prompt's audio codes, for the device-side re-prefill (right-aligned; a shorter prompt leaves the front unused)
         const int md = c.max_delay;
         std::vector<int32_t> tail((size_t)ncb * md, 0);
@@ -834,7 +789,7 @@ static int prefill_slot_impl(sva_batch* b, int slot, const int64_t* ref_content_
                 if (Rt - md + j >= 0) tail[(size_t)q * md + j] = ac[(size_t)q * R + (Rt - md + j)];
         SVA_TRY(h2d(b, b->d_ref_tail + (long)slot * ncb * md, tail.data(), sizeof(int32_t) * tail.size()));
     }
-    b->prefilled[slot] = 1;
+    b->slots.prefilled(slot, c.timbre_tokens + 1, R, Rt, ncb, cc.data(), ac.data());
     return 0;
 }
 
@@ -951,19 +906,14 @@ extern "C" int sva_streams_begin(sva_batch* b) {
     SVA_TRY(quiesce(b));
     SVA_TRY(recover_ar_failure(b));
     const int B = b->B, ncb = b->e->cfg.num_codebooks, c = b->p.chunk_frames;
-    for (int i = 0; i < B; ++i) SVA_CHECK(b->prefilled[i], "every slot needs sva_prefill_prompt before sva_streams_begin");
+    SVA_CHECK(b->slots.all_prefilled(), "every slot needs sva_prefill_prompt before sva_streams_begin");
     // setup_stream_caches (infer_arvc.py:443-460)
     SVA_HIP(hipMemsetAsync(b->ring, 0, sizeof(float) * (size_t)B * b->N, b->stream));
     SVA_HIP(hipMemsetAsync(b->d_step, 0, sizeof(int), b->stream));
     SVA_HIP(hipMemsetAsync(b->d_nframes, 0, sizeof(int) * B, b->stream));
     SVA_HIP(hipMemsetAsync(b->d_ncontent, 0, sizeof(int) * B, b->stream));
-    b->h_step = 0; b->delay_filled = false;
-    std::fill(b->h_ncontent.begin(), b->h_ncontent.end(), 0);
-    std::fill(b->h_phase.begin(), b->h_phase.end(), 1);          // every slot starts in lock step: no restart pending, nothing muted
-    std::fill(b->restarted.begin(), b->restarted.end(), 0);
-    std::fill(b->h_slot_flag.begin(), b->h_slot_flag.end(), 0);
+    b->slots.begin();
     SVA_HIP(hipMemsetAsync(b->d_slot_flag, 0, sizeof(int) * B, b->stream));
-    std::fill(b->h_nframes.begin(), b->h_nframes.end(), 0);
     if (b->enc_incremental) {
         // The reference's window starts as all-zero audio (:451): initialise the per-layer histories and the steady
         // token cache with the network's response to silence by streaming zero frames until every history row and
@@ -972,44 +922,37 @@ extern "C" int sva_streams_begin(sva_batch* b) {
             SVA_HIP(hipMemsetAsync(a.p, 0, sizeof(float) * (size_t)B * a.bstride, b->stream));
             return 0;
         };
-        EncStream& S = b->es;
         SVA_TRY(zero(b->d2c));
         const int warm = 48 / c + 2;             // > receptive field (117 mel frames = 30 tokens) -> histories are steady
-        if (b->enc_merged) {
-            EncMerged& M = b->em;
-            SVA_TRY(zero(M.mel)); SVA_TRY(zero(M.d1)); SVA_TRY(zero(M.d2));
-            for (auto& st_ : M.x) for (auto& a : st_) SVA_TRY(zero(a));
-            sva_engine* e = b->e;
-            std::vector<ShiftDesc> sd(M.n_shift);
-            SVA_HIP(hipMemcpy(sd.data(), M.d_shift, sizeof(ShiftDesc) * M.n_shift, hipMemcpyDeviceToHost));
-            const auto key = std::make_pair(B, c);
-            auto it = e->silence.find(key);
-            if (it == e->silence.end()) {
-                for (int i = 0; i < warm; ++i) SVA_TRY(enc_frontend_merged(b, nullptr, 0, 0));     // (the ring is all zeros here)
-                sva_engine::SilenceState ss;
-                for (const ShiftDesc& d : sd) {          // keep the newest history row of item 0 per buffer, and the token row
-                    float* r = nullptr;
-                    SVA_TRY(dev_alloc(e->allocs, &r, (size_t)d.C, false));
-                    SVA_HIP(hipMemcpyAsync(r, d.ptr + (long)(d.H - 1) * d.C, sizeof(float) * d.C, hipMemcpyDeviceToDevice, b->stream));
-                    ss.rows.push_back(r);
-                }
-                SVA_TRY(dev_alloc(e->allocs, &ss.tok, (size_t)b->e->cfg.tr_dim, false));
-                SVA_HIP(hipMemcpyAsync(ss.tok, b->d2c.p + (long)(b->T2 - 1) * b->e->cfg.tr_dim, sizeof(float) * b->e->cfg.tr_dim, hipMemcpyDeviceToDevice, b->stream));
-                e->silence[key] = ss;
-            } else {
-                const sva_engine::SilenceState& ss = it->second;
-                for (size_t i = 0; i < sd.size(); ++i) {
-                    const ShiftDesc& d = sd[i];
-                    hipLaunchKernelGGL(fill_rows_kernel, dim3(d.H, B), dim3(128), 0, b->stream, d.ptr, d.bstride, d.C, ss.rows[i]);
-                }
-                hipLaunchKernelGGL(fill_rows_kernel, dim3(1, B), dim3(128), 0, b->stream, b->d2c.p + (long)(b->T2 - 1) * b->e->cfg.tr_dim, b->d2c.bstride,
-                                   b->e->cfg.tr_dim, ss.tok);
-                SVA_HIP(hipGetLastError());
+        EncMerged& M = b->em;
+        SVA_TRY(zero(M.mel)); SVA_TRY(zero(M.d1)); SVA_TRY(zero(M.d2));
+        for (auto& st_ : M.x) for (auto& a : st_) SVA_TRY(zero(a));
+        sva_engine* e = b->e;
+        std::vector<ShiftDesc> sd(M.n_shift);
+        SVA_HIP(hipMemcpy(sd.data(), M.d_shift, sizeof(ShiftDesc) * M.n_shift, hipMemcpyDeviceToHost));
+        const auto key = std::make_pair(B, c);
+        auto it = e->silence.find(key);
+        if (it == e->silence.end()) {
+            for (int i = 0; i < warm; ++i) SVA_TRY(enc_frontend_merged(b, nullptr, 0, 0));     // (the ring is all zeros here)
+            sva_engine::SilenceState ss;
+            for (const ShiftDesc& d : sd) {          // keep the newest history row of item 0 per buffer, and the token row
+                float* r = nullptr;
+                SVA_TRY(dev_alloc(e->allocs, &r, (size_t)d.C, false));
+                SVA_HIP(hipMemcpyAsync(r, d.ptr + (long)(d.H - 1) * d.C, sizeof(float) * d.C, hipMemcpyDeviceToDevice, b->stream));
+                ss.rows.push_back(r);
             }
+            SVA_TRY(dev_alloc(e->allocs, &ss.tok, (size_t)b->e->cfg.tr_dim, false));
+            SVA_HIP(hipMemcpyAsync(ss.tok, b->d2c.p + (long)(b->T2 - 1) * b->e->cfg.tr_dim, sizeof(float) * b->e->cfg.tr_dim, hipMemcpyDeviceToDevice, b->stream));
+            e->silence[key] = ss;
         } else {
-            SVA_TRY(zero(S.mel)); SVA_TRY(zero(S.d1)); SVA_TRY(zero(S.d2));
-            for (auto& st_ : S.x) for (auto& a : st_) SVA_TRY(zero(a));
-            for (int i = 0; i < warm; ++i) SVA_TRY(enc_frontend_stream(b, nullptr, 0, 0));
+            const sva_engine::SilenceState& ss = it->second;
+            for (size_t i = 0; i < sd.size(); ++i) {
+                const ShiftDesc& d = sd[i];
+                hipLaunchKernelGGL(fill_rows_kernel, dim3(d.H, B), dim3(128), 0, b->stream, d.ptr, d.bstride, d.C, ss.rows[i]);
+            }
+            hipLaunchKernelGGL(fill_rows_kernel, dim3(1, B), dim3(128), 0, b->stream, b->d2c.p + (long)(b->T2 - 1) * b->e->cfg.tr_dim, b->d2c.bstride,
+                               b->e->cfg.tr_dim, ss.tok);
+            SVA_HIP(hipGetLastError());
         }
         // every cached token of a silent window is that same steady response
         hipLaunchKernelGGL(broadcast_row_kernel, dim3(b->T2, B), dim3(256), 0, b->stream, b->d2c.p, b->d2c.bstride, b->T2 - 1, 0, b->T2,
@@ -1021,18 +964,13 @@ extern "C" int sva_streams_begin(sva_batch* b) {
     // depends on the newest 16 code frames, so running the last (window-1) prompt frames through the
     // ring-buffer vocoder reproduces the windowed output.
     SVA_TRY(sva_vocode_reset(b));
-    int P = b->p.decode_window_frames - 1;
-    for (int i = 0; i < B; ++i) P = std::min(P, b->ref_len[i]);
-    P = (P / c) * c;
+    int P = b->slots.priming_frames(0, b->p.decode_window_frames, c);       // (the shortest stored prompt of the batch decides)
+    for (int i = 1; i < B; ++i) P = std::min(P, b->slots.priming_frames(i, b->p.decode_window_frames, c));
     SVA_CHECK(P >= 16 || P == b->p.decode_window_frames - 1, "prompt shorter than the vocoder receptive field (16 frames)");
     std::vector<int32_t> codes((size_t)B * ncb * c);
     std::vector<float> sink((size_t)B * 2048 * c);
     for (int f = 0; f < P; f += c) {
-        for (int i = 0; i < B; ++i) {
-            const int R = b->ref_len[i];
-            for (int q = 0; q < ncb; ++q)
-                for (int k = 0; k < c; ++k) codes[((size_t)i * ncb + q) * c + k] = b->ref_audio[i][(size_t)q * R + (R - P + f + k)];
-        }
+        for (int i = 0; i < B; ++i) b->slots.prompt_tail(i, ncb, P, f, c, codes.data() + (size_t)i * ncb * c);
         SVA_TRY(sva_vocode_stream(b, codes.data(), c, sink.data()));
     }
     b->begun = true;
@@ -1071,10 +1009,11 @@ int reprefill_slots(sva_batch* b, const std::vector<int>& due) {
         a.row_off[0] = 0;
         for (int i = 0; i < a.n; ++i) {
             const int slot = due[lo + i];
-            const int nf = b->h_nframes[slot], ncon = b->h_ncontent[slot];
-            const int na = std::min(bf, nf);
+            const SlotHost& h = b->slots.s[slot];
+            const int nf = h.nframes, ncon = h.ncontent;
+            const int na = b->slots.reprefill_frames(slot, bf);
             SVA_CHECK(na == std::max(0, (ncon - d) - std::max(0, ncon - bf - d)) && na >= d, "re-prefill: content/audio history length mismatch");
-            a.slot[i] = slot; a.Rt[i] = b->ref_len[slot]; a.nf[i] = nf; a.na[i] = na; a.ncon[i] = ncon;
+            a.slot[i] = slot; a.Rt[i] = h.ref_len; a.nf[i] = nf; a.na[i] = na; a.ncon[i] = ncon;
             a.row_off[i + 1] = a.row_off[i] + 2 * na;
             // BEFORE anything is enqueued: rows past the slot's cache would land in the next slot's
             SVA_CHECK(nspk + 2 * (a.Rt[i] + na) + 2 * d <= c.max_seq_len, "re-prefill: prompt too long for the KV cache");
@@ -1088,7 +1027,7 @@ int reprefill_slots(sva_batch* b, const std::vector<int>& due) {
         hipLaunchKernelGGL(finish_reprefill_kernel, dim3(a.n * d), dim3(256), 0, st, a, e->codebook_emb, b->d_pred_hist, b->hist_cap, b->d_ref_tail,
                            c.max_delay, d, ncb, c.codebook_size, D, nspk, b->cached_ref_emb, b->d_last_pos);
         SVA_HIP(hipGetLastError());
-        for (int i = 0; i < a.n; ++i) b->h_last_pos[a.slot[i]] = nspk + 2 * (a.Rt[i] + a.na[i]) - 1;
+        for (int i = 0; i < a.n; ++i) b->slots.reprefilled(a.slot[i], b->slots.reprefill_end(a.slot[i], nspk, bf));
     }
     return 0;
 }
@@ -1098,9 +1037,10 @@ int reprefill_slot(sva_batch* b, int slot) {
     // [ref content, src content[-buffer-d:-d]]; then delay fill with src content[-d:]
     const sva_config& c = b->e->cfg;
     const int ncb = c.num_codebooks, d = b->p.delay, bf = b->p.buffer_frames;
-    const int R = b->ref_len[slot];
-    const int nf = b->h_nframes[slot], ncon = b->h_ncontent[slot];
-    const int na = std::min(bf, nf);                   // pred_codes[..., -bf:]
+    const SlotHost& h = b->slots.s[slot];
+    const int R = h.ref_len;
+    const int nf = h.nframes, ncon = h.ncontent;
+    const int na = b->slots.reprefill_frames(slot, bf);                   // pred_codes[..., -bf:]
     const int c_hi = ncon - d, c_lo = std::max(0, ncon - bf - d);
     const int nc = std::max(0, c_hi - c_lo);
     SVA_CHECK(na == nc, "re-prefill: content/audio history length mismatch");
@@ -1118,16 +1058,17 @@ int reprefill_slot(sva_batch* b, int slot) {
             for (int i = 0; i < na; ++i) ha[(size_t)q * na + i] = ring[(nf - na + i) & (cap - 1)];
         }
     }
-    std::vector<int64_t> cc(b->ref_content[slot]);
+    std::vector<int64_t> cc(h.ref_content);
     for (int i = 0; i < nc; ++i) cc.push_back(hc[i]);
     const int Rn = R + na;
     std::vector<int32_t> ac((size_t)ncb * Rn);
     for (int q = 0; q < ncb; ++q) {
-        for (int i = 0; i < R; ++i) ac[(size_t)q * Rn + i] = b->ref_audio[slot][(size_t)q * R + i];
+        for (int i = 0; i < R; ++i) ac[(size_t)q * Rn + i] = h.ref_audio[(size_t)q * R + i];
         for (int i = 0; i < na; ++i) ac[(size_t)q * Rn + R + i] = ha[(size_t)q * na + i];
     }
     SVA_TRY(stage_prompt(b, cc, ac, Rn));
     SVA_TRY(ar_prefill_slot(b, slot, Rn));
+    b->slots.reprefilled(slot, SlotBook::prefill_end(c.timbre_tokens + 1, Rn));
     return 0;
 }
 
@@ -1204,7 +1145,7 @@ int steady_pipelined(sva_batch* b) {
         SVA_HIP(hipStreamWaitEvent(sa, ev, 0));
         SVA_HIP(hipStreamWaitEvent(sv, ev, 0));
         SVA_HIP(hipMemcpyAsync(b->d_step_x, b->d_step, sizeof(int), hipMemcpyDeviceToDevice, se));      // the side chain's chunk counter
-        b->pipe_evVc[0] = b->pipe_evVc[1] = nullptr; b->pipe_evR = nullptr; b->pipe_evA[0] = b->pipe_evA[1] = nullptr; b->pipe_evD2C = nullptr;
+        b->pipe_evVc[0] = b->pipe_evVc[1] = nullptr; b->pipe_evR = nullptr; b->pipe_evA[0] = b->pipe_evA[1] = nullptr;
         b->pipe_evFeat[0] = b->pipe_evFeat[1] = nullptr;
     }
     const int par = b->pipe_parity;
@@ -1218,130 +1159,58 @@ int steady_pipelined(sva_batch* b) {
         if (b->trace_n) SVA_HIP(hipEventRecord(b->trace_ev[(size_t)(b->trace_steps % b->trace_n) * 9 + k], st_));
         return 0;
     };
-    if (b->pipe_split_e && b->enc_incremental && b->concurrency && b->aux[0]) {
-        // The encoder is three chains -- head pass (main), streaming pass (side stream sx) and the 8-layer transformer + BSQ,
-        // which needs both -- and as one in-order stage its latency (1.7 ms) was the period of the whole pipeline.  The
-        // transformer therefore moves to the side stream behind the streaming pass:
-        //   main: slide d2c, head pass(n)                         -> evHead
-        //   sx:   streaming pass(n), [evHead] transformer + BSQ(n) -> evE
-        // so head pass(n+1) overlaps transformer(n) and the encoder's period is the side stream's chain.  Hazards: the token
-        // cache d2c (written by the slide, the head rows and the tail rows; read by the transformer in its FIRST layer only --
-        // QKV operand and the residual of the output projection): main(n+1) waits for an event the transformer records
-        // after that layer, and sx is in order; the chunk counter (ring position) is read by the first kernel of each
-        // front-end chain, so each chain advances its own copy when it is done (the append no longer does).
-        hipStream_t sx = b->aux[0];
-        if (b->pipe_evD2C && !b->enc_merged) SVA_HIP(hipStreamWaitEvent(se, b->pipe_evD2C, 0));
+    if (b->enc_incremental && b->concurrency && b->aux0) {
+        // As one in-order stage the encoder's latency (1.7 ms) was the period of the whole pipeline, so it is two chains, both replayed as
+        // hipGraphs (stage_graph) and both near the AR frame time:
+        //   main: the merged front-end's backbone (STFT .. final LayerNorm; the new frames ride in the head-pass launches) -> feat[par]
+        //   sx:   slide d2c, the quantizer's downsampler -> d2c, transformer + BSQ(n)                                       -> evE
+        // so backbone(n+1) overlaps downsampler + transformer(n).  The token cache d2c is written and read on ONE in-order stream (sx).  The
+        // hand-over buffer feat[] alternates; main(n+2) waits until side(n) has read it.  The chunk counter (ring position) is read by the
+        // first kernel of the main chain, whose last kernel advances it (step_bump; the append no longer does).
+        hipStream_t sx = b->aux0;
         b->stream = se;
         if (stage_ev) SVA_HIP(hipEventRecord(b->ev[0], se));
         SVA_TRY(mark(0, se));
-        if (b->enc_merged) {
-            // ONE front-end chain on the main stream (the new frames ride in the head-pass launches); the side stream only carries
-            // the transformer, which overlaps the next step's front-end.  Both chains replay as hipGraphs (stage_graph).
-            if (b->enc_cut) {
-                // Balanced cut: the backbone (STFT .. final LayerNorm) is the main chain, the quantizer's downsampler joins the
-                // transformer on the side chain -- both near the AR frame time, and the token cache d2c is then written and read on
-                // ONE in-order stream.  The hand-over buffer feat[] alternates; main(n+2) waits until side(n) has read it.
-                if (b->pipe_evFeat[par]) SVA_HIP(hipStreamWaitEvent(se, b->pipe_evFeat[par], 0));
-                SVA_TRY(stage_graph(b, &b->gEm[par], se, [&]() -> int {
-                    b->stream = se;
-                    SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se, b->d_slot_flag));
-                    b->step_bump = b->d_step;              // the history shift that ends the chain also advances the chunk counter
-                    const int frc = enc_frontend_merged(b, b->d_step, n, 1, 3, par);
-                    b->step_bump = nullptr;
-                    return frc;
-                }));
-                SVA_TRY(mark(1, se));
-                SVA_TRY(mark(2, sx));
-                SVA_TRY(stream_fork(b, se, sx));
-                int src_ = stage_graph(b, &b->gEs[par], sx, [&]() -> int {
-                    b->stream = sx;
-                    SVA_TRY(launch_shift_history(b->d_shift_d2c, 1, B, sx, 16));               // steady tokens slide down by c
-                    return enc_frontend_merged(b, nullptr, n, 1, 4, par);
-                });
-                b->stream = se;
-                if (src_) return src_;
-                b->pipe_evFeat[par] = next_event(b);
-                SVA_HIP(hipEventRecord(b->pipe_evFeat[par], sx));
-            } else {
-            // the token cache d2c is only touched by the last three kernels of the front-end (slide, head + new tokens in, history
-            // shift): only they wait for transformer(n-1)'s first layer -- the front-end of step n itself starts at once
-            SVA_TRY(stage_graph(b, &b->gE, se, [&]() -> int {
-                b->stream = se;
-                SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se, b->d_slot_flag));
-                return enc_frontend_merged(b, b->d_step, n, 1, 1);
-            }));
-            if (b->pipe_evD2C) SVA_HIP(hipStreamWaitEvent(se, b->pipe_evD2C, 0));
-            SVA_TRY(stage_graph(b, &b->gE2, se, [&]() -> int {
-                b->stream = se;
-                SVA_TRY(launch_shift_history(b->d_shift_d2c, 1, B, se, 16));                   // steady tokens slide down by c
-                SVA_TRY(enc_frontend_merged(b, b->d_step, n, 1, 2));
-                return launch_add_i32(b->d_step, 1, se);
-            }));
-            SVA_TRY(mark(1, se));
-            SVA_TRY(mark(2, sx));
-            SVA_TRY(stream_fork(b, se, sx));                                              // transformer(n) needs the front-end of step n
-            }
-            if (b->pipe_evA[par]) SVA_HIP(hipStreamWaitEvent(sx, b->pipe_evA[par], 0));  // back-pressure: BSQ overwrites the codes A(n-2) read
-            if (b->pipe_evR) { SVA_HIP(hipStreamWaitEvent(sx, b->pipe_evR, 0)); b->pipe_evR = nullptr; }
-            SVA_TRY(mark(3, sx));
-            b->tr_l0_event = nullptr;
-            int trc = stage_graph(b, &b->gT0, sx, [&]() -> int { b->stream = sx; return enc_transformer(b, b->d2c, chunk, 1); });
+        if (b->pipe_evFeat[par]) SVA_HIP(hipStreamWaitEvent(se, b->pipe_evFeat[par], 0));
+        SVA_TRY(stage_graph(b, &b->gEm[par], se, [&]() -> int {
             b->stream = se;
-            if (trc) return trc;
-            b->pipe_evD2C = next_event(b);                                                // the token cache is not read past the first layer
-            SVA_HIP(hipEventRecord(b->pipe_evD2C, sx));
-            trc = stage_graph(b, &b->gT1[par], sx, [&]() -> int {
-                b->stream = sx;
-                SVA_TRY(enc_transformer(b, b->d2c, chunk, 2));
-                hipLaunchKernelGGL(append_content_kernel, dim3((B + 63) / 64), dim3(64), 0, sx, b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap,
-                                   b->d_ncontent, b->d_step_content, B, (int*)nullptr);
-                SVA_HIP(hipGetLastError());
-                return 0;
-            });
-            b->stream = se;
-            if (trc) return trc;
-            if (stage_ev) SVA_HIP(hipEventRecord(b->ev[1], sx));
-            SVA_TRY(mark(4, sx));
-        } else {
-        SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se, b->d_slot_flag));
-        SVA_TRY(launch_shift_history(b->d_shift_d2c, 1, B, se, 16));                       // steady tokens slide down by c
-        int erc = 0;
-        if (b->stream_cut > 0) {          // the first stages of the streaming pass run on main (its chunk counter), the rest on sx
-            SVA_TRY(enc_frontend_stream(b, b->d_step, n, 1, 1));
-            SVA_TRY(stream_fork(b, se, sx));
-            b->stream = sx;
-            SVA_TRY(mark(2, sx));
-            erc = enc_frontend_stream(b, b->d_step, n, 1, 2);
-            if (!erc) erc = launch_add_i32(b->d_step_x, 1, sx);                       // (kept in step although this layout does not read it)
-        } else {
-            SVA_TRY(stream_fork(b, se, sx));
-            b->stream = sx;
-            SVA_TRY(mark(2, sx));
-            erc = enc_frontend_stream(b, b->d_step_x, n, 1);                          // c newest tokens -> d2c tail
-            if (!erc) erc = launch_add_i32(b->d_step_x, 1, sx);
-        }
-        b->stream = se;
-        if (erc) return erc;
-        SVA_TRY(enc_frontend_window(b, b->d_step, n, 1, 4 * b->Ht, nullptr, &b->d2c));     // head pass -> d2c rows [0, Ht)
-        SVA_TRY(launch_add_i32(b->d_step, 1, se));
+            SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se, b->d_slot_flag));
+            b->step_bump = b->d_step;              // the history shift that ends the chain also advances the chunk counter
+            const int frc = enc_frontend_merged(b, b->d_step, n, 1, 3, par);
+            b->step_bump = nullptr;
+            return frc;
+        }));
         SVA_TRY(mark(1, se));
-        SVA_TRY(stream_fork(b, se, sx));                                              // transformer(n) needs head pass(n)
-        // back-pressure: this step's BSQ overwrites the code buffer that A(n-2) read, so E may lead A by at most two steps
-        if (b->pipe_evA[par]) SVA_HIP(hipStreamWaitEvent(sx, b->pipe_evA[par], 0));
+        SVA_TRY(mark(2, sx));
+        SVA_TRY(stream_fork(b, se, sx));
+        int src_ = stage_graph(b, &b->gEs[par], sx, [&]() -> int {
+            b->stream = sx;
+            SVA_TRY(launch_shift_history(b->d_shift_d2c, 1, B, sx, 16));               // steady tokens slide down by c
+            return enc_frontend_merged(b, nullptr, n, 1, 4, par);
+        });
+        b->stream = se;
+        if (src_) return src_;
+        b->pipe_evFeat[par] = next_event(b);
+        SVA_HIP(hipEventRecord(b->pipe_evFeat[par], sx));
+        if (b->pipe_evA[par]) SVA_HIP(hipStreamWaitEvent(sx, b->pipe_evA[par], 0));  // back-pressure: BSQ overwrites the codes A(n-2) read
         if (b->pipe_evR) { SVA_HIP(hipStreamWaitEvent(sx, b->pipe_evR, 0)); b->pipe_evR = nullptr; }
-        b->stream = sx;
         SVA_TRY(mark(3, sx));
-        b->pipe_evD2C = next_event(b);
-        b->tr_l0_event = b->pipe_evD2C;
-        const int trc = enc_transformer(b, b->d2c, chunk);
-        b->tr_l0_event = nullptr;
+        // (two graphs, cut behind the first layer: the cut once released the token cache to the main chain and releases nothing now)
+        int trc = stage_graph(b, &b->gT0, sx, [&]() -> int { b->stream = sx; return enc_transformer(b, b->d2c, chunk, 1); });
         b->stream = se;
         if (trc) return trc;
-        hipLaunchKernelGGL(append_content_kernel, dim3((B + 63) / 64), dim3(64), 0, sx, b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap,
-                           b->d_ncontent, b->d_step_content, B, (int*)nullptr);
+        trc = stage_graph(b, &b->gT1[par], sx, [&]() -> int {
+            b->stream = sx;
+            SVA_TRY(enc_transformer(b, b->d2c, chunk, 2));
+            hipLaunchKernelGGL(append_content_kernel, dim3((B + 63) / 64), dim3(64), 0, sx, b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap,
+                               b->d_ncontent, b->d_step_content, B, (int*)nullptr);
+            SVA_HIP(hipGetLastError());
+            return 0;
+        });
+        b->stream = se;
+        if (trc) return trc;
         if (stage_ev) SVA_HIP(hipEventRecord(b->ev[1], sx));
         SVA_TRY(mark(4, sx));
-        }
         if (b->pipe_evVc[par]) SVA_HIP(hipStreamWaitEvent(sx, b->pipe_evVc[par], 0));     // V(n-2) has read the audio-code buffer A(n) will overwrite (long since)
         evE = next_event(b);
         SVA_HIP(hipEventRecord(evE, sx));
@@ -1436,44 +1305,33 @@ int quiesce(sva_batch* b) {
     SVA_HIP(hipEventRecord(e2, b->sv));
     SVA_HIP(hipStreamWaitEvent(se, e1, 0));
     SVA_HIP(hipStreamWaitEvent(se, e2, 0));
-    if (b->aux[0]) {                       // (carries the encoder's transformer in the pipelined regime)
+    if (b->aux0) {                         // (carries the encoder's transformer in the pipelined regime)
         hipEvent_t e3 = next_event(b);
-        SVA_HIP(hipEventRecord(e3, b->aux[0]));
+        SVA_HIP(hipEventRecord(e3, b->aux0));
         SVA_HIP(hipStreamWaitEvent(se, e3, 0));
     }
     b->pipe_dirty = false;
-    b->pipe_evVc[0] = b->pipe_evVc[1] = nullptr; b->pipe_evR = nullptr; b->pipe_evA[0] = b->pipe_evA[1] = nullptr; b->pipe_evD2C = nullptr;
+    b->pipe_evVc[0] = b->pipe_evVc[1] = nullptr; b->pipe_evR = nullptr; b->pipe_evA[0] = b->pipe_evA[1] = nullptr;
         b->pipe_evFeat[0] = b->pipe_evFeat[1] = nullptr;
     b->out_stream = se;
     return 0;
 }
 
-// ---- per-slot restart (sva_stream_restart / sva_stream_retire) ----
-// A parked slot (retired, or filling its own delay) still rides through the AR launches and decodes throw-away frames.  Whenever it would
-// become due for a re-prefill, and when it is restarted, its position goes back to where its last stored prompt ends: every K / V row
-// up to there was written by that prompt's prefill, so the slot decodes on valid state and never runs past its cache.
-int parked_position(const sva_batch* b, int slot) { return b->e->cfg.timbre_tokens + 2 * b->ref_len[slot]; }
-
-// the slots that sva_streams_begin started together leave their delay phase together
-void lockstep_slots_decode(sva_batch* b) {
-    for (int i = 0; i < b->B; ++i)
-        if (b->h_phase[i] == 1 && !b->restarted[i]) b->h_phase[i] = 2;
-}
-
-int set_slot_flag(sva_batch* b, int slot, int flag) {
-    b->h_slot_flag[slot] = flag;
-    SVA_HIP(hipMemcpyAsync(b->d_slot_flag + slot, &b->h_slot_flag[slot], sizeof(int), hipMemcpyHostToDevice, b->stream));
+// ---- per-slot restart (sva_stream_restart / sva_stream_retire): the rules are SlotBook's (slot_book.h), the device side is here ----
+// the slot's flag as the book holds it -> d_slot_flag
+int upload_slot_flag(sva_batch* b, int slot) {
+    SVA_HIP(hipMemcpyAsync(b->d_slot_flag + slot, &b->slots.s[slot].flag, sizeof(int), hipMemcpyHostToDevice, b->stream));
     SVA_HIP(hipStreamSynchronize(b->stream));
     return 0;
 }
 
 // The restarted slot's front-end as sva_streams_begin leaves every slot: an all-zero audio window (origin-free: the ring position stays
-// the batch's), every history row and every cached token at the network's steady response to silence, no content codes seen.
+// the batch's), every history row and every cached token at the network's steady response to silence, no content codes seen (device side).
 int restart_encoder_state(sva_batch* b, int slot) {
     sva_engine* e = b->e;
     hipStream_t st = b->stream;
     const auto it = e->silence.find(std::make_pair(b->B, b->p.chunk_frames));
-    SVA_CHECK(b->enc_incremental && b->enc_merged && it != e->silence.end(), "restart: no cached silence state for this encoder mode");
+    SVA_CHECK(b->enc_incremental && it != e->silence.end(), "restart: no cached silence state for this encoder mode");
     const sva_engine::SilenceState& ss = it->second;
     EncMerged& M = b->em;
     std::vector<ShiftDesc> sd(M.n_shift);
@@ -1487,14 +1345,7 @@ int restart_encoder_state(sva_batch* b, int slot) {
     hipLaunchKernelGGL(fill_rows_kernel, dim3(b->T2, 1), dim3(128), 0, st, b->d2c.p + (long)slot * b->d2c.bstride, b->d2c.bstride, e->cfg.tr_dim, ss.tok);
     SVA_HIP(hipGetLastError());
     SVA_HIP(hipMemsetAsync(b->d_ncontent + slot, 0, sizeof(int), st));
-    b->h_ncontent[slot] = 0;
     return 0;
-}
-
-// vocoder frames a fresh stream is primed with (sva_streams_begin), for a stored prompt of Rt frames
-int priming_frames(const sva_batch* b, int Rt) {
-    const int c = b->p.chunk_frames;
-    return (std::min(b->p.decode_window_frames - 1, Rt) / c) * c;
 }
 
 // The slot's streaming vocoder state becomes "zero state, then the last P frames of its prompt streamed in chunk-sized calls", as
@@ -1515,7 +1366,7 @@ int prime_vocoder_slot(sva_batch* b, int slot) {
         SVA_TRY(dev_alloc(b->allocs, &b->prime_pcm, (size_t)B * 2048 * c));
         SVA_TRY(dev_alloc(b->allocs, &b->voc_save, (size_t)B * tot));
     }
-    const int R = b->ref_len[slot], P = priming_frames(b, R);
+    const int P = b->slots.priming_frames(slot, b->p.decode_window_frames, c);
     int frames_kept = 0;
     SVA_HIP(hipMemcpy(&frames_kept, b->d_voc_frames, sizeof(int), hipMemcpyDeviceToHost));
     if (nd) hipLaunchKernelGGL(history_rows_copy_kernel, dim3(nd, B), dim3(256), 0, st, b->d_shift, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, 0, 0);
@@ -1530,9 +1381,7 @@ int prime_vocoder_slot(sva_batch* b, int slot) {
     std::vector<int32_t> codes((size_t)(P / c) * B * ncb * c);       // (alive until the copies have landed)
     for (int f = 0; f < P; f += c) {
         int32_t* cf = codes.data() + (size_t)(f / c) * B * ncb * c;
-        for (int i = 0; i < B; ++i)
-            for (int q = 0; q < ncb; ++q)
-                for (int k = 0; k < c; ++k) cf[((size_t)i * ncb + q) * c + k] = b->ref_audio[slot][(size_t)q * R + (R - P + f + k)];
+        for (int i = 0; i < B; ++i) b->slots.prompt_tail(slot, ncb, P, f, c, cf + (size_t)i * ncb * c);
         SVA_TRY(upload_vcodes(b, cf, c));
         SVA_TRY(vocode(b, c, true));
     }
@@ -1554,15 +1403,14 @@ int prime_vocoder_slot_local(sva_batch* b, int slot) {
     sva_batch* w = b->prime_ws;
     SVA_CHECK(w, "slot-local priming without a workspace");
     const int ncb = b->e->cfg.num_codebooks, nd = (int)b->shift_host.size();
-    const int R = b->ref_len[slot], P = priming_frames(b, R);
     SVA_CHECK(slot >= 0 && slot < b->B, "slot-local priming: slot out of range");
+    const int P = b->slots.priming_frames(slot, b->p.decode_window_frames, b->p.chunk_frames);
     SVA_CHECK(P <= w->Tv, "slot-local priming: prompt tail longer than the workspace");
     hipStream_t st = b->stream;
     w->stream = st;
     SVA_TRY(sva_vocode_reset(w));
     std::vector<int32_t> codes((size_t)ncb * std::max(P, 1));        // [1][8][P] (alive until the synchronisation below)
-    for (int q = 0; q < ncb; ++q)
-        for (int k = 0; k < P; ++k) codes[(size_t)q * P + k] = b->ref_audio[slot][(size_t)q * R + (R - P + k)];
+    b->slots.prompt_tail(slot, ncb, P, 0, P, codes.data());
     if (P > 0) {
         SVA_TRY(upload_vcodes(w, codes.data(), P));
         SVA_TRY(vocode(w, P, true));
@@ -1578,27 +1426,22 @@ int prime_vocoder_slot_local(sva_batch* b, int slot) {
 // Runs on drained streams.
 int activate_slot(sva_batch* b, int slot) {
     const auto t0 = std::chrono::steady_clock::now();
-    sva_batch::PendingPrompt& P = b->pending[slot];
+    const PendingPrompt& P = b->slots.s[slot].pending;
     struct Keep { sva_batch* b; const float* src; ~Keep() { b->step_src = src; } } keep{b, b->step_src};
     b->step_src = nullptr;
     SVA_TRY(prefill_slot_impl(b, slot, P.cc.data(), P.ac.data(), P.R, P.style.data(), P.timbre.data(), P.seed, false));
     SVA_HIP(hipMemsetAsync(b->d_nframes + slot, 0, sizeof(int), b->stream));
-    b->h_nframes[slot] = 0;
     SVA_TRY(ar_delay_fill(b, std::vector<int>{slot}));
     SVA_TRY(b->prime_ws ? prime_vocoder_slot_local(b, slot) : prime_vocoder_slot(b, slot));
-    b->h_phase[slot] = 2;
-    b->restarted[slot] = 0;
-    P = sva_batch::PendingPrompt();
-    SVA_TRY(set_slot_flag(b, slot, 0));
+    b->slots.activated(slot);
+    SVA_TRY(upload_slot_flag(b, slot));
     (b->prime_ws ? b->n_act_local : b->n_act_whole) += 1;
     b->last_act_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
 
 int activate_due_slots(sva_batch* b) {
-    std::vector<int> due;
-    for (int i = 0; i < b->B; ++i)
-        if (b->restarted[i] && b->h_phase[i] == 1 && b->h_ncontent[i] >= b->p.delay) due.push_back(i);
+    const std::vector<int> due = b->slots.due_activations(b->p.delay);
     if (due.empty()) return 0;
     // rare: drain the stage streams of the pipelined mode and work on the main stream, as a re-prefill behind a host synchronisation does
     SVA_TRY(quiesce(b));
@@ -1617,11 +1460,11 @@ int step_body(sva_batch* b) {
     SVA_TRY(check_mm_overflow(b));
     const int B = b->B, chunk = b->p.chunk_frames, d = b->p.delay, n = 2048 * chunk;
     hipStream_t st = b->stream;
-    const bool steady = b->delay_filled;          // (set once the lock-step slots hold `delay` content codes; a restarted slot rides along parked)
+    const bool steady = b->slots.delay_filled;    // (set once the lock-step slots hold `delay` content codes; a restarted slot rides along parked)
     if (steady) {
         const bool graph_ok = b->p.use_graph && b->noise_on_device && !b->forced_now && !b->prof_on;
         const bool pipe_ok = b->p.pipeline && b->sa && b->allow_pipe && b->noise_on_device && !b->forced_now && !b->prof_on && !b->p.use_graph &&
-                             b->voc_grouped && b->steady_eager_steps >= 2;
+                             b->steady_eager_steps >= 2;
         if (!pipe_ok) SVA_TRY(quiesce(b));
         if (pipe_ok) {
             SVA_TRY(steady_pipelined(b));
@@ -1654,32 +1497,19 @@ int step_body(sva_batch* b) {
             b->steady_eager_steps += 1;
             b->graph_step = false;
         }
-        b->h_step += 1;
-        for (int i = 0; i < B; ++i) {
-            b->h_ncontent[i] += chunk;
-            b->h_last_pos[i] += 2 * chunk;
-            if (b->h_phase[i] == 2) b->h_nframes[i] += chunk;      // (a parked slot -- retired, or filling its own delay -- decodes throw-away frames)
-        }
-        // re-prefill when current_pos // 2 >= max_seq_frames (:547-564).  Positions are deterministic, so the host
-        // mirror decides without a device round trip; doing it after the vocoder instead of before (as the reference
-        // does) changes nothing: the vocoder consumes the codes just decoded, the re-prefill only rewrites KV state.
-        std::vector<int> redo;
+        // re-prefill when current_pos // 2 >= max_seq_frames (:547-564).  Positions are deterministic, so the book's mirrors decide without
+        // a device round trip (SlotBook::steady_step); doing it after the vocoder instead of before (as the reference does) changes
+        // nothing: the vocoder consumes the codes just decoded, the re-prefill only rewrites KV state.
+        const StepPlan plan = b->slots.steady_step(chunk, b->p.max_seq_frames, e->cfg.timbre_tokens + 1);
+        const std::vector<int>& redo = plan.redo;
         if (b->pipe_dirty) b->stream = b->sa;  // pipelined: the KV rewrite belongs to the AR stream (it already waited for E of this step)
         int rrc = 0;
-        for (int i = 0; i < B; ++i) {
-            if (b->h_last_pos[i] / 2 < b->p.max_seq_frames) continue;
-            if (b->h_phase[i] == 2) { redo.push_back(i); continue; }
-            // a parked slot never becomes due: its position goes back to the end of its last stored prompt, over K / V rows that stay valid
-            const int lp = parked_position(b, i);
-            hipLaunchKernelGGL(set_slot_i32_kernel, dim3(1), dim3(64), 0, b->stream, b->d_last_pos, i, lp);
-            b->h_last_pos[i] = lp;
-        }
+        // a parked slot never becomes due: its position goes back to the end of its last stored prompt, over K / V rows that stay valid
+        for (const auto& rw : plan.rewind) hipLaunchKernelGGL(set_slot_i32_kernel, dim3(1), dim3(64), 0, b->stream, b->d_last_pos, rw.first, rw.second);
         if (!redo.empty()) {
             // one pass for all due slots against the cached prompt prefix (reprefill_slots); SVA_DEBUG reprefill=0: the round-3 path, one
             // whole-prompt prefill per slot behind a host synchronisation (A/B, parity of the two)
-            // (a stream that has decoded fewer than `delay` frames -- a prompt about as long as max_seq_frames -- keeps the general form)
-            bool one_pass = debug_options().reprefill != 0;
-            for (int s_ : redo) one_pass = one_pass && std::min(b->p.buffer_frames, b->h_nframes[s_]) >= b->p.delay;
+            const bool one_pass = debug_options().reprefill != 0 && b->slots.one_pass_ok(redo, b->p.buffer_frames, b->p.delay);
             if (one_pass) rrc = reprefill_slots(b, redo);
             else for (size_t i = 0; i < redo.size() && !rrc; ++i) rrc = reprefill_slot(b, redo[i]);
         }
@@ -1702,19 +1532,10 @@ int step_body(sva_batch* b) {
     SVA_TRY(b->enc_incremental ? encode_incremental(b, b->d_step, n, 1) : encode(b, b->d_step, n, 1));
     hipLaunchKernelGGL(append_content_kernel, dim3((B + 63) / 64), dim3(64), 0, st, b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap,
                        b->d_ncontent, b->d_step_content, B, b->d_step);
-    b->h_step += 1;
-    for (int& nc : b->h_ncontent) nc += chunk;
     SVA_HIP(hipEventRecord(b->ev[1], st));
-    int lock = -1;                                      // a slot of the batch-wide start (they share one count)
-    for (int i = 0; i < B && lock < 0; ++i)
-        if (b->h_phase[i] == 1 && !b->restarted[i]) lock = i;
-    if (lock < 0) {                                     // every slot retired or restarted since sva_streams_begin: nothing left to fill in lock step
-        b->delay_filled = true;
-    } else if (b->h_ncontent[lock] >= d) {
-        SVA_TRY(ar_delay_fill(b));                      // :521-525 -> zeros
-        b->delay_filled = true;
-        lockstep_slots_decode(b);
-    }                                                   // else :519-520 -> zeros
+    // the lock-step slots hold `delay` content codes: :521-525 -> zeros (else :519-520 -> zeros).  With every slot retired or restarted since
+    // sva_streams_begin nothing is left to fill in lock step.
+    if (b->slots.warmup_step(chunk, d)) SVA_TRY(ar_delay_fill(b));
     SVA_HIP(hipEventRecord(b->ev[2], st));
     SVA_HIP(hipMemsetAsync(b->d_pcm, 0, sizeof(float) * (size_t)B * 2048 * b->Tv, st));
     SVA_HIP(hipEventRecord(b->ev[3], st));
@@ -1734,11 +1555,10 @@ static int drain_for_slot_call(sva_batch* b) {
     SVA_HIP(hipStreamSynchronize(b->stream));
     return 0;
 }
-static int park_slot(sva_batch* b, int slot) {
-    const int lp = parked_position(b, slot);
-    SVA_HIP(hipMemcpyAsync(b->d_last_pos + slot, &lp, sizeof(int), hipMemcpyHostToDevice, b->stream));
+// the slot's position as the book holds it -> d_last_pos
+static int upload_slot_position(sva_batch* b, int slot) {
+    SVA_HIP(hipMemcpyAsync(b->d_last_pos + slot, &b->slots.s[slot].last_pos, sizeof(int), hipMemcpyHostToDevice, b->stream));
     SVA_HIP(hipStreamSynchronize(b->stream));
-    b->h_last_pos[slot] = lp;
     return 0;
 }
 
@@ -1751,25 +1571,24 @@ extern "C" int sva_stream_restart(sva_batch* b, int slot, const int64_t* ref_con
     const int ncb = c.num_codebooks, nspk = c.timbre_tokens + 1;
     SVA_CHECK(R > b->p.delay, "sva_stream_restart: the prompt must be longer than the delay");
     SVA_CHECK(R <= b->Pmax && nspk + 2 * R <= b->Mmax && nspk + 2 * R <= c.max_seq_len, "sva_stream_restart: prompt too long for the KV cache");
-    const int P = priming_frames(b, std::min(R, b->p.max_prompt_frames));
+    const int P = SlotBook::priming_frames_for(std::min(R, b->p.max_prompt_frames), b->p.decode_window_frames, b->p.chunk_frames);
     SVA_CHECK(P >= 16 || P == b->p.decode_window_frames - 1, "sva_stream_restart: prompt shorter than the vocoder receptive field (16 frames)");
-    SVA_CHECK(b->enc_incremental && b->enc_merged,
+    SVA_CHECK(b->enc_incremental,
               "sva_stream_restart: this batch runs the full-window encoder (encode_window_frames <= 40 + chunk_frames), which has no cached "
               "silence state to fill one slot from");
     SVA_CHECK(!b->ar_failed && !(b->h_ar_fail && *reinterpret_cast<volatile int*>(b->h_ar_fail) != 0),
               "sva_stream_restart: this batch's persistent AR decode kernel timed out: sva_streams_begin restarts its streams");
     SVA_TRY(drain_for_slot_call(b));
     SVA_TRY(restart_encoder_state(b, slot));           // (its own refusal -- no silence state -- comes before its first write)
-    sva_batch::PendingPrompt& P_ = b->pending[slot];
+    PendingPrompt P_;
     P_.cc.assign(ref_content_codes, ref_content_codes + R);
     P_.ac.assign(ref_audio_codes, ref_audio_codes + (size_t)ncb * R);
     P_.style.assign(style, style + c.style_dim);
     P_.timbre.assign(timbre, timbre + (size_t)c.timbre_tokens * c.timbre_dim);
     P_.R = R; P_.seed = noise_seed;
-    b->restarted[slot] = 1;
-    b->h_phase[slot] = 1;
-    SVA_TRY(park_slot(b, slot));
-    return set_slot_flag(b, slot, kSlotOutputMuted);
+    b->slots.restart(slot, std::move(P_), nspk, kSlotOutputMuted);
+    SVA_TRY(upload_slot_position(b, slot));
+    return upload_slot_flag(b, slot);
 }
 
 extern "C" int sva_stream_retire(sva_batch* b, int slot) {
@@ -1777,17 +1596,15 @@ extern "C" int sva_stream_retire(sva_batch* b, int slot) {
     SVA_CHECK(b->begun, "sva_stream_retire: the batch has not begun");
     SVA_CHECK(slot >= 0 && slot < b->B, "sva_stream_retire: slot out of range");
     SVA_TRY(drain_for_slot_call(b));
-    b->restarted[slot] = 0;
-    b->pending[slot] = sva_batch::PendingPrompt();
-    b->h_phase[slot] = 0;              // (its position is rewound when it would become due for a re-prefill: step_body)
-    return set_slot_flag(b, slot, kSlotInputMuted | kSlotOutputMuted);
+    b->slots.retire(slot, kSlotInputMuted | kSlotOutputMuted);
+    return upload_slot_flag(b, slot);
 }
 
 extern "C" int sva_stream_state(sva_batch* b, int slot, int* phase, long* frames) {
     SVA_CHECK(b && b->begun, "sva_stream_state: the batch has not begun");
     SVA_CHECK(slot >= 0 && slot < b->B, "sva_stream_state: slot out of range");
-    if (phase) *phase = b->h_phase[slot];
-    if (frames) *frames = b->h_phase[slot] == 2 ? b->h_nframes[slot] : 0;
+    if (phase) *phase = b->slots.s[slot].phase;
+    if (frames) *frames = b->slots.stream_frames(slot);
     return 0;
 }
 
@@ -1886,7 +1703,7 @@ extern "C" int sva_join_stream(sva_batch* b, void* caller_stream) {
     hipStream_t cs = (hipStream_t)caller_stream;
     // the caller's stream waits (on the device, not the host) for every chain of the engine: the stage streams of a pipelined batch,
     // the encoder's side stream and the main stream; the pipelined regime itself is left untouched
-    hipStream_t all[4] = {b->main_stream, b->p.pipeline ? b->sa : nullptr, b->p.pipeline ? b->sv : nullptr, b->aux[0]};
+    hipStream_t all[4] = {b->main_stream, b->p.pipeline ? b->sa : nullptr, b->p.pipeline ? b->sv : nullptr, b->aux0};
     for (hipStream_t st_ : all) {
         if (!st_) continue;
         hipEvent_t ev = next_event(b);
@@ -2038,16 +1855,15 @@ extern "C" int sva_ar_delay_fill(sva_batch* b, const int64_t* codes) {
     SVA_TRY(h2d(b, tmp, codes, sizeof(int64_t) * (size_t)B * d));
     hipLaunchKernelGGL(put_codes_kernel, dim3((B + 63) / 64), dim3(64), 0, b->stream, tmp, d, b->d_codes, b->T2, b->d_content_hist, b->hist_cap,
                        b->d_ncontent, B);
-    for (int& nc : b->h_ncontent) nc += d;
+    b->slots.add_content(d);
     SVA_TRY(ar_delay_fill(b));
-    b->delay_filled = true;
-    lockstep_slots_decode(b);
+    b->slots.lockstep_filled();
     SVA_HIP(hipStreamSynchronize(b->stream));
     return 0;
 }
 
 extern "C" int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float* noise, const int32_t* forced, int32_t* codes_out, int32_t* pos_out) {
-    SVA_CHECK(b && code && codes_out && b->begun && b->delay_filled, "sva_ar_decode_one: bad argument / delay not filled");
+    SVA_CHECK(b && code && codes_out && b->begun && b->slots.delay_filled, "sva_ar_decode_one: bad argument / delay not filled");
     SVA_CHECK(b->p.chunk_frames == 1, "sva_ar_decode_one needs chunk_frames == 1");
     SVA_HIP(hipSetDevice(b->e->device));
     (void)hipGetLastError();
@@ -2059,7 +1875,7 @@ extern "C" int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float*
     SVA_TRY(h2d(b, tmp, code, sizeof(int64_t) * (size_t)B));
     hipLaunchKernelGGL(put_codes_kernel, dim3((B + 63) / 64), dim3(64), 0, st, tmp, 1, b->d_codes, b->T2, b->d_content_hist, b->hist_cap,
                        b->d_ncontent, B);
-    for (int& nc : b->h_ncontent) nc += 1;
+    b->slots.add_content(1);
     b->noise_on_device = (noise == nullptr);
     if (noise) SVA_TRY(h2d(b, b->d_noise, noise, sizeof(float) * (size_t)B * (c.ar_vocab + ncb * c.codebook_size)));
     const int uf = forced ? 1 : 0;
@@ -2067,7 +1883,7 @@ extern "C" int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float*
     b->h_use_forced = uf;
     if (forced) SVA_TRY(h2d(b, b->d_forced, forced, sizeof(int) * (size_t)B * ncb));
     SVA_TRY(ar_decode_frame(b, 0));
-    for (int i = 0; i < B; ++i) { b->h_last_pos[i] += 2; b->h_nframes[i] += 1; }
+    for (int i = 0; i < B; ++i) b->slots.frame_decoded(i, 2);
     SVA_HIP(hipMemcpyAsync(codes_out, b->d_step_audio, sizeof(int) * (size_t)B * ncb, hipMemcpyDeviceToHost, st));
     if (pos_out) SVA_HIP(hipMemcpyAsync(pos_out, b->d_last_pos, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
     SVA_HIP(hipStreamSynchronize(st));
@@ -2108,7 +1924,6 @@ extern "C" int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* 
     unsigned long long sd = noise_seed;
     SVA_TRY(h2d(b, b->d_seed, &sd, sizeof(sd)));
     SVA_HIP(hipMemsetAsync(b->d_nframes, 0, sizeof(int), st));
-    b->h_nframes[0] = 0;
     // prefill_cond = [ref_cond, src_cond[:d]] interleaved with [wait4start[:d], embed(ref_audio)]  (:711-715)
     std::vector<int64_t> cc(ref_cc, ref_cc + R);
     for (int i = 0; i < d; ++i) cc.push_back(src_cc[i]);
@@ -2140,7 +1955,7 @@ extern "C" int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* 
                            c.max_seq_len, b->ax, 0, 0));
     const int lp = M - 1;
     SVA_TRY(h2d(b, b->d_last_pos, &lp, sizeof(int)));
-    b->h_last_pos[0] = lp;
+    b->slots.offline_prefilled(0, lp);
     const int nstride = c.ar_vocab + ncb * c.codebook_size;
     const int zero = 0;
     SVA_TRY(h2d(b, b->d_use_forced, &zero, sizeof(int)));
@@ -2158,20 +1973,20 @@ extern "C" int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* 
             b->edits_skip = false;
             b->p.temperature = t_user; b->p.top_p = p_user;
             SVA_TRY(rc0);
+            b->slots.frame_decoded(0, 0);
         } else if (b->use_mega && !b->edits_on) {
             // decode steps of the offline loop (dual_ar_stream.py:735-760) through the persistent kernel: the same two tokens
             // [embed(previous codes), cond_i] at the next two positions, one launch per frame instead of ~200
             SVA_TRY(ar_decode_frame_mega(b, 0, d_remq, i));
-            b->h_last_pos[0] += 2;
+            b->slots.frame_decoded(0, 2);
         } else {
             hipLaunchKernelGGL(prepare_offline_step_kernel, dim3(1), dim3(256), 0, st, b->cached_audio_emb, e->content_emb, d_remq, i, b->d_last_pos, D,
                                b->ax, b->d_slot, b->d_pos);
             SVA_TRY(ar_layers_pass(b, e->ar_layers, 2, b->d_slot, b->d_pos, e->rope_ar, (float*)b->kv_slow, b->kv_slow_layer, b->kv_slow_slot,
                                    c.max_seq_len, b->ax));
             SVA_TRY(ar_frame_tail(b, 0, (long)2 * D, (long)D, d_remq, S, i, 2));
-            b->h_last_pos[0] += 2;
+            b->slots.frame_decoded(0, 2);
         }
-        b->h_nframes[0] += 1;
     }
     SVA_HIP(hipStreamSynchronize(st));
     for (int q = 0; q < ncb; ++q)
@@ -2310,7 +2125,7 @@ extern "C" long sva_get_gemm_profile_table(sva_batch* b, double* out, long max_r
 }
 extern "C" int sva_stream_codes(sva_batch* b, int slot, int n, int32_t* codes_out, long* n_frames_total) {
     SVA_CHECK(b && slot >= 0 && slot < b->B, "bad slot");
-    const int nf = b->h_nframes[slot], cap = b->hist_cap, ncb = b->e->cfg.num_codebooks;
+    const int nf = b->slots.s[slot].nframes, cap = b->hist_cap, ncb = b->e->cfg.num_codebooks;
     if (n_frames_total) *n_frames_total = nf;
     SVA_CHECK(n >= 0 && n <= nf && n <= cap, "more frames requested than the stream has decoded (or than the 4096-frame ring holds)");
     if (!n) return 0;

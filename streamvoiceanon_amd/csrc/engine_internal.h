@@ -67,7 +67,6 @@ bool planes_edge(const Lin& producer, const Lin& consumer, long rows, int stream
 int cnx_block_t(sva_batch* b, const CNX& c, Act& x, int T, float* h1, long h1_bs, float* h2, long h2_bs, Act* out = nullptr, int skip_lo = 0, int skip_hi = 0);
 int cnx_block(sva_batch* b, const CNX& c, Act& x, int T, float* h1, float* h2, Act* out = nullptr);
 int enc_frontend_window(sva_batch* b, const int* step_ptr, int n_chunk, int add, int Tm, const EncFront* front = nullptr, Act* tokens_out = nullptr);
-int enc_frontend_stream(sva_batch* b, const int* step_ptr, int n_chunk, int add, int part = 0);
 int enc_frontend_merged(sva_batch* b, const int* step_ptr, int n_chunk, int add, int part = 0, int fpar = 0);
 int enc_transformer(sva_batch* b, const Act& xin, int need_rows, int part = 0);
 int encode(sva_batch* b, const int* step_ptr, int n_chunk, int add);

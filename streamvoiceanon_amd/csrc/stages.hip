@@ -1,4 +1,4 @@
-// Stage launch sequences of the sva engine: the conv-GEMM call helpers, the content encoder's passes (window / streaming / merged
+// Stage launch sequences of the sva engine: the conv-GEMM call helpers, the content encoder's passes (window / merged
 // incremental front-end, window transformer + BSQ: modules/vqgan/modules/firefly.py:375-520, windowed_transformer.py, bsq.py), the
 // dual AR's layer pass, frame decode, prompt prefill and delay fill (modules/dual_ar_stream.py:764-837, 1168-1219) and the streaming
 // vocoder (firefly.py:243-293).  Everything here only enqueues kernels on b->stream; engine.hip orchestrates the streams and graphs.
@@ -275,62 +275,6 @@ int enc_frontend_window(sva_batch* b, const int* step_ptr, int n_chunk, int add,
     return 0;
 }
 
-// Streaming pass of the exact-incremental formulation: the nm = 4c NEWEST mel frames of the window through the same
-// conv front-end on per-layer 6-row histories (every tensor that feeds a k7 conv keeps its own history; ConvNeXt
-// blocks are therefore out-of-place).  The resulting c token rows land in d2c[T2-c, T2).
-// part 0: the whole pass; 1: front (mel, stem, the first kStreamCut stages and the transition out of them); 2: the rest.  The
-// pipelined step runs the front on the main stream ahead of the head pass and the back on the side stream ahead of the
-// transformer, which evens out the two encoder chains.
-int enc_frontend_stream(sva_batch* b, const int* step_ptr, int n_chunk, int add, int part) {
-    sva_engine* e = b->e;
-    const EncFront& F = e->tokf;
-    const sva_config& c = e->cfg;
-    const int B = b->B, nm = 4 * b->p.chunk_frames;
-    hipStream_t st = b->stream;
-    EncStream& S = b->es;
-    if (part != 2) {
-    SVA_TRY(launch_stft_mag_ring(b->ring, step_ptr, n_chunk, add, B, b->N, e->twiddle, e->hann, S.mag, 1088, (long)nm * 1088, b->T0 - nm, nm, st));
-    {
-        ConvGemm p;
-        p.act = ACT_LOGCLAMP;
-        SVA_TRY(gemm_call(b, S.mag, (long)nm * 1088, 0, 1088, B, nm, 1, 1, 1, 1088, e->mel_fb, S.mel.p, S.mel.bstride, (long)S.mel.H * c.n_mels,
-                          c.n_mels, p));
-    }
-    SVA_TRY(conv_act(b, S.mel, nm, 1, 1, 7, F.stem, S.tmp0));
-    SVA_TRY(launch_layernorm_rows(S.tmp0.p, S.tmp0.bstride, 0, c.enc_dims[0], B, nm, c.enc_dims[0], F.stem_lnw, F.stem_lnb, 1e-6f,
-                                  S.x[0][0].p, S.x[0][0].bstride, (long)S.x[0][0].H * c.enc_dims[0], c.enc_dims[0], st));
-    }
-    const int cut = b->stream_cut;
-    for (int i = 0; i < 4; ++i) {
-        if (part == 1 && i >= cut) return 0;
-        if (part == 2 && i < cut) continue;
-        const int C = c.enc_dims[i];
-        const int nb = (int)F.stages[i].size();
-        for (int j = 0; j < nb; ++j) {
-            Act& out = j + 1 < nb ? S.x[i][j + 1] : S.xout[i];
-            SVA_TRY(cnx_block_t(b, F.stages[i][j], S.x[i][j], nm, S.h1, (long)nm * C, S.h2, (long)nm * 4 * C, &out));
-        }
-        if (i < 3) {
-            const int Cn = c.enc_dims[i + 1];
-            SVA_TRY(launch_layernorm_rows(S.xout[i].p, S.xout[i].bstride, 0, C, B, nm, C, F.trans_lnw[i + 1], F.trans_lnb[i + 1], 1e-6f,
-                                          S.h1, (long)nm * C, 0, C, st));
-            SVA_TRY(gemm_call(b, S.h1, (long)nm * C, 0, C, B, nm, 1, 1, 1, C, F.trans[i + 1], S.x[i + 1][0].p, S.x[i + 1][0].bstride,
-                              (long)S.x[i + 1][0].H * Cn, Cn));
-        }
-    }
-    const int D = c.tr_dim;
-    SVA_TRY(launch_layernorm_rows(S.xout[3].p, S.xout[3].bstride, 0, D, B, nm, D, F.final_lnw, F.final_lnb, 1e-6f, S.feat.p, S.feat.bstride, 0, D, st));
-    SVA_TRY(conv_act(b, S.feat, nm / 2, 2, 1, 2, F.ds_conv[0], S.d1));
-    SVA_TRY(cnx_block_t(b, F.ds_cnx[0], S.d1, nm / 2, S.h1, (long)(nm / 2) * D, S.h2, (long)(nm / 2) * 4 * D, &S.d1o));
-    SVA_TRY(conv_act(b, S.d1o, nm / 4, 2, 1, 2, F.ds_conv[1], S.d2));
-    Act tail = b->d2c;                       // rows [T2 - c, T2) of the steady token cache
-    tail.p = b->d2c.p + (long)(b->T2 - nm / 4) * D;
-    tail.H = 0;
-    SVA_TRY(cnx_block_t(b, F.ds_cnx[1], S.d2, nm / 4, S.h1, (long)(nm / 4) * D, S.h2, (long)(nm / 4) * 4 * D, &tail));
-    SVA_TRY(launch_shift_history(S.d_shift, S.n_shift, B, st));
-    return 0;
-}
-
 __global__ void copy_tokens_kernel(const float* __restrict__ tok, long tok_bstride, int Ht, int gap, int c, float* __restrict__ d2c, long d_bstride,
                                    int T2, int D) {
     // head tokens -> d2c rows [0, Ht); newest c tokens -> d2c rows [T2 - c, T2)
@@ -345,11 +289,26 @@ __global__ void copy_tokens_kernel(const float* __restrict__ tok, long tok_bstri
 // Merged incremental front-end pass (see EncMerged): head rows (the first 4*Ht mel frames of the window, zero left padding as in
 // the reference's window pass) and the 4c newest mel frames (on per-layer 6-row histories) through ONE sequence of launches.
 // Results: token rows [0, Ht) and [T2 - c, T2) of d2c.
-// part 0 = everything; part 1 = up to the token features (does not touch the token cache d2c); part 2 = the hand-over: head and
-// new tokens -> d2c, then the layers' history rows slide (the pipelined step waits for transformer(n-1)'s first layer only here).
-// part 3 / 4 = the cut the balanced pipeline uses: 3 = STFT .. backbone .. final LayerNorm -> feat[fpar] + the history shift of
-// those layers; 4 = quantizer downsampler (2 x (conv k2 s2 + ConvNeXt block)) from feat[fpar] with its own scratch, tokens -> d2c,
-// its two history shifts (runs on the side stream in front of the transformer)
+// part 0 = everything; part 3 / 4 = the cut the pipelined step uses: 3 = STFT .. backbone .. final LayerNorm -> feat[fpar] + the
+// history shift of those layers; 4 = quantizer downsampler from feat[fpar] with its own scratch, tokens -> d2c, its two history
+// shifts (runs on the side stream in front of the transformer).
+//
+// Its downsampler, BSQ downsample x2 (conv k2 s2 + ConvNeXtBlock, bsq_no_upsample.py:48-61): feat -> M.tok with the given
+// ConvNeXt scratch; the strided convs run per row group (head rows, new rows)
+static int merged_downsample(sva_batch* b, const Act& feat, float* h1, float* h2) {
+    const EncFront& F = b->e->tokf;
+    EncMerged& M = b->em;
+    const int B = b->B, Hh = M.Hh, nm = M.nm, D = b->e->cfg.tr_dim;
+    const int R1 = Hh / 2 + 6 + nm / 2, R2 = Hh / 4 + 6 + nm / 4;
+    SVA_TRY(gemm_call(b, feat.p, feat.bstride, 0, D, B, Hh / 2, 2, 1, 2, D, F.ds_conv[0], M.d1.p, M.d1.bstride, (long)M.d1.H * D, D));
+    SVA_TRY(gemm_call(b, feat.p, feat.bstride, (long)(Hh + 6) * D, D, B, nm / 2, 2, 1, 2, D, F.ds_conv[0], M.d1.p, M.d1.bstride,
+                      (long)(M.d1.H + Hh / 2 + 6) * D, D));
+    SVA_TRY(cnx_block_t(b, F.ds_cnx[0], M.d1, R1, h1, (long)R1 * D, h2, (long)R1 * 4 * D, &M.d1o));
+    SVA_TRY(gemm_call(b, M.d1o.p, M.d1o.bstride, 0, D, B, Hh / 4, 2, 1, 2, D, F.ds_conv[1], M.d2.p, M.d2.bstride, (long)M.d2.H * D, D));
+    SVA_TRY(gemm_call(b, M.d1o.p, M.d1o.bstride, (long)(Hh / 2 + 6) * D, D, B, nm / 4, 2, 1, 2, D, F.ds_conv[1], M.d2.p, M.d2.bstride,
+                      (long)(M.d2.H + Hh / 4 + 6) * D, D));
+    return cnx_block_t(b, F.ds_cnx[1], M.d2, R2, h1, (long)R2 * D, h2, (long)R2 * 4 * D, &M.tok);
+}
 int enc_frontend_merged(sva_batch* b, const int* step_ptr, int n_chunk, int add, int part, int fpar) {
     sva_engine* e = b->e;
     const EncFront& F = e->tokf;
@@ -359,25 +318,9 @@ int enc_frontend_merged(sva_batch* b, const int* step_ptr, int n_chunk, int add,
     hipStream_t st = b->stream;
     const int D = c.tr_dim;
     Act& feat = fpar ? M.feat2 : M.feat;
-    float* h1 = part == 4 ? M.h1b : M.h1;
-    float* h2 = part == 4 ? M.h2b : M.h2;
-    const int R1 = Hh / 2 + 6 + nm / 2, R2 = Hh / 4 + 6 + nm / 4;
     const int n_shift_ds = 2;                       // the last two descriptors are the downsampler's (d1, d2)
-    if (part == 2) {
-        hipLaunchKernelGGL(copy_tokens_kernel, dim3(b->Ht + ch, B), dim3(128), 0, st, M.tok.p, M.tok.bstride, b->Ht, 6, ch, b->d2c.p, b->d2c.bstride, b->T2, D);
-        SVA_TRY(launch_shift_history(M.d_shift, M.n_shift, B, st));
-        SVA_HIP(hipGetLastError());
-        return 0;
-    }
     if (part == 4) {
-        SVA_TRY(gemm_call(b, feat.p, feat.bstride, 0, D, B, Hh / 2, 2, 1, 2, D, F.ds_conv[0], M.d1.p, M.d1.bstride, (long)M.d1.H * D, D));
-        SVA_TRY(gemm_call(b, feat.p, feat.bstride, (long)(Hh + 6) * D, D, B, nm / 2, 2, 1, 2, D, F.ds_conv[0], M.d1.p, M.d1.bstride,
-                          (long)(M.d1.H + Hh / 2 + 6) * D, D));
-        SVA_TRY(cnx_block_t(b, F.ds_cnx[0], M.d1, R1, h1, (long)R1 * D, h2, (long)R1 * 4 * D, &M.d1o));
-        SVA_TRY(gemm_call(b, M.d1o.p, M.d1o.bstride, 0, D, B, Hh / 4, 2, 1, 2, D, F.ds_conv[1], M.d2.p, M.d2.bstride, (long)M.d2.H * D, D));
-        SVA_TRY(gemm_call(b, M.d1o.p, M.d1o.bstride, (long)(Hh / 2 + 6) * D, D, B, nm / 4, 2, 1, 2, D, F.ds_conv[1], M.d2.p, M.d2.bstride,
-                          (long)(M.d2.H + Hh / 4 + 6) * D, D));
-        SVA_TRY(cnx_block_t(b, F.ds_cnx[1], M.d2, R2, h1, (long)R2 * D, h2, (long)R2 * 4 * D, &M.tok));
+        SVA_TRY(merged_downsample(b, feat, M.h1b, M.h2b));
         hipLaunchKernelGGL(copy_tokens_kernel, dim3(b->Ht + ch, B), dim3(128), 0, st, M.tok.p, M.tok.bstride, b->Ht, 6, ch, b->d2c.p, b->d2c.bstride, b->T2, D);
         SVA_TRY(launch_shift_history(M.d_shift + (M.n_shift - n_shift_ds), n_shift_ds, B, st));
         SVA_HIP(hipGetLastError());
@@ -417,17 +360,12 @@ int enc_frontend_merged(sva_batch* b, const int* step_ptr, int n_chunk, int add,
     }
     SVA_TRY(launch_layernorm_rows(M.xout[3].p, M.xout[3].bstride, 0, D, B, R0, D, F.final_lnw, F.final_lnb, 1e-6f, feat.p, feat.bstride, 0, D, st));
     if (part == 3) return launch_shift_history(M.d_shift, M.n_shift - n_shift_ds, B, st, 1, b->step_bump, 1);       // (+ the chain's step counter)
-    // BSQ downsample x2 (conv k2 s2 + ConvNeXtBlock, bsq_no_upsample.py:48-61); the strided convs run per row group
-    SVA_TRY(gemm_call(b, feat.p, feat.bstride, 0, D, B, Hh / 2, 2, 1, 2, D, F.ds_conv[0], M.d1.p, M.d1.bstride, (long)M.d1.H * D, D));
-    SVA_TRY(gemm_call(b, feat.p, feat.bstride, (long)(Hh + 6) * D, D, B, nm / 2, 2, 1, 2, D, F.ds_conv[0], M.d1.p, M.d1.bstride,
-                      (long)(M.d1.H + Hh / 2 + 6) * D, D));
-    SVA_TRY(cnx_block_t(b, F.ds_cnx[0], M.d1, R1, M.h1, (long)R1 * D, M.h2, (long)R1 * 4 * D, &M.d1o));
-    SVA_TRY(gemm_call(b, M.d1o.p, M.d1o.bstride, 0, D, B, Hh / 4, 2, 1, 2, D, F.ds_conv[1], M.d2.p, M.d2.bstride, (long)M.d2.H * D, D));
-    SVA_TRY(gemm_call(b, M.d1o.p, M.d1o.bstride, (long)(Hh / 2 + 6) * D, D, B, nm / 4, 2, 1, 2, D, F.ds_conv[1], M.d2.p, M.d2.bstride,
-                      (long)(M.d2.H + Hh / 4 + 6) * D, D));
-    SVA_TRY(cnx_block_t(b, F.ds_cnx[1], M.d2, R2, M.h1, (long)R2 * D, M.h2, (long)R2 * 4 * D, &M.tok));
-    if (part == 1) return 0;
-    return enc_frontend_merged(b, step_ptr, n_chunk, add, 2);
+    SVA_TRY(merged_downsample(b, feat, M.h1, M.h2));
+    // the hand-over: head and new tokens -> d2c, then every layer's history rows slide
+    hipLaunchKernelGGL(copy_tokens_kernel, dim3(b->Ht + ch, B), dim3(128), 0, st, M.tok.p, M.tok.bstride, b->Ht, 6, ch, b->d2c.p, b->d2c.bstride, b->T2, D);
+    SVA_TRY(launch_shift_history(M.d_shift, M.n_shift, B, st));
+    SVA_HIP(hipGetLastError());
+    return 0;
 }
 
 // pre_module (8-layer causal transformer on T2 tokens, windowed_transformer.py:103-143) + BSQ.  Reads the token
@@ -445,7 +383,7 @@ int enc_transformer(sva_batch* b, const Act& xin, int need_rows, int part) {
     float* xw = b->tr_x;                     // work copy [B][T2][D]
     const long xw_bs = (long)T2 * D;
     const int nl = (int)e->tr.size();
-    // part 1 = layer 0 only, part 2 = layers 1.. + final norm + BSQ (the pipelined stage graphs are cut where `xin` is released)
+    // part 1 = layer 0 only, part 2 = layers 1.. + final norm + BSQ (the cut of the pipelined step's two transformer graphs)
     const int l_lo = part == 2 ? 1 : 0, l_hi = part == 1 ? 1 : nl;
     if (part == 2) { xr = xw; xr_bs = xw_bs; xr_off = 0; }
     for (int li = l_lo; li < l_hi; ++li) {
@@ -480,8 +418,7 @@ int enc_transformer(sva_batch* b, const Act& xin, int need_rows, int part) {
         po.gamma = L.ls_attn;
         po.res = xr; po.r_bstride = xr_bs; po.r_off = xr_off + (long)r0 * D; po.ldr = D;
         SVA_TRY(gemm_call(b, b->tr_att, (long)T2 * D, (long)r0 * D, D, B, Tr, 1, 1, 1, D, L.wo, xw, xw_bs, (long)r0 * D, D, po));
-        if (li == 0 && b->tr_l0_event) SVA_HIP(hipEventRecord(b->tr_l0_event, st));     // `xin` is not read past this point
-        xr = xw; xr_bs = xw_bs; xr_off = 0;
+        xr = xw; xr_bs = xw_bs; xr_off = 0;          // (`xin` is not read past the first layer)
         ConvGemm pg;
         pg.w13 = 1;
         ConvGemm pd;
@@ -523,30 +460,13 @@ int encode(sva_batch* b, const int* step_ptr, int n_chunk, int add) {
 
 // exact-incremental formulation (SURVEY.md §7 hard part 1): window rows whose causal receptive field still touches
 // the zero left padding -- mel frames 0..116, tokens 0..38 -- are recomputed every chunk ("head pass" on the first
-// 160 mel frames = 40 tokens); every later token is the true causal feature of its absolute time, computed once by
-// the streaming pass when it entered the window and kept in d2c, which slides by c tokens per chunk.  The 8-layer
-// transformer + BSQ always run on all T2 tokens.  Same values as the window pass up to fp32 summation order.
+// 160 mel frames = 40 tokens); every later token is the true causal feature of its absolute time, computed once from
+// the newest mel frames when it entered the window (they ride in the head pass's launches: enc_frontend_merged) and kept in
+// d2c, which slides by c tokens per chunk.  The 8-layer transformer + BSQ always run on all T2 tokens.  Same values as the
+// window pass up to fp32 summation order.
 int encode_incremental(sva_batch* b, const int* step_ptr, int n_chunk, int add, bool transformer_too) {
-    const int c = b->p.chunk_frames;
-    hipStream_t st = b->stream;
-    SVA_TRY(launch_shift_history(b->d_shift_d2c, 1, b->B, st, 16));                   // steady tokens slide down by c
-    if (b->enc_merged) {
-        SVA_TRY(enc_frontend_merged(b, step_ptr, n_chunk, add));
-        if (transformer_too) return enc_transformer(b, b->d2c, b->p.chunk_frames);
-        return 0;
-    }
-    // the head pass and the streaming pass are independent chains: run the short one on a side stream
-    const bool par = b->concurrency;
-    if (par) {
-        SVA_TRY(stream_fork(b, st, b->aux[0]));
-        b->stream = b->aux[0];
-    }
-    int rc = enc_frontend_stream(b, step_ptr, n_chunk, add);                     // c newest tokens -> d2c tail
-    b->stream = st;
-    if (rc) return rc;
-    SVA_TRY(enc_frontend_window(b, step_ptr, n_chunk, add, 4 * b->Ht, nullptr, &b->d2c));   // head pass -> d2c rows [0, Ht) directly
-    if (par) SVA_TRY(stream_fork(b, b->aux[0], st));                             // join
-    (void)c;
+    SVA_TRY(launch_shift_history(b->d_shift_d2c, 1, b->B, b->stream, 16));            // steady tokens slide down by c
+    SVA_TRY(enc_frontend_merged(b, step_ptr, n_chunk, add));
     if (transformer_too) return enc_transformer(b, b->d2c, b->p.chunk_frames);
     return 0;
 }
@@ -562,7 +482,7 @@ int ar_layers_pass(sva_batch* b, std::vector<TrLayer>& layers, int M, const int*
     const int D = c.ar_dim, I = c.ar_inter, H = c.ar_heads;
     hipStream_t st = b->stream;
     const bool half_kv = b->kv_half && S > 8;           // the slow cache of an ar_dtype = 1 batch (the fast cache stays fp32)
-    if (M <= 4 && b->fused_decode && !half_kv) {
+    if (M <= 4 && !half_kv) {
         // decode at B <= 2: 5 launches per layer -- QKV GEMV (+RMSNorm, +RoPE, +KV write), attention, wo GEMV (+residual),
         // w1|w3 GEMV (+RMSNorm, +SwiGLU), w2 GEMV (+residual)
         for (size_t l = 0; l < layers.size(); ++l) {
@@ -810,7 +730,7 @@ int ar_frame_tail(sva_batch* b, int ci, long hid_stride, long hid_off, const lon
     const int nstride = c.ar_vocab + ncb * cbs;
     const float* noise = b->noise_on_device ? nullptr : b->d_noise + (long)ci * nstride;
     const int ldn = chunk * nstride;
-    const bool fused = B <= 4 && b->fused_decode;
+    const bool fused = B <= 4;               // GEMV heads with the norm folded in
     if (!b->p.skip_semantic) {
         if (fused) {
             Gemv hg;
@@ -907,10 +827,9 @@ int ar_prefill_slot(sva_batch* b, int slot, int R, bool tap_logits) {
         SVA_TRY(launch_rmsnorm_rows(b->hidden + (long)slot * D, D, 0, D, 1, 1, D, e->ar_norm, 1e-5f, b->ahn, D, 0, D, st));
         SVA_TRY(gemm_call(b, b->ahn, D, 0, D, 1, 1, 1, 1, 1, D, e->ar_output, b->slow_logits + (long)slot * c.ar_vocab, c.ar_vocab, 0, c.ar_vocab));
     }
-    const int lp = M - 1;
+    const int lp = SlotBook::prefill_end(nspk, R);       // (= M - 1; the caller tells the book)
     SVA_HIP(hipMemcpyAsync(b->d_last_pos + slot, &lp, sizeof(int), hipMemcpyHostToDevice, st));
     SVA_HIP(hipStreamSynchronize(st));
-    b->h_last_pos[slot] = lp;
     return 0;
 }
 
@@ -929,7 +848,7 @@ int ar_delay_fill(sva_batch* b, const std::vector<int>& slots) {
     SVA_TRY(ar_layers_pass(b, e->ar_layers, n * rows, b->d_slot, b->d_pos, e->rope_ar, (float*)b->kv_slow, b->kv_slow_layer,
                            b->kv_slow_slot, c.max_seq_len, b->ax));
     hipLaunchKernelGGL(add_list_kernel, dim3((n + 63) / 64), dim3(64), 0, st, b->d_last_pos, b->d_slot_list, n, rows);
-    for (int s_ : slots) b->h_last_pos[s_] += rows;
+    b->slots.delay_filled_for(slots, d);
     SVA_HIP(hipGetLastError());
     return 0;
 }
@@ -991,8 +910,8 @@ int vocode(sva_batch* b, int T, bool shift, int part) {
         }
         Tl *= s;
         // ParallelBlock = mean of three ResBlock1 (firefly.py:183-190, 214-215).  The three branches are independent
-        // chains of 6 convs: branch 0 stays on the main stream, branches 1/2 run on side streams; the last conv of each
-        // branch accumulates (x 1/3) into the level output in the fixed order 0, 1, 2 (event chain => deterministic sum).
+        // chains of 6 convs of one shape per stage: every form below runs a conv stage of all three in one launch and
+        // takes the mean of the branch outputs y3 in a kernel of its own (fixed order => deterministic sum).
         Act& out = b->S[i + 1];
         if (voc_level_is_fused(b, Cout)) {
             // narrow levels: the whole ParallelBlock in one launch (three branches x time tiles x streams), intermediates in LDS,
@@ -1099,72 +1018,28 @@ int vocode(sva_batch* b, int T, bool shift, int part) {
             SVA_HIP(hipGetLastError());
             continue;
         }
-        if (b->voc_grouped) {
-            // one launch per conv stage for the three branches (same M, N, Cin; k = 3 / 7 / 11 taps): 12 launches + the
-            // mean per level instead of 18 on three streams -- at small B the step is bound by the number of kernels
-            Act* y[3] = {&b->X[i], &b->X[i], &b->X[i]};
-            for (int j = 0; j < 3; ++j) {
-                ConvGemm g1[3], g2[3];
-                for (int br = 0; br < 3; ++br) {
-                    const ResConv& rcv = e->res[i][br][j];
-                    g1[br].a_silu = 1;
-                    SVA_TRY(conv_desc(b, *y[br], (int)Tl, rcv.dil, rcv.k, rcv.c1, b->tb[i][br][j], g1[br]));
-                    Act& dst = j < 2 ? b->yb[i][br][j] : b->y3[i][br];
-                    g2[br].a_silu = 1;
-                    g2[br].res = y[br]->p; g2[br].r_bstride = y[br]->bstride; g2[br].r_off = (long)y[br]->H * Cout; g2[br].ldr = Cout;
-                    SVA_TRY(conv_desc(b, b->tb[i][br][j], (int)Tl, rcv.dil, rcv.k, rcv.c2, dst, g2[br]));
-                }
-                SVA_TRY(gemm_group_call(b, g1, 3));
-                SVA_TRY(gemm_group_call(b, g2, 3));
-                for (int br = 0; br < 3; ++br) y[br] = j < 2 ? &b->yb[i][br][j] : &b->y3[i][br];
-            }
-            const long n4 = Tl * Cout / 4;
-            hipLaunchKernelGGL(mean3_kernel, dim3((unsigned)((n4 + 255) / 256), B), dim3(256), 0, st, b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p,
-                               b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4);
-            SVA_HIP(hipGetLastError());
-            continue;
-        }
-        const bool par = b->concurrency;
-        if (par) {
-            SVA_TRY(stream_fork(b, st, b->aux[0]));
-            SVA_TRY(stream_fork(b, st, b->aux[1]));
-        }
-        hipStream_t prev_last = nullptr;
-        for (int br = 0; br < 3; ++br) {
-            hipStream_t sbr = (par && br > 0) ? b->aux[br - 1] : st;
-            b->stream = sbr;
-            Act* y = &b->X[i];
-            int rc = 0;
-            for (int j = 0; j < 3 && !rc; ++j) {
+        // fp32 rows: one launch per conv stage for the three branches (same M, N, Cin; k = 3 / 7 / 11 taps), 12 launches + the mean per
+        // level -- at small B the step is bound by the number of kernels
+        Act* y[3] = {&b->X[i], &b->X[i], &b->X[i]};
+        for (int j = 0; j < 3; ++j) {
+            ConvGemm g1[3], g2[3];
+            for (int br = 0; br < 3; ++br) {
                 const ResConv& rcv = e->res[i][br][j];
-                ConvGemm p1;
-                p1.a_silu = 1;
-                rc = conv_act(b, *y, (int)Tl, 1, rcv.dil, rcv.k, rcv.c1, b->tb[i][br][j], p1);
-                if (rc) break;
-                ConvGemm p2;
-                p2.a_silu = 1;
-                p2.res = y->p; p2.r_bstride = y->bstride; p2.r_off = (long)y->H * Cout; p2.ldr = Cout;
-                if (j < 2) {
-                    rc = conv_act(b, b->tb[i][br][j], (int)Tl, 1, rcv.dil, rcv.k, rcv.c2, b->yb[i][br][j], p2);
-                    y = &b->yb[i][br][j];
-                } else {
-                    p2.scale = 1.0f / 3.0f;
-                    p2.accumulate = br > 0;
-                    if (par && br > 0) {
-                        hipError_t he = hipSuccess;
-                        hipEvent_t ev = next_event(b);
-                        he = hipEventRecord(ev, prev_last);
-                        if (he == hipSuccess) he = hipStreamWaitEvent(sbr, ev, 0);
-                        if (he != hipSuccess) { b->stream = st; SVA_HIP(he); }
-                    }
-                    rc = conv_act(b, b->tb[i][br][j], (int)Tl, 1, rcv.dil, rcv.k, rcv.c2, out, p2);
-                }
+                g1[br].a_silu = 1;
+                SVA_TRY(conv_desc(b, *y[br], (int)Tl, rcv.dil, rcv.k, rcv.c1, b->tb[i][br][j], g1[br]));
+                Act& dst = j < 2 ? b->yb[i][br][j] : b->y3[i][br];
+                g2[br].a_silu = 1;
+                g2[br].res = y[br]->p; g2[br].r_bstride = y[br]->bstride; g2[br].r_off = (long)y[br]->H * Cout; g2[br].ldr = Cout;
+                SVA_TRY(conv_desc(b, b->tb[i][br][j], (int)Tl, rcv.dil, rcv.k, rcv.c2, dst, g2[br]));
             }
-            b->stream = st;
-            if (rc) return rc;
-            prev_last = sbr;
+            SVA_TRY(gemm_group_call(b, g1, 3));
+            SVA_TRY(gemm_group_call(b, g2, 3));
+            for (int br = 0; br < 3; ++br) y[br] = j < 2 ? &b->yb[i][br][j] : &b->y3[i][br];
         }
-        if (par) SVA_TRY(stream_fork(b, b->aux[1], st));      // join: branch 2's last conv is ordered after 0 and 1
+        const long n4 = Tl * Cout / 4;
+        hipLaunchKernelGGL(mean3_kernel, dim3((unsigned)((n4 + 255) / 256), B), dim3(256), 0, st, b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p,
+                           b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4);
+        SVA_HIP(hipGetLastError());
     }
     SVA_TRY(launch_conv_post_tanh(b->S[5].p, b->S[5].bstride, (long)(b->S[5].H - (e->post_k - 1)) * b->S[5].C, B, (int)Tl, b->S[5].C, e->post_k,
                                   e->post_w, e->post_b, b->pcm_dst ? b->pcm_dst : b->d_pcm, b->pcm_dst ? b->pcm_dst_bstride : 2048L * b->Tv, 0, st, b->d_slot_flag));

@@ -924,11 +924,11 @@ extern "C" int sva_test_conv_post(int device, int B, int T, int C, int k, const 
 // into its 2 ms limit -- the two streams share a hardware queue.  Synchronises the device; the batch's own state is not touched.
 extern "C" int sva_test_stream_overlap(sva_batch* b, int* pair_ok) {
     SVA_CHECK(b && pair_ok, "sva_test_stream_overlap: a batch and an output array of 6 ints");
-    SVA_CHECK(b->main_stream && b->aux[0] && b->sa && b->sv, "sva_test_stream_overlap: the batch is not pipelined (no AR / vocoder streams)");
+    SVA_CHECK(b->main_stream && b->aux0 && b->sa && b->sv, "sva_test_stream_overlap: the batch is not pipelined (no AR / vocoder streams)");
     SVA_HIP(hipSetDevice(b->e->device));
     DevBuf words;
     SVA_TRY(words.alloc(2 * sizeof(int)));
-    const hipStream_t st[4] = {b->main_stream, b->aux[0], b->sa, b->sv};
+    const hipStream_t st[4] = {b->main_stream, b->aux0, b->sa, b->sv};
     SVA_HIP(sva_overlap::pairs_of_four(st, words.as<int>(), pair_ok));
     return 0;
 }
@@ -976,5 +976,103 @@ extern "C" int sva_test_gemm_plan(const int* desc, int n, int* out) {
     SVA_TRY(conv_gemm_group_of(gs, n, &gg, &lead));
     SVA_TRY(plan_conv_gemm(gg, lead, &p));
     out[0] = (int)p.family; out[1] = p.a; out[2] = p.b; out[3] = p.c; out[4] = p.z; out[5] = plan_report_kind(p, gg.g[lead].pmode);
+    return 0;
+}
+
+// The slot book's transitions, scripted without a device (include/sva.h).  A `step` drives the book the way step_body does: the warm-up or steady
+// step, the re-prefills it plans and their delay fills, then the activations that are due (prefill, delay fill, activated).
+extern "C" int sva_test_slot_book(const int* cfg, const int* ops, int n_ops, int* trace) {
+    SVA_CHECK(cfg && ops && trace && n_ops >= 0, "sva_test_slot_book: null argument");
+    const int B = cfg[0], chunk = cfg[1], delay = cfg[2], max_seq_frames = cfg[3], buffer_frames = cfg[4], window = cfg[5], nspk = cfg[6];
+    SVA_CHECK(B >= 1 && B <= 64 && chunk >= 1 && delay >= 1 && max_seq_frames >= 1 && buffer_frames >= 0 && window >= 1 && nspk >= 1, "sva_test_slot_book: bad config");
+    const int W = 8 * B + 6;
+    SlotBook book;
+    book.reset(B);
+    bool begun = false;
+    auto prefill = [&](int slot, int R) {          // one codebook of zeros stands for the prompt: only its length matters here
+        const std::vector<int64_t> cc((size_t)R, 0);
+        const std::vector<int32_t> ac((size_t)R, 0);
+        book.prefilled(slot, nspk, R, R, 1, cc.data(), ac.data());
+    };
+    for (int k = 0; k < n_ops; ++k) {
+        const int op = ops[3 * k], slot = ops[3 * k + 1], R = ops[3 * k + 2];
+        int* row = trace + (size_t)k * W;
+        std::fill(row, row + W, -1);
+        StepPlan plan;
+        std::vector<int> acts;
+        int one_pass = -1, prime = -1;
+        if (op == 1 || op == 3 || op == 4) SVA_CHECK(slot >= 0 && slot < B, "sva_test_slot_book: slot out of range");
+        if (op == 1 || op == 3) SVA_CHECK(R > delay, "sva_test_slot_book: the prompt must be longer than the delay");
+        if (op >= 2) SVA_CHECK(begun, "sva_test_slot_book: step / restart / retire before begin");
+        if (op == 0) {
+            SVA_CHECK(book.all_prefilled(), "sva_test_slot_book: begin before every slot was prefilled");
+            book.begin();
+            begun = true;
+            prime = book.priming_frames(0, window, chunk);
+            for (int i = 1; i < B; ++i) prime = std::min(prime, book.priming_frames(i, window, chunk));
+        } else if (op == 1) {
+            prefill(slot, R);
+        } else if (op == 2) {
+            if (!book.delay_filled) {
+                if (book.warmup_step(chunk, delay)) {
+                    std::vector<int> all(B);
+                    for (int i = 0; i < B; ++i) all[i] = i;
+                    book.delay_filled_for(all, delay);
+                }
+            } else {
+                plan = book.steady_step(chunk, max_seq_frames, nspk);
+                if (!plan.redo.empty()) one_pass = book.one_pass_ok(plan.redo, buffer_frames, delay) ? 1 : 0;
+                for (int s_ : plan.redo) book.reprefilled(s_, book.reprefill_end(s_, nspk, buffer_frames));
+                book.delay_filled_for(plan.redo, delay);
+            }
+            acts = book.due_activations(delay);
+            for (int s_ : acts) {
+                prefill(s_, book.s[s_].pending.R);
+                book.delay_filled_for(std::vector<int>{s_}, delay);
+                if (prime < 0) prime = book.priming_frames(s_, window, chunk);
+                book.activated(s_);
+            }
+        } else if (op == 3) {
+            PendingPrompt p;
+            p.R = R;
+            book.restart(slot, std::move(p), nspk, kSlotOutputMuted);
+        } else if (op == 4) {
+            book.retire(slot, kSlotInputMuted | kSlotOutputMuted);
+        } else {
+            SVA_CHECK(false, "sva_test_slot_book: unknown op");
+        }
+        for (int i = 0; i < B; ++i) {
+            const SlotHost& h = book.s[i];
+            row[4 * i] = h.phase; row[4 * i + 1] = h.last_pos; row[4 * i + 2] = h.nframes; row[4 * i + 3] = h.ncontent;
+        }
+        row[4 * B] = book.delay_filled ? 1 : 0;
+        row[4 * B + 1] = one_pass;
+        row[4 * B + 2] = (int)plan.redo.size();
+        for (size_t i = 0; i < plan.redo.size(); ++i) row[4 * B + 3 + i] = plan.redo[i];
+        row[5 * B + 3] = (int)plan.rewind.size();
+        for (size_t i = 0; i < plan.rewind.size(); ++i) { row[5 * B + 4 + 2 * i] = plan.rewind[i].first; row[5 * B + 5 + 2 * i] = plan.rewind[i].second; }
+        row[7 * B + 4] = (int)acts.size();
+        for (size_t i = 0; i < acts.size(); ++i) row[7 * B + 5 + i] = acts[i];
+        row[8 * B + 5] = prime;
+    }
+    return 0;
+}
+
+// The stored prompt and its tail, without a device (include/sva.h): a prompt of R frames with content code i at frame i and audio code
+// 1000 q + i in codebook q, stored truncated to Rt frames; out [ncb][n] = frames [first, first + n) of the last P stored frames.
+extern "C" int sva_test_slot_prompt_tail(int R, int Rt, int ncb, int P, int first, int n, int* out, int* stored) {
+    SVA_CHECK(out && stored && R >= 1 && Rt >= 1 && Rt <= R && ncb >= 1, "sva_test_slot_prompt_tail: bad prompt");
+    SVA_CHECK(P >= 0 && P <= Rt && first >= 0 && n >= 0 && first + n <= P, "sva_test_slot_prompt_tail: frames outside the stored prompt's tail");
+    std::vector<int64_t> cc((size_t)R);
+    std::vector<int32_t> ac((size_t)ncb * R);
+    for (int i = 0; i < R; ++i) cc[i] = i;
+    for (int q = 0; q < ncb; ++q)
+        for (int i = 0; i < R; ++i) ac[(size_t)q * R + i] = 1000 * q + i;
+    SlotBook book;
+    book.reset(1);
+    book.prefilled(0, 33, R, Rt, ncb, cc.data(), ac.data());
+    const SlotHost& h = book.s[0];
+    stored[0] = h.ref_len; stored[1] = (int)h.ref_content.size(); stored[2] = (int)h.ref_audio.size(); stored[3] = (int)h.ref_content.back();
+    book.prompt_tail(0, ncb, P, first, n, out);
     return 0;
 }

@@ -112,6 +112,8 @@ def load_library():
     lib.sva_bench_gemm_choice.argtypes = [i32] * 14 + [f32p]
     lib.sva_test_gemm.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp]
     lib.sva_test_gemm_plan.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]
+    lib.sva_test_slot_book.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]
+    lib.sva_test_slot_prompt_tail.argtypes = [i32] * 6 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.sva_test_gemm_choice.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32]
     lib.sva_set_sampler_edits.argtypes = [vp, vp, i32, C.c_float, vp, i32]
     lib.sva_test_prefill_attention.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp]
@@ -141,7 +143,7 @@ EXPORTED_SYMBOLS = [
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
     "sva_op_geglu", "sva_op_l2norm", "sva_ops_capture_begin", "sva_ops_capture_end", "sva_ops_graph_launch", "sva_ops_graph_free",
-    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
+    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
 ]
 
 
@@ -754,6 +756,24 @@ def test_gemm_plan(members):
     out = (C.c_int * 6)()
     _check(load_library().sva_test_gemm_plan(desc, len(members), out), "sva_test_gemm_plan")
     return tuple(out)
+
+
+def test_slot_book(cfg, ops):
+    """the slot book's trace for a script of ops (include/sva.h: sva_test_slot_book); no GPU needed.  cfg = (B, chunk, delay, max_seq_frames,
+    buffer_frames, window, nspk), ops = [(op, slot, R), ...] -> int32 array [len(ops)][8 B + 6]"""
+    B = int(cfg[0])
+    c = (C.c_int * 7)(*[int(x) for x in cfg])
+    o = (C.c_int * (3 * max(len(ops), 1)))(*[int(x) for op in ops for x in op])
+    out = (C.c_int * ((8 * B + 6) * max(len(ops), 1)))()
+    _check(load_library().sva_test_slot_book(c, o, len(ops), out), "sva_test_slot_book")
+    return np.frombuffer(out, dtype=np.int32).reshape(max(len(ops), 1), 8 * B + 6)[:len(ops)].copy()
+
+
+def test_slot_prompt_tail(R, Rt, ncb, P, first, n):
+    """include/sva.h: sva_test_slot_prompt_tail -> (codes int32 [ncb][n], (ref_len, content kept, audio kept, last content code)); no GPU needed"""
+    out, stored = (C.c_int * max(ncb * n, 1))(), (C.c_int * 4)()
+    _check(load_library().sva_test_slot_prompt_tail(R, Rt, ncb, P, first, n, out, stored), "sva_test_slot_prompt_tail")
+    return np.array(out[:ncb * n], dtype=np.int32).reshape(ncb, n), tuple(stored)
 
 
 def host_launch_cost(device=0, iters=300):
