@@ -327,6 +327,23 @@ int sva_test_gemm_choice(int device, int M, int N, int K, const float* A, const 
  * out[6] = {family (GemmFamily of csrc/sva_common.h), a, b, c, z, family number of the profiling tables}; an error (sva_last_error) where the
  * dispatcher refuses the problem. */
 int sva_test_gemm_plan(const int* desc, int n, int* out);
+/* The conv-GEMM in its conv and epilogue forms (csrc/sva_common.h: ConvGemm), n = 1..3 group members, on the production path.  Host arrays in,
+ * host arrays out; every array is the WHOLE array with the caller's strides, offsets and padding, and C is uploaded before the launch, so
+ * `accumulate` reads the caller's values and a sentinel survives wherever nothing is stored.
+ *   desc: n x 32 int64 {B, T, N, Cin, taps, stride, dil, lda, a_off, a_bstride, a_len, ldc, c_off, c_bstride, c_len, ldr, r_off, r_bstride, r_len,
+ *         act (0 / 1 GELU / 2 log-clamp), accumulate, a_silu, w13, skip_lo, skip_hi, use_wk (fragment-major weights packed from W), pmode (-1, or
+ *         1 = H3 / 2 = H1: weight planes made as at finalize), a_planes (1: A handed over as planes over the dense rows of its array, made by the
+ *         engine's activation pass; 2: with SiLU), c_planes (1: C also as planes over the dense rows of its array, 2: as planes only), cp_silu, 0, 0}
+ *   fpar: n x 4 floats {scale, ln_eps, rms_eps, 0}
+ *   ptrs: n x 16 pointers {A [a_len], W [N][taps Cin], bias [N], gamma [N], res [r_len], rms_w [Cin], dw_wT [7][Cin], dw_b, ln_w, ln_b [Cin],
+ *         C [c_len] in and out, Cp uint16 [planes][c_len / ldc x Nout] in and out (K-blocked, csrc/planes_split.h), Ap uint16 [planes][a_len] out
+ *         (optional: the A planes as the kernel read them), 0, 0, 0}; optional operands may be NULL
+ *   plan: {-1} = the dispatcher (launch_conv_gemm_group), else {GemmFamily, a, b, c, z} run under the plan check (launch_conv_gemm_group_plan)
+ *   repeat != 0: the launch runs a second time from the same initial C / Cp; out[1] = 1 when the two results are bit-identical, 0 when not
+ *   out[2] = {family number of the profiling tables of what ran, repeat verdict (-1: not asked)}
+ * Returns 0 when it ran, 1 when the problem was REFUSED before any launch (the dispatcher, the plan check or a launcher's own check; the arrays
+ * come back as they went in), -2 on a HIP error, -4 on arguments the hook declines (an index outside an array); sva_last_error has the text. */
+int sva_test_conv_gemm(int device, int n, const long long* desc, const float* fpar, void* const* ptrs, const int* plan, int repeat, int* out);
 /* The host-side book of the per-slot stream state (csrc/slot_book.h: phases, KV positions, frame and content counters, what a step plans),
  * scripted without a batch and without a GPU.  cfg[7] = {B, chunk_frames, delay, max_seq_frames, buffer_frames, decode_window_frames,
  * speaker prefix rows (timbre tokens + 1)}; ops: n_ops x 3 ints {op, slot, R} with op 0 = begin, 1 = prefilled(slot, R frames),

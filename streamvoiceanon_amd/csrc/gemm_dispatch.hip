@@ -233,20 +233,34 @@ static GemmPlan heuristic_plan(const ConvGemm& g, bool c_vec) {
 // shows that every row passes): parameter ranges, no operand planes on the split kernel, and 16-byte C rows for EVERY tiled variant -- a
 // future 64 x 64 tiled row keyed without the c_vec flag would be dropped, and should be: its float4 epilogue writes past a ragged row end.
 // (The planes-DMA predicates include planes_gemm_supported; which of the variants 9 .. 12 a conv-form problem takes is the launcher's check.)
+// A field a family's kernel never reads is refused here, not dropped: the tiled kernel has no RMSNorm / ConvNeXt prologue, the small-M kernel's
+// prologues are one-of (tests/test_gpu_conv_gemm.py runs every refusal).
 static bool plan_accepts(const ConvGemmGroup& gg, int lead, const GemmPlan& p) {
     const ConvGemm& g = gg.g[lead];
     const bool c_vec = c_rows_vectorised(g);
     const int a = p.a, b = p.b, c = p.c;
+    // the fp32 families (and the fp16-weight kernel) read A and store C as fp32 arrays: operands that exist only as planes are the planes kernel's
+    bool f32_ops = true;
+    for (int i = 0; i < gg.n; ++i) f32_ops = f32_ops && gg.g[i].A && gg.g[i].C && !gg.g[i].Ap && !gg.g[i].Cp;
     switch (p.family) {
         case GemmFamily::SmallM:
+            if (!f32_ops) return false;
+            // (SwiGLU pairs two column tiles of one wave: with c == 1 the kernel stores nothing.  The fused RMSNorm form of the launcher takes no
+            // SiLU and sums the squares of ONE row of Cin values; the ConvNeXt prologue is instantiated for one 16 x 16 tile only, reads seven
+            // consecutive rows whatever the stride, holds at most 512 channels per wave and ignores taps / SiLU / RMSNorm.)
+            if (g.w13 && c == 1) return false;
+            if (g.rms_w && (g.taps != 1 || g.a_silu || gg.n > 1)) return false;
+            if (g.dw_wT && !(a == 1 && c == 1 && g.taps == 1 && g.stride == 1 && g.M <= 16 && g.Cin <= 512 && !g.a_silu && !g.rms_w && !g.w13 && gg.n == 1 &&
+                             g.dw_b && g.ln_w && g.ln_b)) return false;
             return (a >= 1 && a <= 4) && (b == 4 || b == 8 || (b == 16 && a == 1)) &&
-                   (c == 1 || (c == 2 && g.N % 32 == 0) || (c == 4 && g.N % 64 == 0 && a != 3 && b != 16)) && p.z >= 1 && p.z <= 8;
-        case GemmFamily::Tiled: return a >= 0 && a <= 7 && c_vec;
-        case GemmFamily::Ring: return a >= 0 && a <= 6 && c_vec && pipe_gemm_supported(g);
-        case GemmFamily::Split: return a >= 0 && a <= 4 && c_vec && split_gemm_supported(g) && !g.Ap && !g.Cp;
-        case GemmFamily::F16W: return gg.n == 1 && f16w_gemm_supported(g);
+                   (c == 1 || (c == 2 && g.N % 32 == 0) || (c == 4 && g.N % 64 == 0 && a != 3 && b != 16)) && p.z >= 1 && p.z <= 8 && (gg.n == 1 || p.z == 1);
+        // (the tiled kernel has no prologue but SiLU: it never reads rms_w / dw_wT; its 256 x 16 tile cannot hold a SwiGLU column pair)
+        case GemmFamily::Tiled: return f32_ops && a >= 0 && a <= 7 && c_vec && !g.rms_w && !g.dw_wT && !(g.w13 && a == 3);
+        case GemmFamily::Ring: return f32_ops && a >= 0 && a <= 6 && c_vec && pipe_gemm_supported(g);
+        case GemmFamily::Split: return f32_ops && a >= 0 && a <= 4 && c_vec && split_gemm_supported(g);
+        case GemmFamily::F16W: return f32_ops && gg.n == 1 && f16w_gemm_supported(g);
         case GemmFamily::Stream:
-            return gg.n == 1 && stream_gemm_supported(g) && (a == 1 || a == 2 || a == 4) && (c == 1 || c == 2) && (b == 4 || b == 8 || (b == 16 && a * c <= 2)) &&
+            return f32_ops && gg.n == 1 && stream_gemm_supported(g) && (a == 1 || a == 2 || a == 4) && (c == 1 || c == 2) && (b == 4 || b == 8 || (b == 16 && a * c <= 2)) &&
                    !(g.w13 && c != 2) && (g.M + 16 * a - 1) / (16 * a) * (long)((g.N + 16 * c - 1) / (16 * c)) < 65536;
         case GemmFamily::Planes: return a >= 0 && a <= 7 && c_vec && planes_gemm_supported(g);
         case GemmFamily::PlanesDma: return a >= 9 && a <= 14 && c_vec && ((a <= 12 && planes_dma_gemm_supported(g)) || (a != 12 && planes_dma_conv_supported(g)));
@@ -264,7 +278,7 @@ int conv_gemm_group_of(const ConvGemm* gs, int n, ConvGemmGroup* gg, int* lead) 
         const ConvGemm& r = gs[0];
         if (n > 1) {
             SVA_CHECK(a.M == r.M && a.T == r.T && a.N == r.N && a.Cin == r.Cin && a.stride == r.stride && a.a_silu == r.a_silu && a.w13 == r.w13 &&
-                      a.act == r.act && a.accumulate == r.accumulate && !a.rms_w && a.ldc % 4 == r.ldc % 4 && (a.res != nullptr) == (r.res != nullptr) &&
+                      a.act == r.act && a.accumulate == r.accumulate && !a.rms_w && !a.dw_wT && a.ldc % 4 == r.ldc % 4 && (a.res != nullptr) == (r.res != nullptr) &&
                       (a.gamma != nullptr) == (r.gamma != nullptr) && (a.bias != nullptr) == (r.bias != nullptr),
                       "conv_gemm_group: members must share shape and epilogue");
             SVA_CHECK(a.lda % 4 == 0 && a.a_off % 4 == 0 && a.a_bstride % 4 == 0 && a.c_off % 4 == r.c_off % 4 && a.c_bstride % 4 == r.c_bstride % 4 &&
@@ -295,7 +309,7 @@ int plan_conv_gemm(const ConvGemmGroup& gg, int lead, GemmPlan* out) {
     SVA_CHECK(g.M > 0 && g.N > 0 && g.T > 0, "conv_gemm: empty problem");
     if (g.w13) SVA_CHECK(g.N % 32 == 0, "conv_gemm: w13 needs N % 32 == 0");
     if (g.rms_w) SVA_CHECK(g.taps == 1 && !g.a_silu && conv_gemm_can_fuse_rms(g.M, g.N), "conv_gemm: fused RMSNorm needs taps == 1 on the small-M path");
-    if (g.dw_wT) SVA_CHECK(g.taps == 1 && g.M <= 16 && g.Cin <= 512 && !g.a_silu && !g.rms_w && !g.w13 && group_n == 1 && g.dw_b && g.ln_w && g.ln_b,
+    if (g.dw_wT) SVA_CHECK(g.taps == 1 && g.stride == 1 && g.M <= 16 && g.Cin <= 512 && !g.a_silu && !g.rms_w && !g.w13 && group_n == 1 && g.dw_b && g.ln_w && g.ln_b,
                            "conv_gemm: the fused ConvNeXt prologue needs taps == 1, M <= 16, Cin <= 512");
     bool planes_ok = c_vec;
     for (int i = 0; i < gg.n; ++i) planes_ok = planes_ok && planes_gemm_supported(gg.g[i]);
@@ -509,14 +523,19 @@ int launch_conv_gemm_group(const ConvGemm* gs, int n, hipStream_t st, int* kind_
 }
 int launch_conv_gemm(const ConvGemm& g, hipStream_t st, int* kind_out) { return launch_conv_gemm_group(&g, 1, st, kind_out); }
 
-// test / bench hooks: run one given plan
-int launch_conv_gemm_plan(const ConvGemm& g, const GemmPlan& p, hipStream_t st) {
+// test / bench hooks: run one given plan on a problem or a group, under the planner's own preconditions and plan_accepts
+int launch_conv_gemm_group_plan(const ConvGemm* gs, int n, const GemmPlan& p, hipStream_t st) {
     ConvGemmGroup gg;
-    gg.g[0] = g;
-    SVA_CHECK(g.Cin % 16 == 0 && g.lda % 4 == 0 && plan_accepts(gg, 0, p), "conv_gemm_plan: the kernel family does not take this problem in this configuration");
+    int lead = 0;
+    SVA_TRY_RC(conv_gemm_group_of(gs, n, &gg, &lead));
+    const ConvGemm& g = gg.g[lead];
+    SVA_CHECK(g.Cin > 0 && g.Cin % 16 == 0 && g.M > 0 && g.N > 0 && g.T > 0 && g.lda % 4 == 0 && g.a_off % 4 == 0 && g.a_bstride % 4 == 0 &&
+              (!g.w13 || g.N % 32 == 0) && plan_accepts(gg, lead, p),
+              "conv_gemm_plan: the kernel family does not take this problem in this configuration");
     SVA_TRY_RC(run_plan(gg, p, st));
     SVA_HIP(hipGetLastError());
     return 0;
 }
+int launch_conv_gemm_plan(const ConvGemm& g, const GemmPlan& p, hipStream_t st) { return launch_conv_gemm_group_plan(&g, 1, p, st); }
 
 }  // namespace sva

@@ -289,7 +289,7 @@ int launch_pipe(const ConvGemmGroup& gg, hipStream_t st) {
 bool pipe_gemm_supported(const ConvGemm& g) {
     return g.Cin % 64 == 0 && !g.dw_wT && g.N % 4 == 0 && g.ldc % 4 == 0 && g.c_off % 4 == 0 && g.c_bstride % 4 == 0 && g.lda % 4 == 0 &&
            g.a_off % 4 == 0 && g.a_bstride % 4 == 0 && (!g.res || (g.ldr % 4 == 0 && g.r_off % 4 == 0 && g.r_bstride % 4 == 0)) &&
-           (!g.rms_w || (g.taps == 1 && g.Cin <= 2048)) && (!g.w13 || g.N % 32 == 0);
+           (!g.rms_w || (g.taps == 1 && g.Cin <= 2048 && !g.a_silu)) && (!g.w13 || g.N % 32 == 0);      // (launch_pipe takes ONE prologue: RMSNorm would drop SiLU)
 }
 
 // variant (tile, register stages): 0 = 32x64 (4), 1 = 64x64 (3), 2 = 128x64 (3), 3 = 64x128 (3), 4 = 128x128 (2), 5 = 32x128 (3), 6 = 32x32 (4)

@@ -295,5 +295,6 @@ int launch_conv_gemm_group(const ConvGemm* gs, int n, hipStream_t st, int* kind_
 // true when the planner routes an (M, N) problem to the K-split small-M kernel, which can normalise its A rows
 bool conv_gemm_can_fuse_rms(int M, int N);
 int launch_conv_gemm_plan(const ConvGemm& g, const GemmPlan& p, hipStream_t st);        // test / bench hooks: one given plan, checked against the problem
+int launch_conv_gemm_group_plan(const ConvGemm* gs, int n, const GemmPlan& p, hipStream_t st);      // the same for a group of 1..3 members (-1: refused)
 
 }  // namespace sva

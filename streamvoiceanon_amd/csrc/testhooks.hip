@@ -256,6 +256,19 @@ extern "C" int sva_bench_gemm(int device, int B, int T, int N, int Cin, int taps
     return 0;
 }
 
+// W [N][K] -> the fragment-major packing gemm_stream.hip reads (ConvGemm::Wk): [N / 16][K / 16][lane = (n & 15) + 16 * (k4)][4], zero rows past N
+static void pack_fragment_major(const float* W, int N, long K, std::vector<float>& out) {
+    const long nkb = K / 16, nt16 = (N + 15) / 16;
+    out.assign((size_t)nt16 * nkb * 256, 0.f);
+    for (long t = 0; t < nt16; ++t)
+        for (long kb = 0; kb < nkb; ++kb)
+            for (int l = 0; l < 64; ++l) {
+                const long n = t * 16 + (l & 15);
+                if (n >= N) continue;
+                for (int e = 0; e < 4; ++e) out[((t * nkb + kb) * 64 + l) * 4 + e] = W[(size_t)n * K + kb * 16 + 4 * (l >> 4) + e];
+            }
+}
+
 // One dispatch choice of the conv-GEMM family timed on device-resident random data, `nrot` weight copies rotated launch by launch (large nrot:
 // every launch streams its weights from HBM, as inside a step that touches 0.8 GB of weights; 1: the weights stay in L2 / MALL).
 //   kind -1 = the dispatcher; 0 / 1 / 2 / 4 = GemmFamily SmallM (c = column tiles + 16 * grid-level K split) / Tiled / Ring / Split with its parameters
@@ -300,17 +313,7 @@ extern "C" int sva_bench_gemm_choice(int device, int B, int T, int N, int Cin, i
     SVA_HIP(hipMemcpy(dG, hG.data(), sizeof(float) * Cin, hipMemcpyHostToDevice));
     SVA_HIP(hipMemcpy(dR, hR.data(), sizeof(float) * hR.size(), hipMemcpyHostToDevice));
     std::vector<float> hWp;
-    if (packed) {           // fragment-major: [N / 16][K / 16][lane = (n & 15) + 16 * (k4)][4]
-        const long nkb = K / 16, nt16 = (N + 15) / 16;
-        hWp.assign((size_t)nt16 * nkb * 256, 0.f);
-        for (long t = 0; t < nt16; ++t)
-            for (long kb = 0; kb < nkb; ++kb)
-                for (int l = 0; l < 64; ++l) {
-                    const long n = t * 16 + (l & 15);
-                    if (n >= N) continue;
-                    for (int e = 0; e < 4; ++e) hWp[((t * nkb + kb) * 64 + l) * 4 + e] = hW[(size_t)n * K + kb * 16 + 4 * (l >> 4) + e];
-                }
-    }
+    if (packed) pack_fragment_major(hW.data(), N, K, hWp);
     for (int r = 0; r < nrot; ++r) {
         SVA_HIP(hipMalloc(&dW[r], sizeof(float) * hW.size()));
         SVA_HIP(hipMemcpy(dW[r], hW.data(), sizeof(float) * hW.size(), hipMemcpyHostToDevice));
@@ -1074,5 +1077,169 @@ extern "C" int sva_test_slot_prompt_tail(int R, int Rt, int ncb, int P, int firs
     const SlotHost& h = book.s[0];
     stored[0] = h.ref_len; stored[1] = (int)h.ref_content.size(); stored[2] = (int)h.ref_audio.size(); stored[3] = (int)h.ref_content.back();
     book.prompt_tail(0, ncb, P, first, n, out);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The conv-GEMM in its conv and epilogue forms (include/sva.h: sva_test_conv_gemm; tests/test_gpu_conv_gemm.py): 1..3 members as whole host
+// arrays with the caller's strides and offsets, a full ConvGemm per member, the dispatcher or one given plan, whole arrays back.
+// Return codes: 0 ran, 1 REFUSED (the dispatcher, plan_accepts or a launcher's own check declined the problem: nothing was launched), -2 a HIP
+// error, -4 arguments the hook itself declines (an index outside an array, an operand it cannot build).
+// ------------------------------------------------------------------------------------------------------------------------------------
+#define SVA_HOOK_ARG(cond, msg)                                                         \
+    do {                                                                                \
+        if (!(cond)) {                                                                  \
+            ::sva::set_error(std::string("sva_test_conv_gemm: ") + msg + " [" #cond "]"); \
+            return -4;                                                                  \
+        }                                                                               \
+    } while (0)
+namespace {
+enum { CG_B, CG_T, CG_N, CG_CIN, CG_TAPS, CG_STRIDE, CG_DIL, CG_LDA, CG_A_OFF, CG_A_BSTRIDE, CG_A_LEN, CG_LDC, CG_C_OFF, CG_C_BSTRIDE, CG_C_LEN, CG_LDR,
+       CG_R_OFF, CG_R_BSTRIDE, CG_R_LEN, CG_ACT, CG_ACCUMULATE, CG_A_SILU, CG_W13, CG_SKIP_LO, CG_SKIP_HI, CG_USE_WK, CG_PMODE, CG_A_PLANES, CG_C_PLANES,
+       CG_CP_SILU, CG_ND = 32 };
+enum { CP_A, CP_W, CP_BIAS, CP_GAMMA, CP_RES, CP_RMS_W, CP_DW_WT, CP_DW_B, CP_LN_W, CP_LN_B, CP_C, CP_CP, CP_AP, CP_NP = 16 };
+struct ConvMember {
+    DevBuf A, W, Wk, bias, gamma, res, rms, dww, dwb, lnw, lnb, C, Wp, Ap, Cp;
+    std::vector<float> c0;              // C as the caller handed it in
+    std::vector<uint16_t> cp0;          // Cp likewise
+    size_t c_len = 0, cp_elems = 0, ap_elems = 0;
+    float* c_host = nullptr;
+    uint16_t *cp_host = nullptr, *ap_host = nullptr;
+};
+// one member: arguments checked, every index of the launch inside its array, operands uploaded / built
+int conv_member_build(const long long* d, const float* fp, void* const* pp, ConvMember& m, ConvGemm& g) {
+    const long B = d[CG_B], T = d[CG_T], N = d[CG_N], Cin = d[CG_CIN], taps = d[CG_TAPS], stride = d[CG_STRIDE], dil = d[CG_DIL];
+    SVA_HOOK_ARG(B >= 1 && T >= 1 && N >= 1 && Cin >= 1 && taps >= 1 && stride >= 1 && dil >= 1 && B * T < (1 << 24) && N < (1 << 20) && taps * Cin < (1 << 20), "shape");
+    const long K = taps * Cin, Nout = d[CG_W13] ? N / 2 : N;
+    const float *A = (const float*)pp[CP_A], *W = (const float*)pp[CP_W], *bias = (const float*)pp[CP_BIAS], *gamma = (const float*)pp[CP_GAMMA],
+                *res = (const float*)pp[CP_RES], *rms_w = (const float*)pp[CP_RMS_W], *dw_wT = (const float*)pp[CP_DW_WT];
+    SVA_HOOK_ARG(A && W && pp[CP_C], "A, W and C are required");
+    SVA_HOOK_ARG(!dw_wT || (pp[CP_DW_B] && pp[CP_LN_W] && pp[CP_LN_B]), "the ConvNeXt prologue takes dw_wT, dw_b, ln_w and ln_b");
+    // the largest index of every array the launch touches
+    const long lda = d[CG_LDA], a_off = d[CG_A_OFF], a_bs = d[CG_A_BSTRIDE], a_len = d[CG_A_LEN];
+    const long in_rows = (T - 1) * stride + (taps - 1) * dil + 1 + (dw_wT ? 6 : 0);
+    SVA_HOOK_ARG(lda >= Cin && a_off >= 0 && a_bs >= 0 && (B - 1) * a_bs + a_off + (in_rows - 1) * lda + Cin <= a_len, "A index out of range");
+    const long ldc = d[CG_LDC], c_off = d[CG_C_OFF], c_bs = d[CG_C_BSTRIDE], c_len = d[CG_C_LEN];
+    SVA_HOOK_ARG(ldc >= Nout && c_off >= 0 && c_bs >= 0 && (B - 1) * c_bs + c_off + (T - 1) * ldc + Nout <= c_len, "C index out of range");
+    const long ldr = d[CG_LDR], r_off = d[CG_R_OFF], r_bs = d[CG_R_BSTRIDE], r_len = d[CG_R_LEN];
+    SVA_HOOK_ARG(!res || (ldr >= Nout && r_off >= 0 && r_bs >= 0 && (B - 1) * r_bs + r_off + (T - 1) * ldr + Nout <= r_len), "res index out of range");
+    SVA_HOOK_ARG(d[CG_SKIP_LO] >= 0 && d[CG_SKIP_HI] <= T, "skip rows");
+    SVA_TRY(m.A.put(A, sizeof(float) * a_len));
+    SVA_TRY(m.W.put(W, sizeof(float) * N * K));
+    m.c_host = (float*)pp[CP_C];
+    m.c_len = (size_t)c_len;
+    m.c0.assign(m.c_host, m.c_host + c_len);
+    SVA_TRY(m.C.put(m.c0.data(), sizeof(float) * c_len));
+    g.A = m.A.as<float>(); g.a_bstride = a_bs; g.a_off = a_off; g.lda = (int)lda; g.T = (int)T; g.M = (int)(B * T);
+    g.stride = (int)stride; g.dil = (int)dil; g.taps = (int)taps; g.Cin = (int)Cin;
+    g.W = m.W.as<float>(); g.N = (int)N;
+    g.C = m.C.as<float>(); g.c_bstride = c_bs; g.c_off = c_off; g.ldc = (int)ldc;
+    if (bias) { SVA_TRY(m.bias.put(bias, sizeof(float) * N)); g.bias = m.bias.as<float>(); }
+    if (gamma) { SVA_TRY(m.gamma.put(gamma, sizeof(float) * N)); g.gamma = m.gamma.as<float>(); }
+    if (res) { SVA_TRY(m.res.put(res, sizeof(float) * r_len)); g.res = m.res.as<float>(); g.r_bstride = r_bs; g.r_off = r_off; g.ldr = (int)ldr; }
+    if (rms_w) { SVA_TRY(m.rms.put(rms_w, sizeof(float) * Cin)); g.rms_w = m.rms.as<float>(); g.rms_eps = fp[2]; }
+    if (dw_wT) {
+        SVA_TRY(m.dww.put(dw_wT, sizeof(float) * 7 * Cin));
+        SVA_TRY(m.dwb.put(pp[CP_DW_B], sizeof(float) * Cin));
+        SVA_TRY(m.lnw.put(pp[CP_LN_W], sizeof(float) * Cin));
+        SVA_TRY(m.lnb.put(pp[CP_LN_B], sizeof(float) * Cin));
+        g.dw_wT = m.dww.as<float>(); g.dw_b = m.dwb.as<float>(); g.ln_w = m.lnw.as<float>(); g.ln_b = m.lnb.as<float>(); g.ln_eps = fp[1];
+    }
+    g.scale = fp[0]; g.act = (int)d[CG_ACT]; g.accumulate = d[CG_ACCUMULATE] != 0; g.a_silu = d[CG_A_SILU] != 0; g.w13 = d[CG_W13] != 0;
+    g.skip_lo = (int)d[CG_SKIP_LO]; g.skip_hi = (int)d[CG_SKIP_HI];
+    if (d[CG_USE_WK]) {
+        SVA_HOOK_ARG(K % 16 == 0, "packed weights take whole 16-k blocks");
+        std::vector<float> wk;
+        pack_fragment_major(W, (int)N, K, wk);
+        SVA_TRY(m.Wk.put(wk.data(), sizeof(float) * wk.size()));
+        g.Wk = m.Wk.as<float>();
+    }
+    const int pmode = (int)d[CG_PMODE];
+    if (pmode >= 0) {           // weight planes as the engine makes them at finalize
+        SVA_HOOK_ARG((pmode == PLANES_H3 || pmode == PLANES_H1) && Cin % 32 == 0, "planes: H3 or H1, whole 32-k blocks per tap");
+        const int npl = planes_count(pmode);
+        float mx = 0.f;
+        for (long i = 0; i < N * K; ++i) mx = std::max(mx, fabsf(W[i]));
+        SVA_TRY(m.Wp.alloc(2 * (size_t)npl * N * K));
+        g.Wp = m.Wp.as<unsigned short>(); g.wp_pstride = N * K; g.pmode = pmode;
+        SVA_TRY(make_weight_planes(g.W, (int)N, (int)K, mx, pmode, m.Wp.as<unsigned short>(), &g.wp_inv, 0));
+    }
+    if (d[CG_A_PLANES]) {       // the whole A array as planes over its dense rows (every pad row included), by the activation pass of the engine
+        SVA_HOOK_ARG(pmode >= 0 && lda == Cin && a_len % lda == 0 && a_off % lda == 0 && a_bs % lda == 0 && stride == 1 && !d[CG_A_SILU] && !dw_wT && !rms_w,
+                     "A as planes: dense rows of Cin values, stride 1, SiLU belongs to the producer");
+        const long ap_rows = a_len / lda;
+        const int npl = planes_count(pmode);
+        SVA_HOOK_ARG(ap_rows < (1 << 24) && (B - 1) * (a_bs / lda) + a_off / lda + in_rows <= ap_rows, "A planes row out of range");
+        m.ap_elems = (size_t)npl * ap_rows * Cin;
+        SVA_TRY(m.Ap.alloc(2 * m.ap_elems));
+        SVA_TRY(launch_to_planes_act(g.A, 1, ap_rows, 0, (int)ap_rows, (int)Cin, m.Ap.as<unsigned short>(), ap_rows * Cin, pmode, d[CG_A_PLANES] == 2 ? 1 : 0, 0));
+        g.Ap = m.Ap.as<unsigned short>(); g.ap_pstride = ap_rows * Cin; g.ap_rows = ap_rows; g.A = nullptr;
+        m.ap_host = (uint16_t*)pp[CP_AP];
+    }
+    if (d[CG_C_PLANES]) {       // C (also) as planes over the dense rows of the C array; uploaded first like C
+        SVA_HOOK_ARG(pmode >= 0 && pp[CP_CP] && ldc == Nout && Nout % 32 == 0 && c_len % ldc == 0 && c_off % ldc == 0 && c_bs % ldc == 0,
+                     "C as planes: dense rows of whole 32-column blocks");
+        const long cp_rows = c_len / ldc;
+        const int npl = planes_count(pmode);
+        SVA_HOOK_ARG((B - 1) * (c_bs / ldc) + c_off / ldc + T <= cp_rows, "C planes row out of range");
+        m.cp_elems = (size_t)npl * cp_rows * Nout;
+        m.cp_host = (uint16_t*)pp[CP_CP];
+        m.cp0.assign(m.cp_host, m.cp_host + m.cp_elems);
+        SVA_TRY(m.Cp.put(m.cp0.data(), 2 * m.cp_elems));
+        g.Cp = m.Cp.as<unsigned short>(); g.cp_pstride = cp_rows * Nout; g.cp_rows = cp_rows; g.cp_silu = d[CG_CP_SILU] != 0;
+        if (d[CG_C_PLANES] == 2) g.C = nullptr;
+    } else {
+        SVA_HOOK_ARG(!d[CG_CP_SILU], "cp_silu needs C as planes");
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" int sva_test_conv_gemm(int device, int n, const long long* desc, const float* fpar, void* const* ptrs, const int* plan, int repeat, int* out) {
+    SVA_HOOK_ARG(n >= 1 && n <= 3 && desc && fpar && ptrs && plan && out, "1..3 members");
+    SVA_HOOK_ARG(plan[0] >= -1 && plan[0] <= (int)GemmFamily::StreamH, "plan: -1 (the dispatcher) or a GemmFamily");
+    out[0] = -1; out[1] = -1;
+    SVA_HIP(hipSetDevice(device));
+    ConvGemm gs[3];
+    ConvMember mem[3];
+    for (int i = 0; i < n; ++i) SVA_TRY(conv_member_build(desc + (size_t)CG_ND * i, fpar + 4 * i, ptrs + (size_t)CP_NP * i, mem[i], gs[i]));
+    SVA_HIP(hipDeviceSynchronize());
+    const GemmPlan p{(GemmFamily)(plan[0] < 0 ? 0 : plan[0]), plan[1], plan[2], plan[3], plan[4]};
+    int kind_out = -1;
+    auto run = [&]() -> int {
+        const int rc = plan[0] < 0 ? launch_conv_gemm_group(gs, n, 0, &kind_out) : launch_conv_gemm_group_plan(gs, n, p, 0);
+        if (rc == -1) return 1;         // an SVA_CHECK of the dispatcher / plan_accepts / a launcher: refused before any launch
+        if (rc) return rc;
+        SVA_HIP(hipDeviceSynchronize());
+        return 0;
+    };
+    const int rc = run();
+    if (rc != 0 && rc != 1) return rc;
+    if (!rc) out[0] = plan[0] >= 0 ? plan_report_kind(p, gs[0].pmode) : kind_out;
+    for (int i = 0; i < n; ++i) {       // (after a refusal too: the arrays come back as the device holds them, i.e. as they went in)
+        SVA_TRY(mem[i].C.get(mem[i].c_host, sizeof(float) * mem[i].c_len));
+        if (mem[i].cp_host) SVA_TRY(mem[i].Cp.get(mem[i].cp_host, 2 * mem[i].cp_elems));
+        if (mem[i].ap_host) SVA_TRY(mem[i].Ap.get(mem[i].ap_host, 2 * mem[i].ap_elems));
+    }
+    if (rc == 1) return 1;
+    if (repeat) {               // the same launch again from the same initial C: a K split's counters re-armed, the same summation order
+        for (int i = 0; i < n; ++i) {
+            SVA_HIP(hipMemcpy(mem[i].C.p, mem[i].c0.data(), sizeof(float) * mem[i].c_len, hipMemcpyHostToDevice));
+            if (mem[i].cp_host) SVA_HIP(hipMemcpy(mem[i].Cp.p, mem[i].cp0.data(), 2 * mem[i].cp_elems, hipMemcpyHostToDevice));
+        }
+        SVA_TRY(run());
+        bool same = true;
+        for (int i = 0; i < n; ++i) {
+            std::vector<float> c2(mem[i].c_len);
+            SVA_TRY(mem[i].C.get(c2.data(), sizeof(float) * mem[i].c_len));
+            same = same && memcmp(c2.data(), mem[i].c_host, sizeof(float) * mem[i].c_len) == 0;
+            if (mem[i].cp_host) {
+                std::vector<uint16_t> p2(mem[i].cp_elems);
+                SVA_TRY(mem[i].Cp.get(p2.data(), 2 * mem[i].cp_elems));
+                same = same && memcmp(p2.data(), mem[i].cp_host, 2 * mem[i].cp_elems) == 0;
+            }
+        }
+        out[1] = same ? 1 : 0;
+    }
     return 0;
 }

@@ -112,6 +112,7 @@ def load_library():
     lib.sva_bench_gemm_choice.argtypes = [i32] * 14 + [f32p]
     lib.sva_test_gemm.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp]
     lib.sva_test_gemm_plan.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]
+    lib.sva_test_conv_gemm.argtypes = [i32, i32, vp, vp, vp, C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]
     lib.sva_test_slot_book.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]
     lib.sva_test_slot_prompt_tail.argtypes = [i32] * 6 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.sva_test_gemm_choice.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32]
@@ -143,7 +144,7 @@ EXPORTED_SYMBOLS = [
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
     "sva_op_geglu", "sva_op_l2norm", "sva_ops_capture_begin", "sva_ops_capture_end", "sva_ops_graph_launch", "sva_ops_graph_free",
-    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
+    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
 ]
 
 
@@ -756,6 +757,55 @@ def test_gemm_plan(members):
     out = (C.c_int * 6)()
     _check(load_library().sva_test_gemm_plan(desc, len(members), out), "sva_test_gemm_plan")
     return tuple(out)
+
+
+_CONV_GEMM_INTS = ("B", "T", "N", "Cin", "taps", "stride", "dil", "lda", "a_off", "a_bstride", "a_len", "ldc", "c_off", "c_bstride", "c_len", "ldr", "r_off",
+                   "r_bstride", "r_len", "act", "accumulate", "a_silu", "w13", "skip_lo", "skip_hi", "use_wk", "pmode", "a_planes", "c_planes", "cp_silu")
+_CONV_GEMM_PTRS = ("A", "W", "bias", "gamma", "res", "rms_w", "dw_wT", "dw_b", "ln_w", "ln_b", "C", "Cp", "Ap")
+_CONV_GEMM_DEFAULTS = dict(stride=1, dil=1, taps=1, act=0, accumulate=0, a_silu=0, w13=0, skip_lo=0, skip_hi=0, use_wk=0, pmode=-1, a_planes=0, c_planes=0,
+                           cp_silu=0, ldr=0, r_off=0, r_bstride=0, a_off=0, c_off=0)
+
+
+def test_conv_gemm(members, plan=None, repeat=False, device=0):
+    """1..3 conv-GEMM group members through the dispatcher (plan None) or one given plan (GemmFamily number, a, b, c, z) -- include/sva.h:
+    sva_test_conv_gemm.  A member is a dict of the hook's descriptor fields by name (B, T, N, Cin, taps, stride, dil, lda, a_off, a_bstride, ldc,
+    c_off, c_bstride, ldr, r_off, r_bstride, act, accumulate, a_silu, w13, skip_lo, skip_hi, use_wk, pmode, a_planes, c_planes, cp_silu, scale, ln_eps,
+    rms_eps) and of its arrays: A, C and res the WHOLE flat float32 arrays (C, and the uint16 Cp, are written in place), W [N][taps Cin], the optional
+    vectors, Ap an optional uint16 array that receives the A planes.  -> dict(refused, kind, identical): refused = the problem was declined before any
+    launch (the arrays are as they went in), kind = the family number of the profiling tables, identical = the repeat verdict (None: not asked)."""
+    lib = load_library()
+    n = len(members)
+    desc = np.zeros((n, 32), np.int64)
+    fpar = np.zeros((n, 4), np.float32)
+    ptrs = (C.c_void_p * (16 * n))()
+    keep = []
+    for i, m in enumerate(members):
+        m = dict(_CONV_GEMM_DEFAULTS, **m)
+        for name in ("A", "C", "W"):
+            a = m[name]
+            assert isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous, name
+        m["a_len"], m["c_len"], m["r_len"] = m["A"].size, m["C"].size, 0
+        if m.get("res") is not None:
+            assert m["res"].dtype == np.float32 and m["res"].flags.c_contiguous
+            m["r_len"] = m["res"].size
+        for name in ("Cp", "Ap"):
+            if m.get(name) is not None:
+                assert m[name].dtype == np.uint16 and m[name].flags.c_contiguous, name
+        for j, name in enumerate(_CONV_GEMM_INTS):
+            desc[i, j] = int(m[name])
+        fpar[i] = (m.get("scale", 1.0), m.get("ln_eps", 1e-6), m.get("rms_eps", 1e-5), 0.0)
+        for j, name in enumerate(_CONV_GEMM_PTRS):
+            a = m.get(name)
+            if a is not None and name not in ("A", "C", "res", "Cp", "Ap"):
+                a = _f32(a)
+                keep.append(a)
+            ptrs[16 * i + j] = None if a is None else a.ctypes.data
+    pl = (C.c_int * 5)(*([-1, 0, 0, 0, 1] if plan is None else [int(x) for x in plan]))
+    out = (C.c_int * 2)()
+    rc = lib.sva_test_conv_gemm(device, n, _ptr(desc), _ptr(fpar), ptrs, pl, 1 if repeat else 0, out)
+    if rc not in (0, 1):
+        _check(rc, "sva_test_conv_gemm")
+    return dict(refused=rc == 1, kind=int(out[0]), identical=None if out[1] < 0 else bool(out[1]))
 
 
 def test_slot_book(cfg, ops):

@@ -1,5 +1,6 @@
 """NumPy restatements of the non-GEMM operations, written from their definitions (csrc/kernels.h, oracle/sva_oracle.py), for the
-per-kernel GPU tests (test_gpu_kernels.py).  tests/test_kernel_refs.py pins each of them to the oracle's own function on the CPU.
+per-kernel GPU tests (test_gpu_kernels.py), and of the conv-GEMM with its prologues and epilogues (csrc/sva_common.h: ConvGemm) for
+test_gpu_conv_gemm.py.  tests/test_kernel_refs.py pins each of them to the oracle's own function (the conv-GEMM: to torch's conv1d) on the CPU.
 
 Every function takes `dt`: np.float64 is THE reference; np.float32 evaluates the same formula naively in float32 (sequential sums,
 float32 exp / tanh / sqrt), which gives the per-case rounding scale e32 = max |f32 - f64| the GPU tests derive their bounds from
@@ -237,7 +238,112 @@ def enc_attention(qkv, tab, H, window=512, dt=np.float64):
     return o.transpose(0, 2, 1, 3).reshape(B, T, D)
 
 
+# ---- conv-GEMM (csrc/sva_common.h: ConvGemm; epilogue order of gemm.hip) -------------------------------------------------------------
+LOG_CLAMP = np.float32(1e-5)
+
+
+def silu(x, dt=np.float64):
+    x = np.asarray(x, dt)
+    with np.errstate(over="ignore"):        # exp(-x) = inf for a very negative x: x / inf = -0, the limit
+        return x / (dt(1) + np.exp(-x))
+
+
+def gelu_erf(x, dt=np.float64):
+    import torch
+    x = np.asarray(x, dt)
+    return dt(0.5) * x * (dt(1) + torch.erf(torch.from_numpy(np.ascontiguousarray(x * dt(0.70710678118654752))).clone()).numpy())
+
+
+def conv_rows(A, B, T, Cin, taps=1, stride=1, dil=1, lda=None, a_off=0, a_bstride=None, extra_rows=0):
+    """the rows a conv-GEMM reads, gathered from the WHOLE flat array A: element (b, t, tap, k) = A[b a_bstride + a_off + (t stride + tap dil) lda + k]
+    -> [B, T, taps, Cin] (extra_rows: that many more rows behind the last tap, as further 'taps' at dilation 1 -- the ConvNeXt prologue's window)"""
+    lda = Cin if lda is None else lda
+    A = np.asarray(A).reshape(-1)
+    b = np.arange(B)[:, None, None, None] * a_bstride
+    t = np.arange(T)[None, :, None, None] * stride
+    tap = np.concatenate([np.arange(taps) * dil, (taps - 1) * dil + 1 + np.arange(extra_rows)])[None, None, :, None]
+    k = np.arange(Cin)[None, None, None, :]
+    return A[b + a_off + (t + tap) * lda + k]
+
+
+def conv_gemm(rows, W, bias=None, act=0, gamma=None, res=None, scale=1.0, c_in=None, a_silu=False, w13=False, rms_w=None, rms_eps=1e-5,
+              dw=None, dt=np.float64):
+    """rows [B, T, taps, Cin] (conv_rows), W [N, taps Cin] -> [B, T, N] (w13: [B, T, N / 2]):
+         v = sum_{tap, k} A'[b, t, tap, k] W[n, tap Cin + k],  A' = silu(A) | A rms_w rsqrt(mean_k A^2 + eps) (taps = 1) |
+             LayerNorm(dwconv7(x)) (dw = (wT [7, Cin], b, ln_w, ln_b, eps); rows then holds the 7 window rows of x)
+         then + bias, GELU (act 1) or log(max(v, 1e-5)) (act 2), * gamma, + res, * scale, + c_in (accumulate) -- in that order;
+         w13: W rows interleave 16 x w1 | 16 x w3, column 16 g + c = silu(v[32 g + c]) v[32 g + 16 + c], no other stage.
+    float32: sequential rank-1 updates over k = tap Cin + c ascending, float32 exp / erf, the log as log2(x) * float32(ln 2) (the fast intrinsic)"""
+    rows = np.asarray(rows, dt)
+    Bn, T, taps, Cin = rows.shape
+    if dw is not None:
+        wT, db, lw, lb, eps = dw
+        assert taps == 7
+        x = rows.reshape(Bn * T, 7, Cin)                                  # dwconv7_ln over each row's own window: [rows, 7, C] -> one output row
+        a = dwconv7_ln(x, wT, db, lw, lb, eps, dt)[:, 0].reshape(Bn, T, Cin)
+    else:
+        a = rows
+        if a_silu:
+            a = silu(a, dt)
+        if rms_w is not None:
+            assert taps == 1
+            a = rms_norm(a[:, :, 0], rms_w, rms_eps, dt)
+        a = a.reshape(Bn, T, -1)
+    v = _matmul(a, np.asarray(W, dt).T, dt)
+    if w13:
+        N = v.shape[-1]
+        g = v.reshape(Bn, T, N // 32, 2, 16)
+        return (silu(g[..., 0, :], dt) * g[..., 1, :]).reshape(Bn, T, N // 2)
+    if bias is not None:
+        v = v + np.asarray(bias, dt)
+    if act == 1:
+        v = gelu_erf(v, dt)
+    elif act == 2:
+        v = np.maximum(v, dt(LOG_CLAMP))
+        v = np.log2(v) * dt(np.float32(np.log(2.0))) if dt == np.float32 else np.log(v)
+    if gamma is not None:
+        v = v * np.asarray(gamma, dt)
+    if res is not None:
+        v = v + np.asarray(res, dt)
+    v = v * dt(np.float32(scale))
+    if c_in is not None:
+        v = v + np.asarray(c_in, dt)
+    return v.astype(dt)
+
+
 # ---- fp16 planes (csrc/planes_split.h) ---------------------------------------------------------------------------------------------
+def h3_split(x):
+    """(hi, lo) = (fp16(x), fp16(x - hi)) as float32 values -- csrc/planes_split.h h3_split"""
+    x = np.asarray(x, np.float32)
+    hi = round_f16(x)
+    return hi, round_f16(x - hi)
+
+
+def weight_planes(W, n_planes):
+    """the weights as make_weight_planes holds them: parts of W 2^e, e = 8 - exponent(max |W|) (max |W| 2^e in [2^7, 2^8)), times 2^-e;
+    -> (hi, lo) float64 arrays (lo = 0 for one plane)"""
+    W = np.asarray(W, np.float32)
+    mx = float(np.abs(W).max())
+    e = 8 - int(np.frexp(np.float32(mx))[1]) if mx > 0 else 0
+    hi, lo = h3_split(W * np.float32(2.0 ** e))
+    inv = 2.0 ** -e
+    return hi.astype(np.float64) * inv, (lo.astype(np.float64) * inv if n_planes == 2 else np.zeros(W.shape))
+
+
+def bf16_split3(x):
+    """(hi, mid, lo) bf16 parts of float32 x, each rounded to nearest even from the exact residual -- csrc/gemm_split.hip split2"""
+    def rne(v):
+        u = np.asarray(v, np.float32).view(np.uint32).astype(np.uint64)
+        u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+        return u.astype(np.uint32).view(np.float32)
+    x = np.ascontiguousarray(x, np.float32)
+    hi = rne(x)
+    r1 = (x - hi).astype(np.float32)
+    mid = rne(r1)
+    r2 = (r1 - mid).astype(np.float32)
+    return hi, mid, rne(r2)
+
+
 def planes_decode(planes, n_planes, rows, K, blocked):
     """planes uint16 [n_planes, rows * K] -> float32 [rows, K] = hi (+ lo).  blocked: element (row, k) at ((k / 32) * rows + row) * 32 + k % 32,
     else row-major"""

@@ -982,7 +982,9 @@ def test_stream_gemm_packed_weights_and_epilogues_vs_dispatcher():
     """gemm_stream.hip through its product form -- the fragment-major weight copy -- with every prologue / epilogue it serves (fused RMSNorm,
     SiLU on load, bias, GELU, gamma + residual, SwiGLU, conv taps over shifted rows), ragged rows / columns (N = 1000: a partial column tile),
     K from 2 blocks per wave to the looping form (K = 5376: more blocks per wave than its registers hold), every workgroup shape: against the
-    dispatcher's tuned choice on the same operands (itself pinned to fp64 above) within fp32 summation-order noise."""
+    dispatcher's tuned choice on the same operands within fp32 summation-order noise.  (The dispatcher's choice is pinned to fp64 in the dense
+    form above, and in these conv / prologue / epilogue forms by tests/test_gpu_conv_gemm.py, which also runs this kernel on packed weights
+    against float64 directly.)"""
     from streamvoiceanon_amd import engine as E
 
     cases = [(64, 1, 4608, 768, 1, 1, 8 | 16), (64, 1, 2304, 768, 1, 1, 16), (64, 1, 768, 2304, 1, 1, 2), (33, 1, 1000, 768, 1, 1, 16),

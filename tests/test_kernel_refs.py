@@ -253,3 +253,120 @@ def test_planes_decode_layouts():
     blk = np.stack([a.reshape(rows, K // 32, 32).transpose(1, 0, 2).reshape(-1) for a in (hi, lo)]).view(np.uint16)
     assert np.array_equal(R.planes_decode(blk, 2, rows, K, True), R.planes_decode(rm, 2, rows, K, False))
     assert np.array_equal(R.planes_decode(blk, 1, rows, K, True), hi.astype(np.float64))
+
+
+CONV_FORMS = [(3, 45, 64, 136, 3, 2, 1), (3, 45, 64, 136, 4, 1, 2), (2, 150, 32, 32, 7, 3, 1), (1, 37, 16, 160, 1, 1, 1)]      # B, T, Cin, N, taps, dil, stride
+
+
+@pytest.mark.parametrize("B,T,Cin,N,taps,dil,stride", CONV_FORMS)
+def test_conv_gemm_matches_torch_conv1d(B, T, Cin, N, taps, dil, stride):
+    """conv_gemm(float64) is torch's conv1d (float64) over the rows conv_rows gathers from a padded array -- taps, dilation, stride, a front pad,
+    a padded row stride and item stride -- and every epilogue stage applied in torch in the documented order"""
+    rng = np.random.default_rng(11 * taps + stride)
+    F = torch.nn.functional
+    lda, front, tail = Cin + 16, 2, 3
+    used = (T - 1) * stride + (taps - 1) * dil + 1
+    rows_b = front + used + tail
+    A = np.full((B, rows_b, lda), 1e4)
+    x = rng.standard_normal((B, used, Cin)) + 0.1 * np.arange(Cin) / Cin
+    A[:, front:front + used, :Cin] = x
+    W = rng.standard_normal((N, taps * Cin)) / np.sqrt(taps * Cin)
+    geo = dict(taps=taps, stride=stride, dil=dil, lda=lda, a_off=front * lda, a_bstride=rows_b * lda)
+    rows = R.conv_rows(A, B, T, Cin, **geo)
+    assert np.abs(rows).max() < 1e3          # no pad element was gathered
+    wt = torch.from_numpy(W.reshape(N, taps, Cin).transpose(0, 2, 1).copy())
+
+    def conv(inp):
+        return F.conv1d(torch.from_numpy(inp.transpose(0, 2, 1).copy()), wt, stride=stride, dilation=dil)[:, :, :T].transpose(1, 2)
+
+    bias, gamma = rng.standard_normal(N), rng.uniform(0.5, 1.5, N)
+    res, c_in = rng.standard_normal((B, T, N)), rng.standard_normal((B, T, N))
+    tb, tg, tr, tc = (torch.from_numpy(a) for a in (bias, gamma, res, c_in))
+    v = conv(x)
+    _close(R.conv_gemm(rows, W), v.numpy(), "conv")
+    _close(R.conv_gemm(rows, W, bias=bias), (v + tb).numpy(), "bias")
+    _close(R.conv_gemm(rows, W, bias=bias, act=1), F.gelu(v + tb).numpy(), "gelu")
+    _close(R.conv_gemm(rows, W, bias=bias, act=1, gamma=gamma, res=res), (F.gelu(v + tb) * tg + tr).numpy(), "gamma + res")
+    third = float(np.float32(1.0 / 3.0))
+    _close(R.conv_gemm(rows, W, bias=bias, gamma=gamma, res=res, scale=third, c_in=c_in), (((v + tb) * tg + tr) * third + tc).numpy(), "scale + accumulate")
+    _close(R.conv_gemm(rows, W, bias=bias, res=res, a_silu=True), (conv(F.silu(torch.from_numpy(x)).numpy()) + tb + tr).numpy(), "silu on load")
+    Wp = np.abs(W)
+    xp = np.abs(x)
+    for t in (0, 1):                         # every tap row of output rows 0 and 1 is zero
+        xp[:, t * stride + np.arange(taps) * dil] = 0.0
+    Ap = A.copy()
+    Ap[:, front:front + used, :Cin] = xp
+    vp = F.conv1d(torch.from_numpy(xp.transpose(0, 2, 1).copy()), torch.from_numpy(Wp.reshape(N, taps, Cin).transpose(0, 2, 1).copy()), stride=stride,
+                  dilation=dil)[:, :, :T].transpose(1, 2)
+    want = torch.log(torch.clamp(vp, min=float(R.LOG_CLAMP)))
+    got = R.conv_gemm(R.conv_rows(Ap, B, T, Cin, **geo), Wp, act=2)
+    _close(got, want.numpy(), "log-clamp")
+    assert (vp.numpy() < 1e-5).any()         # the clamp branch is taken
+    if N % 32 == 0:
+        g = v.reshape(B, T, N // 32, 2, 16)
+        _close(R.conv_gemm(rows, W, w13=True), (F.silu(g[..., 0, :]) * g[..., 1, :]).reshape(B, T, N // 2).numpy(), "w13")
+    if taps == 1:
+        rw = rng.uniform(0.5, 1.5, Cin)
+        xn = R.rms_norm(x[:, ::stride][:, :T], rw, 1e-5)                  # pinned to the oracle above
+        _close(R.conv_gemm(rows, W, bias=bias, rms_w=rw), (torch.from_numpy(xn) @ torch.from_numpy(W).T + tb).numpy(), "fused rmsnorm")
+    # the float32 restatement is the same formula
+    r64, r32 = R.conv_gemm(rows, W, bias=bias, act=1, gamma=gamma, res=res), R.conv_gemm(rows, W, bias=bias, act=1, gamma=gamma, res=res, dt=np.float32)
+    assert r32.dtype == np.float32 and np.abs(r64 - r32).max() <= 1e-5 * np.abs(r64).max()
+    l64, l32 = got, R.conv_gemm(R.conv_rows(Ap, B, T, Cin, **geo), Wp, act=2, dt=np.float32)
+    assert np.abs(l64 - l32).max() <= 1e-5 * np.abs(l64).max()
+
+
+def test_conv_gemm_convnext_prologue_matches_dwconv7_ln():
+    """dw = (...): the A rows are LayerNorm(dwconv7(x)) of the seven rows from the addressed one on -- dwconv7_ln (pinned above) on the same window"""
+    rng = np.random.default_rng(12)
+    B, T, C, N = 2, 7, 128, 136
+    x = rng.standard_normal((B, T + 6, C))
+    wT, db, lw, lb = rng.standard_normal((7, C)) * 0.4, rng.standard_normal(C), rng.uniform(0.5, 1.5, C), rng.standard_normal(C)
+    W, bias = rng.standard_normal((N, C)) / np.sqrt(C), rng.standard_normal(N)
+    rows = R.conv_rows(x, B, T, C, a_bstride=(T + 6) * C, extra_rows=6)
+    want = R.dwconv7_ln(x, wT, db, lw, lb, 1e-6) @ W.T + bias
+    _close(R.conv_gemm(rows, W, bias=bias, dw=(wT, db, lw, lb, 1e-6)), want, "ConvNeXt prologue")
+
+
+def test_operand_splits_restate_the_kernels():
+    """bf16 hi + mid + lo and fp16 hi + lo of float32 values: the parts are representable in their format and sum back to the value to the
+    documented precision (gemm_split.hip: exactly; planes_split.h: 2^-22 relative inside the fp16 range)"""
+    rng = np.random.default_rng(13)
+    x = (rng.standard_normal(4096) * np.exp(rng.uniform(-3, 3, 4096))).astype(np.float32)
+    hi, mid, lo = R.bf16_split3(x)
+    for p in (hi, mid, lo):
+        assert not (p.view(np.uint32) & 0xFFFF).any()
+    assert np.array_equal(hi.astype(np.float64) + mid + lo, x.astype(np.float64))
+    assert (np.abs(mid) <= np.abs(hi) * 2.0 ** -8).all() and (np.abs(lo) <= np.abs(hi) * 2.0 ** -16).all()
+    h, l = R.h3_split(x)
+    assert np.abs(h.astype(np.float64) + l - x).max() <= 2.0 ** -22 * np.abs(x).max()
+    W = rng.standard_normal((8, 64)).astype(np.float32) * 0.03
+    whi, wlo = R.weight_planes(W, 2)
+    assert np.abs(whi + wlo - W).max() <= 2.0 ** -21 * np.abs(W).max()
+    w1, z = R.weight_planes(W, 1)
+    assert not z.any() and np.abs(w1 - W).max() <= 2.0 ** -11 * np.abs(W).max()
+
+
+def test_conv_gemm_acceptance_table_matches_the_plan_check():
+    """The (family, form) pairs tests/conv_gemm_cases.py lists as refused by design are exactly the pairs for which the restated plan check
+    (csrc/gemm_dispatch.hip: plan_accepts) refuses EVERY plan of the family on the form's shape; each other pair has an accepted plan; and each of
+    the fp32 families takes every one of E0 .. E6 on P0 -- so no GPU case of test_gpu_conv_gemm.py is skipped silently."""
+    import conv_gemm_cases as G
+
+    fam_plans = {G.SMALLM: G.SKINNY + G.SKINNY_Z, G.TILED: G.TILED_PLANS, G.RING: G.RING_PLANS, G.SPLIT: G.SPLIT_PLANS, G.STREAM: G.STREAM_PLANS}
+    for form in G.FORMS:
+        P = G.case(G.shape_of(form), form).problem()
+        for fam, plans in fam_plans.items():
+            accepted = [p for p in plans if G.plan_accepts(p, P)]
+            assert bool(accepted) != ((fam, form) in G.REFUSED_BY_DESIGN), (G.FAMILY_NAME[fam], form, accepted[:3])
+            if form in ("E0", "E1", "E2", "E3", "E4", "E5", "E6"):
+                assert G.shape_of(form) == "P0" and accepted, (G.FAMILY_NAME[fam], form)
+    # plan-level refusals of an accepted pair: SwiGLU on single column tiles, the ConvNeXt prologue beyond one 16 x 16 tile
+    P5, P8 = G.case("P0", "E5").problem(), G.case("PD", "E8").problem()
+    assert not G.plan_accepts((G.SMALLM, 1, 4, 1, 1), P5) and G.plan_accepts((G.SMALLM, 1, 4, 2, 1), P5) and not G.plan_accepts((G.TILED, 3, 0, 0, 1), P5)
+    assert not G.plan_accepts((G.STREAM, 1, 4, 1, 1), P5) and G.plan_accepts((G.STREAM, 1, 4, 2, 1), P5)
+    assert [p for p in G.SKINNY if G.plan_accepts(p, P8)] == [(G.SMALLM, 1, 4, 1, 1), (G.SMALLM, 1, 8, 1, 1), (G.SMALLM, 1, 16, 1, 1)]
+    # E6: the reference has clamped elements, and no un-clamped pre-log value near 1 (where the log's absolute error is all relative error)
+    m = G.case("P0", "E6")
+    v = m.rows().astype(np.float64).reshape(m.B, m.T, -1) @ m.W.astype(np.float64).T
+    assert (v <= 1e-5).sum() == 2 * m.N and v[v > 1e-5].min() >= 2.0
