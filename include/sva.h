@@ -416,9 +416,47 @@ int sva_test_stft_ring(int device, int B, int N, const float* ring, const int* s
  * [G][gdim][4], bs [G][gdim]) */
 int sva_test_fsq(int device, int encode, int B, int T, int G, int gdim, float* lat, long l_len, long l_bstride, long l_off, int ld, const float* Wt,
                  const float* bs, int* codes, long c_len, long c_bstride, long c_gstride);
-/* launch_conv_post_tanh: x rows [T + k - 1][C] per item -> pcm [T] per item */
+/* launch_conv_post_tanh: x rows [T + k - 1][C] per item -> pcm [T] per item; slot_flag [B] (per-slot flag words, kSlotOutputMuted = 2) or NULL */
 int sva_test_conv_post(int device, int B, int T, int C, int k, const float* x, long x_len, long x_bstride, long x_off, const float* w, const float* bias,
-                       float* pcm, long p_len, long p_bstride, long p_off);
+                       float* pcm, long p_len, long p_bstride, long p_off, const int* slot_flag);
+
+/* The tail of the AR decode, kernel by kernel (tests/test_gpu_decode_tail.py).  Arguments: desc (integers), fpar (floats), ptrs (host arrays, NULL =
+ * absent), in the order listed.  Arrays marked in/out are uploaded first and downloaded whole, so a sentinel survives where nothing is written.
+ * Returns 0 ran, 1 REFUSED by the launcher's own check (nothing launched, sva_last_error has its message), -2 HIP error, -4 declined by the hook
+ * (an index outside an array).
+ *
+ * sva_test_sampler_launch: launch_sampler (small = 0) or launch_sampler_small (small = 1) with every argument, optionally after launch_logit_edits on
+ * the same device rows.
+ *   desc  0 small, 1 rows, 2 V, 3 ldl, 4 column offset of the rows in logits, 5 len(logits), 6 ldn, 7 offset of the rows in noise, 8 len(noise),
+ *         9 kind, 10 noise_elem_off, 11 tok_stride, 12 offset into tok_raw / tok, 13 len(tok_raw) = len(tok), 14 forced_stride, 15 offset into forced,
+ *         16 len(forced), 17 *use_forced (-1: NULL pointer), 18 rows of emb_table (>= V), 19 D, 20 ldo, 21 len(emb_out),
+ *         22 edits first (0 / 1), 23 W, 24 prev_cap, 25 len(prev), 26 n_suppress, 27 len(suppress)
+ *   fpar  temperature, top_p, repetition penalty
+ *   ptrs  0 logits (in/out), 1 noise or NULL (device RNG), 2 seed uint64 [rows], 3 frame int [rows], 4 tok_raw (in/out), 5 tok (in/out, small only),
+ *         6 forced, 7 emb_table, 8 emb_out (in/out), 9 prev, 10 suppress */
+int sva_test_sampler_launch(int device, const long long* desc, const float* fpar, void* const* ptrs);
+/* sva_test_ar_device: the device helpers of the persistent decode kernels (csrc/ar_device.h) in the instantiations their call sites use.
+ *   op 0  nucleus_sample: inst 0 <4,4> at 256 threads, 1 <4,32> at 256, 2 <8,16> at 512 (one workgroup per row), 3 <1,16> at 512 (one wave per row)
+ *     desc  0 inst, 1 rows, 2 V, 3 ldl, 4 len(logits), 5 ldn, 6 len(noise), 7 kind, 8 noise_elem_off;  fpar temperature, top_p
+ *     ptrs  0 logits, 1 noise or NULL, 2 seed, 3 frame, 4 tok int [rows] (out), 5 same int [rows] (out: every participating thread returned tok)
+ *   op 1  gemv<WT, K, ROWS, M, NORM>, one wave per group of ROWS weight rows: inst 0..9 = (768,6,2,norm) (768,2,2,-) (768,12,2,norm) (2304,2,2,-)
+ *         (768,11,1,norm) (768,6,1,norm) (768,2,1,-) (768,12,1,norm) (2304,2,1,-) (768,3,1,norm)
+ *     desc  0 inst, 1 WT = __half (weights rounded here), 2 groups, 3 index of the first weight row on the device (rows in front are allocated, never
+ *           read), 4 ldx, 5 len(x), 6 ldo, 7 len(out);  fpar eps
+ *     ptrs  0 W [groups ROWS][K], 1 x, 2 norm weight [K], 3 out [M][ldo] (in/out), 4 same int [groups] (out: all 64 lanes held the same values) */
+int sva_test_ar_device(int device, int op, const long long* desc, const float* fpar, void* const* ptrs);
+/* sva_test_gemv: launch_gemv modes 0 (plain) and 1 (SwiGLU over the w1 | w3 interleave); modes 3 / 4 with zero operands, to reach its refusals.
+ *   desc  0 M, 1 N, 2 K, 3 ldx, 4 len(X), 5 rows of W, 6 ldy, 7 column offset into Y, 8 len(Y), 9 ldr, 10 len(res), 11 mode, 12 res = Y (alias), 13 S, 14 H
+ *   fpar  eps;  ptrs  0 X, 1 W, 2 norm_w, 3 bias, 4 res, 5 Y (in/out) */
+int sva_test_gemv(int device, const long long* desc, const float* fpar, void* const* ptrs);
+/* sva_test_token_ops:
+ *   kind 0 launch_logit_edits  desc rows, V, ldl, len(logits), W, prev_cap, len(prev), n_suppress, len(suppress); fpar penalty; ptrs logits (in/out), prev, suppress
+ *   kind 1 launch_gather_rows  desc rows, D, ldo, len(out), table rows, len(idx), idx_stride, idx_offset; ptrs table, idx, out (in/out)
+ *   kind 2 launch_audio_embed  desc rows, D, ldo, len(out), table rows, len(codes), code_stride, cb_stride, ncb, codebook_size; ptrs table, codes, out (in/out)
+ *   kind 3 launch_shift_history  desc n_desc, B, col_slices, counter given, counter_add, len(buf), then (offset, bstride, H, T, C) per descriptor;
+ *          ptrs buf (in/out), counter int [1] (in/out)
+ *   kind 4 launch_ring_write   desc B, N, n, step given (0: NULL), step; ptrs ring [B][N] (in/out), chunk [B][n], slot_flag [B] or NULL */
+int sva_test_token_ops(int device, int kind, const long long* desc, const float* fpar, void* const* ptrs);
 
 /* host cost (microseconds) of enqueueing one kernel from the calling thread, measured over `iters` launches of a one-element
  * kernel into an idle stream.  A synchronous single-stream step is ~170 launches (a pipelined one: four graph launches + the persistent

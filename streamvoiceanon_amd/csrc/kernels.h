@@ -117,6 +117,7 @@ int launch_shift_history(const ShiftDesc* descs_dev, int n_desc, int B, hipStrea
 // small helpers
 int launch_fill_i32(int* p, int n, int v, hipStream_t st);
 int launch_add_i32(int* p, int v, hipStream_t st);
+// chunk [B][n] -> ring [B][N] at ((*step) * n) % N (step == nullptr -> 0), n <= N
 int launch_ring_write(float* ring, int* step, int B, int N, const float* chunk, int n, hipStream_t st, const int* slot_flag = nullptr);
 // per-slot flag word of a batch (sva_batch::d_slot_flag, [B], all zero by default): what launch_ring_write / launch_conv_post_tanh read
 constexpr int kSlotInputMuted = 1;      // retired slot: its chunk is written as zeros, the caller's memory is not read
@@ -134,7 +135,7 @@ struct Gemv {
     const float* bias = nullptr;
     const float* res = nullptr; int ldr = 0;
     float* Y = nullptr; int ldy = 0;
-    int mode = 0;                                         // 0 plain, 1 SwiGLU (w13 interleave), 2 q/k RoPE + KV write,
+    int mode = 0;                                         // 0 plain, 1 SwiGLU (w13 interleave: N = the 2 I interleaved rows, N % 32 == 0), 2 q/k RoPE + KV write,
                                                           // 3 X = decode attention of the qkv rows over <= 8 cached keys (fast AR)
                                                           // 4 X = merge of split-key attention partials, S = #splits (slow AR)
     const int* slot = nullptr; const int* pos = nullptr; const float* rope = nullptr;

@@ -20,7 +20,7 @@ __global__ void ring_write_kernel(float* ring, const int* step, int N, const flo
     const int b = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int start = (int)(((long)(*step) * n) % N);
+    const int start = (int)(((long)(step ? *step : 0) * n) % N);       // (step == nullptr -> 0, as the STFT reads the ring)
     int idx = start + i;
     if (idx >= N) idx -= N;
     const bool muted = slot_flag && (slot_flag[b] & kSlotInputMuted);
@@ -2217,6 +2217,8 @@ int launch_gemv(const Gemv& g, hipStream_t st) {
     SVA_CHECK(g.M >= 1 && g.M <= 4, "gemv: M must be 1..4");
     SVA_CHECK(g.K % 256 == 0 && g.ldx % 4 == 0, "gemv: K must be a multiple of 256");
     SVA_CHECK(g.N % 4 == 0, "gemv: N must be a multiple of 4");
+    // (SwiGLU: feature f reads rows (f >> 4) * 32 + (f & 15) and + 16 -- whole 32-row groups of the w1 | w3 interleave, or the last group reads past W)
+    SVA_CHECK(g.mode != 1 || g.N % 32 == 0, "gemv: SwiGLU needs N (the interleaved w1 | w3 rows) to be a multiple of 32");
     const int n_units = g.mode == 1 ? g.N / 4 : g.N / 2;
     dim3 grid((n_units + 3) / 4);
     const int ki = g.K / 256;

@@ -3,6 +3,7 @@
 #include "kernels.h"
 #include "engine.h"
 #include "stream_overlap.h"
+#include "ar_device.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -905,19 +906,427 @@ extern "C" int sva_test_fsq(int device, int encode, int B, int T, int G, int gdi
 
 // launch_conv_post_tanh: x element (b, r, c) at b * x_bstride + x_off + r * C + c (rows 0 .. T + k - 2), pcm (b, t) at b * p_bstride + p_off + t
 extern "C" int sva_test_conv_post(int device, int B, int T, int C, int k, const float* x, long x_len, long x_bstride, long x_off, const float* w, const float* bias,
-                                  float* pcm, long p_len, long p_bstride, long p_off) {
+                                  float* pcm, long p_len, long p_bstride, long p_off, const int* slot_flag) {
     SVA_HIP(hipSetDevice(device));
     SVA_CHECK(B >= 1 && T >= 1 && C >= 1 && k >= 1, "sva_test_conv_post: bad arguments");
     SVA_CHECK(x_bstride >= 0 && x_off >= 0 && (long)(B - 1) * x_bstride + x_off + (long)(T + k - 1) * C <= x_len, "sva_test_conv_post: input range outside x");
     SVA_CHECK(p_bstride >= 0 && p_off >= 0 && (long)(B - 1) * p_bstride + p_off + T <= p_len, "sva_test_conv_post: output range outside pcm");
-    DevBuf bx, bw, bb, bp;
+    DevBuf bx, bw, bb, bp, bf;
     SVA_TRY(bx.put(x, sizeof(float) * (size_t)x_len));
     SVA_TRY(bw.put(w, sizeof(float) * (size_t)k * C));
     SVA_TRY(bb.put(bias, sizeof(float)));
     SVA_TRY(bp.put(pcm, sizeof(float) * (size_t)p_len));
-    SVA_TRY(launch_conv_post_tanh(bx.as<float>(), x_bstride, x_off, B, T, C, k, bw.as<float>(), bb.as<float>(), bp.as<float>(), p_bstride, p_off, 0));
+    if (slot_flag) SVA_TRY(bf.put(slot_flag, sizeof(int) * B));
+    SVA_TRY(launch_conv_post_tanh(bx.as<float>(), x_bstride, x_off, B, T, C, k, bw.as<float>(), bb.as<float>(), bp.as<float>(), p_bstride, p_off, 0,
+                                  slot_flag ? bf.as<int>() : nullptr));
     SVA_HIP(hipDeviceSynchronize());
     SVA_TRY(bp.get(pcm, sizeof(float) * (size_t)p_len));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The tail of the AR decode (tests/test_gpu_decode_tail.py): the production samplers, the device helpers of the persistent kernels
+// (ar_device.h), launch_gemv in its plain and SwiGLU modes, the token and history kernels.  Same convention as above; arguments arrive
+// as desc (integers), fpar (floats) and ptrs (host arrays, NULL = absent) in the order include/sva.h lists.  Return codes: 0 ran,
+// 1 REFUSED by the launcher's own check (nothing was launched; sva_last_error has its message), -2 a HIP error, -4 arguments the hook
+// itself declines (an index outside an array).
+// ------------------------------------------------------------------------------------------------------------------------------------
+#define SVA_HOOK_CHECK(cond, msg)                                             \
+    do {                                                                      \
+        if (!(cond)) {                                                        \
+            set_error(std::string(msg) + " [" #cond "]");                    \
+            return -4;                                                        \
+        }                                                                     \
+    } while (0)
+
+// a launcher's SVA_CHECK (-1) is a refusal, anything else non-zero an error
+#define SVA_LAUNCH_OR_REFUSED(expr) \
+    do {                            \
+        const int _rc = (expr);     \
+        if (_rc == -1) return 1;    \
+        if (_rc) return _rc;        \
+    } while (0)
+
+namespace {
+struct EditArgs { int on, W, prev_cap, prev_len, n_sup, sup_len; };
+// the logit edits in front of a sampler, on the same device rows (stages.hip): every index checked, params = {W, n_suppress, penalty bits}
+int run_logit_edits(float* d_rows, int rows, int V, int ldl, const EditArgs& e, float penalty, const int* prev, const int* suppress, DevBuf& bprev, DevBuf& bsup,
+                    DevBuf& bpar, int* refused) {
+    SVA_HOOK_CHECK(e.prev_cap >= 0 && e.prev_len >= 0 && e.n_sup >= 0 && e.sup_len >= e.n_sup, "logit edits hook: list lengths");
+    SVA_HOOK_CHECK((long)std::min(std::max(e.W, 0), e.prev_cap) <= (long)e.prev_len, "logit edits hook: prev shorter than min(W, prev_cap)");
+    SVA_HOOK_CHECK((e.prev_len == 0 || prev) && (e.sup_len == 0 || suppress), "logit edits hook: list missing");
+    int pbits;
+    memcpy(&pbits, &penalty, 4);
+    const int params[4] = {e.W, e.n_sup, pbits, 0};
+    SVA_TRY(bprev.put(prev, sizeof(int) * (size_t)e.prev_len));
+    SVA_TRY(bsup.put(suppress, sizeof(int) * (size_t)e.sup_len));
+    SVA_TRY(bpar.put(params, sizeof(params)));
+    const int rc = launch_logit_edits(d_rows, rows, V, ldl, bprev.as<int>(), e.prev_cap, bsup.as<int>(), bpar.as<int>(), 0);
+    if (rc == -1) { *refused = 1; return 0; }
+    return rc;
+}
+}  // namespace
+
+extern "C" int sva_test_sampler_launch(int device, const long long* d, const float* fpar, void* const* ptrs) {
+    SVA_HIP(hipSetDevice(device));
+    const int small = (int)d[0], rows = (int)d[1], V = (int)d[2], ldl = (int)d[3], ldn = (int)d[6], kind = (int)d[9], noise_elem_off = (int)d[10];
+    const int tok_stride = (int)d[11], forced_stride = (int)d[14], use_forced = (int)d[17], emb_rows = (int)d[18], D = (int)d[19], ldo = (int)d[20];
+    const long col_off = d[4], l_len = d[5], noise_off = d[7], n_len = d[8], tok_off = d[12], t_len = d[13], forced_off = d[15], f_len = d[16], e_len = d[21];
+    const EditArgs ed = {(int)d[22], (int)d[23], (int)d[24], (int)d[25], (int)d[26], (int)d[27]};
+    float* logits = (float*)ptrs[0];
+    const float* noise = (const float*)ptrs[1];
+    const unsigned long long* seed = (const unsigned long long*)ptrs[2];
+    const int* frame = (const int*)ptrs[3];
+    int *tok_raw = (int*)ptrs[4], *tok = (int*)ptrs[5];
+    const int* forced = (const int*)ptrs[6];
+    const float* emb_table = (const float*)ptrs[7];
+    float* emb_out = (float*)ptrs[8];
+    SVA_HOOK_CHECK(rows >= 1 && V >= 1 && ldl >= V && col_off >= 0 && logits && col_off + (long)(rows - 1) * ldl + V <= l_len, "sampler hook: logits range");
+    SVA_HOOK_CHECK(!noise || (ldn >= 0 && noise_off >= 0 && noise_off + (long)(rows - 1) * ldn + V <= n_len), "sampler hook: noise range");
+    SVA_HOOK_CHECK(noise || (seed && frame && noise_elem_off >= 0), "sampler hook: seed / frame missing");
+    SVA_HOOK_CHECK(tok_raw && tok_stride >= 1 && tok_off >= 0 && tok_off + (long)(rows - 1) * tok_stride < t_len, "sampler hook: token range");
+    SVA_HOOK_CHECK(small || (!tok && !forced && !emb_table && !emb_out), "sampler hook: only the V <= 1024 entry point fuses forcing and the gather");
+    if (forced) {
+        SVA_HOOK_CHECK(tok && use_forced >= 0 && forced_stride >= 0 && forced_off >= 0 && forced_off + (long)(rows - 1) * forced_stride < f_len, "sampler hook: forced range");
+        for (long i = 0; i < f_len; ++i) SVA_HOOK_CHECK(!emb_table || (forced[i] >= 0 && forced[i] < emb_rows), "sampler hook: forced code outside the table");
+    }
+    if (emb_table) SVA_HOOK_CHECK(tok && emb_out && emb_rows >= V && D >= 1 && ldo >= D && (long)(rows - 1) * ldo + D <= e_len, "sampler hook: embedding range");
+    DevBuf bl, bn, bs, bf, btr, bt, bfo, buf, bet, beo, bprev, bsup, bpar;
+    SVA_TRY(btr.put(tok_raw, sizeof(int) * (size_t)t_len));
+    if (tok) SVA_TRY(bt.put(tok, sizeof(int) * (size_t)t_len));
+    if (emb_out) SVA_TRY(beo.put(emb_out, sizeof(float) * (size_t)e_len));          // (uploaded and handed over without a table too: nothing may be written then)
+    SVA_TRY(bl.put(logits, sizeof(float) * (size_t)l_len));
+    if (noise) SVA_TRY(bn.put(noise, sizeof(float) * (size_t)n_len));
+    if (seed) SVA_TRY(bs.put(seed, sizeof(unsigned long long) * rows));
+    if (frame) SVA_TRY(bf.put(frame, sizeof(int) * rows));
+    if (forced) SVA_TRY(bfo.put(forced, sizeof(int) * (size_t)f_len));
+    if (use_forced >= 0) SVA_TRY(buf.put(&use_forced, sizeof(int)));
+    if (emb_table) SVA_TRY(bet.put(emb_table, sizeof(float) * (size_t)emb_rows * D));
+    float* dl = bl.as<float>() + col_off;
+    int refused = 0;
+    if (ed.on) SVA_TRY(run_logit_edits(dl, rows, V, ldl, ed, fpar[2], (const int*)ptrs[9], (const int*)ptrs[10], bprev, bsup, bpar, &refused));
+    if (refused) return 1;
+    const float* dn = noise ? bn.as<float>() + noise_off : nullptr;
+    int rc;
+    if (small)
+        rc = launch_sampler_small(dl, rows, V, ldl, dn, ldn, seed ? bs.as<unsigned long long>() : nullptr, frame ? bf.as<int>() : nullptr, kind, noise_elem_off, fpar[0], fpar[1],
+                                  btr.as<int>() + tok_off, tok ? bt.as<int>() + tok_off : nullptr, tok_stride, forced ? bfo.as<int>() + forced_off : nullptr, forced_stride,
+                                  use_forced >= 0 ? buf.as<int>() : nullptr, emb_table ? bet.as<float>() : nullptr, D, emb_out ? beo.as<float>() : nullptr, ldo, 0);
+    else
+        rc = launch_sampler(dl, rows, V, ldl, dn, ldn, seed ? bs.as<unsigned long long>() : nullptr, frame ? bf.as<int>() : nullptr, kind, noise_elem_off, fpar[0], fpar[1],
+                            btr.as<int>() + tok_off, tok_stride, 0);
+    SVA_LAUNCH_OR_REFUSED(rc);
+    SVA_HIP(hipDeviceSynchronize());
+    SVA_TRY(bl.get(logits, sizeof(float) * (size_t)l_len));
+    SVA_TRY(btr.get(tok_raw, sizeof(int) * (size_t)t_len));
+    if (tok) SVA_TRY(bt.get(tok, sizeof(int) * (size_t)t_len));
+    if (emb_out) SVA_TRY(beo.get(emb_out, sizeof(float) * (size_t)e_len));
+    return 0;
+}
+
+// ---- ar_device.h: nucleus_sample and gemv exactly as ar_decode.hip / ar_batch.hip instantiate them ----
+namespace {
+// One workgroup per row (NW == 1: one WAVE per row, red = nullptr, as the fast head of ar_batch.hip).  PER == 16 (ar_batch.hip) loads through a clamped
+// index and selects, the others (ar_decode.hip) under the predicate.  tok[row] = thread 0's (lane 0's) return value, same[row] = 1 when every
+// participating thread returned it.
+template <int NW, int PER, int NTH>
+__global__ __launch_bounds__(NTH) void test_nucleus_kernel(const float* __restrict__ logits, int rows, int V, int ldl, const float* __restrict__ noise, int ldn,
+                                                           const unsigned long long* __restrict__ seed, const int* __restrict__ frame, int kind, int noise_elem_off,
+                                                           float inv_temp, float top_p, int* __restrict__ tok, int* __restrict__ same) {
+    __shared__ double red[64];
+    __shared__ int first_tok, mismatch;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int row = NW == 1 ? (int)blockIdx.x * (NTH / 64) + (tid >> 6) : (int)blockIdx.x;
+    const int e0 = NW == 1 ? lane : tid;
+    if (NW == 1 && row >= rows) return;             // (wave-uniform; the one-wave form has no barrier)
+    const float* lg = logits + (long)row * ldl;
+    float l[PER];
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+        const int e = e0 + NW * 64 * r;
+        if constexpr (PER == 16) {
+            const float v = lg[e < V ? e : V - 1];
+            l[r] = e < V ? v : -INFINITY;
+        } else {
+            l[r] = e < V ? lg[e] : -INFINITY;
+        }
+    }
+    const float* nz = noise ? noise + (long)row * ldn : nullptr;
+    const unsigned long long sd = seed ? seed[row] : 0ull;
+    const int fr = frame ? frame[row] : 0;
+    const int t = ardev::nucleus_sample<NW, PER>(l, V, e0, nz, sd, fr, kind, noise_elem_off, inv_temp, top_p, NW == 1 ? nullptr : red);
+    if constexpr (NW == 1) {
+        const int t0 = __builtin_amdgcn_readfirstlane(t);
+        const bool ok = __all(t == t0);
+        if (lane == 0) { tok[row] = t0; same[row] = ok ? 1 : 0; }
+    } else {
+        if (tid == 0) { first_tok = t; mismatch = 0; }
+        __syncthreads();
+        if (t != first_tok) atomicOr(&mismatch, 1);
+        __syncthreads();
+        if (tid == 0) { tok[row] = t; same[row] = mismatch ? 0 : 1; }
+    }
+}
+
+// One wave per group of ROWS consecutive weight rows (row0 + group * ROWS ...): out[m][group * ROWS + r] from lane 0, same[group] = 1 when all 64 lanes
+// hold bit-identical values.
+template <typename WT, int K, int ROWS, int M, bool NORM>
+__global__ __launch_bounds__(64) void test_ardev_gemv_kernel(const void* __restrict__ W, long row0, const float* __restrict__ x, int ldx, const float* __restrict__ nw,
+                                                             float eps, float* __restrict__ out, int ldo, int* __restrict__ same) {
+    const int lane = threadIdx.x;
+    ardev::WFrag<WT, K> w[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) w[r].load(W, row0 + (long)blockIdx.x * ROWS + r, lane);
+    float o[M][ROWS];
+    ardev::gemv<WT, K, ROWS, M, NORM>(w, x, ldx, nw, eps, lane, o);
+    bool ok = true;
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const int bits = __builtin_bit_cast(int, o[m][r]);
+            ok = ok && bits == __builtin_amdgcn_readfirstlane(bits);
+        }
+    ok = __all(ok);
+    if (lane == 0) {
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) out[(long)m * ldo + (long)blockIdx.x * ROWS + r] = o[m][r];
+        same[blockIdx.x] = ok ? 1 : 0;
+    }
+}
+
+struct ArdevGemvInst { int K, ROWS, M, norm; };
+// the ten instantiations of ar_decode.hip (M = 2 rows of a frame) and ar_batch.hip (M = 1)
+constexpr ArdevGemvInst kArdevGemv[10] = {{768, 6, 2, 1},  {768, 2, 2, 0}, {768, 12, 2, 1}, {2304, 2, 2, 0}, {768, 11, 1, 1},
+                                          {768, 6, 1, 1},  {768, 2, 1, 0}, {768, 12, 1, 1}, {2304, 2, 1, 0}, {768, 3, 1, 1}};
+template <int I>
+int launch_test_ardev_gemv(bool half, int groups, const void* W, long row0, const float* x, int ldx, const float* nw, float eps, float* out, int ldo, int* same) {
+    constexpr ArdevGemvInst c = kArdevGemv[I];
+    if (half) hipLaunchKernelGGL((test_ardev_gemv_kernel<__half, c.K, c.ROWS, c.M, c.norm != 0>), dim3(groups), dim3(64), 0, 0, W, row0, x, ldx, nw, eps, out, ldo, same);
+    else hipLaunchKernelGGL((test_ardev_gemv_kernel<float, c.K, c.ROWS, c.M, c.norm != 0>), dim3(groups), dim3(64), 0, 0, W, row0, x, ldx, nw, eps, out, ldo, same);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+extern "C" int sva_test_ar_device(int device, int op, const long long* d, const float* fpar, void* const* ptrs) {
+    SVA_HIP(hipSetDevice(device));
+    if (op == 0) {
+        const int inst = (int)d[0], rows = (int)d[1], V = (int)d[2], ldl = (int)d[3], ldn = (int)d[5], kind = (int)d[7], noise_elem_off = (int)d[8];
+        const long l_len = d[4], n_len = d[6];
+        const float* logits = (const float*)ptrs[0];
+        const float* noise = (const float*)ptrs[1];
+        const unsigned long long* seed = (const unsigned long long*)ptrs[2];
+        const int* frame = (const int*)ptrs[3];
+        int *tok = (int*)ptrs[4], *same = (int*)ptrs[5];
+        SVA_HOOK_CHECK(inst >= 0 && inst <= 3 && rows >= 1 && V >= 1 && V <= ((inst == 0 || inst == 3) ? 1024 : 8192), "ar_device sampler hook: instantiation / V");
+        SVA_HOOK_CHECK(logits && tok && same && ldl >= V && (long)(rows - 1) * ldl + V <= l_len, "ar_device sampler hook: logits range");
+        SVA_HOOK_CHECK(!noise || (ldn >= 0 && (long)(rows - 1) * ldn + V <= n_len), "ar_device sampler hook: noise range");
+        SVA_HOOK_CHECK(noise || (seed && frame && noise_elem_off >= 0), "ar_device sampler hook: seed / frame missing");
+        DevBuf bt, bsm, bl, bn, bs, bf;
+        SVA_TRY(bt.put(tok, sizeof(int) * rows));
+        SVA_TRY(bsm.put(same, sizeof(int) * rows));
+        SVA_TRY(bl.put(logits, sizeof(float) * (size_t)l_len));
+        if (noise) SVA_TRY(bn.put(noise, sizeof(float) * (size_t)n_len));
+        if (seed) SVA_TRY(bs.put(seed, sizeof(unsigned long long) * rows));
+        if (frame) SVA_TRY(bf.put(frame, sizeof(int) * rows));
+        const float tclamp = fpar[0] > 1e-5f ? fpar[0] : 1e-5f;
+#define SVA_NS_ARGS bl.as<float>(), rows, V, ldl, noise ? bn.as<float>() : nullptr, ldn, seed ? bs.as<unsigned long long>() : nullptr, frame ? bf.as<int>() : nullptr, \
+                    kind, noise_elem_off, 1.0f / tclamp, fpar[1], bt.as<int>(), bsm.as<int>()
+        if (inst == 0) hipLaunchKernelGGL((test_nucleus_kernel<4, 4, 256>), dim3(rows), dim3(256), 0, 0, SVA_NS_ARGS);
+        else if (inst == 1) hipLaunchKernelGGL((test_nucleus_kernel<4, 32, 256>), dim3(rows), dim3(256), 0, 0, SVA_NS_ARGS);
+        else if (inst == 2) hipLaunchKernelGGL((test_nucleus_kernel<8, 16, 512>), dim3(rows), dim3(512), 0, 0, SVA_NS_ARGS);
+        else hipLaunchKernelGGL((test_nucleus_kernel<1, 16, 512>), dim3((rows + 7) / 8), dim3(512), 0, 0, SVA_NS_ARGS);
+#undef SVA_NS_ARGS
+        SVA_HIP(hipGetLastError());
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(bt.get(tok, sizeof(int) * rows));
+        SVA_TRY(bsm.get(same, sizeof(int) * rows));
+        return 0;
+    }
+    SVA_HOOK_CHECK(op == 1, "ar_device hook: op 0 (nucleus_sample) or 1 (gemv)");
+    const int inst = (int)d[0], half = (int)d[1], groups = (int)d[2], ldx = (int)d[4], ldo = (int)d[6];
+    const long row0 = d[3], x_len = d[5], o_len = d[7];
+    SVA_HOOK_CHECK(inst >= 0 && inst < 10 && groups >= 1 && row0 >= 0, "ar_device gemv hook: instantiation / groups");
+    const ArdevGemvInst c = kArdevGemv[inst];
+    const float *W = (const float*)ptrs[0], *x = (const float*)ptrs[1], *nw = (const float*)ptrs[2];
+    float* out = (float*)ptrs[3];
+    int* same = (int*)ptrs[4];
+    const long n_rows = (long)groups * c.ROWS;
+    SVA_HOOK_CHECK(W && x && out && same && (!c.norm || nw), "ar_device gemv hook: array missing");
+    SVA_HOOK_CHECK(ldx >= c.K && ldx % 4 == 0 && (long)(c.M - 1) * ldx + c.K <= x_len, "ar_device gemv hook: x range (rows are read as float4)");
+    SVA_HOOK_CHECK(ldo >= n_rows && (long)(c.M - 1) * ldo + n_rows <= o_len, "ar_device gemv hook: out range");
+    // the weight array holds rows [0, row0 + n_rows); only the caller's rows [row0, ...) are uploaded, the ones in front are never read
+    const size_t esz = half ? 2 : 4, w_elems = (size_t)(row0 + n_rows) * c.K;
+    DevBuf bo, bsm, bw, bx, bnw;
+    SVA_TRY(bo.put(out, sizeof(float) * (size_t)o_len));
+    SVA_TRY(bsm.put(same, sizeof(int) * groups));
+    SVA_TRY(bw.alloc(w_elems * esz));
+    if (half) {
+        const std::vector<uint16_t> hb = to_half_bits(W, (size_t)n_rows * c.K);
+        SVA_HIP(hipMemcpy(bw.as<char>() + (size_t)row0 * c.K * esz, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
+    } else {
+        SVA_HIP(hipMemcpy(bw.as<char>() + (size_t)row0 * c.K * esz, W, (size_t)n_rows * c.K * 4, hipMemcpyHostToDevice));
+    }
+    SVA_TRY(bx.put(x, sizeof(float) * (size_t)x_len));
+    if (c.norm) SVA_TRY(bnw.put(nw, sizeof(float) * c.K));
+    const float* dnw = c.norm ? bnw.as<float>() : nullptr;
+    int rc = 0;
+    switch (inst) {
+#define SVA_AG(I_) case I_: rc = launch_test_ardev_gemv<I_>(half != 0, groups, bw.p, row0, bx.as<float>(), ldx, dnw, fpar[0], bo.as<float>(), ldo, bsm.as<int>()); break;
+        SVA_AG(0) SVA_AG(1) SVA_AG(2) SVA_AG(3) SVA_AG(4) SVA_AG(5) SVA_AG(6) SVA_AG(7) SVA_AG(8) SVA_AG(9)
+#undef SVA_AG
+    }
+    if (rc) return rc;
+    SVA_HIP(hipDeviceSynchronize());
+    SVA_TRY(bo.get(out, sizeof(float) * (size_t)o_len));
+    SVA_TRY(bsm.get(same, sizeof(int) * groups));
+    return 0;
+}
+
+// launch_gemv, modes 0 (plain) and 1 (SwiGLU), a whole Gemv from host arrays; modes 3 / 4 only to reach the launcher's refusals (operands of the
+// right size, all zero).  Only array lengths are checked here: what the launcher accepts is the launcher's business.
+extern "C" int sva_test_gemv(int device, const long long* d, const float* fpar, void* const* ptrs) {
+    SVA_HIP(hipSetDevice(device));
+    const int M = (int)d[0], N = (int)d[1], K = (int)d[2], ldx = (int)d[3], ldy = (int)d[6], ldr = (int)d[9], mode = (int)d[11], alias = (int)d[12], S = (int)d[13], H = (int)d[14];
+    const long x_len = d[4], w_rows = d[5], y_off = d[7], y_len = d[8], r_len = d[10];
+    const float *X = (const float*)ptrs[0], *W = (const float*)ptrs[1], *norm_w = (const float*)ptrs[2], *bias = (const float*)ptrs[3], *res = (const float*)ptrs[4];
+    float* Y = (float*)ptrs[5];
+    SVA_HOOK_CHECK(mode == 0 || mode == 1 || mode == 3 || mode == 4, "gemv hook: modes 0, 1 (and 3, 4 for their refusals)");
+    SVA_HOOK_CHECK(M >= 0 && M <= 64 && N >= 1 && K >= 1 && ldx >= 0 && ldy >= 0 && ldr >= 0 && y_off >= 0 && W && Y, "gemv hook: bad arguments");
+    const int Mr = M < 1 ? 1 : M;                                   // (the kernel reads row 0 in place of rows >= M)
+    const int n_units = mode == 1 ? N / 4 : N / 2, n_out = mode == 1 ? N / 2 : N;
+    long w_top = 0;                                                 // one past the highest weight row a wave reads
+    for (int u = 0; u < n_units; ++u)
+        for (int q = 0; q < 2; ++q) {
+            const int f = 2 * u + q;
+            w_top = std::max<long>(w_top, mode == 1 ? (long)(f >> 4) * 32 + (f & 15) + 16 + 1 : (long)f + 1);
+        }
+    SVA_HOOK_CHECK(w_top <= w_rows, "gemv hook: weight rows outside W");
+    SVA_HOOK_CHECK(y_off + (long)(Mr - 1) * ldy + n_out <= y_len, "gemv hook: output range outside Y");
+    SVA_HOOK_CHECK(!alias || (!res && ldr == ldy), "gemv hook: the aliased residual is Y itself");
+    SVA_HOOK_CHECK(!res || (long)(Mr - 1) * ldr + N <= r_len, "gemv hook: residual range outside res");
+    DevBuf by, bx, bw, bn, bb, br, bsl, bkv;
+    SVA_TRY(by.put(Y, sizeof(float) * (size_t)y_len));
+    SVA_TRY(bw.put(W, sizeof(float) * (size_t)w_rows * K));
+    if (norm_w) SVA_TRY(bn.put(norm_w, sizeof(float) * K));
+    if (bias) SVA_TRY(bb.put(bias, sizeof(float) * N));
+    if (res) SVA_TRY(br.put(res, sizeof(float) * (size_t)r_len));
+    Gemv g;
+    g.M = M; g.W = bw.as<float>(); g.N = N; g.K = K; g.norm_w = norm_w ? bn.as<float>() : nullptr; g.eps = fpar[0];
+    g.bias = bias ? bb.as<float>() : nullptr; g.Y = by.as<float>() + y_off; g.ldy = ldy; g.mode = mode; g.ldx = ldx;
+    if (alias) { g.res = g.Y; g.ldr = ldy; }
+    else if (res) { g.res = br.as<float>(); g.ldr = ldr; }
+    if (mode <= 1) {
+        SVA_HOOK_CHECK(X && (long)(Mr - 1) * ldx + K <= x_len, "gemv hook: input range outside X");
+        SVA_TRY(bx.put(X, sizeof(float) * (size_t)x_len));
+        g.X = bx.as<float>();
+    } else {
+        SVA_HOOK_CHECK(H == 12 && K == 768 && S >= 1 && S <= 64, "gemv hook: the attention modes are sized for K = 12 x 64");
+        std::vector<int> zi(Mr, 0);
+        SVA_TRY(bsl.put(zi.data(), sizeof(int) * Mr));
+        g.slot = bsl.as<int>(); g.pos = bsl.as<int>(); g.H = H; g.S = S;
+        if (mode == 3) {                                            // X = qkv rows [M][3 K], kv = one slot [2][H][S][64]
+            std::vector<float> z((size_t)std::max((long)Mr * 3 * K, (long)2 * H * S * 64), 0.f);
+            SVA_TRY(bx.put(z.data(), sizeof(float) * (size_t)Mr * 3 * K));
+            SVA_TRY(bkv.put(z.data(), sizeof(float) * (size_t)2 * H * S * 64));
+            g.X = bx.as<float>(); g.ldx = 3 * K; g.kv = bkv.as<float>(); g.kv_slot_stride = (long)2 * H * S * 64;
+        } else {                                                    // X = partials [M][H][S][68]
+            std::vector<float> z((size_t)Mr * H * S * 68, 0.f);
+            SVA_TRY(bx.put(z.data(), sizeof(float) * z.size()));
+            g.X = bx.as<float>(); g.ldx = 0;
+        }
+    }
+    SVA_LAUNCH_OR_REFUSED(launch_gemv(g, 0));
+    SVA_HIP(hipDeviceSynchronize());
+    SVA_TRY(by.get(Y, sizeof(float) * (size_t)y_len));
+    return 0;
+}
+
+// kind 0 launch_logit_edits, 1 launch_gather_rows, 2 launch_audio_embed, 3 launch_shift_history (descriptors built on the device), 4 launch_ring_write
+extern "C" int sva_test_token_ops(int device, int kind, const long long* d, const float* fpar, void* const* ptrs) {
+    SVA_HIP(hipSetDevice(device));
+    if (kind == 0) {
+        const int rows = (int)d[0], V = (int)d[1], ldl = (int)d[2];
+        const long l_len = d[3];
+        const EditArgs ed = {1, (int)d[4], (int)d[5], (int)d[6], (int)d[7], (int)d[8]};
+        float* logits = (float*)ptrs[0];
+        SVA_HOOK_CHECK(rows >= 1 && V >= 1 && ldl >= V && logits && (long)(rows - 1) * ldl + V <= l_len, "logit edits hook: logits range");
+        DevBuf bl, bprev, bsup, bpar;
+        SVA_TRY(bl.put(logits, sizeof(float) * (size_t)l_len));
+        int refused = 0;
+        SVA_TRY(run_logit_edits(bl.as<float>(), rows, V, ldl, ed, fpar[0], (const int*)ptrs[1], (const int*)ptrs[2], bprev, bsup, bpar, &refused));
+        if (refused) return 1;
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(bl.get(logits, sizeof(float) * (size_t)l_len));
+        return 0;
+    }
+    if (kind == 1 || kind == 2) {
+        // d: rows, D, ldo, o_len, t_rows, idx_len, (1) idx_stride, idx_offset | (2) code_stride, cb_stride, ncb, codebook_size
+        const int rows = (int)d[0], D = (int)d[1], ldo = (int)d[2], s0 = (int)d[6], s1 = (int)d[7], ncb = kind == 2 ? (int)d[8] : 1, cbs = kind == 2 ? (int)d[9] : 0;
+        const long o_len = d[3], t_rows = d[4], i_len = d[5];
+        const float* table = (const float*)ptrs[0];
+        const int* idx = (const int*)ptrs[1];
+        float* out = (float*)ptrs[2];
+        SVA_HOOK_CHECK(rows >= 1 && D >= 1 && ldo >= D && table && idx && out && (long)(rows - 1) * ldo + D <= o_len && ncb >= 1 && s0 >= 0 && cbs >= 0, "token ops hook: bad arguments");
+        for (int r = 0; r < rows; ++r)
+            for (int i = 0; i < ncb; ++i) {
+                const long at = kind == 1 ? (long)r * s0 : (long)r * s0 + (long)i * s1;
+                SVA_HOOK_CHECK(at >= 0 && at < i_len, "token ops hook: index position outside idx");
+                const long row = kind == 1 ? (long)idx[at] + s1 : (long)idx[at] + (long)i * cbs;
+                SVA_HOOK_CHECK(row >= 0 && row < t_rows, "token ops hook: table row outside the table");
+            }
+        DevBuf bo, bt, bi;
+        SVA_TRY(bo.put(out, sizeof(float) * (size_t)o_len));
+        SVA_TRY(bt.put(table, sizeof(float) * (size_t)t_rows * D));
+        SVA_TRY(bi.put(idx, sizeof(int) * (size_t)i_len));
+        if (kind == 1) SVA_LAUNCH_OR_REFUSED(launch_gather_rows(bt.as<float>(), bi.as<int>(), s0, s1, rows, D, bo.as<float>(), ldo, 0));
+        else SVA_LAUNCH_OR_REFUSED(launch_audio_embed(bt.as<float>(), bi.as<int>(), s0, s1, rows, ncb, cbs, D, bo.as<float>(), ldo, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(bo.get(out, sizeof(float) * (size_t)o_len));
+        return 0;
+    }
+    if (kind == 3) {
+        // d: n_desc, B, col_slices, has_counter, counter_add, buf_len, then per descriptor: offset, bstride, H, T, C
+        const int n_desc = (int)d[0], B = (int)d[1], zs = (int)d[2], has_counter = (int)d[3], counter_add = (int)d[4];
+        const long b_len = d[5];
+        float* buf = (float*)ptrs[0];
+        int* counter = (int*)ptrs[1];
+        SVA_HOOK_CHECK(n_desc >= 0 && n_desc <= 64 && B >= 1 && B <= 65535 && zs >= 1 && zs <= 64 && buf && (!has_counter || counter), "shift_history hook: bad arguments");
+        DevBuf bb, bc, bd;
+        SVA_TRY(bb.put(buf, sizeof(float) * (size_t)b_len));
+        if (has_counter) SVA_TRY(bc.put(counter, sizeof(int)));
+        std::vector<ShiftDesc> hd(n_desc);
+        for (int i = 0; i < n_desc; ++i) {
+            const long off = d[6 + 5 * i], bs = d[7 + 5 * i], Hh = d[8 + 5 * i], T = d[9 + 5 * i], Cc = d[10 + 5 * i];
+            SVA_HOOK_CHECK(off >= 0 && bs >= 0 && Hh >= 0 && T >= 0 && Cc >= 1 && Hh < (1 << 20) && T < (1 << 20) && Cc < (1 << 20) &&
+                           off + (long)(B - 1) * bs + (Hh + T) * Cc <= b_len, "shift_history hook: tensor outside the buffer");
+            hd[i].ptr = bb.as<float>() + off; hd[i].bstride = bs; hd[i].H = (int)Hh; hd[i].T = (int)T; hd[i].C = (int)Cc; hd[i].pad = 0;
+        }
+        SVA_TRY(bd.put(hd.data(), sizeof(ShiftDesc) * (size_t)n_desc));
+        SVA_LAUNCH_OR_REFUSED(launch_shift_history(bd.as<ShiftDesc>(), n_desc, B, 0, zs, has_counter ? bc.as<int>() : nullptr, counter_add));
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(bb.get(buf, sizeof(float) * (size_t)b_len));
+        if (has_counter) SVA_TRY(bc.get(counter, sizeof(int)));
+        return 0;
+    }
+    SVA_HOOK_CHECK(kind == 4, "token ops hook: kind 0 .. 4");
+    // d: B, N, n, has_step, step; ptrs: ring [B][N] (in / out), chunk [B][n], slot_flag [B] or NULL
+    const int B = (int)d[0], N = (int)d[1], n = (int)d[2], has_step = (int)d[3], step = (int)d[4];
+    float* ring = (float*)ptrs[0];
+    const float* chunk = (const float*)ptrs[1];
+    const int* flag = (const int*)ptrs[2];
+    SVA_HOOK_CHECK(B >= 1 && N >= 1 && n >= 1 && n <= N && step >= 0 && ring && chunk, "ring_write hook: bad arguments (n <= N, step >= 0)");
+    DevBuf br, bc, bs, bf;
+    SVA_TRY(br.put(ring, sizeof(float) * (size_t)B * N));
+    SVA_TRY(bc.put(chunk, sizeof(float) * (size_t)B * n));
+    if (has_step) SVA_TRY(bs.put(&step, sizeof(int)));
+    if (flag) SVA_TRY(bf.put(flag, sizeof(int) * B));
+    SVA_LAUNCH_OR_REFUSED(launch_ring_write(br.as<float>(), has_step ? bs.as<int>() : nullptr, B, N, bc.as<float>(), n, 0, flag ? bf.as<int>() : nullptr));
+    SVA_HIP(hipDeviceSynchronize());
+    SVA_TRY(br.get(ring, sizeof(float) * (size_t)B * N));
     return 0;
 }
 

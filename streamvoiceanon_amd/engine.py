@@ -126,7 +126,11 @@ def load_library():
     lib.sva_test_bsq.argtypes = [i32] * 4 + [vp, i64, i64, i64, i32, vp, C.c_float, vp, vp, vp, i32, vp, i64, i32, i32, vp]
     lib.sva_test_stft_ring.argtypes = [i32] * 3 + [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32]
     lib.sva_test_fsq.argtypes = [i32] * 6 + [vp, i64, i64, i64, i32, vp, vp, vp, i64, i64, i64]
-    lib.sva_test_conv_post.argtypes = [i32] * 5 + [vp, i64, i64, i64, vp, vp, vp, i64, i64, i64]
+    lib.sva_test_conv_post.argtypes = [i32] * 5 + [vp, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp]
+    lib.sva_test_sampler_launch.argtypes = [i32, vp, vp, vp]
+    lib.sva_test_ar_device.argtypes = [i32, i32, vp, vp, vp]
+    lib.sva_test_gemv.argtypes = [i32, vp, vp, vp]
+    lib.sva_test_token_ops.argtypes = [i32, i32, vp, vp, vp]
     lib.sva_test_gemm_f16w.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp]
     lib.sva_test_gemm_planes.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.sva_test_gemm_h16.argtypes = [i32] * 8 + [vp] * 5 + [i32] * 4 + [vp, i32, vp]
@@ -144,7 +148,7 @@ EXPORTED_SYMBOLS = [
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
     "sva_op_geglu", "sva_op_l2norm", "sva_ops_capture_begin", "sva_ops_capture_end", "sva_ops_graph_launch", "sva_ops_graph_free",
-    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
+    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_test_sampler_launch", "sva_test_ar_device", "sva_test_gemv", "sva_test_token_ops", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
 ]
 
 
@@ -728,13 +732,158 @@ def test_fsq(encode, lat, codes, B, T, G, gdim, Wt, bs, l_bstride, l_off, ld, c_
     return lat, codes
 
 
-def test_conv_post(x, pcm, B, T, Cc, k, w, bias, x_bstride, x_off, p_bstride, p_off, device=0):
+def test_conv_post(x, pcm, B, T, Cc, k, w, bias, x_bstride, x_off, p_bstride, p_off, slot_flag=None, device=0):
     lib = load_library()
     x, w, bias = _f32(x).reshape(-1), _f32(w), _f32(bias)
     assert pcm.dtype == np.float32 and pcm.flags.c_contiguous
+    flag = None if slot_flag is None else np.ascontiguousarray(slot_flag, dtype=np.int32)
+    assert flag is None or flag.shape == (B,)
     _check(lib.sva_test_conv_post(device, B, T, Cc, k, _ptr(x), x.size, int(x_bstride), int(x_off), _ptr(w), _ptr(bias), _ptr(pcm), pcm.size, int(p_bstride),
-                                  int(p_off)), "sva_test_conv_post")
+                                  int(p_off), _ptr(flag)), "sva_test_conv_post")
     return pcm
+
+
+# ---- the tail of the AR decode (include/sva.h; tests/test_gpu_decode_tail.py) ----
+class Refused(RuntimeError):
+    """a launcher's own check declined the problem before any launch"""
+
+
+def _hook_call(fn, what, desc, fpar, arrays, *lead):
+    """desc / fpar / ptrs convention of the decode-tail hooks; rc 1 (the launcher refused) raises Refused with the launcher's message"""
+    d = np.array([int(v) for v in desc], np.int64)
+    f = np.array([float(v) for v in fpar] + [0.0], np.float32)
+    ptrs = (C.c_void_p * max(len(arrays), 1))()
+    for i, a in enumerate(arrays):
+        assert a is None or (isinstance(a, np.ndarray) and a.flags.c_contiguous), (what, i)
+        ptrs[i] = None if a is None else a.ctypes.data
+    rc = fn(*lead, _ptr(d), _ptr(f), ptrs)
+    if rc == 1:
+        raise Refused(load_library().sva_last_error().decode("utf-8", "replace"))
+    _check(rc, what)
+
+
+def _i32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+
+
+def test_sampler_launch(logits, rows, V, ldl, col_off=0, small=False, noise=None, ldn=0, noise_off=0, seed=None, frame=None, kind=0, noise_elem_off=0,
+                        temperature=0.7, top_p=0.7, tok_raw=None, tok=None, tok_stride=1, tok_off=0, forced=None, forced_stride=0, forced_off=0,
+                        use_forced=None, emb_table=None, emb_out=None, ldo=0, edits=None, device=0):
+    """launch_sampler / launch_sampler_small (small) over the flat float32 array `logits` (rows at col_off + r ldl; edited in place when
+    edits = dict(prev, prev_cap, W, suppress, penalty) is given: launch_logit_edits runs first on the same device rows).  noise: flat array or None
+    (device RNG from seed [rows] uint64, frame [rows]).  tok_raw / tok (int32, flat) and emb_out (float32, flat) are updated in place."""
+    lib = load_library()
+    assert logits.dtype == np.float32 and logits.ndim == 1 and tok_raw.dtype == np.int32
+    noise, emb_table = _f32(noise), _f32(emb_table)
+    seed = None if seed is None else np.ascontiguousarray(seed, dtype=np.uint64)
+    frame, forced = _i32(frame), _i32(forced)
+    assert tok is None or (tok.dtype == np.int32 and tok.size == tok_raw.size)
+    assert emb_out is None or emb_out.dtype == np.float32
+    e = edits or {}
+    prev, sup = _i32(e.get("prev", [])), _i32(e.get("suppress", []))
+    desc = [int(bool(small)), rows, V, ldl, col_off, logits.size, ldn, noise_off, 0 if noise is None else noise.size, kind, noise_elem_off, tok_stride, tok_off,
+            tok_raw.size, forced_stride, forced_off, 0 if forced is None else forced.size, -1 if use_forced is None else int(use_forced),
+            0 if emb_table is None else emb_table.shape[0], 0 if emb_table is None else emb_table.shape[1], ldo, 0 if emb_out is None else emb_out.size,
+            int(edits is not None), e.get("W", prev.size), e.get("prev_cap", 4096), prev.size, e.get("n_suppress", sup.size), sup.size]
+    _hook_call(lib.sva_test_sampler_launch, "sva_test_sampler_launch", desc, [temperature, top_p, e.get("penalty", 1.5)],
+               [logits, noise, seed, frame, tok_raw, tok, forced, emb_table, emb_out, prev if prev.size else None, sup if sup.size else None], device)
+    return tok_raw
+
+
+AR_NUCLEUS_INSTS = {0: (4, 4, 1024), 1: (4, 32, 8192), 2: (8, 16, 8192), 3: (1, 16, 1024)}        # inst -> (NW, PER, largest V)
+
+
+def test_ar_nucleus(inst, logits, noise=None, seed=None, frame=None, kind=0, noise_elem_off=0, temperature=0.7, top_p=0.7, device=0):
+    """ardev::nucleus_sample in one of its four instantiations over logits [rows, V] (noise [rows, V] or None: device RNG) ->
+    (tokens [rows], every participating thread returned the token [rows] bool)"""
+    lib = load_library()
+    L, Q = _f32(logits), _f32(noise)
+    rows, V = L.shape
+    assert Q is None or Q.shape == L.shape
+    seed = None if seed is None else np.ascontiguousarray(seed, dtype=np.uint64)
+    tok, same = np.full(rows, -1, np.int32), np.full(rows, -1, np.int32)
+    _hook_call(lib.sva_test_ar_device, "sva_test_ar_device", [inst, rows, V, V, L.size, V, 0 if Q is None else Q.size, kind, noise_elem_off], [temperature, top_p],
+               [L.reshape(-1), None if Q is None else Q.reshape(-1), seed, _i32(frame), tok, same], device, 0)
+    return tok, same == 1
+
+
+AR_GEMV_INSTS = [(768, 6, 2, True), (768, 2, 2, False), (768, 12, 2, True), (2304, 2, 2, False), (768, 11, 1, True),
+                 (768, 6, 1, True), (768, 2, 1, False), (768, 12, 1, True), (2304, 2, 1, False), (768, 3, 1, True)]      # (K, ROWS, M, NORM)
+
+
+def test_ar_gemv(inst, W, x, norm_w=None, eps=1e-5, half=False, row0=0, ldo=None, fill=0.0, device=0):
+    """ardev::gemv<WT, K, ROWS, M, NORM> of instantiation `inst` over W [groups ROWS, K] (rounded to fp16 when half; placed at row `row0` of the device
+    array), x [M, ldx] -> (out [M, ldo] pre-filled with `fill`, all 64 lanes agreed [groups] bool)"""
+    lib = load_library()
+    K, ROWS, M, norm = AR_GEMV_INSTS[inst]
+    W, x, norm_w = _f32(W), _f32(x), _f32(norm_w)
+    assert W.shape[1] == K and W.shape[0] % ROWS == 0 and x.shape[0] == M
+    groups = W.shape[0] // ROWS
+    ldo = W.shape[0] if ldo is None else ldo
+    out, same = np.full((M, ldo), fill, np.float32), np.full(groups, -1, np.int32)
+    _hook_call(lib.sva_test_ar_device, "sva_test_ar_device", [inst, int(bool(half)), groups, row0, x.shape[1], x.size, ldo, out.size], [eps],
+               [W, x, norm_w, out, same], device, 1)
+    return out, same == 1
+
+
+def test_gemv(W, Y, M, N, K, X=None, ldx=None, ldy=None, y_off=0, norm_w=None, bias=None, res=None, ldr=0, alias=False, mode=0, eps=1e-5, S=0, H=0, device=0):
+    """launch_gemv (modes 0, 1; 3 / 4 with zero operands) over W [rows, K], X flat / [M, ldx], Y flat float32 (updated in place); raises Refused when
+    launch_gemv declines"""
+    lib = load_library()
+    W, X, norm_w, bias, res = _f32(W), _f32(X), _f32(norm_w), _f32(bias), _f32(res)
+    assert Y.dtype == np.float32 and Y.flags.c_contiguous
+    desc = [M, N, K, K if ldx is None else ldx, 0 if X is None else X.size, W.shape[0], N if ldy is None else ldy, y_off, Y.size, ldr, 0 if res is None else res.size,
+            mode, int(bool(alias)), S, H]
+    _hook_call(lib.sva_test_gemv, "sva_test_gemv", desc, [eps], [X, W, norm_w, bias, res, Y], device)
+    return Y
+
+
+def test_logit_edits(logits, rows, V, ldl, prev, suppress, penalty, W=None, prev_cap=4096, device=0):
+    """launch_logit_edits in place on the flat float32 array logits"""
+    lib = load_library()
+    assert logits.dtype == np.float32 and logits.ndim == 1
+    prev, sup = _i32(prev), _i32(suppress)
+    _hook_call(lib.sva_test_token_ops, "sva_test_token_ops", [rows, V, ldl, logits.size, prev.size if W is None else W, prev_cap, prev.size, sup.size, sup.size], [penalty],
+               [logits, prev if prev.size else None, sup if sup.size else None], device, 0)
+    return logits
+
+
+def test_gather_rows(table, idx, idx_stride, idx_offset, rows, out, ldo, device=0):
+    lib = load_library()
+    table, idx = _f32(table), _i32(idx)
+    assert out.dtype == np.float32 and out.ndim == 1
+    _hook_call(lib.sva_test_token_ops, "sva_test_token_ops", [rows, table.shape[1], ldo, out.size, table.shape[0], idx.size, idx_stride, idx_offset], [],
+               [table, idx, out], device, 1)
+    return out
+
+
+def test_audio_embed(table, codes, code_stride, cb_stride, rows, ncb, codebook_size, out, ldo, device=0):
+    lib = load_library()
+    table, codes = _f32(table), _i32(codes)
+    assert out.dtype == np.float32 and out.ndim == 1
+    _hook_call(lib.sva_test_token_ops, "sva_test_token_ops",
+               [rows, table.shape[1], ldo, out.size, table.shape[0], codes.size, code_stride, cb_stride, ncb, codebook_size], [], [table, codes, out], device, 2)
+    return out
+
+
+def test_shift_history(buf, descs, B, col_slices=1, counter=None, counter_add=0, device=0):
+    """launch_shift_history over the flat float32 array buf (in place); descs = [(offset, bstride, H, T, C), ...] -> the counter after the launch"""
+    lib = load_library()
+    assert buf.dtype == np.float32 and buf.ndim == 1
+    cnt = None if counter is None else np.array([counter], np.int32)
+    desc = [len(descs), B, col_slices, int(counter is not None), counter_add, buf.size] + [v for dsc in descs for v in dsc]
+    _hook_call(lib.sva_test_token_ops, "sva_test_token_ops", desc, [], [buf, cnt], device, 3)
+    return None if cnt is None else int(cnt[0])
+
+
+def test_ring_write(ring, chunk, step=None, slot_flag=None, device=0):
+    """launch_ring_write: chunk [B, n] into ring [B, N] (in place) at (step n) % N; step None -> the launcher's nullptr"""
+    lib = load_library()
+    chunk = np.ascontiguousarray(chunk, dtype=np.float32)
+    assert ring.dtype == np.float32 and ring.flags.c_contiguous and ring.shape[0] == chunk.shape[0]
+    _hook_call(lib.sva_test_token_ops, "sva_test_token_ops", [ring.shape[0], ring.shape[1], chunk.shape[1], int(step is not None), 0 if step is None else step], [],
+               [ring, chunk, _i32(slot_flag)], device, 4)
+    return ring
 
 
 def test_gemm_choice(A, W, choice, bias=None, device=0):

@@ -352,3 +352,109 @@ def planes_decode(planes, n_planes, rows, K, blocked):
         f = np.asarray(planes[p], np.uint16).view(np.float16).astype(np.float64)
         out += f.reshape(K // 32, rows, 32).transpose(1, 0, 2).reshape(rows, K) if blocked else f.reshape(rows, K)
     return out
+
+
+# ---- the tail of the AR decode: sampler, decode GEMV, token and history kernels (csrc/kernels.h, csrc/ar_device.h) ------------------------
+def nucleus_token(logits, noise, temperature, top_p):
+    """logits_to_probs + multinomial_sample_one_no_sync in float64: softmax; order by descending p, smaller id first; inclusive cumulative sum;
+    entries with cum > top_p removed, rank 0 kept; softmax at max(temperature, 1e-5); argmax of p / noise, ties to the smaller id.
+    -> (token, decidable, lead).  A row is DECIDABLE when float32 rounding inside a kernel cannot change its winner:
+      - the winner is the same with top_p moved by a relative 2e-6 either way (the float32 softmax and its cumulative sum against the threshold),
+      - and with the cut moved by one id either way when it falls inside a class of tied probabilities (n p by repeated addition),
+      - and the winning ratio leads the runner-up of the kept set by more than 1e-4 relative (lead = best / second; float32 exp and divide)."""
+    l, q = np.asarray(logits, np.float64), np.asarray(noise, np.float64)
+    V = l.size
+    with np.errstate(under="ignore"):
+        p = np.exp(l - l.max())
+        p = p / p.sum()
+        score = np.exp((l - l.max()) / max(float(temperature), 1e-5)) / q          # the temperature softmax up to its (positive) normaliser
+    order = np.lexsort((np.arange(V), -p))
+    ps = p[order]
+    cum = np.cumsum(ps)
+
+    def n_kept(tp):
+        return max(int(np.searchsorted(cum, tp, side="right")), 1)              # entries with cum <= tp; rank 0 always
+
+    def winner(n):
+        ids = order[:n]
+        s = score[ids]
+        return int(ids[s == s.max()].min())
+
+    tp = float(np.float32(top_p))                                               # the launchers take a float
+    n = n_kept(tp)
+    tok = winner(n)
+    trials = [n_kept(tp * (1 + 2e-6)), n_kept(tp * (1 - 2e-6))]
+    if n < V and ps[n] == ps[n - 1]:
+        trials += [n + 1] + ([n - 1] if n >= 2 else [])
+    s = np.sort(score[order[:n]])
+    lead = float("inf") if n == 1 or s[-2] == 0 else float(s[-1] / s[-2])
+    return tok, all(winner(k) == tok for k in trials) and lead > 1 + 1e-4, lead
+
+
+def swiglu_rows(n_feat):
+    """weight rows (w1, w3) of SwiGLU feature f in the 16-row interleave Packer::w13 writes (csrc/packer.hip): group g of 32 rows = w1 rows
+    16 g .. 16 g + 15, then w3 rows 16 g .. 16 g + 15"""
+    f = np.arange(n_feat)
+    r1 = (f >> 4) * 32 + (f & 15)
+    return r1, r1 + 16
+
+
+def pack_w13(w1, w3):
+    """[2 I, D] as Packer::w13 interleaves w1 [I, D] and w3 [I, D] (I % 16 == 0)"""
+    I, Dm = w1.shape
+    return np.stack([np.asarray(w1).reshape(I // 16, 16, Dm), np.asarray(w3).reshape(I // 16, 16, Dm)], 1).reshape(2 * I, Dm)
+
+
+def gemv_ref(x, W, norm_w=None, eps=1e-5, bias=None, res=None, swiglu=False, half=False, dt=np.float64):
+    """the decode GEMV (launch_gemv modes 0 / 1, ardev::gemv): y = (RMSNorm(x) norm_w | x) W^T, then + bias + res, or -- swiglu, W = pack_w13 --
+    silu(y[w1 row f]) y[w3 row f] per feature f.  half: the weights as the fp16 fragments hold them."""
+    W = round_f16(W) if half else W
+    a = rms_norm(x, norm_w, eps, dt) if norm_w is not None else np.asarray(x, dt)
+    v = _matmul(a, np.asarray(W, dt).T, dt)
+    if swiglu:
+        r1, r3 = swiglu_rows(v.shape[-1] // 2)
+        return silu(v[..., r1], dt) * v[..., r3]
+    if bias is not None:
+        v = v + np.asarray(bias, dt)
+    if res is not None:
+        v = v + np.asarray(res, dt)
+    return v
+
+
+def logit_edits(row, prev, suppress, penalty, W=None, prev_cap=4096):
+    """launch_logit_edits on one float32 row, in float32 (one multiply or one divide per listed token, from the ORIGINAL score, each token once):
+    prev[: min(W, prev_cap)] with negative and >= V entries skipped: s < 0 ? s * penalty : s / penalty; then suppress ids in [0, V) -> -inf"""
+    row = np.array(row, np.float32)
+    V = row.size
+    prev = np.asarray(prev, np.int64).reshape(-1)
+    ids = prev[:max(min(len(prev) if W is None else W, prev_cap), 0)]
+    ids = np.unique(ids[(ids >= 0) & (ids < V)])
+    sc = row[ids].copy()
+    with np.errstate(over="ignore"):
+        row[ids] = np.where(sc < 0, sc * np.float32(penalty), sc / np.float32(penalty))
+    sup = np.asarray(suppress, np.int64).reshape(-1)
+    row[sup[(sup >= 0) & (sup < V)]] = -np.inf
+    return row
+
+
+def audio_embed(table, codes, codebook_size):
+    """codes [rows, ncb] -> float32 sum over codebooks of table[code_i + i codebook_size], added in codebook order from 0"""
+    acc = np.zeros((codes.shape[0], table.shape[1]), np.float32)
+    for i in range(codes.shape[1]):
+        acc = acc + np.asarray(table, np.float32)[np.asarray(codes)[:, i] + i * codebook_size]
+    return acc
+
+
+def shift_history(x, H, T):
+    """x [..., >= H + T rows, C]: rows [T, T + H) move to [0, H), everything else stays"""
+    out = np.array(x)
+    out[..., :H, :] = x[..., T:T + H, :]
+    return out
+
+
+def ring_write(ring, chunk, step):
+    """chunk [B, n] into ring [B, N] at ((step n) % N + i) % N"""
+    out = np.array(ring)
+    n, N = chunk.shape[1], ring.shape[1]
+    out[:, (step * n + np.arange(n)) % N] = chunk
+    return out

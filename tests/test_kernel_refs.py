@@ -370,3 +370,115 @@ def test_conv_gemm_acceptance_table_matches_the_plan_check():
     m = G.case("P0", "E6")
     v = m.rows().astype(np.float64).reshape(m.B, m.T, -1) @ m.W.astype(np.float64).T
     assert (v <= 1e-5).sum() == 2 * m.N and v[v > 1e-5].min() >= 2.0
+
+
+# ---- the tail of the AR decode --------------------------------------------------------------------------------------------------------
+def test_every_gpu_sampler_row_is_decidable():
+    """The GPU sampler tests compare tokens exactly.  That is sound only where float32 rounding inside a kernel cannot change the winner:
+    kernel_refs.nucleus_token's decidability rule, asserted here over every row of every generator and seed those tests use
+    (decode_tail_cases.all_sampler_cases).  A condition on the inputs, not a tolerance: no row is left out."""
+    import decode_tail_cases as G
+    n, worst = 0, float("inf")
+    for tag, L, Q, tp, temp in G.all_sampler_cases():
+        for r in range(L.shape[0]):
+            _, ok, lead = R.nucleus_token(L[r], Q[r], temp, tp)
+            assert ok, (tag, r, tp, temp, lead)
+            n, worst = n + 1, min(worst, lead)
+    print("decidable rows", n, "smallest lead", worst)
+    assert n >= 960 and worst > 1 + 1e-4
+
+
+def test_nucleus_token_matches_oracle_sample_token():
+    """exact, on the random rows of the existing sampler test (48 per V) at its settings plus (0.999, 1.3), and with previous_tokens and
+    suppress_tokens through kernel_refs.logit_edits"""
+    import decode_tail_cases as G
+    for V in (1000, 1024, 8191, 8192):
+        L, Q = G.random_rows(V)
+        for tp, temp in G.RANDOM_SETTINGS:
+            for r in range(L.shape[0]):
+                want = O.sample_token(_t(L[r]), _t(Q[r]), temp, tp)
+                assert R.nucleus_token(L[r], Q[r], temp, tp)[0] == want, (V, tp, temp, r)
+    rng = np.random.default_rng(77)
+    for V in (1000, 8192):
+        L, Q = G.random_rows(V)
+        for r in range(12):
+            prev = np.concatenate([np.argsort(-L[r])[:5], rng.integers(0, V, 30), np.argsort(-L[r])[:3]])        # duplicates included
+            sup = np.argsort(-L[r])[5:8]
+            want = O.sample_token(_t(L[r]), _t(Q[r]), 0.7, 0.7, torch.from_numpy(prev), 1.5, [int(s) for s in sup])
+            row = R.logit_edits(L[r], prev, sup, 1.5)
+            tok, ok, _ = R.nucleus_token(row, Q[r], 0.7, 0.7)
+            assert tok == want, (V, r)
+
+
+def test_logit_edits_matches_the_edit_part_of_token_probs():
+    """token_probs with previous_tokens / suppress_tokens == token_probs of the rows logit_edits returns, bit for bit (the edit is one float32
+    multiply or divide per listed token, from the original score); entries the kernel skips (negative, >= V) and the W / prev_cap clamp"""
+    rng = np.random.default_rng(78)
+    V = 1000
+    row = (rng.standard_normal(V) * 4).astype(np.float32)
+    row[7] = 0.0
+    prev = np.array([3, 7, 3, 999, 500, 3, 0, 500], np.int64)
+    sup = [11, 12, 999]
+    for penalty in (1.5, 1.1, 3.0):
+        want = O.token_probs(_t(row), 0.7, 0.7, torch.from_numpy(prev), penalty, sup).numpy()
+        got = O.token_probs(_t(R.logit_edits(row, prev, sup, penalty)), 0.7, 0.7).numpy()
+        assert np.array_equal(want, got), penalty
+    e = R.logit_edits(row, prev, sup, 1.5)
+    assert e[3] == (row[3] * np.float32(1.5) if row[3] < 0 else row[3] / np.float32(1.5)) and e[7] == 0.0 and np.isneginf(e[[11, 12, 999]]).all()
+    untouched = np.setdiff1d(np.arange(V), np.concatenate([prev, sup]))
+    assert np.array_equal(e[untouched], row[untouched])
+    assert np.array_equal(R.logit_edits(row, [-1, V, V + 7, 3], [-5, V], 1.5), R.logit_edits(row, [3], [], 1.5))
+    assert np.array_equal(R.logit_edits(row, prev, [], 1.5, W=2), R.logit_edits(row, prev[:2], [], 1.5))
+    assert np.array_equal(R.logit_edits(row, prev, [], 1.5, W=100, prev_cap=4), R.logit_edits(row, prev[:4], [], 1.5))
+
+
+def test_swiglu_row_map_is_the_packers_and_gemv_ref_matches_the_oracle_feed_forward():
+    """Packer::w13 (csrc/packer.hip): out row 32 g + r = w1 row 16 g + r, out row 32 g + 16 + r = w3 row 16 g + r.  Restated as pack_w13; the
+    rows swiglu_rows names for feature f must be w1 row f and w3 row f.  Then gemv_ref's SwiGLU and plain forms against DualAR._block's
+    feed-forward on one small layer (wo = 0, so the block is x + w2(silu(w1 h) w3 h) with h = RMSNorm(x) ffn_norm)."""
+    I, Dm = 64, 8
+    w1 = np.arange(I * Dm, dtype=np.float32).reshape(I, Dm)
+    w3 = -w1 - 1
+    Wp = R.pack_w13(w1, w3)
+    for g in range(I // 16):
+        for r in range(16):
+            assert np.array_equal(Wp[g * 32 + r], w1[g * 16 + r]) and np.array_equal(Wp[g * 32 + 16 + r], w3[g * 16 + r])
+    r1, r3 = R.swiglu_rows(I)
+    assert np.array_equal(Wp[r1], w1) and np.array_equal(Wp[r3], w3)
+    rng = np.random.default_rng(79)
+    H, hd, M, I = 1, 64, 3, 96
+    D = H * hd
+    p = "l."
+    g = lambda *s: (rng.standard_normal(s) / np.sqrt(s[-1])).astype(np.float32)
+    Wn = {p + "attention_norm.weight": np.ones(D, np.float32), p + "attention.wqkv.weight": g(3 * D, D), p + "attention.wo.weight": np.zeros((D, D), np.float32),
+          p + "ffn_norm.weight": rng.uniform(0.5, 1.5, D).astype(np.float32), p + "feed_forward.w1.weight": g(I, D) * 2, p + "feed_forward.w3.weight": g(I, D) * 2,
+          p + "feed_forward.w2.weight": g(D, I)}
+    x = rng.standard_normal((M, D)).astype(np.float32)
+    me = types.SimpleNamespace(W={k: _t(v) for k, v in Wn.items()}, cfg=types.SimpleNamespace(n_head=H), hd=hd)
+    kc, vc = torch.zeros(H, 8, hd), torch.zeros(H, 8, hd)
+    want = O.DualAR._block(me, _t(x), p, O.rope_table(8, hd), kc, vc, torch.arange(M)).numpy()
+    act = R.gemv_ref(x, R.pack_w13(Wn[p + "feed_forward.w1.weight"], Wn[p + "feed_forward.w3.weight"]), norm_w=Wn[p + "ffn_norm.weight"], eps=1e-5, swiglu=True)
+    _close(R.gemv_ref(act, Wn[p + "feed_forward.w2.weight"], res=x), want, "gemv_ref: SwiGLU, then plain with a residual")
+    # fp16 weights: the reference runs on the rounded weights
+    Wh = g(5, D)
+    assert np.array_equal(R.gemv_ref(x, Wh, half=True), R.gemv_ref(x, R.round_f16(Wh)))
+    # bias, and the float32 restatement within the same distance
+    b = g(5)
+    _close(R.gemv_ref(x, Wh, norm_w=Wn[p + "ffn_norm.weight"], bias=b), (O.rms_norm(_t(x), _t(Wn[p + "ffn_norm.weight"])) @ _t(Wh).T + _t(b)).numpy(), "gemv_ref: norm + bias")
+    _close(R.gemv_ref(x, Wh, norm_w=Wn[p + "ffn_norm.weight"], bias=b), R.gemv_ref(x, Wh, norm_w=Wn[p + "ffn_norm.weight"], bias=b, dt=np.float32), "gemv_ref f32 restatement")
+
+
+def test_history_ring_and_embedding_refs():
+    x = np.arange(2 * 7 * 3, dtype=np.float32).reshape(2, 7, 3)
+    s = R.shift_history(x, 4, 3)
+    assert np.array_equal(s[:, :4], x[:, 3:7]) and np.array_equal(s[:, 4:], x[:, 4:])
+    s = R.shift_history(x, 5, 2)                                           # overlap: the source rows are the ORIGINAL ones
+    assert np.array_equal(s[:, :5], x[:, 2:7])
+    ring = np.zeros((2, 15), np.float32)
+    for step in range(7):                                                  # the reference shifts the window left and appends the chunk
+        ring = R.ring_write(ring, np.full((2, 3), step + 1, np.float32), step)
+    assert np.array_equal(R.ring_to_window(ring, (7 * 3) % 15)[0], np.repeat(np.arange(3, 8, dtype=np.float32), 3))
+    table = np.random.default_rng(80).standard_normal((8 * 10, 5)).astype(np.float32)
+    codes = np.array([[1, 2, 3, 4, 5, 6, 7, 8], [9, 0, 9, 0, 9, 0, 9, 0]])
+    want = torch.stack([_t(table)[torch.from_numpy(codes[:, i]) + 10 * i] for i in range(8)], 0).sum(0).numpy()      # BaseTransformer.embed
+    _close(R.audio_embed(table, codes, 10), want, "audio_embed")
