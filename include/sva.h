@@ -347,7 +347,7 @@ int sva_test_conv_gemm(int device, int n, const long long* desc, const float* fp
 /* The host-side book of the per-slot stream state (csrc/slot_book.h: phases, KV positions, frame and content counters, what a step plans),
  * scripted without a batch and without a GPU.  cfg[7] = {B, chunk_frames, delay, max_seq_frames, buffer_frames, decode_window_frames,
  * speaker prefix rows (timbre tokens + 1)}; ops: n_ops x 3 ints {op, slot, R} with op 0 = begin, 1 = prefilled(slot, R frames),
- * 2 = one chunk step, 3 = restart(slot, R frames), 4 = retire(slot); prompts are stored untruncated.  trace: n_ops rows of 8 B + 6 ints, the
+ * 2 = one chunk step, 3 = restart(slot, R frames), 4 = retire(slot), 5 = prefilled(slot, delay + 1 + R frames) stored truncated to R frames; the other prompts are stored untruncated.  trace: n_ops rows of 8 B + 6 ints, the
  * state after the op:  B x {phase, last_pos, nframes, ncontent} | delay_filled | one-pass re-prefill possible (-1: none planned) |
  * n_redo, redo[B] | n_rewind, rewind[B] x {slot, position} | n_activated, activated[B] | vocoder priming frames (begin: of the batch; a step:
  * of its first activated slot; else -1).  Unused list entries are -1; the lists are what the step planned before it carried them out. */
@@ -457,6 +457,42 @@ int sva_test_gemv(int device, const long long* desc, const float* fpar, void* co
  *          ptrs buf (in/out), counter int [1] (in/out)
  *   kind 4 launch_ring_write   desc B, N, n, step given (0: NULL), step; ptrs ring [B][N] (in/out), chunk [B][n], slot_flag [B] or NULL */
 int sva_test_token_ops(int device, int kind, const long long* desc, const float* fpar, void* const* ptrs);
+/* sva_test_step_ops: the bookkeeping kernels of the chunk step (csrc/engine_kernels.h), each through its launcher -- the grid and block size the engine
+ * uses.  Whole host arrays; "(io)" arrays go up with the caller's sentinels and come back whole.  Every code, slot, counter capacity and row count a
+ * launch would index with is checked against the lengths below first: rc 1 (refused, nothing launched) when such a check or the launcher's own fails,
+ * -4 for sizes the hook does not lay out.  int arrays are int32, codes / src / rem int64, everything else float32.
+ *   kind 0  ar_prepare_step   desc B, T2, code_off, D, chunk, ci, content rows; ptrs cached_audio_emb [B][D], content_emb, codes [B][T2], last_pos [B],
+ *                             x [2 B][D] (io), slot [2 B] (io), pos [2 B] (io), step_content [B][chunk] (io)
+ *   kind 1  apply_forced      desc B, ncb, cb, chunk, ci, use_forced; ptrs raw [B][ncb], forced [B][ncb][chunk], tok [B][ncb] (io)
+ *   kind 2  ar_finish_frame   desc B, ncb, hist_cap, chunk, ci, last_pos_inc; ptrs tok [B][ncb], last_pos [B] (io), nframes [B] (io), pred_hist [B][ncb][hist_cap] (io),
+ *                             step_audio [B][ncb][chunk] (io)
+ *   kind 3  append_content    desc B, T2, chunk, hist_cap, counter given; ptrs codes [B][T2], content_hist [B][hist_cap] (io), ncontent [B] (io),
+ *                             step_content [B][chunk] (io), step counter [1] (io) or NULL
+ *   kind 4  put_codes         desc B, T2, n_per, hist_cap; ptrs src [B][n_per], codes [B][T2] (io), content_hist (io), ncontent (io)
+ *   kind 5  build_prompt      desc nspk, R, d, ncb, codebook_size, D, Pmax, content rows, max_delay, rows; ptrs spk [nspk][D], content_emb, codebook_emb
+ *                             [ncb codebook_size][D], wait4start [max_delay][D], cc [R], ac [ncb][Pmax], x [rows][D] (io)
+ *   kind 6  build_delayfill   desc B, n, d, D, hist_cap, max_delay, content rows; ptrs content_emb, content_hist, ncontent, cached_ref_emb [B][max_delay][D], last_pos,
+ *                             slot_list [n], x [n (2 d - 1)][D] (io), slot (io), pos (io), cached_audio_emb [B][D] (io)
+ *   kind 7  build_reprefill   desc B, n, d, ncb, codebook_size, D, nspk, hist_cap, max_delay, content rows; ptrs slot [n], Rt [n], nf [n], na [n], ncon [n], content_emb,
+ *                             codebook_emb, content_hist, pred_hist, ref_tail [B][ncb][max_delay], x [sum 2 na][D] (io), slot_out (io), pos_out (io)
+ *   kind 8  finish_reprefill  desc as kind 7; ptrs slot, Rt, nf, na, ncon, codebook_emb, pred_hist, ref_tail, cached_ref_emb [B][max_delay][D] (io), last_pos [B] (io)
+ *   kind 9 / 10  copy_rows / copy_rows2   desc rows, D, src_stride, src_off, len(src); ptrs src, dst [rows][D] (io), (10) dst2 (io)
+ *   kind 11 broadcast_row     desc B, bstride, C, len(p), src_row, lo, hi; ptrs p (io)
+ *   kind 12 fill_rows         desc B, bstride, C, len(p), rows; ptrs p (io), src [C]
+ *   kind 13 .. 16  inc / add_list / add_vec / set_slot_i32   desc len(p), v, (14, 15) n | (16) slot; ptrs p (io), (14) list [n]
+ *   kind 17 history_rows_copy desc n_desc, n_slots, slot_lo, to_live, len(buf), len(save), save_bstride, then (offset, bstride, H, C, save offset) per descriptor;
+ *                             ptrs buf (io), save (io)
+ *   kind 18 history_rows_move desc n_desc, slot, len(src), len(dst), then (source offset, destination offset, destination bstride, H, C) per descriptor; ptrs src, dst (io)
+ *   kind 19 put_row           desc table rows, code, D; ptrs table, dst [D] (io)
+ *   kind 20 prepare_offline_step  desc D, step, len(rem), content rows; ptrs cached_audio_emb [D], content_emb, rem, last_pos [1], x [2][D] (io), slot [2] (io), pos [2] (io)
+ *   kind 21 mean3             desc B, y_bstride, len(y), o_bstride, o_off, len(out), n4; ptrs y0, y1, y2, out (io)
+ *   kind 22 copy_tokens       desc B, Ht, gap, c, T2, D, tok_bstride, len(tok), d_bstride, len(d2c); ptrs tok, d2c (io) */
+int sva_test_step_ops(int device, int kind, const long long* desc, const float* fpar, void* const* ptrs);
+/* sva_test_voc_level: launch_voc_level (the fused HiFiGAN level, C = 16 / 32) with the caller's arguments.
+ *   desc C, B, Tl, xH, x_bstride, len(X), y_bstride, len(Y), dil0, dil1, dil2, rows_per_frame, frames_done
+ *   ptrs X (xH history rows, then Tl rows per stream), Y3[0], Y3[1], Y3[2] (io, len(Y) each), the 18 weights back to back in (branch, conv) order
+ *        ([C][k C], k = 3 / 7 / 11 per branch), bias [18][C], int [1] (out): the tile height the launcher chose.  rc 1: the launcher refused. */
+int sva_test_voc_level(int device, const long long* desc, const float* fpar, void* const* ptrs);
 
 /* host cost (microseconds) of enqueueing one kernel from the calling thread, measured over `iters` launches of a one-element
  * kernel into an idle stream.  A synchronous single-stream step is ~170 launches (a pipelined one: four graph launches + the persistent

@@ -283,7 +283,7 @@ struct sva_batch {
     float* d_noise = nullptr;              // [B][chunk][vocab + 8*cb]
     bool noise_on_device = false;
     int h_use_forced = -1;                 // host mirror of d_use_forced (-1 = unknown): skips the per-step reset launch
-    // histories (per slot, linear with device counters)
+    // histories (per slot, rings of hist_cap entries indexed by device counters mod hist_cap)
     int hist_cap = 0;
     int* d_slot_list = nullptr;            // [B] scratch list of slots for partial delay fills
     int* d_content_hist = nullptr;         // [B][hist_cap] ring

@@ -55,6 +55,7 @@ static void parse_debug(DebugOptions& o, const char* env) {
             else if (k == "ar_pairs") o.ar_pairs = atoi(v.c_str());
             else if (k == "head_fuse") o.head_fuse = atoi(v.c_str());
             else if (k == "voc_fused_mask") o.voc_fused_mask = atoi(v.c_str());
+            else if (k == "hist_cap") o.hist_cap = atoi(v.c_str());
             else if (k == "autotune") o.autotune = atoi(v.c_str());
             else if (k == "tune_log") o.tune_log = atoi(v.c_str());
             else if (k == "tune_table") o.tune_table = atoi(v.c_str());
@@ -665,8 +666,9 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
     SVA_TRY(dev_alloc(A, &b->d_tok_raw, B * ncb));
     SVA_TRY(dev_alloc(A, &b->d_forced, (size_t)B * ncb * chunk));
     SVA_TRY(dev_alloc(A, &b->d_noise, (size_t)B * chunk * (c.ar_vocab + ncb * c.codebook_size)));
-    b->hist_cap = 4096;                      // power of two (ring indexing); >= buffer_frames + delay + chunk
-    SVA_CHECK(p->buffer_frames + p->delay + chunk < b->hist_cap, "buffer_frames too large");
+    b->hist_cap = debug_options().hist_cap;   // 4096 unless SVA_DEBUG hist_cap=N (the ring-wrap tests); power of two (ring indexing); > buffer_frames + delay + chunk
+    SVA_CHECK(b->hist_cap >= 1 && (b->hist_cap & (b->hist_cap - 1)) == 0, "hist_cap must be a power of two");
+    SVA_CHECK(p->buffer_frames + p->delay + chunk < b->hist_cap, "buffer_frames too large for the history rings (buffer_frames + delay + chunk < hist_cap)");
     SVA_TRY(dev_alloc(A, &b->d_slot_list, B));
     SVA_TRY(dev_alloc(A, &b->d_content_hist, (size_t)B * b->hist_cap));
     SVA_TRY(dev_alloc(A, &b->d_pred_hist, (size_t)B * ncb * b->hist_cap));
@@ -948,15 +950,12 @@ extern "C" int sva_streams_begin(sva_batch* b) {
             const sva_engine::SilenceState& ss = it->second;
             for (size_t i = 0; i < sd.size(); ++i) {
                 const ShiftDesc& d = sd[i];
-                hipLaunchKernelGGL(fill_rows_kernel, dim3(d.H, B), dim3(128), 0, b->stream, d.ptr, d.bstride, d.C, ss.rows[i]);
+                SVA_TRY(launch_fill_rows(d.ptr, d.bstride, d.C, ss.rows[i], d.H, B, b->stream));
             }
-            hipLaunchKernelGGL(fill_rows_kernel, dim3(1, B), dim3(128), 0, b->stream, b->d2c.p + (long)(b->T2 - 1) * b->e->cfg.tr_dim, b->d2c.bstride,
-                               b->e->cfg.tr_dim, ss.tok);
-            SVA_HIP(hipGetLastError());
+            SVA_TRY(launch_fill_rows(b->d2c.p + (long)(b->T2 - 1) * b->e->cfg.tr_dim, b->d2c.bstride, b->e->cfg.tr_dim, ss.tok, 1, B, b->stream));
         }
         // every cached token of a silent window is that same steady response
-        hipLaunchKernelGGL(broadcast_row_kernel, dim3(b->T2, B), dim3(256), 0, b->stream, b->d2c.p, b->d2c.bstride, b->T2 - 1, 0, b->T2,
-                           b->e->cfg.tr_dim);
+        SVA_TRY(launch_broadcast_row(b->d2c.p, b->d2c.bstride, b->T2 - 1, 0, b->T2, b->e->cfg.tr_dim, B, b->stream));
         SVA_HIP(hipStreamSynchronize(b->stream));
     }
     // prime the streaming vocoder with the tail of the (truncated) prompt: the reference left-fills its
@@ -1020,13 +1019,12 @@ int reprefill_slots(sva_batch* b, const std::vector<int>& due) {
         }
         const int M = a.row_off[a.n];
         SVA_CHECK(M <= b->Mmax, "re-prefill: more rows than the AR scratch holds");
-        hipLaunchKernelGGL(build_reprefill_kernel, dim3(M), dim3(256), 0, st, a, e->content_emb, e->codebook_emb, b->d_content_hist, b->d_pred_hist,
-                           b->hist_cap, b->d_ref_tail, c.max_delay, d, ncb, c.codebook_size, D, nspk, b->ax, b->d_slot, b->d_pos);
+        SVA_TRY(launch_build_reprefill(a, e->content_emb, e->codebook_emb, b->d_content_hist, b->d_pred_hist, b->hist_cap, b->d_ref_tail, c.max_delay, d, ncb,
+                                       c.codebook_size, D, nspk, b->ax, b->d_slot, b->d_pos, st));
         SVA_TRY(ar_layers_pass(b, e->ar_layers, M, b->d_slot, b->d_pos, e->rope_ar, (float*)b->kv_slow, b->kv_slow_layer, b->kv_slow_slot,
                                c.max_seq_len, b->ax));
-        hipLaunchKernelGGL(finish_reprefill_kernel, dim3(a.n * d), dim3(256), 0, st, a, e->codebook_emb, b->d_pred_hist, b->hist_cap, b->d_ref_tail,
-                           c.max_delay, d, ncb, c.codebook_size, D, nspk, b->cached_ref_emb, b->d_last_pos);
-        SVA_HIP(hipGetLastError());
+        SVA_TRY(launch_finish_reprefill(a, e->codebook_emb, b->d_pred_hist, b->hist_cap, b->d_ref_tail, c.max_delay, d, ncb, c.codebook_size, D, nspk,
+                                        b->cached_ref_emb, b->d_last_pos, st));
         for (int i = 0; i < a.n; ++i) b->slots.reprefilled(a.slot[i], b->slots.reprefill_end(a.slot[i], nspk, bf));
     }
     return 0;
@@ -1081,8 +1079,7 @@ int steady_launches(sva_batch* b, bool timing_events) {
     if (timing_events) SVA_HIP(hipEventRecord(b->ev[0], st));
     SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, st, b->d_slot_flag));
     SVA_TRY(b->enc_incremental ? encode_incremental(b, b->d_step, n, 1) : encode(b, b->d_step, n, 1));
-    hipLaunchKernelGGL(append_content_kernel, dim3((B + 63) / 64), dim3(64), 0, st, b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap,
-                       b->d_ncontent, b->d_step_content, B, b->d_step);
+    SVA_TRY(launch_append_content(b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap, b->d_ncontent, b->d_step_content, B, b->d_step, st));
     if (timing_events) SVA_HIP(hipEventRecord(b->ev[1], st));
     for (int ci = 0; ci < chunk; ++ci) SVA_TRY(ar_decode_frame(b, ci));          // :534-538
     if (timing_events) SVA_HIP(hipEventRecord(b->ev[2], st));
@@ -1202,10 +1199,7 @@ int steady_pipelined(sva_batch* b) {
         trc = stage_graph(b, &b->gT1[par], sx, [&]() -> int {
             b->stream = sx;
             SVA_TRY(enc_transformer(b, b->d2c, chunk, 2));
-            hipLaunchKernelGGL(append_content_kernel, dim3((B + 63) / 64), dim3(64), 0, sx, b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap,
-                               b->d_ncontent, b->d_step_content, B, (int*)nullptr);
-            SVA_HIP(hipGetLastError());
-            return 0;
+            return launch_append_content(b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap, b->d_ncontent, b->d_step_content, B, nullptr, sx);
         });
         b->stream = se;
         if (trc) return trc;
@@ -1222,8 +1216,7 @@ int steady_pipelined(sva_batch* b) {
         if (stage_ev) SVA_HIP(hipEventRecord(b->ev[0], se));
         SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, se, b->d_slot_flag));
         SVA_TRY(b->enc_incremental ? encode_incremental(b, b->d_step, n, 1) : encode(b, b->d_step, n, 1));
-        hipLaunchKernelGGL(append_content_kernel, dim3((B + 63) / 64), dim3(64), 0, se, b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap,
-                           b->d_ncontent, b->d_step_content, B, b->d_step);
+        SVA_TRY(launch_append_content(b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap, b->d_ncontent, b->d_step_content, B, b->d_step, se));
         if (stage_ev) SVA_HIP(hipEventRecord(b->ev[1], se));
         if (b->pipe_evVc[par]) SVA_HIP(hipStreamWaitEvent(se, b->pipe_evVc[par], 0));
         evE = next_event(b);
@@ -1340,10 +1333,9 @@ int restart_encoder_state(sva_batch* b, int slot) {
     SVA_HIP(hipMemsetAsync(b->ring + (long)slot * b->N, 0, sizeof(float) * (size_t)b->N, st));
     for (size_t i = 0; i < sd.size(); ++i) {
         const ShiftDesc& d = sd[i];
-        hipLaunchKernelGGL(fill_rows_kernel, dim3(d.H, 1), dim3(128), 0, st, d.ptr + (long)slot * d.bstride, d.bstride, d.C, ss.rows[i]);
+        SVA_TRY(launch_fill_rows(d.ptr + (long)slot * d.bstride, d.bstride, d.C, ss.rows[i], d.H, 1, st));
     }
-    hipLaunchKernelGGL(fill_rows_kernel, dim3(b->T2, 1), dim3(128), 0, st, b->d2c.p + (long)slot * b->d2c.bstride, b->d2c.bstride, e->cfg.tr_dim, ss.tok);
-    SVA_HIP(hipGetLastError());
+    SVA_TRY(launch_fill_rows(b->d2c.p + (long)slot * b->d2c.bstride, b->d2c.bstride, e->cfg.tr_dim, ss.tok, b->T2, 1, st));
     SVA_HIP(hipMemsetAsync(b->d_ncontent + slot, 0, sizeof(int), st));
     return 0;
 }
@@ -1369,8 +1361,7 @@ int prime_vocoder_slot(sva_batch* b, int slot) {
     const int P = b->slots.priming_frames(slot, b->p.decode_window_frames, c);
     int frames_kept = 0;
     SVA_HIP(hipMemcpy(&frames_kept, b->d_voc_frames, sizeof(int), hipMemcpyDeviceToHost));
-    if (nd) hipLaunchKernelGGL(history_rows_copy_kernel, dim3(nd, B), dim3(256), 0, st, b->d_shift, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, 0, 0);
-    SVA_HIP(hipGetLastError());
+    SVA_TRY(launch_history_rows_copy(b->d_shift, nd, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, 0, B, 0, st));
     SVA_TRY(sva_vocode_reset(b));
     // the step that activates the slot may hold its PCM in d_pcm or in the caller's buffer: the priming run writes its own sink
     struct Keep {
@@ -1385,11 +1376,8 @@ int prime_vocoder_slot(sva_batch* b, int slot) {
         SVA_TRY(upload_vcodes(b, cf, c));
         SVA_TRY(vocode(b, c, true));
     }
-    if (nd) {
-        hipLaunchKernelGGL(history_rows_copy_kernel, dim3(nd, 1), dim3(256), 0, st, b->d_shift, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, slot, 0);
-        hipLaunchKernelGGL(history_rows_copy_kernel, dim3(nd, B), dim3(256), 0, st, b->d_shift, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, 0, 1);
-    }
-    SVA_HIP(hipGetLastError());
+    SVA_TRY(launch_history_rows_copy(b->d_shift, nd, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, slot, 1, 0, st));
+    SVA_TRY(launch_history_rows_copy(b->d_shift, nd, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, 0, B, 1, st));
     SVA_HIP(hipMemcpyAsync(b->d_voc_frames, &frames_kept, sizeof(int), hipMemcpyHostToDevice, st));
     SVA_HIP(hipStreamSynchronize(st));
     return 0;
@@ -1415,8 +1403,7 @@ int prime_vocoder_slot_local(sva_batch* b, int slot) {
         SVA_TRY(upload_vcodes(w, codes.data(), P));
         SVA_TRY(vocode(w, P, true));
     }
-    if (nd) hipLaunchKernelGGL(history_rows_move_kernel, dim3(nd), dim3(256), 0, st, w->d_shift, b->d_shift, slot);
-    SVA_HIP(hipGetLastError());
+    SVA_TRY(launch_history_rows_move(w->d_shift, b->d_shift, nd, slot, st));
     SVA_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -1505,8 +1492,9 @@ int step_body(sva_batch* b) {
         if (b->pipe_dirty) b->stream = b->sa;  // pipelined: the KV rewrite belongs to the AR stream (it already waited for E of this step)
         int rrc = 0;
         // a parked slot never becomes due: its position goes back to the end of its last stored prompt, over K / V rows that stay valid
-        for (const auto& rw : plan.rewind) hipLaunchKernelGGL(set_slot_i32_kernel, dim3(1), dim3(64), 0, b->stream, b->d_last_pos, rw.first, rw.second);
-        if (!redo.empty()) {
+        for (const auto& rw : plan.rewind)
+            if (!rrc) rrc = launch_set_slot_i32(b->d_last_pos, rw.first, rw.second, b->stream);
+        if (!rrc && !redo.empty()) {
             // one pass for all due slots against the cached prompt prefix (reprefill_slots); SVA_DEBUG reprefill=0: the round-3 path, one
             // whole-prompt prefill per slot behind a host synchronisation (A/B, parity of the two)
             const bool one_pass = debug_options().reprefill != 0 && b->slots.one_pass_ok(redo, b->p.buffer_frames, b->p.delay);
@@ -1530,8 +1518,7 @@ int step_body(sva_batch* b) {
     // E0: shift window / append chunk (:495-496), then E1..E8
     SVA_TRY(launch_ring_write(b->ring, b->d_step, B, b->N, b->step_src ? b->step_src : b->d_chunk, n, st, b->d_slot_flag));
     SVA_TRY(b->enc_incremental ? encode_incremental(b, b->d_step, n, 1) : encode(b, b->d_step, n, 1));
-    hipLaunchKernelGGL(append_content_kernel, dim3((B + 63) / 64), dim3(64), 0, st, b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap,
-                       b->d_ncontent, b->d_step_content, B, b->d_step);
+    SVA_TRY(launch_append_content(b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap, b->d_ncontent, b->d_step_content, B, b->d_step, st));
     SVA_HIP(hipEventRecord(b->ev[1], st));
     // the lock-step slots hold `delay` content codes: :521-525 -> zeros (else :519-520 -> zeros).  With every slot retired or restarted since
     // sva_streams_begin nothing is left to fill in lock step.
@@ -1762,7 +1749,13 @@ static int check_ar_fail(sva_batch* b) {
 // see them -- the GEMM dispatch table and the autotune switch are read once, before the first launch)
 extern "C" int sva_debug_configure(const char* kv) {
     SVA_CHECK(kv, "null argument");
-    parse_debug(sva::debug_options_mut(), kv);
+    DebugOptions& o = sva::debug_options_mut();
+    const int cap_before = o.hist_cap;
+    parse_debug(o, kv);
+    if (o.hist_cap < 1 || (o.hist_cap & (o.hist_cap - 1)) != 0) {       // (the other half of the rule, buffer_frames + delay + chunk < N, is the batch's to check)
+        o.hist_cap = cap_before;
+        SVA_CHECK(false, "sva_debug_configure: hist_cap must be a power of two");
+    }
     return 0;
 }
 
@@ -1832,19 +1825,6 @@ extern "C" int sva_sync(sva_batch* b) {
 }
 
 // ---- AR seams: DualARWrapper.prefill_src_condition4delay / decode_one driven with caller-supplied content codes ----
-__global__ void put_codes_kernel(const long long* __restrict__ src, int n_per, long long* __restrict__ codes, int T2, int* __restrict__ content_hist,
-                                 int hist_cap, int* __restrict__ ncontent, int B) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const int n = ncontent[b];
-    for (int i = 0; i < n_per; ++i) {
-        const long long c = src[(long)b * n_per + i];
-        codes[(long)b * T2 + T2 - n_per + i] = c;
-        content_hist[(long)b * hist_cap + ((n + i) & (hist_cap - 1))] = (int)c;
-    }
-    ncontent[b] = n + n_per;
-}
-
 extern "C" int sva_ar_delay_fill(sva_batch* b, const int64_t* codes) {
     SVA_CHECK(b && codes && b->begun, "sva_ar_delay_fill: bad argument");
     SVA_HIP(hipSetDevice(b->e->device));
@@ -1853,8 +1833,7 @@ extern "C" int sva_ar_delay_fill(sva_batch* b, const int64_t* codes) {
     const int B = b->B, d = b->p.delay;
     long long* tmp = (long long*)b->d_noise;       // scratch (>= B*d*8 bytes)
     SVA_TRY(h2d(b, tmp, codes, sizeof(int64_t) * (size_t)B * d));
-    hipLaunchKernelGGL(put_codes_kernel, dim3((B + 63) / 64), dim3(64), 0, b->stream, tmp, d, b->d_codes, b->T2, b->d_content_hist, b->hist_cap,
-                       b->d_ncontent, B);
+    SVA_TRY(launch_put_codes(tmp, d, b->d_codes, b->T2, b->d_content_hist, b->hist_cap, b->d_ncontent, B, b->stream));
     b->slots.add_content(d);
     SVA_TRY(ar_delay_fill(b));
     b->slots.lockstep_filled();
@@ -1873,8 +1852,7 @@ extern "C" int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float*
     hipStream_t st = b->stream;
     long long* tmp = (long long*)b->d_tok_raw;     // scratch: B*8 ints >= B int64
     SVA_TRY(h2d(b, tmp, code, sizeof(int64_t) * (size_t)B));
-    hipLaunchKernelGGL(put_codes_kernel, dim3((B + 63) / 64), dim3(64), 0, st, tmp, 1, b->d_codes, b->T2, b->d_content_hist, b->hist_cap,
-                       b->d_ncontent, B);
+    SVA_TRY(launch_put_codes(tmp, 1, b->d_codes, b->T2, b->d_content_hist, b->hist_cap, b->d_ncontent, B, st));
     b->slots.add_content(1);
     b->noise_on_device = (noise == nullptr);
     if (noise) SVA_TRY(h2d(b, b->d_noise, noise, sizeof(float) * (size_t)B * (c.ar_vocab + ncb * c.codebook_size)));
@@ -1891,20 +1869,6 @@ extern "C" int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float*
 }
 
 // ---- offline ARVCWrapper.generate (modules/arvc_wrapper.py:82-98 + DualARWrapper.generate, dual_ar_stream.py:698-762) ----
-__global__ void put_row_kernel(const float* __restrict__ table, long long code, int D, float* __restrict__ dst) {
-    for (int i = threadIdx.x; i < D; i += blockDim.x) dst[i] = table[code * D + i];
-}
-__global__ void prepare_offline_step_kernel(const float* __restrict__ cached_audio_emb, const float* __restrict__ content_emb,
-                                            const long long* __restrict__ rem, int step, const int* __restrict__ last_pos, int D,
-                                            float* __restrict__ x, int* __restrict__ slot, int* __restrict__ pos) {
-    const long long code = rem[step];
-    for (int i = threadIdx.x; i < D; i += blockDim.x) {
-        x[i] = cached_audio_emb[i];
-        x[D + i] = content_emb[code * D + i];
-    }
-    if (threadIdx.x == 0) { slot[0] = 0; slot[1] = 0; pos[0] = last_pos[0] + 1; pos[1] = last_pos[0] + 2; }
-}
-
 extern "C" int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* ref_ac, int R, const int64_t* src_cc, int S,
                             const float* style, const float* timbre, uint64_t noise_seed, const float* noise, int32_t* codes_out) {
     SVA_CHECK(b && ref_cc && ref_ac && src_cc && style && timbre && codes_out, "sva_generate: null argument");
@@ -1943,9 +1907,9 @@ extern "C" int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* 
     SVA_TRY(gemm_call(b, b->d_timbre, (long)c.timbre_tokens * c.timbre_dim, 0, c.timbre_dim, 1, c.timbre_tokens, 1, 1, 1, c.timbre_dim, e->context_in,
                       b->spk, (long)nspk * D, 0, D));
     SVA_TRY(gemm_call(b, b->d_style, c.style_dim, 0, c.style_dim, 1, 1, 1, 1, 1, c.style_dim, e->style_in, b->spk + (long)c.timbre_tokens * D, D, 0, D));
-    hipLaunchKernelGGL(build_prompt_kernel, dim3(M - 1), dim3(256), 0, st, b->spk, nspk, e->content_emb, e->codebook_emb, e->wait4start,
-                       b->d_prompt_cc, b->d_prompt_ac, b->Pmax, Rp, d, ncb, c.codebook_size, D, b->ax);
-    hipLaunchKernelGGL(put_row_kernel, dim3(1), dim3(256), 0, st, e->content_emb, (long long)rem[0], D, b->ax + (long)(M - 1) * D);
+    SVA_TRY(launch_build_prompt(b->spk, nspk, e->content_emb, e->codebook_emb, e->wait4start, b->d_prompt_cc, b->d_prompt_ac, b->Pmax, Rp, d, ncb, c.codebook_size,
+                                D, b->ax, M - 1, st));
+    SVA_TRY(launch_put_row(e->content_emb, (long long)rem[0], D, b->ax + (long)(M - 1) * D, st));
     std::vector<int> hs(M, 0), hp(M);
     for (int i = 0; i < M; ++i) hp[i] = i;
     SVA_HIP(hipMemcpyAsync(b->d_slot, hs.data(), sizeof(int) * M, hipMemcpyHostToDevice, st));
@@ -1980,8 +1944,7 @@ extern "C" int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* 
             SVA_TRY(ar_decode_frame_mega(b, 0, d_remq, i));
             b->slots.frame_decoded(0, 2);
         } else {
-            hipLaunchKernelGGL(prepare_offline_step_kernel, dim3(1), dim3(256), 0, st, b->cached_audio_emb, e->content_emb, d_remq, i, b->d_last_pos, D,
-                               b->ax, b->d_slot, b->d_pos);
+            SVA_TRY(launch_prepare_offline_step(b->cached_audio_emb, e->content_emb, d_remq, i, b->d_last_pos, D, b->ax, b->d_slot, b->d_pos, st));
             SVA_TRY(ar_layers_pass(b, e->ar_layers, 2, b->d_slot, b->d_pos, e->rope_ar, (float*)b->kv_slow, b->kv_slow_layer, b->kv_slow_slot,
                                    c.max_seq_len, b->ax));
             SVA_TRY(ar_frame_tail(b, 0, (long)2 * D, (long)D, d_remq, S, i, 2));

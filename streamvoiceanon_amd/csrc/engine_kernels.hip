@@ -252,3 +252,240 @@ __global__ __launch_bounds__(256) void history_rows_move_kernel(const sva::Shift
         for (long i = threadIdx.x; i < n; i += blockDim.x) to[i] = from[i];
     }
 }
+
+// ---- kernels of the AR seams, the offline loop and the stage hand-overs (launched from engine.hip / stages.hip through the launchers below) ----
+__global__ void put_codes_kernel(const long long* __restrict__ src, int n_per, long long* __restrict__ codes, int T2, int* __restrict__ content_hist,
+                                 int hist_cap, int* __restrict__ ncontent, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int n = ncontent[b];
+    for (int i = 0; i < n_per; ++i) {
+        const long long c = src[(long)b * n_per + i];
+        codes[(long)b * T2 + T2 - n_per + i] = c;
+        content_hist[(long)b * hist_cap + ((n + i) & (hist_cap - 1))] = (int)c;
+    }
+    ncontent[b] = n + n_per;
+}
+
+__global__ void put_row_kernel(const float* __restrict__ table, long long code, int D, float* __restrict__ dst) {
+    for (int i = threadIdx.x; i < D; i += blockDim.x) dst[i] = table[code * D + i];
+}
+__global__ void prepare_offline_step_kernel(const float* __restrict__ cached_audio_emb, const float* __restrict__ content_emb,
+                                            const long long* __restrict__ rem, int step, const int* __restrict__ last_pos, int D,
+                                            float* __restrict__ x, int* __restrict__ slot, int* __restrict__ pos) {
+    const long long code = rem[step];
+    for (int i = threadIdx.x; i < D; i += blockDim.x) {
+        x[i] = cached_audio_emb[i];
+        x[D + i] = content_emb[code * D + i];
+    }
+    if (threadIdx.x == 0) { slot[0] = 0; slot[1] = 0; pos[0] = last_pos[0] + 1; pos[1] = last_pos[0] + 2; }
+}
+
+__global__ void mean3_kernel(const float* __restrict__ y0, const float* __restrict__ y1, const float* __restrict__ y2, long y_bstride,
+                             float* __restrict__ out, long o_bstride, long o_off, long n4) {
+    // ParallelBlock: torch.stack([...]).mean(0) (firefly.py:214-215) of the three branch outputs, float4 lanes
+    const int b = blockIdx.y;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const float4 a = reinterpret_cast<const float4*>(y0 + (long)b * y_bstride)[i];
+    const float4 c = reinterpret_cast<const float4*>(y1 + (long)b * y_bstride)[i];
+    const float4 d = reinterpret_cast<const float4*>(y2 + (long)b * y_bstride)[i];
+    float4 r;
+    r.x = ((a.x + c.x) + d.x) / 3.0f; r.y = ((a.y + c.y) + d.y) / 3.0f; r.z = ((a.z + c.z) + d.z) / 3.0f; r.w = ((a.w + c.w) + d.w) / 3.0f;
+    reinterpret_cast<float4*>(out + (long)b * o_bstride + o_off)[i] = r;
+}
+
+__global__ void copy_tokens_kernel(const float* __restrict__ tok, long tok_bstride, int Ht, int gap, int c, float* __restrict__ d2c, long d_bstride,
+                                   int T2, int D) {
+    // head tokens -> d2c rows [0, Ht); newest c tokens -> d2c rows [T2 - c, T2)
+    const int r = blockIdx.x, bi = blockIdx.y;
+    const int src = r < Ht ? r : Ht + gap + (r - Ht);
+    const int dst = r < Ht ? r : T2 - c + (r - Ht);
+    const float4* s = reinterpret_cast<const float4*>(tok + (long)bi * tok_bstride + (long)src * D);
+    float4* d = reinterpret_cast<float4*>(d2c + (long)bi * d_bstride + (long)dst * D);
+    for (int i = threadIdx.x; i < D / 4; i += blockDim.x) d[i] = s[i];
+}
+
+// ============================================================================================
+// launchers: grid, block and the host-checkable arguments of every kernel above, in one place each
+// ============================================================================================
+namespace {
+inline bool pow2(int v) { return v >= 1 && (v & (v - 1)) == 0; }
+inline unsigned per_slot_blocks(int B) { return (unsigned)((B + 63) / 64); }          // the one-thread-per-slot kernels: 64 slots a block
+}  // namespace
+
+int launch_ar_prepare_step(const float* cached_audio_emb, const float* content_emb, const long long* codes, int T2, int code_off, const int* last_pos,
+                           int D, float* x, int* slot, int* pos, int* step_content, int chunk, int ci, int B, hipStream_t st) {
+    SVA_CHECK(B >= 1 && D >= 1 && code_off >= 0 && code_off < T2 && ci >= 0 && ci < chunk, "ar_prepare_step: bad arguments");
+    hipLaunchKernelGGL(ar_prepare_step_kernel, dim3(B), dim3(256), 0, st, cached_audio_emb, content_emb, codes, T2, code_off, last_pos, D, x, slot, pos,
+                       step_content, chunk, ci);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_apply_forced(const int* raw, const int* forced, const int* use_forced, int chunk, int ci, int cb, int ncb, int* tok, int B, hipStream_t st) {
+    SVA_CHECK(B >= 1 && cb >= 0 && cb < ncb && ci >= 0 && ci < chunk, "apply_forced: bad arguments");
+    hipLaunchKernelGGL(apply_forced_kernel, dim3(per_slot_blocks(B)), dim3(64), 0, st, raw, forced, use_forced, chunk, ci, cb, ncb, tok, B);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_ar_finish_frame(const int* tok, int ncb, int* last_pos, int* nframes, int* pred_hist, int hist_cap, int* step_audio, int chunk, int ci,
+                           int B, int last_pos_inc, hipStream_t st) {
+    SVA_CHECK(B >= 1 && ncb >= 1 && pow2(hist_cap) && ci >= 0 && ci < chunk, "ar_finish_frame: bad arguments (the history capacity is a power of two)");
+    hipLaunchKernelGGL(ar_finish_frame_kernel, dim3(per_slot_blocks(B)), dim3(64), 0, st, tok, ncb, last_pos, nframes, pred_hist, hist_cap, step_audio, chunk,
+                       ci, (const long long*)nullptr, 0, 0, (int*)nullptr, (int*)nullptr, B, last_pos_inc);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_append_content(const long long* codes, int T2, int chunk, int* content_hist, int hist_cap, int* ncontent, int* step_content, int B,
+                          int* step_counter, hipStream_t st) {
+    SVA_CHECK(B >= 1 && chunk >= 1 && chunk <= T2 && pow2(hist_cap) && chunk <= hist_cap, "append_content: bad arguments (the history capacity is a power of two)");
+    hipLaunchKernelGGL(append_content_kernel, dim3(per_slot_blocks(B)), dim3(64), 0, st, codes, T2, chunk, content_hist, hist_cap, ncontent, step_content, B,
+                       step_counter);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_put_codes(const long long* src, int n_per, long long* codes, int T2, int* content_hist, int hist_cap, int* ncontent, int B, hipStream_t st) {
+    SVA_CHECK(B >= 1 && n_per >= 1 && n_per <= T2 && pow2(hist_cap) && n_per <= hist_cap, "put_codes: bad arguments (the history capacity is a power of two)");
+    hipLaunchKernelGGL(put_codes_kernel, dim3(per_slot_blocks(B)), dim3(64), 0, st, src, n_per, codes, T2, content_hist, hist_cap, ncontent, B);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_build_prompt(const float* spk, int nspk, const float* content_emb, const float* codebook_emb, const float* wait4start, const int* cc,
+                        const int* ac, int Pmax, int R, int d, int ncb, int cbsize, int D, float* x, int rows, hipStream_t st) {
+    SVA_CHECK(rows >= 1 && rows <= nspk + 2 * R && nspk >= 0 && d >= 1 && R <= Pmax && ncb >= 1 && D >= 1, "build_prompt: bad arguments");
+    hipLaunchKernelGGL(build_prompt_kernel, dim3(rows), dim3(256), 0, st, spk, nspk, content_emb, codebook_emb, wait4start, cc, ac, Pmax, R, d, ncb, cbsize, D, x);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_build_delayfill(const float* content_emb, const int* content_hist, int hist_cap, const int* ncontent, const float* cached_ref_emb,
+                           int max_delay, const int* last_pos, int d, int D, float* x, int* slot, int* pos, float* cached_audio_emb,
+                           const int* slot_list, int n, hipStream_t st) {
+    SVA_CHECK(n >= 1 && d >= 1 && d <= max_delay && d <= hist_cap && pow2(hist_cap) && D >= 1, "build_delayfill: bad arguments (the history capacity is a power of two)");
+    hipLaunchKernelGGL(build_delayfill_kernel, dim3(n * (2 * d - 1)), dim3(256), 0, st, content_emb, content_hist, hist_cap, ncontent, cached_ref_emb, max_delay,
+                       last_pos, d, D, x, slot, pos, cached_audio_emb, slot_list);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+namespace {
+int check_reprefill_args(const ReprefillArgs& a, int hist_cap, int max_delay, int d, int ncb) {
+    SVA_CHECK(a.n >= 1 && a.n <= 128, "re-prefill: 1 .. 128 slots per pass");
+    SVA_CHECK(ncb >= 1 && ncb <= 8 && d >= 1 && d <= max_delay && pow2(hist_cap), "re-prefill: bad arguments (at most 8 codebooks, a power-of-two history capacity)");
+    SVA_CHECK(a.row_off[0] == 0, "re-prefill: row offsets start at 0");
+    for (int i = 0; i < a.n; ++i) {
+        SVA_CHECK(a.row_off[i + 1] == a.row_off[i] + 2 * a.na[i], "re-prefill: row offsets are the running sum of 2 na");
+        SVA_CHECK(a.na[i] >= d && a.na[i] <= a.nf[i] && a.na[i] + d <= a.ncon[i] && a.na[i] + d <= hist_cap, "re-prefill: the appended frames lie inside the histories (d <= na <= nf, na + d <= ncontent)");
+        SVA_CHECK(a.Rt[i] >= d, "re-prefill: a stored prompt shorter than the delay needs the whole-prompt prefill (its wait4start rows)");
+    }
+    return 0;
+}
+}  // namespace
+int launch_build_reprefill(const ReprefillArgs& a, const float* content_emb, const float* codebook_emb, const int* content_hist, const int* pred_hist,
+                           int hist_cap, const int* ref_tail, int max_delay, int d, int ncb, int cbsize, int D, int nspk, float* x, int* slot_out,
+                           int* pos_out, hipStream_t st) {
+    SVA_TRY_RC(check_reprefill_args(a, hist_cap, max_delay, d, ncb));
+    hipLaunchKernelGGL(build_reprefill_kernel, dim3(a.row_off[a.n]), dim3(256), 0, st, a, content_emb, codebook_emb, content_hist, pred_hist, hist_cap, ref_tail,
+                       max_delay, d, ncb, cbsize, D, nspk, x, slot_out, pos_out);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_finish_reprefill(const ReprefillArgs& a, const float* codebook_emb, const int* pred_hist, int hist_cap, const int* ref_tail, int max_delay,
+                            int d, int ncb, int cbsize, int D, int nspk, float* cached_ref_emb, int* last_pos, hipStream_t st) {
+    SVA_TRY_RC(check_reprefill_args(a, hist_cap, max_delay, d, ncb));
+    hipLaunchKernelGGL(finish_reprefill_kernel, dim3(a.n * d), dim3(256), 0, st, a, codebook_emb, pred_hist, hist_cap, ref_tail, max_delay, d, ncb, cbsize, D,
+                       nspk, cached_ref_emb, last_pos);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_put_row(const float* table, long long code, int D, float* dst, hipStream_t st) {
+    SVA_CHECK(code >= 0 && D >= 1, "put_row: bad arguments");
+    hipLaunchKernelGGL(put_row_kernel, dim3(1), dim3(256), 0, st, table, code, D, dst);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_prepare_offline_step(const float* cached_audio_emb, const float* content_emb, const long long* rem, int step, const int* last_pos, int D,
+                                float* x, int* slot, int* pos, hipStream_t st) {
+    SVA_CHECK(step >= 0 && D >= 1, "prepare_offline_step: bad arguments");
+    hipLaunchKernelGGL(prepare_offline_step_kernel, dim3(1), dim3(256), 0, st, cached_audio_emb, content_emb, rem, step, last_pos, D, x, slot, pos);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_copy_rows(const float* src, long src_stride, long src_off, float* dst, int D, int rows, hipStream_t st) {
+    SVA_CHECK(rows >= 1 && D >= 1 && src_stride >= 0 && src_off >= 0, "copy_rows: bad arguments");
+    hipLaunchKernelGGL(copy_rows_kernel, dim3(rows), dim3(256), 0, st, src, src_stride, src_off, dst, D);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_copy_rows2(const float* src, long src_stride, long src_off, float* dst1, float* dst2, int D, int rows, hipStream_t st) {
+    SVA_CHECK(rows >= 1 && D >= 1 && src_stride >= 0 && src_off >= 0, "copy_rows2: bad arguments");
+    hipLaunchKernelGGL(copy_rows2_kernel, dim3(rows), dim3(256), 0, st, src, src_stride, src_off, dst1, dst2, D);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_broadcast_row(float* p, long bstride, int src_row, int lo, int hi, int C, int B, hipStream_t st) {
+    SVA_CHECK(B >= 1 && B <= 65535 && C >= 1 && lo >= 0 && hi > lo && src_row >= 0, "broadcast_row: bad arguments");
+    hipLaunchKernelGGL(broadcast_row_kernel, dim3(hi - lo, B), dim3(256), 0, st, p, bstride, src_row, lo, hi, C);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_fill_rows(float* p, long bstride, int C, const float* src, int rows, int B, hipStream_t st) {
+    SVA_CHECK(B >= 1 && B <= 65535 && C >= 1 && rows >= 0, "fill_rows: bad arguments");
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(fill_rows_kernel, dim3(rows, B), dim3(128), 0, st, p, bstride, C, src);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_copy_tokens(const float* tok, long tok_bstride, int Ht, int gap, int c, float* d2c, long d_bstride, int T2, int D, int B, hipStream_t st) {
+    SVA_CHECK(B >= 1 && B <= 65535 && Ht >= 0 && gap >= 0 && c >= 1 && Ht + c <= T2 && D >= 4 && D % 4 == 0 && tok_bstride % 4 == 0 && d_bstride % 4 == 0,
+              "copy_tokens: bad arguments (float4 rows; head and newest tokens do not overlap)");
+    hipLaunchKernelGGL(copy_tokens_kernel, dim3(Ht + c, B), dim3(128), 0, st, tok, tok_bstride, Ht, gap, c, d2c, d_bstride, T2, D);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_mean3(const float* y0, const float* y1, const float* y2, long y_bstride, float* out, long o_bstride, long o_off, long n4, int B, hipStream_t st) {
+    SVA_CHECK(B >= 1 && B <= 65535 && n4 >= 1 && y_bstride % 4 == 0 && o_bstride % 4 == 0 && o_off >= 0 && o_off % 4 == 0, "mean3: bad arguments (float4 lanes)");
+    hipLaunchKernelGGL(mean3_kernel, dim3((unsigned)((n4 + 255) / 256), B), dim3(256), 0, st, y0, y1, y2, y_bstride, out, o_bstride, o_off, n4);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_inc(int* p, int v, hipStream_t st) {
+    hipLaunchKernelGGL(inc_kernel, dim3(1), dim3(64), 0, st, p, v);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_add_list(int* p, const int* list, int n, int v, hipStream_t st) {
+    SVA_CHECK(n >= 1, "add_list: bad arguments");
+    hipLaunchKernelGGL(add_list_kernel, dim3(per_slot_blocks(n)), dim3(64), 0, st, p, list, n, v);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_add_vec(int* p, int n, int v, hipStream_t st) {
+    SVA_CHECK(n >= 1, "add_vec: bad arguments");
+    hipLaunchKernelGGL(add_vec_kernel, dim3(per_slot_blocks(n)), dim3(64), 0, st, p, n, v);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_set_slot_i32(int* p, int slot, int v, hipStream_t st) {
+    SVA_CHECK(slot >= 0, "set_slot_i32: bad arguments");
+    hipLaunchKernelGGL(set_slot_i32_kernel, dim3(1), dim3(64), 0, st, p, slot, v);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_history_rows_copy(const sva::ShiftDesc* descs, int n_desc, const long* offs, float* save, long save_bstride, int slot_lo, int n_slots,
+                             int to_live, hipStream_t st) {
+    SVA_CHECK(n_desc >= 0 && slot_lo >= 0 && n_slots >= 1 && n_slots <= 65535 && save_bstride >= 0, "history_rows_copy: bad arguments");
+    if (n_desc == 0) return 0;
+    hipLaunchKernelGGL(history_rows_copy_kernel, dim3(n_desc, n_slots), dim3(256), 0, st, descs, offs, save, save_bstride, slot_lo, to_live);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}
+int launch_history_rows_move(const sva::ShiftDesc* src_descs, const sva::ShiftDesc* dst_descs, int n_desc, int slot, hipStream_t st) {
+    SVA_CHECK(n_desc >= 0 && slot >= 0, "history_rows_move: bad arguments");
+    if (n_desc == 0) return 0;
+    hipLaunchKernelGGL(history_rows_move_kernel, dim3(n_desc), dim3(256), 0, st, src_descs, dst_descs, slot);
+    SVA_HIP(hipGetLastError());
+    return 0;
+}

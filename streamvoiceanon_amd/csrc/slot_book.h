@@ -137,10 +137,11 @@ struct SlotBook {
         return plan;
     }
     // all due slots in one pass against the cached prompt prefix?  (a stream that has decoded fewer than `delay` frames -- a prompt about as
-    // long as max_seq_frames -- keeps the general form, one whole-prompt prefill per slot)
+    // long as max_seq_frames -- keeps the general form, one whole-prompt prefill per slot; so does a stored prompt shorter than the delay: the
+    // audio rows of its frames Rt .. delay - 1 are wait4start rows (prefill_prompt), which the one-pass row builder does not hold)
     bool one_pass_ok(const std::vector<int>& redo, int buffer_frames, int delay) const {
         for (int i : redo)
-            if (reprefill_frames(i, buffer_frames) < delay) return false;
+            if (reprefill_frames(i, buffer_frames) < delay || s[i].ref_len < delay) return false;
         return true;
     }
     void reprefilled(int slot, int last_pos) { s[slot].last_pos = last_pos; }

@@ -139,20 +139,6 @@ int voc_conv_call(sva_batch* b, const VocConvGroup& gg, int C, int pmode) {
     return launch_voc_conv(gg, C, pmode, b->enc_cus, b->stream);
 }
 
-__global__ void mean3_kernel(const float* __restrict__ y0, const float* __restrict__ y1, const float* __restrict__ y2, long y_bstride,
-                             float* __restrict__ out, long o_bstride, long o_off, long n4) {
-    // ParallelBlock: torch.stack([...]).mean(0) (firefly.py:214-215) of the three branch outputs, float4 lanes
-    const int b = blockIdx.y;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    const float4 a = reinterpret_cast<const float4*>(y0 + (long)b * y_bstride)[i];
-    const float4 c = reinterpret_cast<const float4*>(y1 + (long)b * y_bstride)[i];
-    const float4 d = reinterpret_cast<const float4*>(y2 + (long)b * y_bstride)[i];
-    float4 r;
-    r.x = ((a.x + c.x) + d.x) / 3.0f; r.y = ((a.y + c.y) + d.y) / 3.0f; r.z = ((a.z + c.z) + d.z) / 3.0f; r.w = ((a.w + c.w) + d.w) / 3.0f;
-    reinterpret_cast<float4*>(out + (long)b * o_bstride + o_off)[i] = r;
-}
-
 // Two chained GEMMs of `rows` rows can hand their intermediate tensor over as operand planes (gemm_planes.hip) when both weights carry
 // planes of one fp16 format -- two fp16 planes (or one) fill exactly the bytes (half the bytes) of the fp32 tensor they replace, so
 // they live in its buffer -- and the problem is at the scale where the planes kernel is the dispatcher's choice anyway.
@@ -275,17 +261,6 @@ int enc_frontend_window(sva_batch* b, const int* step_ptr, int n_chunk, int add,
     return 0;
 }
 
-__global__ void copy_tokens_kernel(const float* __restrict__ tok, long tok_bstride, int Ht, int gap, int c, float* __restrict__ d2c, long d_bstride,
-                                   int T2, int D) {
-    // head tokens -> d2c rows [0, Ht); newest c tokens -> d2c rows [T2 - c, T2)
-    const int r = blockIdx.x, bi = blockIdx.y;
-    const int src = r < Ht ? r : Ht + gap + (r - Ht);
-    const int dst = r < Ht ? r : T2 - c + (r - Ht);
-    const float4* s = reinterpret_cast<const float4*>(tok + (long)bi * tok_bstride + (long)src * D);
-    float4* d = reinterpret_cast<float4*>(d2c + (long)bi * d_bstride + (long)dst * D);
-    for (int i = threadIdx.x; i < D / 4; i += blockDim.x) d[i] = s[i];
-}
-
 // Merged incremental front-end pass (see EncMerged): head rows (the first 4*Ht mel frames of the window, zero left padding as in
 // the reference's window pass) and the 4c newest mel frames (on per-layer 6-row histories) through ONE sequence of launches.
 // Results: token rows [0, Ht) and [T2 - c, T2) of d2c.
@@ -321,7 +296,7 @@ int enc_frontend_merged(sva_batch* b, const int* step_ptr, int n_chunk, int add,
     const int n_shift_ds = 2;                       // the last two descriptors are the downsampler's (d1, d2)
     if (part == 4) {
         SVA_TRY(merged_downsample(b, feat, M.h1b, M.h2b));
-        hipLaunchKernelGGL(copy_tokens_kernel, dim3(b->Ht + ch, B), dim3(128), 0, st, M.tok.p, M.tok.bstride, b->Ht, 6, ch, b->d2c.p, b->d2c.bstride, b->T2, D);
+        SVA_TRY(launch_copy_tokens(M.tok.p, M.tok.bstride, b->Ht, 6, ch, b->d2c.p, b->d2c.bstride, b->T2, D, B, st));
         SVA_TRY(launch_shift_history(M.d_shift + (M.n_shift - n_shift_ds), n_shift_ds, B, st));
         SVA_HIP(hipGetLastError());
         return 0;
@@ -362,7 +337,7 @@ int enc_frontend_merged(sva_batch* b, const int* step_ptr, int n_chunk, int add,
     if (part == 3) return launch_shift_history(M.d_shift, M.n_shift - n_shift_ds, B, st, 1, b->step_bump, 1);       // (+ the chain's step counter)
     SVA_TRY(merged_downsample(b, feat, M.h1, M.h2));
     // the hand-over: head and new tokens -> d2c, then every layer's history rows slide
-    hipLaunchKernelGGL(copy_tokens_kernel, dim3(b->Ht + ch, B), dim3(128), 0, st, M.tok.p, M.tok.bstride, b->Ht, 6, ch, b->d2c.p, b->d2c.bstride, b->T2, D);
+    SVA_TRY(launch_copy_tokens(M.tok.p, M.tok.bstride, b->Ht, 6, ch, b->d2c.p, b->d2c.bstride, b->T2, D, B, st));
     SVA_TRY(launch_shift_history(M.d_shift, M.n_shift, B, st));
     SVA_HIP(hipGetLastError());
     return 0;
@@ -613,14 +588,14 @@ int ar_decode_frame(sva_batch* b, int ci) {
         if (b->use_mega) {
             SVA_TRY(ar_decode_frame_mega(b, ci, b->d_codes, code_off));
         } else {
-            hipLaunchKernelGGL(ar_prepare_step_kernel, dim3(B), dim3(256), 0, st, b->cached_audio_emb, e->content_emb, b->d_codes, b->T2,
-                               code_off, b->d_last_pos, D, b->ax, b->d_slot, b->d_pos, b->d_step_content, chunk, ci);
+            SVA_TRY(launch_ar_prepare_step(b->cached_audio_emb, e->content_emb, b->d_codes, b->T2, code_off, b->d_last_pos, D, b->ax, b->d_slot, b->d_pos,
+                                           b->d_step_content, chunk, ci, B, st));
             SVA_TRY(ar_decode_frame_batch(b, ci));
         }
         return chain.finish();
     }
-    hipLaunchKernelGGL(ar_prepare_step_kernel, dim3(B), dim3(256), 0, st, b->cached_audio_emb, e->content_emb, b->d_codes, b->T2,
-                       code_off, b->d_last_pos, D, b->ax, b->d_slot, b->d_pos, b->d_step_content, chunk, ci);
+    SVA_TRY(launch_ar_prepare_step(b->cached_audio_emb, e->content_emb, b->d_codes, b->T2, code_off, b->d_last_pos, D, b->ax, b->d_slot, b->d_pos,
+                                   b->d_step_content, chunk, ci, B, st));
     SVA_TRY(ar_layers_pass(b, e->ar_layers, 2 * B, b->d_slot, b->d_pos, e->rope_ar, (float*)b->kv_slow, b->kv_slow_layer,
                            b->kv_slow_slot, c.max_seq_len, b->ax, -2));         // (-2: ar_prepare_step_kernel's row pairs)
     return ar_frame_tail(b, ci, (long)2 * D, (long)D, b->d_codes, b->T2, code_off, 2);
@@ -726,7 +701,7 @@ int ar_frame_tail(sva_batch* b, int ci, long hid_stride, long hid_off, const lon
     const int B = b->B, D = c.ar_dim, chunk = b->p.chunk_frames, ncb = c.num_codebooks, cbs = c.codebook_size;
     hipStream_t st = b->stream;
     // hidden = pre-norm state of the content token (forward_generate :340-341); it also seeds the fast AR
-    hipLaunchKernelGGL(copy_rows2_kernel, dim3(B), dim3(256), 0, st, b->ax, hid_stride, hid_off, b->hidden, b->xf, D);
+    SVA_TRY(launch_copy_rows2(b->ax, hid_stride, hid_off, b->hidden, b->xf, D, B, st));
     const int nstride = c.ar_vocab + ncb * cbs;
     const float* noise = b->noise_on_device ? nullptr : b->d_noise + (long)ci * nstride;
     const int ldn = chunk * nstride;
@@ -779,18 +754,13 @@ int ar_frame_tail(sva_batch* b, int ci, long hid_stride, long hid_off, const lon
         } else {
             SVA_TRY(launch_sampler(lg, B, cbs, ncb * cbs, nz, ldn, b->d_seed, b->d_nframes, 1, cb * cbs, b->p.temperature, b->p.top_p,
                                    b->d_tok_raw + cb, ncb, st));
-            hipLaunchKernelGGL(apply_forced_kernel, dim3((B + 63) / 64), dim3(64), 0, st, b->d_tok_raw, b->d_forced, b->d_use_forced, chunk, ci,
-                               cb, ncb, b->d_tok, B);
+            SVA_TRY(launch_apply_forced(b->d_tok_raw, b->d_forced, b->d_use_forced, chunk, ci, cb, ncb, b->d_tok, B, st));
             if (cb + 1 < ncb) SVA_TRY(launch_gather_rows(e->fast_emb, b->d_tok + cb, ncb, 0, B, D, b->xf, D, st));
         }
     }
     // cached_new_audio_emb = embed(codes) (:834); positions advance by 2 (:835-836)
     SVA_TRY(launch_audio_embed(e->codebook_emb, b->d_tok, ncb, 1, B, ncb, cbs, D, b->cached_audio_emb, D, st));
-    hipLaunchKernelGGL(ar_finish_frame_kernel, dim3((B + 63) / 64), dim3(64), 0, st, b->d_tok, ncb, b->d_last_pos, b->d_nframes,
-                       b->d_pred_hist, b->hist_cap, b->d_step_audio, chunk, ci, codes, codes_ld, code_off, b->d_content_hist,
-                       b->d_ncontent, B, last_pos_inc);
-    SVA_HIP(hipGetLastError());
-    return 0;
+    return launch_ar_finish_frame(b->d_tok, ncb, b->d_last_pos, b->d_nframes, b->d_pred_hist, b->hist_cap, b->d_step_audio, chunk, ci, B, last_pos_inc, st);
 }
 
 // prefill of ONE slot from prompt codes already staged in d_prompt_cc / d_prompt_ac (R frames)
@@ -807,8 +777,8 @@ int ar_prefill_slot(sva_batch* b, int slot, int R, bool tap_logits) {
                       c.timbre_tokens, 1, 1, 1, c.timbre_dim, e->context_in, b->spk, (long)nspk * D, 0, D));
     SVA_TRY(gemm_call(b, b->d_style + (long)slot * c.style_dim, c.style_dim, 0, c.style_dim, 1, 1, 1, 1, 1, c.style_dim, e->style_in,
                       b->spk + (long)c.timbre_tokens * D, D, 0, D));
-    hipLaunchKernelGGL(build_prompt_kernel, dim3(M), dim3(256), 0, st, b->spk, nspk, e->content_emb, e->codebook_emb, e->wait4start,
-                       b->d_prompt_cc, b->d_prompt_ac, b->Pmax, R, d, c.num_codebooks, c.codebook_size, D, b->ax);
+    SVA_TRY(launch_build_prompt(b->spk, nspk, e->content_emb, e->codebook_emb, e->wait4start, b->d_prompt_cc, b->d_prompt_ac, b->Pmax, R, d, c.num_codebooks,
+                                c.codebook_size, D, b->ax, M, st));
     // positions 0..M-1, all rows in this slot
     std::vector<int> hs(M, slot), hp(M);
     for (int i = 0; i < M; ++i) hp[i] = i;
@@ -823,7 +793,7 @@ int ar_prefill_slot(sva_batch* b, int slot, int R, bool tap_logits) {
     // logits / pre-norm hidden state of the last prompt token, as forward_generate returns them for a prefill
     // (dual_ar_stream.py:338-356); nobody consumes them downstream, they are taps for the parity tests ("slow_logits", "hidden")
     if (tap_logits) {       // (the initial prefill only: a re-prefill inside a stream must not overwrite the frame's taps)
-        hipLaunchKernelGGL(copy_rows_kernel, dim3(1), dim3(256), 0, st, b->ax, (long)D, (long)(M - 1) * D, b->hidden + (long)slot * D, D);
+        SVA_TRY(launch_copy_rows(b->ax, (long)D, (long)(M - 1) * D, b->hidden + (long)slot * D, D, 1, st));
         SVA_TRY(launch_rmsnorm_rows(b->hidden + (long)slot * D, D, 0, D, 1, 1, D, e->ar_norm, 1e-5f, b->ahn, D, 0, D, st));
         SVA_TRY(gemm_call(b, b->ahn, D, 0, D, 1, 1, 1, 1, 1, D, e->ar_output, b->slow_logits + (long)slot * c.ar_vocab, c.ar_vocab, 0, c.ar_vocab));
     }
@@ -842,14 +812,12 @@ int ar_delay_fill(sva_batch* b, const std::vector<int>& slots) {
     hipStream_t st = b->stream;
     SVA_HIP(hipMemcpyAsync(b->d_slot_list, slots.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
     SVA_HIP(hipStreamSynchronize(st));          // `slots` may be a temporary
-    hipLaunchKernelGGL(build_delayfill_kernel, dim3(n * rows), dim3(256), 0, st, e->content_emb, b->d_content_hist, b->hist_cap,
-                       b->d_ncontent, b->cached_ref_emb, c.max_delay, b->d_last_pos, d, D, b->ax, b->d_slot, b->d_pos, b->cached_audio_emb,
-                       b->d_slot_list);
+    SVA_TRY(launch_build_delayfill(e->content_emb, b->d_content_hist, b->hist_cap, b->d_ncontent, b->cached_ref_emb, c.max_delay, b->d_last_pos, d, D, b->ax,
+                                   b->d_slot, b->d_pos, b->cached_audio_emb, b->d_slot_list, n, st));
     SVA_TRY(ar_layers_pass(b, e->ar_layers, n * rows, b->d_slot, b->d_pos, e->rope_ar, (float*)b->kv_slow, b->kv_slow_layer,
                            b->kv_slow_slot, c.max_seq_len, b->ax));
-    hipLaunchKernelGGL(add_list_kernel, dim3((n + 63) / 64), dim3(64), 0, st, b->d_last_pos, b->d_slot_list, n, rows);
+    SVA_TRY(launch_add_list(b->d_last_pos, b->d_slot_list, n, rows, st));
     b->slots.delay_filled_for(slots, d);
-    SVA_HIP(hipGetLastError());
     return 0;
 }
 int ar_delay_fill(sva_batch* b) {
@@ -935,9 +903,7 @@ int vocode(sva_batch* b, int T, bool shift, int part) {
                 b->gemm_bytes += 4.0 * ((double)B * (Tl + b->X[i].H) * Cout + kk * Cout * Cout + 3.0 * B * (double)Tl * Cout);
             }
             const long n4 = Tl * Cout / 4;
-            hipLaunchKernelGGL(mean3_kernel, dim3((unsigned)((n4 + 255) / 256), B), dim3(256), 0, st, b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p,
-                               b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4);
-            SVA_HIP(hipGetLastError());
+            SVA_TRY(launch_mean3(b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p, b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4, B, st));
             continue;
         }
         if (b->voc_dma[i] == 2) {
@@ -972,9 +938,7 @@ int vocode(sva_batch* b, int T, bool shift, int part) {
                 for (int br = 0; br < 3 && j < 2; ++br) { y[br] = &b->yb[i][br][j]; yp[br] = b->ybP[i][br][j]; }
             }
             const long n4 = Tl * Cout / 4;
-            hipLaunchKernelGGL(mean3_kernel, dim3((unsigned)((n4 + 255) / 256), B), dim3(256), 0, st, b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p,
-                               b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4);
-            SVA_HIP(hipGetLastError());
+            SVA_TRY(launch_mean3(b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p, b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4, B, st));
             continue;
         }
         if (b->voc_dma[i]) {
@@ -1013,9 +977,7 @@ int vocode(sva_batch* b, int T, bool shift, int part) {
                 for (int br = 0; br < 3 && j < 2; ++br) { y[br] = &b->yb[i][br][j]; yp[br] = b->ybP[i][br][j]; }
             }
             const long n4 = Tl * Cout / 4;
-            hipLaunchKernelGGL(mean3_kernel, dim3((unsigned)((n4 + 255) / 256), B), dim3(256), 0, st, b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p,
-                               b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4);
-            SVA_HIP(hipGetLastError());
+            SVA_TRY(launch_mean3(b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p, b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4, B, st));
             continue;
         }
         // fp32 rows: one launch per conv stage for the three branches (same M, N, Cin; k = 3 / 7 / 11 taps), 12 launches + the mean per
@@ -1037,9 +999,7 @@ int vocode(sva_batch* b, int T, bool shift, int part) {
             for (int br = 0; br < 3; ++br) y[br] = j < 2 ? &b->yb[i][br][j] : &b->y3[i][br];
         }
         const long n4 = Tl * Cout / 4;
-        hipLaunchKernelGGL(mean3_kernel, dim3((unsigned)((n4 + 255) / 256), B), dim3(256), 0, st, b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p,
-                           b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4);
-        SVA_HIP(hipGetLastError());
+        SVA_TRY(launch_mean3(b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p, b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4, B, st));
     }
     SVA_TRY(launch_conv_post_tanh(b->S[5].p, b->S[5].bstride, (long)(b->S[5].H - (e->post_k - 1)) * b->S[5].C, B, (int)Tl, b->S[5].C, e->post_k,
                                   e->post_w, e->post_b, b->pcm_dst ? b->pcm_dst : b->d_pcm, b->pcm_dst ? b->pcm_dst_bstride : 2048L * b->Tv, 0, st, b->d_slot_flag));

@@ -21,6 +21,8 @@ void set_error(const std::string& msg);
 //   ar_batch=0|2     batched persistent decode kernel (ar_batch.hip) off / for every batch size incl. the ones ar_decode.hip serves (A/B, parity)
 //   ar_batch_wgs=N   workgroups of its launch (default: one per 16-column tile of the widest phase, capped by what is resident)
 //   voc_fused_mask=M which narrow HiFiGAN levels run as the fused kernel (bit 0: C = 16, bit 1: C = 32; parity tests)
+//   hist_cap=N       capacity of the content / prediction history rings of batches created from now on (default 4096; a power of two with
+//                    buffer_frames + delay + chunk < N, refused at batch creation otherwise): the ring-wrap tests reach the wrap in a few dozen frames
 //   autotune=1, tune_log=1, tune_table=0, tune_dump=PATH   timed search / its log / ignore the compiled-in table / dump the choices
 //                    (tools/make_tune_table.py); tune_kinds=MASK: only table rows whose kernel kind has its bit set are honoured (bisection)
 //   cu_partition=0|1  force the disjoint CU masks of the pipelined mode (AR 96 | encoder + vocoder 160) off / on (default: by stream count)
@@ -46,7 +48,7 @@ void set_error(const std::string& msg);
 //   f16_weights=0|2   ar_dtype = 1 batched decode on the fp32 copy of the rounded weights instead of gemm_f16w.hip (A/B) / on gemm_f16w.hip even when
 //                     the library was built with a compiler the kernel was not validated with
 struct DebugOptions {
-    int ar_timing = 0, pipe_trace = 0, concurrency = 1, ar_persistent = 1, ar_batch = 1, ar_batch_wgs = 0, voc_fused_mask = -1, autotune = 0, tune_log = 0, tune_table = 1, f16_weights = 1, cu_partition = -1, cu_ar = 0, stream_queues = -1, pipe_skip = 0, planes_dbg = 0, reprefill = 1, planes_dma = 1, voc_dma = -1, voc_dma_variant = 11, planes_lw = 1, planes_min_streams = 10, ar_graph = -1, ar_pairs = 1, head_fuse = 1, tune_kinds = -1;
+    int ar_timing = 0, pipe_trace = 0, concurrency = 1, ar_persistent = 1, ar_batch = 1, ar_batch_wgs = 0, voc_fused_mask = -1, hist_cap = 4096, autotune = 0, tune_log = 0, tune_table = 1, f16_weights = 1, cu_partition = -1, cu_ar = 0, stream_queues = -1, pipe_skip = 0, planes_dbg = 0, reprefill = 1, planes_dma = 1, voc_dma = -1, voc_dma_variant = 11, planes_lw = 1, planes_min_streams = 10, ar_graph = -1, ar_pairs = 1, head_fuse = 1, tune_kinds = -1;
     std::string tune_dump;
 };
 const DebugOptions& debug_options();
@@ -195,7 +197,8 @@ __device__ __forceinline__ void xcd_tile(int swz, int nx, int ny, int& bx, int& 
 // fused HiFiGAN ParallelBlock level for C = 16 / 32 (voc_fused.hip)
 bool voc_level_supported(int C);
 int launch_voc_level(const float* X, long x_bstride, int xH, int C, int B, int Tl, const float* const W[3][6], const float* const bias[3][6],
-                     const int dil[3], float* const y3[3], long y_bstride, const int* frames_done, int rows_per_frame, hipStream_t st);
+                     const int dil[3], float* const y3[3], long y_bstride, const int* frames_done, int rows_per_frame, hipStream_t st,
+                     int* tile_rows_out = nullptr);          // (tile_rows_out: the tile height the launcher chose, for sva_test_voc_level)
 int conv_gemm_prepare_stream(hipStream_t st);
 int conv_gemm_check_errors();          // split-K hand-off fault word of every stream (checked at sva_sync)
 // gemm_split.hip: fp32 GEMM as six bf16 part products on v_mfma_f32_16x16x32_bf16 (variant 0..3 = 128x128, 128x64, 64x128, 64x64)

@@ -2,6 +2,7 @@
 #include "../../include/sva.h"
 #include "kernels.h"
 #include "engine.h"
+#include "engine_kernels.h"
 #include "stream_overlap.h"
 #include "ar_device.h"
 #include <algorithm>
@@ -1330,6 +1331,346 @@ extern "C" int sva_test_token_ops(int device, int kind, const long long* d, cons
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The bookkeeping kernels of the chunk step through their launchers (engine_kernels.h; include/sva.h: sva_test_step_ops; tests/test_gpu_step_ops.py).
+// Whole host arrays in (outputs first carry the caller's sentinels), the launcher, every array the kernel may write back.  Everything a launch
+// would index with -- codes, slots, counters' capacities, row counts -- is checked against the array lengths of the descriptor first: a failed
+// check returns 1 (refused) or -4 (arguments the hook cannot lay out) and nothing is launched.
+// ------------------------------------------------------------------------------------------------------------------------------------
+#define SVA_HOOK_REFUSE(cond, msg)                                  \
+    do {                                                            \
+        if (!(cond)) {                                              \
+            set_error(std::string(msg) + " [" #cond "]");          \
+            return 1;                                               \
+        }                                                           \
+    } while (0)
+namespace {
+struct StepBufs {
+    DevBuf b[13];
+    void* const* ptrs;
+    int up(int i, size_t bytes) {
+        SVA_HOOK_CHECK(ptrs[i], "step ops hook: a required array is missing");
+        return b[i].put(ptrs[i], bytes);
+    }
+    int down(int i, size_t bytes) { return b[i].get(ptrs[i], bytes); }
+    template <typename T> T* at(int i) const { return b[i].as<T>(); }
+};
+bool all_in(const int* v, size_t n, long lo, long hi) {
+    for (size_t i = 0; i < n; ++i)
+        if (v[i] < lo || v[i] >= hi) return false;
+    return true;
+}
+bool all_in64(const long long* v, size_t n, long lo, long hi) {
+    for (size_t i = 0; i < n; ++i)
+        if (v[i] < lo || v[i] >= hi) return false;
+    return true;
+}
+bool is_pow2(long v) { return v >= 1 && (v & (v - 1)) == 0; }
+const long kStepMax = 1L << 26;          // elements of any one array of the hook
+}  // namespace
+
+extern "C" int sva_test_step_ops(int device, int kind, const long long* d, const float* fpar, void* const* ptrs) {
+    (void)fpar;
+    SVA_CHECK(d && ptrs, "sva_test_step_ops: null argument");
+    SVA_HIP(hipSetDevice(device));
+    StepBufs s;
+    s.ptrs = ptrs;
+    const size_t F = sizeof(float), I = sizeof(int), L = sizeof(long long);
+    if (kind == 0) {          // ar_prepare_step
+        const long B = d[0], T2 = d[1], code_off = d[2], D = d[3], chunk = d[4], ci = d[5], n_rows = d[6];
+        SVA_HOOK_CHECK(B >= 1 && B <= 4096 && T2 >= 1 && T2 <= 4096 && D >= 1 && D <= 8192 && chunk >= 1 && chunk <= 64 && n_rows >= 1 && n_rows * D <= kStepMax, "ar_prepare_step hook: sizes");
+        SVA_HOOK_REFUSE(code_off >= 0 && code_off < T2 && ci >= 0 && ci < chunk, "ar_prepare_step hook: code_off / ci outside their arrays");
+        SVA_HOOK_CHECK(ptrs[2], "ar_prepare_step hook: codes");
+        SVA_HOOK_REFUSE(all_in64((const long long*)ptrs[2], (size_t)(B * T2), 0, n_rows), "ar_prepare_step hook: a code outside the content table");
+        SVA_TRY(s.up(4, F * 2 * B * D)); SVA_TRY(s.up(5, I * 2 * B)); SVA_TRY(s.up(6, I * 2 * B)); SVA_TRY(s.up(7, I * B * chunk));
+        SVA_TRY(s.up(0, F * B * D)); SVA_TRY(s.up(1, F * n_rows * D)); SVA_TRY(s.up(2, L * B * T2)); SVA_TRY(s.up(3, I * B));
+        SVA_LAUNCH_OR_REFUSED(launch_ar_prepare_step(s.at<float>(0), s.at<float>(1), s.at<long long>(2), (int)T2, (int)code_off, s.at<int>(3), (int)D, s.at<float>(4),
+                                                     s.at<int>(5), s.at<int>(6), s.at<int>(7), (int)chunk, (int)ci, (int)B, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(s.down(4, F * 2 * B * D)); SVA_TRY(s.down(5, I * 2 * B)); SVA_TRY(s.down(6, I * 2 * B)); SVA_TRY(s.down(7, I * B * chunk));
+        return 0;
+    }
+    if (kind == 1) {          // apply_forced
+        const long B = d[0], ncb = d[1], cb = d[2], chunk = d[3], ci = d[4], use = d[5];
+        SVA_HOOK_CHECK(B >= 1 && B <= 4096 && chunk >= 1 && chunk <= 64 && ncb >= 1, "apply_forced hook: sizes");
+        SVA_HOOK_REFUSE(ncb <= 8 && cb >= 0 && cb < ncb && ci >= 0 && ci < chunk, "apply_forced hook: ncb <= 8, cb < ncb, ci < chunk");
+        const int use_i = use ? 1 : 0;
+        SVA_TRY(s.up(2, I * B * ncb)); SVA_TRY(s.up(0, I * B * ncb)); SVA_TRY(s.up(1, I * B * ncb * chunk)); SVA_TRY(s.b[3].put(&use_i, I));
+        SVA_LAUNCH_OR_REFUSED(launch_apply_forced(s.at<int>(0), s.at<int>(1), s.at<int>(3), (int)chunk, (int)ci, (int)cb, (int)ncb, s.at<int>(2), (int)B, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        return s.down(2, I * B * ncb);
+    }
+    if (kind == 2) {          // ar_finish_frame
+        const long B = d[0], ncb = d[1], cap = d[2], chunk = d[3], ci = d[4], inc = d[5];
+        SVA_HOOK_CHECK(B >= 1 && B <= 4096 && chunk >= 1 && chunk <= 64 && ncb >= 1 && cap >= 1 && cap <= 65536, "ar_finish_frame hook: sizes");
+        SVA_HOOK_REFUSE(ncb <= 8 && is_pow2(cap) && ci >= 0 && ci < chunk, "ar_finish_frame hook: ncb <= 8, a power-of-two capacity, ci < chunk");
+        SVA_TRY(s.up(1, I * B)); SVA_TRY(s.up(2, I * B)); SVA_TRY(s.up(3, I * B * ncb * cap)); SVA_TRY(s.up(4, I * B * ncb * chunk)); SVA_TRY(s.up(0, I * B * ncb));
+        SVA_LAUNCH_OR_REFUSED(launch_ar_finish_frame(s.at<int>(0), (int)ncb, s.at<int>(1), s.at<int>(2), s.at<int>(3), (int)cap, s.at<int>(4), (int)chunk, (int)ci, (int)B,
+                                                     (int)inc, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(s.down(1, I * B)); SVA_TRY(s.down(2, I * B)); SVA_TRY(s.down(3, I * B * ncb * cap)); SVA_TRY(s.down(4, I * B * ncb * chunk));
+        return 0;
+    }
+    if (kind == 3 || kind == 4) {          // append_content (d: B, T2, chunk, cap, counter given) / put_codes (d: B, T2, n_per, cap)
+        const long B = d[0], T2 = d[1], n = d[2], cap = d[3], has_counter = kind == 3 ? d[4] : 0;
+        SVA_HOOK_CHECK(B >= 1 && B <= 4096 && T2 >= 1 && T2 <= 4096 && n >= 1 && cap >= 1 && cap <= 65536, "content ring hook: sizes");
+        SVA_HOOK_REFUSE(is_pow2(cap) && n <= T2 && n <= cap, "content ring hook: a power-of-two capacity, n <= T2, n <= capacity");
+        if (kind == 3) {
+            SVA_TRY(s.up(1, I * B * cap)); SVA_TRY(s.up(2, I * B)); SVA_TRY(s.up(3, I * B * n)); SVA_TRY(s.up(0, L * B * T2));
+            if (has_counter) SVA_TRY(s.up(4, I));
+            SVA_LAUNCH_OR_REFUSED(launch_append_content(s.at<long long>(0), (int)T2, (int)n, s.at<int>(1), (int)cap, s.at<int>(2), s.at<int>(3), (int)B,
+                                                        has_counter ? s.at<int>(4) : nullptr, 0));
+            SVA_HIP(hipDeviceSynchronize());
+            SVA_TRY(s.down(1, I * B * cap)); SVA_TRY(s.down(2, I * B)); SVA_TRY(s.down(3, I * B * n));
+            if (has_counter) SVA_TRY(s.down(4, I));
+            return 0;
+        }
+        SVA_TRY(s.up(1, L * B * T2)); SVA_TRY(s.up(2, I * B * cap)); SVA_TRY(s.up(3, I * B)); SVA_TRY(s.up(0, L * B * n));
+        SVA_LAUNCH_OR_REFUSED(launch_put_codes(s.at<long long>(0), (int)n, s.at<long long>(1), (int)T2, s.at<int>(2), (int)cap, s.at<int>(3), (int)B, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(s.down(1, L * B * T2)); SVA_TRY(s.down(2, I * B * cap)); SVA_TRY(s.down(3, I * B));
+        return 0;
+    }
+    if (kind == 5) {          // build_prompt
+        const long nspk = d[0], R = d[1], dl = d[2], ncb = d[3], cbs = d[4], D = d[5], Pmax = d[6], n_rows = d[7], md = d[8], rows = d[9];
+        SVA_HOOK_CHECK(nspk >= 0 && nspk <= 64 && R >= 1 && R <= 4096 && dl >= 1 && ncb >= 1 && cbs >= 1 && D >= 1 && D <= 8192 && Pmax >= 1 && Pmax <= 8192 && n_rows >= 1 &&
+                       md >= 1 && md <= 64 && rows >= 1 && n_rows * D <= kStepMax && ncb * cbs * D <= kStepMax, "build_prompt hook: sizes");
+        SVA_HOOK_REFUSE(ncb <= 8 && dl <= md && R <= Pmax && rows <= nspk + 2 * R, "build_prompt hook: ncb <= 8, d <= max_delay, R <= Pmax, rows <= nspk + 2 R");
+        SVA_HOOK_CHECK(ptrs[4] && ptrs[5], "build_prompt hook: codes");
+        SVA_HOOK_REFUSE(all_in((const int*)ptrs[4], (size_t)R, 0, n_rows), "build_prompt hook: a content code outside the table");
+        for (long q = 0; q < ncb; ++q)
+            SVA_HOOK_REFUSE(all_in((const int*)ptrs[5] + q * Pmax, (size_t)R, 0, cbs), "build_prompt hook: an audio code outside its codebook");
+        SVA_TRY(s.up(6, F * rows * D));
+        SVA_TRY(s.up(0, F * std::max(nspk, 1L) * D)); SVA_TRY(s.up(1, F * n_rows * D)); SVA_TRY(s.up(2, F * ncb * cbs * D)); SVA_TRY(s.up(3, F * md * D));
+        SVA_TRY(s.up(4, I * R)); SVA_TRY(s.up(5, I * ncb * Pmax));
+        SVA_LAUNCH_OR_REFUSED(launch_build_prompt(s.at<float>(0), (int)nspk, s.at<float>(1), s.at<float>(2), s.at<float>(3), s.at<int>(4), s.at<int>(5), (int)Pmax, (int)R,
+                                                  (int)dl, (int)ncb, (int)cbs, (int)D, s.at<float>(6), (int)rows, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        return s.down(6, F * rows * D);
+    }
+    if (kind == 6) {          // build_delayfill
+        const long B = d[0], n = d[1], dl = d[2], D = d[3], cap = d[4], md = d[5], n_rows = d[6], rows = 2 * dl - 1;
+        SVA_HOOK_CHECK(B >= 1 && B <= 4096 && n >= 1 && n <= B && dl >= 1 && D >= 1 && D <= 8192 && cap >= 1 && cap <= 65536 && md >= 1 && md <= 64 && n_rows >= 1 &&
+                       n_rows * D <= kStepMax && B * md * D <= kStepMax, "build_delayfill hook: sizes");
+        SVA_HOOK_REFUSE(is_pow2(cap) && dl <= md && dl <= cap, "build_delayfill hook: a power-of-two capacity, d <= max_delay, d <= capacity");
+        SVA_HOOK_CHECK(ptrs[1] && ptrs[5], "build_delayfill hook: history / slot list");
+        SVA_HOOK_REFUSE(all_in((const int*)ptrs[5], (size_t)n, 0, B), "build_delayfill hook: a listed slot outside the batch");
+        SVA_HOOK_REFUSE(all_in((const int*)ptrs[1], (size_t)(B * cap), 0, n_rows), "build_delayfill hook: a content code outside the table");
+        SVA_TRY(s.up(6, F * n * rows * D)); SVA_TRY(s.up(7, I * n * rows)); SVA_TRY(s.up(8, I * n * rows)); SVA_TRY(s.up(9, F * B * D));
+        SVA_TRY(s.up(0, F * n_rows * D)); SVA_TRY(s.up(1, I * B * cap)); SVA_TRY(s.up(2, I * B)); SVA_TRY(s.up(3, F * B * md * D)); SVA_TRY(s.up(4, I * B)); SVA_TRY(s.up(5, I * n));
+        SVA_LAUNCH_OR_REFUSED(launch_build_delayfill(s.at<float>(0), s.at<int>(1), (int)cap, s.at<int>(2), s.at<float>(3), (int)md, s.at<int>(4), (int)dl, (int)D, s.at<float>(6),
+                                                     s.at<int>(7), s.at<int>(8), s.at<float>(9), s.at<int>(5), (int)n, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(s.down(6, F * n * rows * D)); SVA_TRY(s.down(7, I * n * rows)); SVA_TRY(s.down(8, I * n * rows)); SVA_TRY(s.down(9, F * B * D));
+        return 0;
+    }
+    if (kind == 7 || kind == 8) {          // build_reprefill / finish_reprefill
+        const long B = d[0], n = d[1], dl = d[2], ncb = d[3], cbs = d[4], D = d[5], nspk = d[6], cap = d[7], md = d[8], n_rows = d[9];
+        SVA_HOOK_CHECK(B >= 1 && B <= 4096 && n >= 1 && dl >= 1 && ncb >= 1 && cbs >= 1 && D >= 1 && D <= 8192 && nspk >= 0 && cap >= 1 && cap <= 65536 && md >= 1 && md <= 64 &&
+                       n_rows >= 1 && n_rows * D <= kStepMax && ncb * cbs * D <= kStepMax && B * md * D <= kStepMax, "re-prefill hook: sizes");
+        SVA_HOOK_REFUSE(n <= 128 && ncb <= 8 && is_pow2(cap) && dl <= md, "re-prefill hook: n <= 128, ncb <= 8, a power-of-two capacity, d <= max_delay");
+        for (int i = 0; i < 5; ++i) SVA_HOOK_CHECK(ptrs[i], "re-prefill hook: per-slot arrays");
+        const int *hs = (const int*)ptrs[0], *hRt = (const int*)ptrs[1], *hnf = (const int*)ptrs[2], *hna = (const int*)ptrs[3], *hnc = (const int*)ptrs[4];
+        SVA_HOOK_REFUSE(all_in(hs, (size_t)n, 0, B), "re-prefill hook: a slot outside the batch");
+        ReprefillArgs a;
+        a.n = (int)n;
+        a.row_off[0] = 0;
+        for (long i = 0; i < n; ++i) {
+            SVA_HOOK_REFUSE(hna[i] >= 0 && hna[i] <= cap && hRt[i] >= 0 && hRt[i] <= 65536, "re-prefill hook: na / Rt out of range");
+            a.slot[i] = hs[i]; a.Rt[i] = hRt[i]; a.nf[i] = hnf[i]; a.na[i] = hna[i]; a.ncon[i] = hnc[i];
+            a.row_off[i + 1] = a.row_off[i] + 2 * hna[i];
+        }
+        const long M = std::max(a.row_off[n], 1);
+        const int ic = kind == 7 ? 7 : -1, ip = kind == 7 ? 8 : 6, it = kind == 7 ? 9 : 7;       // content_hist, pred_hist, ref_tail
+        SVA_HOOK_CHECK(ptrs[ip] && ptrs[it] && (ic < 0 || ptrs[ic]), "re-prefill hook: histories");
+        if (ic >= 0) SVA_HOOK_REFUSE(all_in((const int*)ptrs[ic], (size_t)(B * cap), 0, n_rows), "re-prefill hook: a content code outside the table");
+        SVA_HOOK_REFUSE(all_in((const int*)ptrs[ip], (size_t)(B * ncb * cap), 0, cbs), "re-prefill hook: a predicted code outside its codebook");
+        SVA_HOOK_REFUSE(all_in((const int*)ptrs[it], (size_t)(B * ncb * md), 0, cbs), "re-prefill hook: a reference code outside its codebook");
+        if (kind == 7) {
+            SVA_TRY(s.up(10, F * M * D)); SVA_TRY(s.up(11, I * M)); SVA_TRY(s.up(12, I * M));
+            SVA_TRY(s.up(5, F * n_rows * D)); SVA_TRY(s.up(6, F * ncb * cbs * D)); SVA_TRY(s.up(7, I * B * cap)); SVA_TRY(s.up(8, I * B * ncb * cap)); SVA_TRY(s.up(9, I * B * ncb * md));
+            SVA_LAUNCH_OR_REFUSED(launch_build_reprefill(a, s.at<float>(5), s.at<float>(6), s.at<int>(7), s.at<int>(8), (int)cap, s.at<int>(9), (int)md, (int)dl, (int)ncb, (int)cbs,
+                                                         (int)D, (int)nspk, s.at<float>(10), s.at<int>(11), s.at<int>(12), 0));
+            SVA_HIP(hipDeviceSynchronize());
+            SVA_TRY(s.down(10, F * M * D)); SVA_TRY(s.down(11, I * M)); SVA_TRY(s.down(12, I * M));
+            return 0;
+        }
+        SVA_TRY(s.up(8, F * B * md * D)); SVA_TRY(s.up(9, I * B));
+        SVA_TRY(s.up(5, F * ncb * cbs * D)); SVA_TRY(s.up(6, I * B * ncb * cap)); SVA_TRY(s.up(7, I * B * ncb * md));
+        SVA_LAUNCH_OR_REFUSED(launch_finish_reprefill(a, s.at<float>(5), s.at<int>(6), (int)cap, s.at<int>(7), (int)md, (int)dl, (int)ncb, (int)cbs, (int)D, (int)nspk,
+                                                      s.at<float>(8), s.at<int>(9), 0));
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(s.down(8, F * B * md * D)); SVA_TRY(s.down(9, I * B));
+        return 0;
+    }
+    if (kind == 9 || kind == 10) {          // copy_rows / copy_rows2
+        const long rows = d[0], D = d[1], stride = d[2], off = d[3], s_len = d[4];
+        SVA_HOOK_CHECK(rows >= 1 && rows <= 4096 && D >= 1 && D <= 8192 && s_len >= 1 && s_len <= kStepMax, "copy_rows hook: sizes");
+        SVA_HOOK_REFUSE(stride >= 0 && off >= 0 && off + (rows - 1) * stride + D <= s_len, "copy_rows hook: source rows outside src");
+        SVA_TRY(s.up(1, F * rows * D));
+        if (kind == 10) SVA_TRY(s.up(2, F * rows * D));
+        SVA_TRY(s.up(0, F * s_len));
+        if (kind == 9) SVA_LAUNCH_OR_REFUSED(launch_copy_rows(s.at<float>(0), stride, off, s.at<float>(1), (int)D, (int)rows, 0));
+        else SVA_LAUNCH_OR_REFUSED(launch_copy_rows2(s.at<float>(0), stride, off, s.at<float>(1), s.at<float>(2), (int)D, (int)rows, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(s.down(1, F * rows * D));
+        if (kind == 10) SVA_TRY(s.down(2, F * rows * D));
+        return 0;
+    }
+    if (kind == 11 || kind == 12) {          // broadcast_row (d: B, bstride, C, len, src_row, lo, hi) / fill_rows (d: B, bstride, C, len, rows)
+        const long B = d[0], bs = d[1], C = d[2], len = d[3];
+        SVA_HOOK_CHECK(B >= 1 && B <= 4096 && C >= 1 && C <= 8192 && len >= 1 && len <= kStepMax && bs >= 0, "row fill hook: sizes");
+        if (kind == 11) {
+            const long src_row = d[4], lo = d[5], hi = d[6];
+            SVA_HOOK_REFUSE(src_row >= 0 && lo >= 0 && hi > lo && hi <= 65535 && (B - 1) * bs + std::max(hi, src_row + 1) * C <= len, "broadcast_row hook: rows outside the buffer");
+            SVA_TRY(s.up(0, F * len));
+            SVA_LAUNCH_OR_REFUSED(launch_broadcast_row(s.at<float>(0), bs, (int)src_row, (int)lo, (int)hi, (int)C, (int)B, 0));
+        } else {
+            const long rows = d[4];
+            SVA_HOOK_REFUSE(rows >= 0 && rows <= 65535 && (B - 1) * bs + rows * C <= len, "fill_rows hook: rows outside the buffer");
+            SVA_TRY(s.up(0, F * len)); SVA_TRY(s.up(1, F * C));
+            SVA_LAUNCH_OR_REFUSED(launch_fill_rows(s.at<float>(0), bs, (int)C, s.at<float>(1), (int)rows, (int)B, 0));
+        }
+        SVA_HIP(hipDeviceSynchronize());
+        return s.down(0, F * len);
+    }
+    if (kind >= 13 && kind <= 16) {          // inc (d: len, v) / add_list (d: len, v, n) / add_vec (d: len, v, n) / set_slot_i32 (d: len, v, slot)
+        const long len = d[0], v = d[1], x = kind == 13 ? 0 : d[2];
+        SVA_HOOK_CHECK(len >= 1 && len <= kStepMax, "counter hook: sizes");
+        SVA_TRY(s.up(0, I * len));
+        if (kind == 13) SVA_LAUNCH_OR_REFUSED(launch_inc(s.at<int>(0), (int)v, 0));
+        else if (kind == 14) {
+            SVA_HOOK_CHECK(x >= 1 && x <= kStepMax && ptrs[1], "add_list hook: list");
+            SVA_HOOK_REFUSE(all_in((const int*)ptrs[1], (size_t)x, 0, len), "add_list hook: a listed index outside the array");
+            SVA_TRY(s.up(1, I * x));
+            SVA_LAUNCH_OR_REFUSED(launch_add_list(s.at<int>(0), s.at<int>(1), (int)x, (int)v, 0));
+        } else if (kind == 15) {
+            SVA_HOOK_REFUSE(x >= 1 && x <= len, "add_vec hook: n outside the array");
+            SVA_LAUNCH_OR_REFUSED(launch_add_vec(s.at<int>(0), (int)x, (int)v, 0));
+        } else {
+            SVA_HOOK_REFUSE(x >= 0 && x < len, "set_slot_i32 hook: slot outside the array");
+            SVA_LAUNCH_OR_REFUSED(launch_set_slot_i32(s.at<int>(0), (int)x, (int)v, 0));
+        }
+        SVA_HIP(hipDeviceSynchronize());
+        return s.down(0, I * len);
+    }
+    if (kind == 17) {          // history_rows_copy: d n_desc, n_slots, slot_lo, to_live, len(buf), len(save), save_bstride, then (offset, bstride, H, C, save offset) per descriptor
+        const long nd = d[0], ns = d[1], slot_lo = d[2], to_live = d[3], b_len = d[4], s_len = d[5], sbs = d[6];
+        SVA_HOOK_CHECK(nd >= 0 && nd <= 64 && ns >= 1 && ns <= 4096 && slot_lo >= 0 && slot_lo <= 4096 && b_len >= 1 && b_len <= kStepMax && s_len >= 1 && s_len <= kStepMax && sbs >= 0,
+                       "history_rows_copy hook: sizes");
+        SVA_TRY(s.up(0, F * b_len)); SVA_TRY(s.up(1, F * s_len));
+        std::vector<ShiftDesc> hd(nd);
+        std::vector<long> offs(nd);
+        const long top = slot_lo + ns - 1;
+        for (long i = 0; i < nd; ++i) {
+            const long off = d[7 + 5 * i], bs = d[8 + 5 * i], H = d[9 + 5 * i], C = d[10 + 5 * i], so = d[11 + 5 * i];
+            SVA_HOOK_REFUSE(off >= 0 && bs >= 0 && H >= 0 && C >= 1 && H < (1 << 20) && C < (1 << 20) && so >= 0 && off + top * bs + H * C <= b_len && top * sbs + so + H * C <= s_len,
+                            "history_rows_copy hook: rows outside the buffers");
+            hd[i].ptr = s.at<float>(0) + off; hd[i].bstride = bs; hd[i].H = (int)H; hd[i].T = 0; hd[i].C = (int)C; hd[i].pad = 0;
+            offs[i] = so;
+        }
+        SVA_TRY(s.b[2].put(hd.data(), sizeof(ShiftDesc) * (size_t)nd)); SVA_TRY(s.b[3].put(offs.data(), sizeof(long) * (size_t)nd));
+        SVA_LAUNCH_OR_REFUSED(launch_history_rows_copy(s.at<ShiftDesc>(2), (int)nd, s.at<long>(3), s.at<float>(1), sbs, (int)slot_lo, (int)ns, (int)to_live, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(s.down(0, F * b_len));
+        return s.down(1, F * s_len);
+    }
+    if (kind == 18) {          // history_rows_move: d n_desc, slot, len(src), len(dst), then (source offset, destination offset, destination bstride, H, C) per descriptor
+        const long nd = d[0], slot = d[1], s_len = d[2], t_len = d[3];
+        SVA_HOOK_CHECK(nd >= 0 && nd <= 64 && slot >= 0 && slot <= 4096 && s_len >= 1 && s_len <= kStepMax && t_len >= 1 && t_len <= kStepMax, "history_rows_move hook: sizes");
+        SVA_TRY(s.up(1, F * t_len)); SVA_TRY(s.up(0, F * s_len));
+        std::vector<ShiftDesc> sd(nd), dd(nd);
+        for (long i = 0; i < nd; ++i) {
+            const long so = d[4 + 5 * i], to = d[5 + 5 * i], bs = d[6 + 5 * i], H = d[7 + 5 * i], C = d[8 + 5 * i];
+            SVA_HOOK_REFUSE(so >= 0 && to >= 0 && bs >= 0 && H >= 0 && C >= 1 && H < (1 << 20) && C < (1 << 20) && so + H * C <= s_len && to + slot * bs + H * C <= t_len,
+                            "history_rows_move hook: rows outside the buffers");
+            sd[i].ptr = s.at<float>(0) + so; sd[i].bstride = 0; sd[i].H = (int)H; sd[i].T = 0; sd[i].C = (int)C; sd[i].pad = 0;
+            dd[i].ptr = s.at<float>(1) + to; dd[i].bstride = bs; dd[i].H = (int)H; dd[i].T = 0; dd[i].C = (int)C; dd[i].pad = 0;
+        }
+        SVA_TRY(s.b[2].put(sd.data(), sizeof(ShiftDesc) * (size_t)nd)); SVA_TRY(s.b[3].put(dd.data(), sizeof(ShiftDesc) * (size_t)nd));
+        SVA_LAUNCH_OR_REFUSED(launch_history_rows_move(s.at<ShiftDesc>(2), s.at<ShiftDesc>(3), (int)nd, (int)slot, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        return s.down(1, F * t_len);
+    }
+    if (kind == 19) {          // put_row
+        const long n_rows = d[0], code = d[1], D = d[2];
+        SVA_HOOK_CHECK(n_rows >= 1 && D >= 1 && D <= 8192 && n_rows * D <= kStepMax, "put_row hook: sizes");
+        SVA_HOOK_REFUSE(code >= 0 && code < n_rows, "put_row hook: the code outside the table");
+        SVA_TRY(s.up(1, F * D)); SVA_TRY(s.up(0, F * n_rows * D));
+        SVA_LAUNCH_OR_REFUSED(launch_put_row(s.at<float>(0), code, (int)D, s.at<float>(1), 0));
+        SVA_HIP(hipDeviceSynchronize());
+        return s.down(1, F * D);
+    }
+    if (kind == 20) {          // prepare_offline_step
+        const long D = d[0], step = d[1], n_rem = d[2], n_rows = d[3];
+        SVA_HOOK_CHECK(D >= 1 && D <= 8192 && n_rem >= 1 && n_rem <= kStepMax && n_rows >= 1 && n_rows * D <= kStepMax && ptrs[2], "prepare_offline_step hook: sizes");
+        SVA_HOOK_REFUSE(step >= 0 && step < n_rem && all_in64((const long long*)ptrs[2], (size_t)n_rem, 0, n_rows), "prepare_offline_step hook: step / code outside their arrays");
+        SVA_TRY(s.up(4, F * 2 * D)); SVA_TRY(s.up(5, I * 2)); SVA_TRY(s.up(6, I * 2));
+        SVA_TRY(s.up(0, F * D)); SVA_TRY(s.up(1, F * n_rows * D)); SVA_TRY(s.up(2, L * n_rem)); SVA_TRY(s.up(3, I));
+        SVA_LAUNCH_OR_REFUSED(launch_prepare_offline_step(s.at<float>(0), s.at<float>(1), s.at<long long>(2), (int)step, s.at<int>(3), (int)D, s.at<float>(4), s.at<int>(5),
+                                                          s.at<int>(6), 0));
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(s.down(4, F * 2 * D)); SVA_TRY(s.down(5, I * 2));
+        return s.down(6, I * 2);
+    }
+    if (kind == 21) {          // mean3
+        const long B = d[0], ybs = d[1], y_len = d[2], obs = d[3], o_off = d[4], o_len = d[5], n4 = d[6];
+        SVA_HOOK_CHECK(B >= 1 && B <= 4096 && y_len >= 1 && y_len <= kStepMax && o_len >= 1 && o_len <= kStepMax, "mean3 hook: sizes");
+        SVA_HOOK_REFUSE(n4 >= 1 && ybs >= 0 && obs >= 0 && o_off >= 0 && (B - 1) * ybs + 4 * n4 <= y_len && (B - 1) * obs + o_off + 4 * n4 <= o_len, "mean3 hook: lanes outside the arrays");
+        SVA_TRY(s.up(3, F * o_len)); SVA_TRY(s.up(0, F * y_len)); SVA_TRY(s.up(1, F * y_len)); SVA_TRY(s.up(2, F * y_len));
+        SVA_LAUNCH_OR_REFUSED(launch_mean3(s.at<float>(0), s.at<float>(1), s.at<float>(2), ybs, s.at<float>(3), obs, o_off, n4, (int)B, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        return s.down(3, F * o_len);
+    }
+    SVA_HOOK_CHECK(kind == 22, "step ops hook: kind 0 .. 22");          // copy_tokens
+    const long B = d[0], Ht = d[1], gap = d[2], c = d[3], T2 = d[4], D = d[5], tbs = d[6], t_len = d[7], dbs = d[8], d_len = d[9];
+    SVA_HOOK_CHECK(B >= 1 && B <= 4096 && D >= 1 && D <= 8192 && t_len >= 1 && t_len <= kStepMax && d_len >= 1 && d_len <= kStepMax, "copy_tokens hook: sizes");
+    SVA_HOOK_REFUSE(Ht >= 0 && gap >= 0 && c >= 1 && T2 >= Ht + c && Ht + c <= 65535 && tbs >= 0 && dbs >= 0 && (B - 1) * tbs + (Ht + gap + c) * D <= t_len && (B - 1) * dbs + T2 * D <= d_len,
+                    "copy_tokens hook: rows outside the arrays");
+    SVA_TRY(s.up(1, F * d_len)); SVA_TRY(s.up(0, F * t_len));
+    SVA_LAUNCH_OR_REFUSED(launch_copy_tokens(s.at<float>(0), tbs, (int)Ht, (int)gap, (int)c, s.at<float>(1), dbs, (int)T2, (int)D, (int)B, 0));
+    SVA_HIP(hipDeviceSynchronize());
+    return s.down(1, F * d_len);
+}
+
+// launch_voc_level (voc_fused.hip) from host arrays.  d: C, B, Tl, xH, x_bstride, len(X), y_bstride, len(Y), dil0, dil1, dil2, rows_per_frame, frames_done;
+// ptrs: 0 X, 1 .. 3 the branch outputs Y3[br] (in / out, len(Y) each), 4 W: the 18 weights back to back in (branch, conv) order, [C][k C] each, k = 3 / 7 / 11,
+// 5 bias [18][C], 6 int [1] (out): the tile height TR the launcher chose.  Returns 1 when the launcher refuses.
+extern "C" int sva_test_voc_level(int device, const long long* d, const float* fpar, void* const* ptrs) {
+    (void)fpar;
+    SVA_CHECK(d && ptrs, "sva_test_voc_level: null argument");
+    SVA_HIP(hipSetDevice(device));
+    const long C = d[0], B = d[1], Tl = d[2], xH = d[3], xbs = d[4], x_len = d[5], ybs = d[6], y_len = d[7], rpf = d[11], fd = d[12];
+    const int dil[3] = {(int)d[8], (int)d[9], (int)d[10]};
+    SVA_HOOK_CHECK(C >= 1 && C <= 64 && B >= 1 && B <= 64 && Tl >= 1 && Tl <= (1 << 16) && xH >= 0 && xH <= 4096 && xbs >= 0 && ybs >= 0 && x_len >= 1 && x_len <= kStepMax &&
+                   y_len >= 1 && y_len <= kStepMax && rpf >= 0 && fd >= 0, "voc_level hook: sizes");
+    for (int j = 0; j < 3; ++j) SVA_HOOK_CHECK(dil[j] >= 1 && dil[j] <= 8, "voc_level hook: dilations 1 .. 8");
+    SVA_HOOK_CHECK((B - 1) * xbs + (xH + Tl) * C <= x_len && (B - 1) * ybs + Tl * C <= y_len, "voc_level hook: rows outside X / Y");
+    SVA_HOOK_CHECK((xbs * 4) % 16 == 0 && (ybs * 4) % 16 == 0, "voc_level hook: 16-byte rows");
+    for (int i = 0; i < 7; ++i) SVA_HOOK_CHECK(ptrs[i], "voc_level hook: a required array is missing");
+    static const int ks[3] = {3, 7, 11};
+    const long w_total = 6 * (3 + 7 + 11) * C * C;
+    DevBuf bx, by[3], bw, bb, bf;
+    for (int br = 0; br < 3; ++br) SVA_TRY(by[br].put(ptrs[1 + br], sizeof(float) * (size_t)y_len));
+    SVA_TRY(bx.put(ptrs[0], sizeof(float) * (size_t)x_len));
+    SVA_TRY(bw.put(ptrs[4], sizeof(float) * (size_t)w_total));
+    SVA_TRY(bb.put(ptrs[5], sizeof(float) * (size_t)(18 * C)));
+    const int fdi = (int)fd;
+    SVA_TRY(bf.put(&fdi, sizeof(int)));
+    const float* W[3][6];
+    const float* bias[3][6];
+    float* y3[3];
+    long wo = 0;
+    for (int br = 0; br < 3; ++br) {
+        for (int q = 0; q < 6; ++q) { W[br][q] = bw.as<float>() + wo; wo += (long)ks[br] * C * C; bias[br][q] = bb.as<float>() + (long)(br * 6 + q) * C; }
+        y3[br] = by[br].as<float>();
+    }
+    SVA_LAUNCH_OR_REFUSED(launch_voc_level(bx.as<float>(), xbs, (int)xH, (int)C, (int)B, (int)Tl, W, bias, dil, y3, ybs, bf.as<int>(), (int)rpf, 0, (int*)ptrs[6]));
+    SVA_HIP(hipDeviceSynchronize());
+    for (int br = 0; br < 3; ++br) SVA_TRY(by[br].get(ptrs[1 + br], sizeof(float) * (size_t)y_len));
+    return 0;
+}
+
 // Do the four chain streams of a pipelined batch (main, encoder side stream, AR, vocoder) each have a hardware queue of their own?  For
 // every unordered pair (X, Y), in the order (main, aux0) (main, sa) (main, sv) (aux0, sa) (aux0, sv) (sa, sv): a bounded waiter kernel on
 // X and, enqueued after it, a setter kernel on Y (stream_overlap.h); pair_ok[k] = 1 when the waiter saw the setter's store, 0 when it ran
@@ -1413,9 +1754,9 @@ extern "C" int sva_test_slot_book(const int* cfg, const int* ops, int n_ops, int
         StepPlan plan;
         std::vector<int> acts;
         int one_pass = -1, prime = -1;
-        if (op == 1 || op == 3 || op == 4) SVA_CHECK(slot >= 0 && slot < B, "sva_test_slot_book: slot out of range");
+        if (op == 1 || op == 3 || op == 4 || op == 5) SVA_CHECK(slot >= 0 && slot < B, "sva_test_slot_book: slot out of range");
         if (op == 1 || op == 3) SVA_CHECK(R > delay, "sva_test_slot_book: the prompt must be longer than the delay");
-        if (op >= 2) SVA_CHECK(begun, "sva_test_slot_book: step / restart / retire before begin");
+        if (op >= 2 && op != 5) SVA_CHECK(begun, "sva_test_slot_book: step / restart / retire before begin");
         if (op == 0) {
             SVA_CHECK(book.all_prefilled(), "sva_test_slot_book: begin before every slot was prefilled");
             book.begin();
@@ -1450,6 +1791,11 @@ extern "C" int sva_test_slot_book(const int* cfg, const int* ops, int n_ops, int
             book.restart(slot, std::move(p), nspk, kSlotOutputMuted);
         } else if (op == 4) {
             book.retire(slot, kSlotInputMuted | kSlotOutputMuted);
+        } else if (op == 5) {          // a prompt of delay + 1 + R frames whose stored copy is truncated to R frames (max_prompt_frames = R)
+            SVA_CHECK(R >= 1, "sva_test_slot_book: a stored prompt has at least one frame");
+            const std::vector<int64_t> cc((size_t)(delay + 1 + R), 0);
+            const std::vector<int32_t> ac((size_t)(delay + 1 + R), 0);
+            book.prefilled(slot, nspk, delay + 1 + R, R, 1, cc.data(), ac.data());
         } else {
             SVA_CHECK(false, "sva_test_slot_book: unknown op");
         }

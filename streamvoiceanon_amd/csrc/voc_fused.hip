@@ -161,7 +161,7 @@ bool voc_level_supported(int C) { return C == 16 || C == 32; }
 
 // X: level input (after the transposed conv); res[br][j]: the level's ResBlock convs; y3: the three branch outputs
 int launch_voc_level(const float* X, long x_bstride, int xH, int C, int B, int Tl, const float* const W[3][6], const float* const bias[3][6],
-                     const int dil[3], float* const y3[3], long y_bstride, const int* frames_done, int rows_per_frame, hipStream_t st) {
+                     const int dil[3], float* const y3[3], long y_bstride, const int* frames_done, int rows_per_frame, hipStream_t st, int* tile_rows_out) {
     SVA_CHECK(voc_level_supported(C), "voc_level: unsupported channel count");
     const int rf_max = 10 * 2 * (dil[0] + dil[1] + dil[2]);
     SVA_CHECK(xH >= rf_max, "voc_level: the level input keeps too little history");
@@ -171,6 +171,7 @@ int launch_voc_level(const float* X, long x_bstride, int xH, int C, int B, int T
     const int tr_max = three ? (C == 16 ? 256 : 128) : (C == 16 ? 512 : 256);
     int TR = 64;
     while (TR < tr_max && (long)((Tl + 2 * TR - 1) / (2 * TR)) * 3 * B >= 256) TR *= 2;
+    if (tile_rows_out) *tile_rows_out = TR;
     VocLevelArgs a;
     a.X = X; a.x_bstride = x_bstride; a.xH = xH; a.Tl = Tl; a.TR = TR; a.rows_alloc = TR + rf_max + 16; a.three = three;
     const size_t act_bytes = sizeof(float) * (three ? 3 : 2) * (size_t)a.rows_alloc * (C + 4);

@@ -131,6 +131,8 @@ def load_library():
     lib.sva_test_ar_device.argtypes = [i32, i32, vp, vp, vp]
     lib.sva_test_gemv.argtypes = [i32, vp, vp, vp]
     lib.sva_test_token_ops.argtypes = [i32, i32, vp, vp, vp]
+    lib.sva_test_step_ops.argtypes = [i32, i32, vp, vp, vp]
+    lib.sva_test_voc_level.argtypes = [i32, vp, vp, vp]
     lib.sva_test_gemm_f16w.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp]
     lib.sva_test_gemm_planes.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.sva_test_gemm_h16.argtypes = [i32] * 8 + [vp] * 5 + [i32] * 4 + [vp, i32, vp]
@@ -148,7 +150,7 @@ EXPORTED_SYMBOLS = [
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
     "sva_op_geglu", "sva_op_l2norm", "sva_ops_capture_begin", "sva_ops_capture_end", "sva_ops_graph_launch", "sva_ops_graph_free",
-    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_test_sampler_launch", "sva_test_ar_device", "sva_test_gemv", "sva_test_token_ops", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
+    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_test_sampler_launch", "sva_test_ar_device", "sva_test_gemv", "sva_test_token_ops", "sva_test_step_ops", "sva_test_voc_level", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
 ]
 
 
@@ -836,6 +838,28 @@ def test_gemv(W, Y, M, N, K, X=None, ldx=None, ldy=None, y_off=0, norm_w=None, b
             mode, int(bool(alias)), S, H]
     _hook_call(lib.sva_test_gemv, "sva_test_gemv", desc, [eps], [X, W, norm_w, bias, res, Y], device)
     return Y
+
+
+STEP_OPS = {"ar_prepare_step": 0, "apply_forced": 1, "ar_finish_frame": 2, "append_content": 3, "put_codes": 4, "build_prompt": 5, "build_delayfill": 6,
+            "build_reprefill": 7, "finish_reprefill": 8, "copy_rows": 9, "copy_rows2": 10, "broadcast_row": 11, "fill_rows": 12, "inc": 13, "add_list": 14,
+            "add_vec": 15, "set_slot_i32": 16, "history_rows_copy": 17, "history_rows_move": 18, "put_row": 19, "prepare_offline_step": 20, "mean3": 21,
+            "copy_tokens": 22}          # kernel of csrc/engine_kernels.hip -> kind of sva_test_step_ops
+
+
+def test_step_op(name, desc, arrays, device=0):
+    """the launcher of one bookkeeping kernel (sva_test_step_ops, include/sva.h: descriptor and array order per kind); the "(io)" arrays are updated in
+    place; raises Refused when the hook or the launcher declines the arguments"""
+    _hook_call(load_library().sva_test_step_ops, "sva_test_step_ops", desc, [], arrays, device, STEP_OPS[name])
+
+
+def test_voc_level(X, Y3, W, bias, C, B, Tl, xH, x_bstride, y_bstride, dil, rows_per_frame, frames_done, device=0):
+    """launch_voc_level over flat float32 arrays: X, the three branch outputs Y3 (updated in place), the 18 weights W back to back, bias [18, C]
+    -> the tile height the launcher chose"""
+    assert all(a.dtype == np.float32 and a.flags.c_contiguous for a in [X, W, bias] + list(Y3)) and len(Y3) == 3 and Y3[0].size == Y3[1].size == Y3[2].size
+    tr = np.full(1, -1, np.int32)
+    _hook_call(load_library().sva_test_voc_level, "sva_test_voc_level",
+               [C, B, Tl, xH, x_bstride, X.size, y_bstride, Y3[0].size, dil[0], dil[1], dil[2], rows_per_frame, frames_done], [], [X, Y3[0], Y3[1], Y3[2], W, bias, tr], device)
+    return int(tr[0])
 
 
 def test_logit_edits(logits, rows, V, ldl, prev, suppress, penalty, W=None, prev_cap=4096, device=0):

@@ -458,3 +458,164 @@ def ring_write(ring, chunk, step):
     n, N = chunk.shape[1], ring.shape[1]
     out[:, (step * n + np.arange(n)) % N] = chunk
     return out
+
+
+# ---- the chunk step's bookkeeping kernels (csrc/engine_kernels.hip): integer and copy models, exact -----------------------------------------
+def ring_append(hist, count, new):
+    """hist [B, cap] (cap a power of two), count [B], new [B, n]: entry (count[b] + i) mod cap of ring b <- new[b, i] -> (hist, count + n)
+    (append_content / put_codes; one codebook row of ar_finish_frame)"""
+    hist, count, new = np.array(hist), np.array(count), np.asarray(new)
+    cap = hist.shape[-1]
+    for b in range(hist.shape[0]):
+        for i in range(new.shape[1]):
+            hist[b, (int(count[b]) + i) % cap] = new[b, i]
+    return hist, count + new.shape[1]
+
+
+def ring_window(hist_row, end, n):
+    """the n entries in front of counter `end` of one ring row, oldest first: what a list that grew to `end` entries holds at [end - n, end)"""
+    cap = hist_row.shape[-1]
+    return hist_row[..., (end - n + np.arange(n)) % cap]
+
+
+def finish_frame(tok, last_pos, nframes, pred_hist, step_audio, ci, last_pos_inc):
+    """tok [B, ncb] -> pred_hist [B, ncb, cap] at nframes mod cap, step_audio [B, ncb, chunk] column ci; nframes + 1, last_pos + last_pos_inc"""
+    pred_hist, step_audio = np.array(pred_hist), np.array(step_audio)
+    for q in range(tok.shape[1]):
+        pred_hist[:, q], _ = ring_append(pred_hist[:, q], nframes, tok[:, q:q + 1])
+    step_audio[:, :, ci] = tok
+    return np.asarray(last_pos) + last_pos_inc, np.asarray(nframes) + 1, pred_hist, step_audio
+
+
+def apply_forced(raw, forced, use_forced, ci, cb, tok):
+    """tok [B, ncb]: column cb <- forced[:, cb, ci] when use_forced else raw[:, cb]; the other columns stay"""
+    tok = np.array(tok)
+    tok[:, cb] = forced[:, cb, ci] if use_forced else raw[:, cb]
+    return tok
+
+
+def prepare_step(cached_audio_emb, content_emb, codes, code_off, last_pos, step_content, ci):
+    """decode_one's two tokens per stream: x rows (2 b, 2 b + 1) = (cached_audio_emb[b], content_emb[codes[b, code_off]]) in slot b at
+    positions last_pos[b] + 1, + 2 -> (x [2 B, D], slot [2 B], pos [2 B], step_content with column ci = the code)"""
+    B = codes.shape[0]
+    code = np.asarray(codes)[:, code_off]
+    x = np.stack([cached_audio_emb, content_emb[code]], axis=1).reshape(2 * B, -1)
+    slot = np.repeat(np.arange(B), 2)
+    pos = (np.asarray(last_pos)[:, None] + np.array([1, 2])).reshape(-1)
+    step_content = np.array(step_content)
+    step_content[:, ci] = code
+    return x, slot, pos, step_content
+
+
+def prompt_rows(content_emb, codebook_emb, wait4start, cc, ac, d, codebook_size):
+    """the rows of DualAR.prefill_prompt behind the speaker prefix, R frames: row 2 i = content_emb[cc[i]], row 2 i + 1 = wait4start[i] for i < d,
+    else the in-order float32 codebook sum of frame i - d -> (rows [2 R, D], cached_ref_emb [d, D] = the embeddings of the last d frames)"""
+    cc, ac = np.asarray(cc), np.asarray(ac)
+    R = cc.shape[0]
+    emb = audio_embed(codebook_emb, ac[:, :R].T, codebook_size)
+    rows = np.empty((2 * R, content_emb.shape[1]), np.float32)
+    rows[0::2] = content_emb[cc]
+    for i in range(R):
+        rows[2 * i + 1] = wait4start[i] if i < d else emb[i - d]
+    return rows, emb[R - d:]
+
+
+def delayfill_rows(content_emb, content_hist, ncontent, cached_ref_emb, last_pos, d, slot_list):
+    """prefill_src_condition4delay per listed slot: [c_0, r_0, ..., c_{d-1}] with c = the slot's last d content codes (ring), r = cached_ref_emb
+    -> (x [n (2 d - 1), D], slot, pos = last_pos + 1 + r, cached_new_audio_emb per listed slot [n, D] = r_{d-1})"""
+    xs, slots, poss, cna = [], [], [], []
+    for b in slot_list:
+        codes = ring_window(content_hist[b], int(ncontent[b]), d)
+        seq = np.stack([content_emb[codes], cached_ref_emb[b, :d]], axis=1).reshape(2 * d, -1)
+        cna.append(seq[-1])
+        xs.append(seq[:-1])
+        slots += [b] * (2 * d - 1)
+        poss += [int(last_pos[b]) + 1 + r for r in range(2 * d - 1)]
+    return np.concatenate(xs).astype(np.float32), np.array(slots), np.array(poss), np.stack(cna).astype(np.float32)
+
+
+def _reprefill_audio(pred_hist_b, ref_tail_b, Rt, nf, na):
+    """the concatenated audio codes [ref (its last max_delay frames are known), the last na predicted frames] as a dict frame -> codes [ncb]"""
+    md = ref_tail_b.shape[1]
+    ac = {Rt - md + k: ref_tail_b[:, k] for k in range(md) if Rt - md + k >= 0}        # (the upload leaves the entries in front of frame 0 unset)
+    new = ring_window(pred_hist_b, nf, na)
+    ac.update({Rt + k: new[:, k] for k in range(na)})
+    return ac
+
+
+def reprefill_rows(content_emb, codebook_emb, wait4start, content_hist, pred_hist, ref_tail, slots, Rt, nf, na, ncon, d, codebook_size, nspk):
+    """the re-prefill of StreamSession.process_one_chunk seen from the rings: per due slot the rows of frames Rt .. Rt + na - 1 of
+    prefill_prompt([ref, src_content[-na - d:-d]], [ref_audio, pred[-na:]]) (everything in front is the cached prefix) -> (x, slot_out, pos_out)"""
+    xs, so, po = [], [], []
+    for b, R0, f, a, c in zip(slots, Rt, nf, na, ncon):
+        ac = _reprefill_audio(pred_hist[b], ref_tail[b], R0, f, a)
+        cont = ring_window(content_hist[b], c - d, a)
+        for k in range(a):
+            i = R0 + k
+            xs.append(content_emb[cont[k]])
+            xs.append(wait4start[i] if i < d else audio_embed(codebook_emb, ac[i - d][None], codebook_size)[0])
+            so += [b, b]
+            po += [nspk + 2 * i, nspk + 2 * i + 1]
+    return np.stack(xs).astype(np.float32), np.array(so), np.array(po)
+
+
+def reprefill_finish(codebook_emb, pred_hist, ref_tail, slots, Rt, nf, na, d, codebook_size, nspk):
+    """cached_ref_emb [n, d, D] = the embeddings of the new prompt's last d audio frames, last_pos [n] = its last position"""
+    embs, lps = [], []
+    for b, R0, f, a in zip(slots, Rt, nf, na):
+        ac = _reprefill_audio(pred_hist[b], ref_tail[b], R0, f, a)
+        embs.append(audio_embed(codebook_emb, np.stack([ac[R0 + a - d + k] for k in range(d)]), codebook_size))
+        lps.append(nspk + 2 * (R0 + a) - 1)
+    return np.stack(embs), np.array(lps)
+
+
+def copy_tokens(tok, d2c, Ht, gap, c):
+    """tok [B, >= Ht + gap + c, D]: rows [0, Ht) -> d2c rows [0, Ht), rows [Ht + gap, Ht + gap + c) -> the last c rows of d2c [B, T2, D]"""
+    out = np.array(d2c)
+    out[:, :Ht] = tok[:, :Ht]
+    out[:, out.shape[1] - c:] = tok[:, Ht + gap:Ht + gap + c]
+    return out
+
+
+def mean3(a, b, c):
+    """ParallelBlock's mean of the three branches as the kernel evaluates it: ((a + b) + c) / 3 in float32"""
+    a, b, c = (np.asarray(v, np.float32) for v in (a, b, c))
+    return ((a + b) + c) / np.float32(3.0)
+
+
+# ---- fused HiFiGAN level (csrc/voc_fused.hip) ---------------------------------------------------------------------------------------------
+VOC_LEVEL_K = (3, 7, 11)
+
+
+def _causal_conv_rows(x, w, b, k, dil, dt):
+    """x [B, N, C] -> bias + sum over taps t of x[r - (k - 1 - t) dil] @ w[:, t C:(t + 1) C].T, rows in front of the array read as zero"""
+    B, N, C = x.shape
+    xp = np.concatenate([np.zeros((B, (k - 1) * dil, C), dt), x], axis=1)
+    acc = np.broadcast_to(np.asarray(b, dt), (B, N, w.shape[0])).copy()
+    for t in range(k):
+        acc = acc + _matmul(xp[:, t * dil:t * dil + N], np.asarray(w[:, t * C:(t + 1) * C], dt).T, dt)
+    return acc
+
+
+def voc_level(x_hist_and_new, W, bias, dil, frames_before, dt=np.float64, hist=None):
+    """The three ResBlock1 branches y += c2(silu(c1(silu(y)))) for the three dilations, kernel sizes 3 / 7 / 11, over x_hist_and_new [B, hist + T, C]
+    (`hist` history rows -- default: the chain's receptive field 20 sum(dil), what the kernel asks for -- then T new rows; channel-last).
+    W[br][q] [C, k C] with column t C + c = tap t, input channel c (q = 2 j: conv 1 of dilation j, 2 j + 1: conv 2), bias[br][q] [C].
+    `frames_before` = stream rows in front of the first new row: every conv's input is zero on the left of the stream start, so history rows in
+    front of it are never read (they may hold anything) and every intermediate is zero there; history rows inside the stream are used -> [3, B, T, C]"""
+    hist = 20 * sum(dil) if hist is None else hist
+    x = np.array(x_hist_and_new, dtype=dt)
+    outside = np.arange(x.shape[1]) < hist - frames_before          # rows in front of the stream start
+    x[:, outside] = 0
+    out = []
+    for br, k in enumerate(VOC_LEVEL_K):
+        assert hist >= (k - 1) * 2 * sum(dil)
+        y = x.copy()
+        for j, dl in enumerate(dil):
+            t = _causal_conv_rows(silu(y, dt), W[br][2 * j], bias[br][2 * j], k, dl, dt)
+            t[:, outside] = 0
+            t = _causal_conv_rows(silu(t, dt), W[br][2 * j + 1], bias[br][2 * j + 1], k, dl, dt)
+            t[:, outside] = 0
+            y = (t + y).astype(dt)
+        out.append(y[:, hist:])
+    return np.stack(out)

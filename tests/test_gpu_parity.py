@@ -2472,3 +2472,117 @@ def test_fp16_planes_range_check_reports_an_operand_beyond_the_fp16_range():
     for mode, variant, ap in ((1, 3, False), (2, 3, False), (1, 9, True), (1, 10, True)):
         with pytest.raises(RuntimeError, match="non-finite"):
             E.test_gemm_planes(A, W, mode=mode, variant=variant, a_planes=ap, range_check=True)
+
+
+# =====================================================================================================================================
+# the history rings across their wrap (SVA_DEBUG hist_cap=N: the default 4096 is reached only after 4096 frames of one stream)
+# =====================================================================================================================================
+def _with_hist_cap(cap, mode, make):
+    """make() creates the batch while the options hold (they are read at batch creation); the defaults are back before anything runs"""
+    from streamvoiceanon_amd import engine as E
+    lib = E.load_library()
+    assert lib.sva_debug_configure(f"hist_cap={cap},{mode}".encode()) == 0
+    try:
+        return make()
+    finally:
+        lib.sva_debug_configure(b"hist_cap=4096,ar_batch=1,ar_persistent=1")
+
+
+_WRAP_ORACLE = {}
+
+
+def _wrap_run(eng, B, mode, cap):
+    import step_ops_cases as S
+    from streamvoiceanon_amd import engine as E
+    from streamvoiceanon_amd.synth_audio import frame_noise, synth_prompt, synth_utterance
+
+    prompts = [synth_prompt(2100 + s, S.WRAP_PROMPTS[s]) for s in range(B)]
+    b = _with_hist_cap(cap, mode, lambda: E.Batch(eng, n_streams=B, **S.WRAP_KW))
+    path = b.decode_path()
+    for s, (ac, cc, style, timbre) in enumerate(prompts):
+        b.prefill_prompt(s, cc, ac, style, timbre, noise_seed=3100 + s)
+    b.begin()
+    audio = np.stack([synth_utterance(3100 + s, 2048 * S.WRAP_CHUNKS) for s in range(B)])
+    pcm, codes, content, pos = [], [], [], []
+    for k in range(S.WRAP_CHUNKS):
+        nz = []
+        for s in range(B):          # host noise, frame k - delay of stream s: the oracle's draws
+            ns, nf = frame_noise(3100 + s, max(k - S.WRAP_KW["delay"], 0))
+            nz.append(np.concatenate([ns, nf.reshape(-1)]))
+        pcm.append(b.step(audio[:, k * 2048:(k + 1) * 2048], noise=np.stack(nz)))
+        codes.append(b.tap("audio_codes", (B, 8, 1), np.int32).copy())
+        content.append(b.tap("content_codes", (B, 1), np.int32).copy())
+        pos.append(b.tap("last_pos", (B,), np.int32).copy())
+    b.close()
+    return path, np.concatenate(pcm, axis=1), np.concatenate(codes, axis=2), np.concatenate(content, axis=1), np.stack(pos)
+
+
+def _wrap_oracle_codes(weights0, content0):
+    """the oracle's codes of slot 0's stream (prompt 112 frames), its content codes taken from the engine (the encoder is pinned by its own tests)"""
+    import step_ops_cases as S
+    from oracle import sva_oracle as O
+    from streamvoiceanon_amd.synth_audio import frame_noise, synth_prompt
+
+    if "codes" not in _WRAP_ORACLE:
+        ac, cc, style, timbre = synth_prompt(2100, S.WRAP_PROMPTS[0])
+        kw = S.WRAP_KW
+        sess = O.StreamSession(weights0, torch.from_numpy(cc), torch.from_numpy(ac), torch.from_numpy(style), torch.from_numpy(timbre),
+                               noise_fn=lambda f: tuple(torch.from_numpy(a) for a in frame_noise(3100, f)), delay=kw["delay"], max_seq_frames=kw["max_seq_frames"],
+                               buffer_frames=kw["buffer_frames"], decode_chunk_frames=kw["chunk_frames"])
+        for k in range(S.WRAP_CHUNKS):
+            sess.process_one_chunk(torch.zeros(1, 2048), content_override=torch.from_numpy(content0[k:k + 1].astype(np.int64)), vocode=False)
+        _WRAP_ORACLE["codes"], _WRAP_ORACLE["n_reprefill"] = sess.pred_codes.numpy().copy(), sess.n_reprefill
+    return _WRAP_ORACLE["codes"], _WRAP_ORACLE["n_reprefill"]
+
+
+@pytest.mark.parametrize("B,mode,path", [(1, "ar_batch=1,ar_persistent=1", 1), (2, "ar_batch=1,ar_persistent=1", None), (8, "ar_batch=1,ar_persistent=1", 2),
+                                         (3, "ar_batch=0,ar_persistent=0", 0)])
+def test_history_rings_wrap_through_every_decode_path(eng, weights0, B, mode, path):
+    """max_seq_frames = 160 / buffer_frames = 16 streams with history rings of 32 entries: the persistent one-stream kernel, two streams, ar_batch.hip at
+    8 streams and the multi-launch decode write across the wrap (ar_decode_kernel / ar_batch_kernel / ar_finish_frame, append_content) and the re-prefill
+    and delay-fill builders read across it -- test_kernel_refs.py shows on the oracle's trace that in each of these runs a re-prefill's 16-frame window
+    and a delay fill straddle a multiple of 32 in both rings.  Codes and PCM are bit-identical to the same run at the default capacity (which never
+    wraps), positions drop at the same steps, and slot 0's codes are the oracle's."""
+    import step_ops_cases as S
+    assert (B, mode, path) in S.WRAP_RUNS
+    p32, pcm32, codes32, content32, pos32 = _wrap_run(eng, B, mode, S.WRAP_CAP)
+    p0, pcm0, codes0, content0, pos0 = _wrap_run(eng, B, mode, 4096)
+    assert p32 == p0 and (path is None or p32 == path), (p32, p0, path)
+    np.testing.assert_array_equal(content32, content0)
+    np.testing.assert_array_equal(codes32, codes0)
+    np.testing.assert_array_equal(pos32, pos0)
+    assert pcm32.tobytes() == pcm0.tobytes()
+    for s in range(B):
+        assert (np.diff(pos32[:, s]) < 0).any(), s          # every slot re-prefilled
+    want, n_re = _wrap_oracle_codes(weights0, content0[0])
+    d = S.WRAP_KW["delay"]
+    assert n_re >= 2 and int((np.diff(pos32[:, 0]) < 0).sum()) == n_re
+    np.testing.assert_array_equal(codes32[0][:, d:], want)
+
+
+def test_stream_reprefill_fixture_at_the_smallest_ring_it_fits(eng, weights0):
+    """The re-prefill fixture keeps buffer_frames = 32, so its rings need buffer_frames + delay + chunk < hist_cap: 32 is refused when the batch is
+    created, 64 replays it -- codes equal to the reference's, codes and PCM bit-identical to the default capacity.  (Its 30 chunks stay below one lap
+    of either ring: the wrap itself is the business of the test above.)"""
+    from streamvoiceanon_amd import engine as E
+    g = load_golden("stream_reprefill")
+    kw = dict(n_streams=1, chunk_frames=int(g["chunk"]), delay=int(g["delay"]), max_seq_frames=int(g["max_seq_frames"]), buffer_frames=int(g["buffer_frames"]))
+    with pytest.raises(RuntimeError, match="hist_cap"):
+        _with_hist_cap(32, "ar_persistent=1", lambda: E.Batch(eng, **kw))
+    assert E.load_library().sva_debug_configure(b"hist_cap=48") != 0          # not a power of two: refused at once, the option keeps its value
+    orig = E.Batch
+
+    def run(cap):
+        E.Batch = lambda *a, **k: _with_hist_cap(cap, "ar_persistent=1", lambda: orig(*a, **k))
+        try:
+            return _stream_vs_golden(eng, weights0, "stream_reprefill")
+        finally:
+            E.Batch = orig
+
+    g, outs64, content64, audio64, _, _, last64 = run(64)
+    _, outs0, content0, audio0, _, _, last0 = run(4096)
+    np.testing.assert_array_equal(audio64, g["audio_codes"])
+    np.testing.assert_array_equal(content64, g["content_codes"])
+    assert last64 == last0 == int(g["final_pos"])
+    np.testing.assert_array_equal(audio64, audio0)
+    assert np.stack(outs64).tobytes() == np.stack(outs0).tobytes()

@@ -7,6 +7,7 @@ import types
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 from oracle import sva_oracle as O
 import kernel_refs as R
@@ -482,3 +483,255 @@ def test_history_ring_and_embedding_refs():
     codes = np.array([[1, 2, 3, 4, 5, 6, 7, 8], [9, 0, 9, 0, 9, 0, 9, 0]])
     want = torch.stack([_t(table)[torch.from_numpy(codes[:, i]) + 10 * i] for i in range(8)], 0).sum(0).numpy()      # BaseTransformer.embed
     _close(R.audio_embed(table, codes, 10), want, "audio_embed")
+
+
+# =====================================================================================================================================
+# the chunk step's bookkeeping references (test_gpu_step_ops.py): integer / copy models, pinned EXACTLY to the sequences the oracle builds
+# =====================================================================================================================================
+def _int_tables(rng, dim, n_content=40):
+    """small-integer tables: every sum of eight entries is exact in float32 in any order, so `exactly` does not depend on how torch orders a sum"""
+    g = lambda *s: rng.integers(-8, 9, s).astype(np.float32)
+    return {"arvc.embedding.weight": _t(g(n_content, dim)), "arvc.decoder.model.codebook_embeddings.weight": _t(g(8 * 1000, dim)),
+            "arvc.decoder.wait4start_embedding.weight": _t(g(8, dim)), "arvc.context_in.weight": _t(g(dim, 4)), "arvc.context_in.bias": _t(g(dim)),
+            "arvc.style_in.weight": _t(g(dim, 4)), "arvc.style_in.bias": _t(g(dim))}
+
+
+class _Rings:
+    """the histories as the engine keeps them: rings of `cap` entries and their counters, the stored prompt's last max_delay audio frames"""
+
+    def __init__(self, cap, ref_audio_stored, md=8):
+        self.cap, self.md = cap, md
+        self.content, self.pred = np.full((1, cap), -1, np.int64), np.full((1, 8, cap), -1, np.int64)
+        self.ncontent, self.nframes = np.zeros(1, np.int64), np.zeros(1, np.int64)
+        Rt = ref_audio_stored.shape[1]
+        self.ref_tail = np.full((1, 8, md), 999, np.int64)          # (right-aligned; a shorter prompt leaves the front unset: 999 must never be read)
+        for j in range(md):
+            if Rt - md + j >= 0:
+                self.ref_tail[0, :, j] = ref_audio_stored[:, Rt - md + j]
+
+
+@pytest.mark.parametrize("delay,max_prompt_frames,cap", [(2, 8, 16), (1, 256, 16), (8, 9, 32), (2, 1, 16), (3, 2, 16)])
+def test_row_builder_refs_are_the_oracles_sequences(delay, max_prompt_frames, cap, monkeypatch):
+    """DualAR.prefill_prompt, prefill_src_condition4delay and the re-prefill branch of StreamSession.process_one_chunk hand slow_forward their
+    (seq, pos); the references rebuild every such sequence from the rings (capacity 16 / 32: they wrap many times), the counters and ref_tail.
+    Also holds the premise of the one-pass re-prefill -- the rows of the stored prompt are the ones the first prefill wrote -- and, for the last two
+    cases (a stored prompt shorter than the delay), that the rows of frames Rt .. d - 1 are wait4start rows, which ref_tail never feeds."""
+    rng = np.random.default_rng(100 * delay + max_prompt_frames)
+    dim, NCt, bf, max_seq_frames, Rp = 768, 40, (6 if delay <= 3 else 12), (41 if delay <= 3 else 53), 10          # (an odd period between re-prefills: the windows meet every ring phase)
+    W = _int_tables(rng, dim, NCt)
+    calls = []
+
+    def slow_forward(self, x, pos):
+        calls.append((x.numpy().copy(), pos.numpy().copy()))
+        return torch.zeros(dim), torch.zeros(8192)
+
+    def decode_tokens(self, x, pos, noise_slow, noise_fast, forced=None):
+        calls.append((x.numpy().copy(), pos.numpy().copy()))
+        return dict(semantic=0, codes=torch.from_numpy(rng.integers(0, 1000, 8).astype(np.int32)), hidden=None, logits=None, fast_logits=None)
+
+    monkeypatch.setattr(O.DualAR, "slow_forward", slow_forward)
+    monkeypatch.setattr(O.DualAR, "decode_tokens", decode_tokens)
+    cc, ac = rng.integers(0, NCt, Rp), rng.integers(0, 1000, (8, Rp))
+    style, timbre = _t(rng.integers(-2, 3, 4)), _t(rng.integers(-2, 3, (32, 4)))
+    sess = O.StreamSession(W, torch.from_numpy(cc), torch.from_numpy(ac), style, timbre, noise_fn=lambda f: (None, None), delay=delay,
+                           max_prompt_frames=max_prompt_frames, max_seq_frames=max_seq_frames, buffer_frames=bf)
+    ce, cbe, w4s = (W[k].numpy() for k in ("arvc.embedding.weight", "arvc.decoder.model.codebook_embeddings.weight", "arvc.decoder.wait4start_embedding.weight"))
+    nspk, Rt = 33, min(Rp, max_prompt_frames)
+    # the prompt prefill: the UNTRUNCATED prompt
+    seq0, pos0 = calls.pop(0)
+    rows, cre = R.prompt_rows(ce, cbe, w4s, cc, ac, delay, 1000)
+    assert np.array_equal(seq0[nspk:], rows) and np.array_equal(pos0, np.arange(nspk + 2 * Rp))
+    assert np.array_equal(sess.ar.cached_ref_emb.numpy(), cre)
+    rings = _Rings(cap, ac[:, :Rt])
+    last_pos, cached_ref = np.array([nspk + 2 * Rp - 1]), cre[None].copy()
+    n_re = n_fill = 0
+    straddles = dict(content=0, pred=0, fill=0)
+    for step in range(270):          # (enough re-prefills for their windows to meet every phase of the ring)
+        code = int(rng.integers(0, NCt))
+        before = sess.n_reprefill
+        sess.process_one_chunk(torch.zeros(1, 2048), content_override=torch.tensor([code]), vocode=False)
+        rings.content, rings.ncontent = R.ring_append(rings.content, rings.ncontent, np.array([[code]]))
+        if rings.ncontent[0] < delay:
+            assert not calls
+            continue
+
+        def check_fill():
+            nonlocal last_pos, n_fill
+            seq, pos = calls.pop(0)
+            x, so, po, cna = R.delayfill_rows(ce, rings.content, rings.ncontent, np.pad(cached_ref, ((0, 0), (0, 8 - delay), (0, 0))), last_pos, delay, [0])
+            assert np.array_equal(seq, x) and np.array_equal(pos, po) and not so.any()
+            assert np.array_equal(sess.ar.cached_new_audio_emb.numpy(), cna)
+            lo, hi = int(rings.ncontent[0]) - delay, int(rings.ncontent[0])
+            straddles["fill"] += lo // cap != (hi - 1) // cap
+            last_pos = last_pos + 2 * delay - 1
+            n_fill += 1
+            return cna
+
+        if rings.ncontent[0] == delay:
+            cna = check_fill()
+            assert not calls
+            continue
+        # one decoded frame: decode_one's two rows, then the frame's codes enter the prediction ring
+        seq, pos = calls.pop(0)
+        x, so, po, _ = R.prepare_step(cna, ce, np.array([[code]]), 0, last_pos, np.zeros((1, 1), np.int64), 0)
+        assert np.array_equal(seq, x) and np.array_equal(pos, po)
+        tok = sess.pred_codes[:, -1].numpy()[None]
+        last_pos, rings.nframes, rings.pred, _ = R.finish_frame(tok, last_pos, rings.nframes, rings.pred, np.zeros((1, 8, 1), np.int64), 0, 2)
+        cna = R.audio_embed(cbe, tok, 1000)
+        if sess.n_reprefill == before:
+            assert np.array_equal(sess.ar.cached_new_audio_emb.numpy(), cna) and sess.ar.last_pos == last_pos[0] and not calls
+            continue
+        # the re-prefill: [stored prompt, the last min(bf, frames) frames]; the one-pass form builds the rows behind the stored prompt only
+        n_re += 1
+        nf, ncon = int(rings.nframes[0]), int(rings.ncontent[0])
+        na = min(bf, nf)
+        assert na >= delay
+        seq, pos = calls.pop(0)
+        assert np.array_equal(seq[:nspk + 2 * Rt], seq0[:nspk + 2 * Rt]), "the stored prompt's rows are the first prefill's"
+        x, so, po = R.reprefill_rows(ce, cbe, w4s, rings.content, rings.pred, rings.ref_tail, [0], [Rt], [nf], [na], [ncon], delay, 1000, nspk)
+        assert np.array_equal(seq[nspk + 2 * Rt:], x) and np.array_equal(pos[nspk + 2 * Rt:], po) and not so.any()
+        emb, lp = R.reprefill_finish(cbe, rings.pred, rings.ref_tail, [0], [Rt], [nf], [na], delay, 1000, nspk)
+        assert np.array_equal(sess.ar.cached_ref_emb.numpy(), emb[0]) and lp[0] == len(pos) - 1
+        straddles["content"] += (ncon - delay - na) // cap != (ncon - delay - 1) // cap
+        straddles["pred"] += (nf - na) // cap != (nf - 1) // cap
+        last_pos, cached_ref = lp, emb
+        cna = check_fill()
+        assert not calls and sess.ar.last_pos == last_pos[0]
+    assert n_re >= 5 and n_fill == n_re + 1 and straddles["content"] >= 1 and straddles["pred"] >= 1 and (delay < 3 or straddles["fill"] >= 1), (n_re, n_fill, straddles)
+
+
+def test_step_ops_cases_hold_their_preconditions():
+    """every case of the GPU tests indexes inside its arrays (the hook refuses anything else), no generator is left out, every kernel of the hook has
+    cases, and the ring counters really sit where their names say: each access ends before a multiple of the capacity, on it, across it and far above it"""
+    import step_ops_cases as S
+    from streamvoiceanon_amd import engine as E
+    cases = S.all_cases()
+    seen = {}
+    for c in cases:
+        S.validate(c)
+        seen.setdefault(c["op"], []).append(c)
+    assert set(seen) == set(E.STEP_OPS), set(E.STEP_OPS) ^ set(seen)
+    assert len({c["id"] for c in cases}) == len(cases)
+
+    def classes(cap, spans):
+        got = set()
+        for lo, hi in spans:          # entries [lo, hi)
+            if lo // cap != (hi - 1) // cap:
+                got.add("straddles")
+            elif hi % cap == 0:
+                got.add("ends on")
+            elif hi % cap == cap - 1:
+                got.add("ends before")
+            if lo >= 4 * cap:
+                got.add("far above")
+        return got
+
+    for cap in S.CAPS:
+        spans = {"ar_finish_frame": [], "append_content": [], "put_codes": [], "build_delayfill": [], "reprefill content": [], "reprefill pred": []}
+        for c in cases:
+            d, a = c["desc"], c["arrays"]
+            if c["op"] == "ar_finish_frame" and d[2] == cap:
+                spans[c["op"]] += [(n, n + 1) for n in a[2]]
+            elif c["op"] == "append_content" and d[3] == cap:
+                spans[c["op"]] += [(n, n + d[2]) for n in a[2]]
+            elif c["op"] == "put_codes" and d[3] == cap:
+                spans[c["op"]] += [(n, n + d[2]) for n in a[3]]
+            elif c["op"] == "build_delayfill" and d[4] == cap:
+                spans[c["op"]] += [(a[2][b] - d[2], a[2][b]) for b in a[5]]
+            elif c["op"] == "build_reprefill" and d[7] == cap:
+                spans["reprefill content"] += [(nc - d[2] - na, nc - d[2]) for na, nc in zip(a[3], a[4])]
+                spans["reprefill pred"] += [(nf - na, nf) for nf, na in zip(a[2], a[3])]
+        for what, sp in spans.items():
+            want = {"ends on", "ends before", "far above"} | ({"straddles"} if max(hi - lo for lo, hi in sp) > 1 else set())
+            assert classes(cap, sp) >= want, (cap, what, classes(cap, sp))
+    # re-prefill: na = d and na = the buffer, 1 / 3 / 128 slots, slots out of order
+    re = [c for c in seen["build_reprefill"]]
+    assert {c["desc"][1] for c in re} >= {1, 3, 128}
+    assert any((c["arrays"][3] == c["desc"][2]).any() and (c["arrays"][3] > c["desc"][2]).any() for c in re)
+    assert any(np.any(np.diff(c["arrays"][0]) < 0) for c in re)
+    arms = set()
+    for c in seen["history_rows_move"]:
+        d = c["desc"]
+        arms |= {S.move_arm(d[4 + 5 * i], d[5 + 5 * i], d[6 + 5 * i], d[1], d[7 + 5 * i], d[8 + 5 * i]) + (" odd length" if d[7 + 5 * i] * d[8 + 5 * i] % 4 else "") for i in range(d[0])}
+    assert arms >= {"float4", "scalar", "scalar odd length"}, arms
+    voc = S.voc_cases()
+    for c in voc:
+        S.validate_voc(c)
+    assert {c["C"] for c in voc} == {16, 32} and {c["Tl"] for c in voc} >= set(S.VOC_TL) and {c["frames_done"] for c in voc} == {0, 1, 5}
+
+
+def test_mean3_and_copy_refs():
+    a, b, c = (np.random.default_rng(i).standard_normal(50).astype(np.float32) for i in range(3))
+    want = torch.stack([_t(a), _t(b), _t(c)]).mean(0).numpy()          # ParallelBlock: torch.stack([...]).mean(0)
+    got = R.mean3(a, b, c)
+    assert got.dtype == np.float32 and np.abs(got.astype(np.float64) - want).max() <= 2 * R.ulp32(np.abs(want).max())
+    tok = np.arange(2 * 9 * 4, dtype=np.float32).reshape(2, 9, 4)
+    out = R.copy_tokens(tok, np.full((2, 5, 4), -1.0, np.float32), 2, 6, 1)
+    assert np.array_equal(out[:, :2], tok[:, :2]) and np.array_equal(out[:, 4], tok[:, 8]) and (out[:, 2:4] == -1).all()
+
+
+def _oracle_level(x_ct, W, bias, dil):
+    """the inner loop of O.hifigan over one level's input [B, C, T]: the three ResBlock1 branches, before their mean"""
+    out = []
+    for br, k in enumerate(R.VOC_LEVEL_K):
+        y = x_ct
+        for j, dl in enumerate(dil):
+            w1 = _t(W[br][2 * j]).reshape(-1, k, x_ct.shape[1]).permute(0, 2, 1).contiguous()          # [Cout][k Cin] tap-major -> torch's [Cout, Cin, k]
+            w2 = _t(W[br][2 * j + 1]).reshape(-1, k, x_ct.shape[1]).permute(0, 2, 1).contiguous()
+            t = O.causal_conv1d(F.silu(y), w1, _t(bias[br][2 * j]), dilation=dl)
+            t = O.causal_conv1d(F.silu(t), w2, _t(bias[br][2 * j + 1]), dilation=dl)
+            y = t + y
+        out.append(y.permute(0, 2, 1).numpy())
+    return np.stack(out)
+
+
+@pytest.mark.parametrize("C", [16, 32])
+def test_voc_level_matches_the_oracles_resblock_loop(C):
+    """a window that starts at the stream start (the history rows hold NaN: never read), and the continuation window whose history is the previous
+    window's tail, against the oracle's causal_conv1d + F.silu loop over the whole stream"""
+    import step_ops_cases as S
+    rng = np.random.default_rng(C)
+    W, bias = S.voc_weights(C)
+    B, T1, T2, H = 2, 200, 77, S.RF_MAX
+    x = rng.standard_normal((B, T1 + T2, C)).astype(np.float32)
+    want = _oracle_level(_t(x).permute(0, 2, 1), W, bias, S.DIL)
+    first = np.concatenate([np.full((B, H, C), np.nan, np.float32), x[:, :T1]], axis=1)
+    got1 = R.voc_level(first, W, bias, S.DIL, 0)
+    _close(got1, want[:, :, :T1], "voc_level at the stream start")
+    got2 = R.voc_level(x[:, T1 - H:], W, bias, S.DIL, T1)
+    _close(got2, want[:, :, T1:], "voc_level continuation")
+    # a stream start inside the history: 30 stream rows in front of the window
+    part = np.concatenate([np.full((B, H - 30, C), np.nan, np.float32), x[:, :30 + T2]], axis=1)
+    _close(R.voc_level(part, W, bias, S.DIL, 30), want[:, :, 30:30 + T2], "voc_level, stream start inside the history")
+    _close(got1, R.voc_level(first, W, bias, S.DIL, 0, dt=np.float32), "voc_level f32 restatement")
+
+
+def test_ring_wrap_runs_straddle_the_capacity_on_the_oracles_trace(monkeypatch):
+    """test_gpu_parity.py replays max_seq_frames = 160 / buffer_frames = 16 streams at hist_cap = 32 through every decode path.  On the oracle's own
+    state machine (StreamSession; the transformer stubbed out -- positions do not depend on it) every such run has a re-prefill whose na-frame window
+    straddles a multiple of 32 in the prediction ring and in the content ring, and a delay fill whose d entries do"""
+    import step_ops_cases as S
+    monkeypatch.setattr(O.DualAR, "slow_forward", lambda self, x, pos: (torch.zeros(768), torch.zeros(8192)))
+    monkeypatch.setattr(O.DualAR, "decode_tokens", lambda self, x, pos, ns, nf, forced=None: dict(
+        semantic=0, codes=torch.zeros(8, dtype=torch.int32), hidden=None, logits=None, fast_logits=None))
+    W = _int_tables(np.random.default_rng(0), 768)
+    kw = S.WRAP_KW
+    per_prompt = {}
+    for Rp in sorted(set(S.WRAP_PROMPTS)):
+        sess = O.StreamSession(W, torch.zeros(Rp, dtype=torch.long), torch.zeros(8, Rp, dtype=torch.long), torch.zeros(4), torch.zeros(32, 4), noise_fn=lambda f: (None, None),
+                               delay=kw["delay"], max_seq_frames=kw["max_seq_frames"], buffer_frames=kw["buffer_frames"], decode_chunk_frames=kw["chunk_frames"])
+        res, ncon = [], 0
+        for i in range(S.WRAP_CHUNKS):
+            before = sess.n_reprefill
+            sess.process_one_chunk(torch.zeros(1, 2048), content_override=torch.zeros(1, dtype=torch.long), vocode=False)
+            ncon += 1
+            if sess.n_reprefill != before:
+                res.append((sess.frame_idx, ncon, min(kw["buffer_frames"], sess.frame_idx)))
+        per_prompt[Rp] = res
+        assert res and all(nf >= na >= kw["delay"] and ncon < 4096 for nf, ncon, na in res)          # (every slot of the GPU runs re-prefills)
+    assert kw["buffer_frames"] + kw["delay"] + kw["chunk_frames"] < S.WRAP_CAP
+    for B, _, _ in S.WRAP_RUNS:
+        got = [S.wrap_straddles(per_prompt[Rp], S.WRAP_CAP, kw["delay"]) for Rp in S.WRAP_PROMPTS[:B]]
+        for what in ("pred", "content", "fill"):
+            assert any(g[what] for g in got), (B, what, got)
+    assert all(S.wrap_straddles(per_prompt[112], S.WRAP_CAP, kw["delay"]).values())          # (slot 0 alone, the one-stream run)

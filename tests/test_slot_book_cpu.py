@@ -223,6 +223,24 @@ def test_reprefill_with_fewer_decoded_frames_than_the_delay_is_not_one_pass():
     assert t[first + 1, C.one_pass] == 1                          # two frames by then
 
 
+@pytest.mark.parametrize("Rt,one_pass", [(1, 0), (2, 1), (3, 1)])
+def test_reprefill_of_a_stored_prompt_shorter_than_the_delay_is_not_one_pass(Rt, one_pass):
+    """A prompt stored truncated to Rt < delay frames (op 5: max_prompt_frames below the delay): frames Rt .. delay - 1 of the re-prefilled prompt carry
+    wait4start rows (DualAR.prefill_prompt), which only the whole-prompt prefill builds -- the one-pass launchers refuse Rt < delay
+    (test_gpu_step_ops.py).  The positions are the reference's either way."""
+    TRUNCATED = 5
+    cfg = (1, 1, 2, 30, 6, 4, 33)          # delay 2: a prompt of 3 + Rt frames; position 33 + 2 (3 + Rt) - 1 + 3 after the delay fill
+    t = E.test_slot_book(cfg, [(TRUNCATED, 0, Rt), (BEGIN, 0, 0)] + [(STEP, 0, 0)] * 20)
+    C = Cols(1)
+    due = np.nonzero(t[:, C.n_redo] > 0)[0]
+    assert due.size >= 1
+    first = int(due[0])
+    nf = int(t[first, C.nframes(0)])
+    assert nf >= 6 and t[first - 1, C.pos(0)] + 2 >= 60
+    assert (t[due, C.one_pass] == one_pass).all()
+    assert t[first, C.pos(0)] == 33 + 2 * (Rt + 6) - 1 + 3          # [stored prompt, the last buffer_frames = 6 frames], then the delay fill
+
+
 def test_hook_refuses_what_the_engine_refuses():
     with pytest.raises(RuntimeError):
         E.test_slot_book((1, 1, 2, 100, 32, 64, 33), [(BEGIN, 0, 0)])            # begin before every slot was prefilled
