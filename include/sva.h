@@ -195,6 +195,17 @@ int sva_stream_restart(sva_batch* b, int slot, const int64_t* ref_content_codes,
 int sva_stream_retire(sva_batch* b, int slot);
 /* phase: 0 retired, 1 delay filling, 2 decoding; frames = frames decoded since the slot's stream began (0 unless decoding) */
 int sva_stream_state(sva_batch* b, int slot, int* phase, long* frames);
+/* The sampler settings of one slot.  Every slot owns a pair (temperature, top_p) in device memory, filled from sva_stream_params at
+ * sva_batch_create and read by every sampler per stream, so slots with different settings share a batch and a captured graph stays valid
+ * when a pair changes.  Valid any time after sva_batch_create, before or after sva_streams_begin; takes effect from the slot's next decoded
+ * frame; every other slot is unaffected, and a slot holding the batch's values computes what it computed before.  temperature is clamped
+ * at 1e-5 like the batch value; every top_p >= 0 is accepted, top_p = 0 keeps rank 0 only (the reference's rule: cum > top_p except
+ * rank 0), i.e. the slot is greedy whatever the noise.  A slot keeps its pair until it is set again or the slot is restarted:
+ * sva_stream_restart puts the batch's values back ("a slot of a fresh batch"), sva_streams_begin and sva_stream_retire leave the pair.
+ * Drains the batch's streams.  Fails, changing nothing, for a slot out of range and for a NaN, negative or infinite argument. */
+int sva_stream_set_sampling(sva_batch* b, int slot, float temperature, float top_p);
+/* the slot's pair as it was set (temperature before the clamp); either pointer may be NULL */
+int sva_stream_get_sampling(sva_batch* b, int slot, float* temperature, float* top_p);
 /* activations since the batch was created: counts[0] slot-local ones (slot_priming = 1), counts[1] whole-batch ones; last_ms (may be NULL):
  * host wall time of the last activation -- prompt prefill, delay fill, vocoder priming -- taken after its final synchronise (0 before the first) */
 int sva_stream_activations(sva_batch* b, long counts[2], float* last_ms);
@@ -435,6 +446,11 @@ int sva_test_conv_post(int device, int B, int T, int C, int k, const float* x, l
  *   ptrs  0 logits (in/out), 1 noise or NULL (device RNG), 2 seed uint64 [rows], 3 frame int [rows], 4 tok_raw (in/out), 5 tok (in/out, small only),
  *         6 forced, 7 emb_table, 8 emb_out (in/out), 9 prev, 10 suppress */
 int sva_test_sampler_launch(int device, const long long* desc, const float* fpar, void* const* ptrs);
+/* sva_test_sampler_rows: the same launchers and operands with per-row sampling pairs, as the engine hands them its per-slot pairs: samp float
+ * [n_pairs][2] = {1 / max(temperature, 1e-5), top_p}, row r reads pair row_slot[r] (row_slot int [rows], NULL: pair r).  samp NULL: the scalars
+ * of fpar, exactly sva_test_sampler_launch.  Declined (-4) for fewer pairs than rows or a row_slot entry outside the pairs. */
+int sva_test_sampler_rows(int device, const long long* desc, const float* fpar, void* const* ptrs, const float* samp, int n_pairs,
+                          const int* row_slot);
 /* sva_test_ar_device: the device helpers of the persistent decode kernels (csrc/ar_device.h) in the instantiations their call sites use.
  *   op 0  nucleus_sample: inst 0 <4,4> at 256 threads, 1 <4,32> at 256, 2 <8,16> at 512 (one workgroup per row), 3 <1,16> at 512 (one wave per row)
  *     desc  0 inst, 1 rows, 2 V, 3 ldl, 4 len(logits), 5 ldn, 6 len(noise), 7 kind, 8 noise_elem_off;  fpar temperature, top_p

@@ -49,7 +49,7 @@ struct ArBatchArgs {
     long noise_ld;
     const int* forced;            // [B][8][chunk] teacher-forced codes (used when *use_forced)
     const int* use_forced;
-    float inv_temp, top_p;
+    const float* samp;            // [B][2] {inv_temp, top_p} per stream
     int skip_semantic;
     int vocab, codebook_size;
 };

@@ -798,7 +798,7 @@ __global__ __launch_bounds__(NTH, 2) void ar_batch_kernel(const ArBatchArgs a) {
                 if (tid + NTH * r < a.vocab) a.slow_logits[(long)s * a.vocab + tid + NTH * r] = lv[r];
             __syncthreads();                   // the previous unit has read `red`
             const int sm = nucleus_sample<NWV, 16>(lv, a.vocab, tid, a.noise ? a.noise + (long)s * a.noise_ld : nullptr, a.seed[s], a.nframes[s], 0, 0,
-                                                   a.inv_temp, a.top_p, reinterpret_cast<double*>(red));
+                                                   a.samp[2 * s], a.samp[2 * s + 1], reinterpret_cast<double*>(red));
             if (tid == 0) a.sem[s] = sm;
         }
         AB_MARK();
@@ -1032,7 +1032,7 @@ __global__ __launch_bounds__(NTH, 2) void ar_batch_kernel(const ArBatchArgs a) {
                 for (int r = 0; r < 16; ++r)
                     if (lane + 64 * r < V) a.fast_logits[((long)s * NCB + cb) * V + lane + 64 * r] = lv[r];
                 const float* nz = a.noise ? a.noise + (long)s * a.noise_ld + a.vocab + (long)cb * V : nullptr;
-                const int raw = nucleus_sample<1, 16>(lv, V, lane, nz, a.seed[s], a.nframes[s], 1, cb * V, a.inv_temp, a.top_p, nullptr);
+                const int raw = nucleus_sample<1, 16>(lv, V, lane, nz, a.seed[s], a.nframes[s], 1, cb * V, a.samp[2 * s], a.samp[2 * s + 1], nullptr);
                 int t = raw;
                 if (use_forced) t = a.forced[((long)s * NCB + cb) * a.chunk + a.ci];
                 if (lane == 0) { a.tok_raw[s * NCB + cb] = raw; a.tok[s * NCB + cb] = t; toks[wave * NCB + cb] = t; }

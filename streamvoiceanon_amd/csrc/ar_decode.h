@@ -49,7 +49,7 @@ struct ArDecodeArgs {
     const float* noise;           // [vocab + 8 * codebook_size] Exp(1) draws of this frame, or null = counter RNG
     const int* forced;            // [8][chunk] teacher-forced codes (used when *use_forced)
     const int* use_forced;
-    float inv_temp, top_p;
+    const float* samp;            // [slots][2] {inv_temp, top_p} of every slot of the batch (slot-indexed like seed / nframes)
     int skip_semantic;
     int vocab, codebook_size;
     // several streams in one launch: gridDim.y = streams, workgroup row y works on slot y = every per-stream pointer above advanced by

@@ -122,6 +122,11 @@ __global__ __launch_bounds__(256, 1) void ar_decode_kernel(const ArDecodeArgs a)
     const int p0 = *s_last_pos + 1;           // positions of the two new tokens (dual_ar_stream.py:821-824)
     const int frame = *s_nframes;
     const unsigned long long seed = *s_seed;
+    // this slot's sampling pair: uniform and constant for the launch, so a scalar load -- issued here, ahead of the first hand-off, it returns
+    // beside the vector-memory queue that the prologue's gathers wait on
+    typedef const __attribute__((address_space(4))) float* ConstF;
+    const ConstF sp = (ConstF)(unsigned long long)(a.samp + 2 * y);
+    const float inv_temp = sp[0], top_p = sp[1];
     const int code = (int)s_codes[a.code_off];
     const int use_forced = *a.use_forced;
     KVT* kv = s_kv_slow;
@@ -576,7 +581,7 @@ __global__ __launch_bounds__(256, 1) void ar_decode_kernel(const ArDecodeArgs a)
             float l[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) l[r] = (tid + 256 * r) < V ? lg[tid + 256 * r] : -INFINITY;
-            const int raw = nucleus_sample<4, 4>(l, V, tid, s_noise ? s_noise + a.vocab + (long)cb * V : nullptr, seed, frame, 1, cb * V, a.inv_temp, a.top_p,
+            const int raw = nucleus_sample<4, 4>(l, V, tid, s_noise ? s_noise + a.vocab + (long)cb * V : nullptr, seed, frame, 1, cb * V, inv_temp, top_p,
                                                  reinterpret_cast<double*>(scr), (s_dbg && wg == 0 && cb == 1) ? s_dbg + 900 : nullptr);
             if (s_dbg && wg == 0 && cb == 1 && tid == 0) s_dbg[906] = wall_clock64();
             int t = raw;
@@ -620,7 +625,7 @@ __global__ __launch_bounds__(256, 1) void ar_decode_kernel(const ArDecodeArgs a)
             l[r] = e < a.vocab ? __hip_atomic_load(s_slow_logits + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -INFINITY;
         }
         __syncthreads();
-        const int s = nucleus_sample<4, 32>(l, a.vocab, tid, s_noise, seed, frame, 0, 0, a.inv_temp, a.top_p, reinterpret_cast<double*>(scr));
+        const int s = nucleus_sample<4, 32>(l, a.vocab, tid, s_noise, seed, frame, 0, 0, inv_temp, top_p, reinterpret_cast<double*>(scr));
         if (tid == 0) *s_sem = s;
     }
 }

@@ -230,6 +230,7 @@ struct sva_batch {
     int* d_nframes = nullptr;              // [B] decoded frames (sampler noise counter)
     int* d_ncontent = nullptr;             // [B] content codes seen
     unsigned long long* d_seed = nullptr;  // [B]
+    float* d_samp = nullptr;               // [B][2] {inv_temp, top_p} of each slot, read by every sampler (host mirror: SlotHost::samp)
     int* d_use_forced = nullptr;           // [1]
     // sampler edits (sva_set_sampler_edits): previous_tokens [1 + num_codebooks][EDIT_CAP], suppress list, {W, n_suppress, penalty}
     int* d_edit_prev = nullptr;

@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include <math.h>
+#include <cmath>
 #include <stdlib.h>
 #include <string.h>
 
@@ -481,6 +482,7 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
     SVA_TRY(dev_alloc(A, &b->d_nframes, B));
     SVA_TRY(dev_alloc(A, &b->d_ncontent, B));
     SVA_TRY(dev_alloc(A, &b->d_seed, B));
+    SVA_TRY(dev_alloc(A, &b->d_samp, (size_t)B * 2));
     SVA_TRY(dev_alloc(A, &b->d_use_forced, 1));
     SVA_TRY(dev_alloc(A, &b->d_slot_flag, B));
     // encoder
@@ -680,6 +682,10 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
     SVA_TRY(dev_alloc(A, &b->d_prompt_cc, b->Pmax));
     SVA_TRY(dev_alloc(A, &b->d_prompt_ac, (size_t)ncb * b->Pmax));
     b->slots.reset(B);
+    b->slots.sampling_defaults(p->temperature, p->top_p);
+    for (int i = 0; i < B; ++i)
+        SVA_HIP(hipMemcpyAsync(b->d_samp + 2 * i, b->slots.s[i].samp, sizeof(float) * 2, hipMemcpyHostToDevice, b->stream));
+    SVA_HIP(hipStreamSynchronize(b->stream));
     // vocoder
     SVA_TRY(alloc_vocoder(b, b->p.voc_max_frames, nullptr));
     if (b->p.slot_priming) SVA_TRY(create_priming_workspace(b));
@@ -1548,6 +1554,12 @@ static int upload_slot_position(sva_batch* b, int slot) {
     SVA_HIP(hipStreamSynchronize(b->stream));
     return 0;
 }
+// the slot's sampling pair as the book holds it -> d_samp
+static int upload_slot_sampling(sva_batch* b, int slot) {
+    SVA_HIP(hipMemcpyAsync(b->d_samp + 2 * slot, b->slots.s[slot].samp, sizeof(float) * 2, hipMemcpyHostToDevice, b->stream));
+    SVA_HIP(hipStreamSynchronize(b->stream));
+    return 0;
+}
 
 extern "C" int sva_stream_restart(sva_batch* b, int slot, const int64_t* ref_content_codes, const int32_t* ref_audio_codes, int R, const float* style,
                                   const float* timbre, uint64_t noise_seed) {
@@ -1573,8 +1585,9 @@ extern "C" int sva_stream_restart(sva_batch* b, int slot, const int64_t* ref_con
     P_.style.assign(style, style + c.style_dim);
     P_.timbre.assign(timbre, timbre + (size_t)c.timbre_tokens * c.timbre_dim);
     P_.R = R; P_.seed = noise_seed;
-    b->slots.restart(slot, std::move(P_), nspk, kSlotOutputMuted);
+    b->slots.restart(slot, std::move(P_), nspk, kSlotOutputMuted);      // (... and back to the batch's sampling pair)
     SVA_TRY(upload_slot_position(b, slot));
+    SVA_TRY(upload_slot_sampling(b, slot));
     return upload_slot_flag(b, slot);
 }
 
@@ -1585,6 +1598,24 @@ extern "C" int sva_stream_retire(sva_batch* b, int slot) {
     SVA_TRY(drain_for_slot_call(b));
     b->slots.retire(slot, kSlotInputMuted | kSlotOutputMuted);
     return upload_slot_flag(b, slot);
+}
+
+extern "C" int sva_stream_set_sampling(sva_batch* b, int slot, float temperature, float top_p) {
+    SVA_CHECK(b, "sva_stream_set_sampling: null batch");
+    SVA_CHECK(slot >= 0 && slot < b->B, "sva_stream_set_sampling: slot out of range");
+    SVA_CHECK(std::isfinite(temperature) && temperature >= 0.f, "sva_stream_set_sampling: temperature must be finite and >= 0");
+    SVA_CHECK(std::isfinite(top_p) && top_p >= 0.f, "sva_stream_set_sampling: top_p must be finite and >= 0");
+    SVA_TRY(drain_for_slot_call(b));
+    b->slots.set_sampling(slot, temperature, top_p);
+    return upload_slot_sampling(b, slot);
+}
+
+extern "C" int sva_stream_get_sampling(sva_batch* b, int slot, float* temperature, float* top_p) {
+    SVA_CHECK(b, "sva_stream_get_sampling: null batch");
+    SVA_CHECK(slot >= 0 && slot < b->B, "sva_stream_get_sampling: slot out of range");
+    if (temperature) *temperature = b->slots.s[slot].temperature;
+    if (top_p) *top_p = b->slots.s[slot].samp[1];
+    return 0;
 }
 
 extern "C" int sva_stream_state(sva_batch* b, int slot, int* phase, long* frames) {
@@ -1930,13 +1961,15 @@ extern "C" int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* 
         if (i == 0) {
             // the prefill's decode ignores the caller's sampling_kwargs: generate() calls decode_one_token_ar without them
             // (dual_ar_stream.py:722), i.e. with temperature = top_p = 0.7
-            const float t_user = b->p.temperature, p_user = b->p.top_p;
-            b->p.temperature = 0.7f; b->p.top_p = 0.7f;
+            // -- written into slot 0's device pair for this one frame; the slot's own pair comes back from the book
+            const float quirk[2] = {1.0f / 0.7f, 0.7f};
+            SVA_TRY(h2d(b, b->d_samp, quirk, sizeof(quirk)));
             b->edits_skip = true;                     // ... and without previous_tokens / suppress_tokens
             const int rc0 = ar_frame_tail(b, 0, 0, (long)(M - 1) * D, d_remq, S, 0, 0);
             b->edits_skip = false;
-            b->p.temperature = t_user; b->p.top_p = p_user;
+            const int rc1 = h2d(b, b->d_samp, b->slots.s[0].samp, sizeof(float) * 2);
             SVA_TRY(rc0);
+            SVA_TRY(rc1);
             b->slots.frame_decoded(0, 0);
         } else if (b->use_mega && !b->edits_on) {
             // decode steps of the offline loop (dual_ar_stream.py:735-760) through the persistent kernel: the same two tokens

@@ -74,9 +74,12 @@ int launch_ar_prefill_attention(const float* qkv, int M, int H, int hd, int slot
 // nucleus + temperature + Exp(1)-argmax sampler (modules/dual_ar_stream.py:1092-1132), one
 // workgroup per row.  noise: [rows, ldn] or nullptr -> on-device counter RNG keyed by
 // (seed[row], frame[row], kind) at element offset noise_elem_off.
+// samp != null: row r samples with the device-resident pair {inv_temp, top_p} = samp[2 * q], q = row_slot ? row_slot[r] : r, and
+// the two scalars are ignored (the per-slot pairs of a batch: sva_batch::d_samp)
 int launch_sampler(const float* logits, int rows, int V, int ldl, const float* noise, int ldn,
                    const unsigned long long* seed, const int* frame, int kind, int noise_elem_off,
-                   float temperature, float top_p, int* tok_out, int tok_stride, hipStream_t st);
+                   float temperature, float top_p, int* tok_out, int tok_stride, hipStream_t st, const float* samp = nullptr,
+                   const int* row_slot = nullptr);
 
 // logits_to_probs' edits ahead of the nucleus cut (modules/dual_ar_stream.py:1107-1117), in place on rows [rows][ldl]:
 //   repetition penalty on the tokens of prev[0 .. W) (negative entries skipped): l < 0 ? l * penalty : l / penalty, every listed token
@@ -151,5 +154,6 @@ int launch_sampler_variant(int variant, const float* logits, int rows, int V, in
 int launch_sampler_small(const float* logits, int rows, int V, int ldl, const float* noise, int ldn,
                          const unsigned long long* seed, const int* frame, int kind, int noise_elem_off, float temperature,
                          float top_p, int* tok_raw, int* tok, int tok_stride, const int* forced, int forced_stride,
-                         const int* use_forced, const float* emb_table, int D, float* emb_out, int ldo, hipStream_t st);
+                         const int* use_forced, const float* emb_table, int D, float* emb_out, int ldo, hipStream_t st,
+                         const float* samp = nullptr, const int* row_slot = nullptr);      // (samp / row_slot: as launch_sampler)
 }  // namespace sva

@@ -1185,6 +1185,13 @@ int launch_ar_fast_attention(const float* qkv, int M, int H, const int* slot, co
     return 0;
 }
 
+// per-row sampling pair of a sampler workgroup (one workgroup = one row, so the pair is uniform): read once at kernel entry
+#define SVA_ROW_SAMPLING()                                                     \
+    if (samp) {                                                                \
+        const int ps_ = row_slot ? row_slot[blockIdx.x] : (int)blockIdx.x;     \
+        inv_temp = samp[2 * (long)ps_];                                        \
+        top_p = samp[2 * (long)ps_ + 1];                                       \
+    }
 // ------------------------------------------------------------------------------------------
 // A5 sampler (modules/dual_ar_stream.py:1092-1132, defaults T = 0.7, top_p = 0.7, no repetition
 // penalty): sort descending, inclusive cumsum of softmax, drop every sorted entry with
@@ -1195,7 +1202,11 @@ __global__ __launch_bounds__(1024) void sampler_kernel(const float* __restrict__
                                                        const float* __restrict__ noise, int ldn,
                                                        const unsigned long long* __restrict__ seed, const int* __restrict__ frame,
                                                        int kind, int noise_elem_off, float inv_temp, float top_p,
-                                                       int* __restrict__ tok_out, int tok_stride) {
+                                                       int* __restrict__ tok_out, int tok_stride,
+                                                       // optional per-row {inv_temp, top_p} pairs: row r reads pair row_slot[r] (null: pair r);
+                                                       // samp null: the two scalars above
+                                                       const float* __restrict__ samp = nullptr, const int* __restrict__ row_slot = nullptr) {
+    SVA_ROW_SAMPLING();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* val = smem;                                  // [P]
     unsigned short* ids = (unsigned short*)(val + P);   // [P]
@@ -1319,7 +1330,9 @@ __global__ __launch_bounds__(THREADS) void sampler_reg_kernel(const float* __res
                                                            // optional fusion (fast-AR heads): teacher forcing + gather of the next input embedding
                                                            int* __restrict__ tok, const int* __restrict__ forced, int forced_stride,
                                                            const int* __restrict__ use_forced, const float* __restrict__ emb_table, int D,
-                                                           float* __restrict__ emb_out, int ldo) {
+                                                           float* __restrict__ emb_out, int ldo,
+                                                           const float* __restrict__ samp = nullptr, const int* __restrict__ row_slot = nullptr) {
+    SVA_ROW_SAMPLING();
     constexpr int P = THREADS * PER, NW = THREADS / 64;
     __shared__ float xv[P];
     __shared__ unsigned short xi[P];
@@ -1546,7 +1559,9 @@ __global__ __launch_bounds__(THREADS) void sampler_bisect_kernel(const float* __
                                                               int* __restrict__ tok_out, int tok_stride,
                                                               int* __restrict__ tok, const int* __restrict__ forced, int forced_stride,
                                                               const int* __restrict__ use_forced, const float* __restrict__ emb_table, int D,
-                                                              float* __restrict__ emb_out, int ldo) {
+                                                              float* __restrict__ emb_out, int ldo,
+                                                              const float* __restrict__ samp = nullptr, const int* __restrict__ row_slot = nullptr) {
+    SVA_ROW_SAMPLING();
     constexpr int NW = THREADS / 64;
     __shared__ double dred[2][NW];
     __shared__ unsigned ured[2][2][NW];
@@ -1764,7 +1779,7 @@ static constexpr int sampler_mode() { return 0; }
 
 int launch_sampler(const float* logits, int rows, int V, int ldl, const float* noise, int ldn,
                    const unsigned long long* seed, const int* frame, int kind, int noise_elem_off, float temperature,
-                   float top_p, int* tok_out, int tok_stride, hipStream_t st) {
+                   float top_p, int* tok_out, int tok_stride, hipStream_t st, const float* samp, const int* row_slot) {
     int P = 1024;
     while (P < V) P <<= 1;
     SVA_CHECK(P <= 16384, "sampler: vocabulary too large");
@@ -1781,27 +1796,27 @@ int launch_sampler(const float* logits, int rows, int V, int ldl, const float* n
         if (bv == 1 && srch)
             hipLaunchKernelGGL((sampler_bisect_kernel<512, 16, 2>), dim3(rows), dim3(512), 0, st, logits, V, ldl, noise, ldn, seed, frame, kind,
                                noise_elem_off, 1.0f / tclamp, top_p, tok_out, tok_stride, (int*)nullptr, (const int*)nullptr, 0,
-                               (const int*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0);
+                               (const int*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0, samp, row_slot);
         else if (bv == 1)
             hipLaunchKernelGGL((sampler_bisect_kernel<512, 16>), dim3(rows), dim3(512), 0, st, logits, V, ldl, noise, ldn, seed, frame, kind,
                                noise_elem_off, 1.0f / tclamp, top_p, tok_out, tok_stride, (int*)nullptr, (const int*)nullptr, 0,
-                               (const int*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0);
+                               (const int*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0, samp, row_slot);
         else
             hipLaunchKernelGGL((sampler_bisect_kernel<1024, 8>), dim3(rows), dim3(1024), 0, st, logits, V, ldl, noise, ldn, seed, frame, kind,
                                noise_elem_off, 1.0f / tclamp, top_p, tok_out, tok_stride, (int*)nullptr, (const int*)nullptr, 0,
-                               (const int*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0);
+                               (const int*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0, samp, row_slot);
         SVA_HIP(hipGetLastError());
         return 0;
     }
     if (P == 8192 && !legacy) {
         hipLaunchKernelGGL((sampler_reg_kernel<1024, 8>), dim3(rows), dim3(1024), 0, st, logits, V, ldl, noise, ldn, seed, frame, kind,
                            noise_elem_off, 1.0f / tclamp, top_p, tok_out, tok_stride, (int*)nullptr, (const int*)nullptr, 0,
-                           (const int*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0);
+                           (const int*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0, samp, row_slot);
         SVA_HIP(hipGetLastError());
         return 0;
     }
     hipLaunchKernelGGL(sampler_kernel, dim3(rows), dim3(1024), smem, st, logits, V, ldl, P, noise, ldn, seed, frame, kind,
-                       noise_elem_off, 1.0f / tclamp, top_p, tok_out, tok_stride);
+                       noise_elem_off, 1.0f / tclamp, top_p, tok_out, tok_stride, samp, row_slot);
     SVA_HIP(hipGetLastError());
     return 0;
 }
@@ -2263,7 +2278,9 @@ __global__ __launch_bounds__(1024) void sampler_small_kernel(const float* __rest
                                                              int* __restrict__ tok_raw, int* __restrict__ tok, int tok_stride,
                                                              const int* __restrict__ forced, int forced_stride,
                                                              const int* __restrict__ use_forced, const float* __restrict__ emb_table,
-                                                             int D, float* __restrict__ emb_out, int ldo) {
+                                                             int D, float* __restrict__ emb_out, int ldo,
+                                                             const float* __restrict__ samp = nullptr, const int* __restrict__ row_slot = nullptr) {
+    SVA_ROW_SAMPLING();
     __shared__ float xv[1024];
     __shared__ int xi[1024];
     __shared__ float fred[16];
@@ -2365,7 +2382,8 @@ __global__ __launch_bounds__(1024) void sampler_small_kernel(const float* __rest
 int launch_sampler_small(const float* logits, int rows, int V, int ldl, const float* noise, int ldn,
                          const unsigned long long* seed, const int* frame, int kind, int noise_elem_off, float temperature,
                          float top_p, int* tok_raw, int* tok, int tok_stride, const int* forced, int forced_stride,
-                         const int* use_forced, const float* emb_table, int D, float* emb_out, int ldo, hipStream_t st) {
+                         const int* use_forced, const float* emb_table, int D, float* emb_out, int ldo, hipStream_t st, const float* samp,
+                         const int* row_slot) {
     SVA_CHECK(V <= 1024, "sampler_small: V <= 1024");
     const float tclamp = temperature > 1e-5f ? temperature : 1e-5f;
     constexpr int variant = 0, sbv = 1;
@@ -2373,7 +2391,7 @@ int launch_sampler_small(const float* logits, int rows, int V, int ldl, const fl
 #define SVA_BIS(T_, P_)                                                                                                          \
     hipLaunchKernelGGL((sampler_bisect_kernel<T_, P_>), dim3(rows), dim3(T_), 0, st, logits, V, ldl, noise, ldn, seed, frame, kind, \
                        noise_elem_off, 1.0f / tclamp, top_p, tok_raw, tok_stride, tok, forced, forced_stride, use_forced, emb_table, D, \
-                       emb_out, ldo)
+                       emb_out, ldo, samp, row_slot)
         constexpr int srch = 2;
         if (sbv == 2) SVA_BIS(128, 8);
         else if (sbv == 3) SVA_BIS(64, 16);
@@ -2382,7 +2400,7 @@ int launch_sampler_small(const float* logits, int rows, int V, int ldl, const fl
         else
             hipLaunchKernelGGL((sampler_bisect_kernel<256, 4, 2>), dim3(rows), dim3(256), 0, st, logits, V, ldl, noise, ldn, seed, frame, kind,
                                noise_elem_off, 1.0f / tclamp, top_p, tok_raw, tok_stride, tok, forced, forced_stride, use_forced, emb_table, D,
-                               emb_out, ldo);
+                               emb_out, ldo, samp, row_slot);
 #undef SVA_BIS
         SVA_HIP(hipGetLastError());
         return 0;
@@ -2390,26 +2408,26 @@ int launch_sampler_small(const float* logits, int rows, int V, int ldl, const fl
     if (variant == 2) {
         hipLaunchKernelGGL((sampler_reg_kernel<512, 2>), dim3(rows), dim3(512), 0, st, logits, V, ldl, noise, ldn, seed, frame, kind,
                            noise_elem_off, 1.0f / tclamp, top_p, tok_raw, tok_stride, tok, forced, forced_stride, use_forced, emb_table, D,
-                           emb_out, ldo);
+                           emb_out, ldo, samp, row_slot);
         SVA_HIP(hipGetLastError());
         return 0;
     }
     if (variant == 3) {
         hipLaunchKernelGGL((sampler_reg_kernel<1024, 1>), dim3(rows), dim3(1024), 0, st, logits, V, ldl, noise, ldn, seed, frame, kind,
                            noise_elem_off, 1.0f / tclamp, top_p, tok_raw, tok_stride, tok, forced, forced_stride, use_forced, emb_table, D,
-                           emb_out, ldo);
+                           emb_out, ldo, samp, row_slot);
         SVA_HIP(hipGetLastError());
         return 0;
     }
     if (variant == 1) {     // 256 threads x 4 entries: 3 LDS exchange stages instead of 10, 4 waves at the barriers instead of 16
         hipLaunchKernelGGL((sampler_reg_kernel<256, 4>), dim3(rows), dim3(256), 0, st, logits, V, ldl, noise, ldn, seed, frame, kind,
                            noise_elem_off, 1.0f / tclamp, top_p, tok_raw, tok_stride, tok, forced, forced_stride, use_forced, emb_table, D,
-                           emb_out, ldo);
+                           emb_out, ldo, samp, row_slot);
         SVA_HIP(hipGetLastError());
         return 0;
     }
     hipLaunchKernelGGL(sampler_small_kernel, dim3(rows), dim3(1024), 0, st, logits, V, ldl, noise, ldn, seed, frame, kind, noise_elem_off,
-                       1.0f / tclamp, top_p, tok_raw, tok, tok_stride, forced, forced_stride, use_forced, emb_table, D, emb_out, ldo);
+                       1.0f / tclamp, top_p, tok_raw, tok, tok_stride, forced, forced_stride, use_forced, emb_table, D, emb_out, ldo, samp, row_slot);
     SVA_HIP(hipGetLastError());
     return 0;
 }

@@ -35,6 +35,8 @@ struct SlotHost {
     std::vector<int64_t> ref_content;      // [ref_len]      kept for re-prefill / vocoder priming
     std::vector<int32_t> ref_audio;        // [ncb][ref_len]
     PendingPrompt pending;
+    float temperature = 0.7f;              // the slot's sampling pair as set (sva_stream_get_sampling) ...
+    float samp[2] = {1.0f / 0.7f, 0.7f};   // ... and as the samplers read it: host mirror of d_samp[slot] = {inv_temp, top_p}
 };
 
 // what the end of a steady step asks of the device
@@ -52,6 +54,7 @@ struct SlotBook {
     std::vector<SlotHost> s;
     bool delay_filled = false;             // the lock-step slots hold `delay` content codes
     int h_step = 0;                        // chunks consumed since begin()
+    float def_temperature = 0.7f, def_top_p = 0.7f;      // the batch's sampling pair (sva_stream_params): a restarted slot goes back to it
 
     // ---- positions (nspk = speaker prefix rows = timbre tokens + 1) ----
     static int prefill_end(int nspk, int R) { return nspk + 2 * R - 1; }                  // a prompt of R frames: rows 0 .. nspk + 2R - 1
@@ -68,6 +71,19 @@ struct SlotBook {
         const int R = h.ref_len;
         for (int q = 0; q < ncb; ++q)
             for (int k = 0; k < n; ++k) dst[(size_t)q * n + k] = h.ref_audio[(size_t)q * R + (R - P + first + k)];
+    }
+
+    // ---- sampling pair ----
+    // temperature is clamped at 1e-5 like the batch value; inv_temp in float, the quotient every launcher used to form from the scalar
+    void set_sampling(int slot, float temperature, float top_p) {
+        SlotHost& h = s[slot];
+        h.temperature = temperature;
+        h.samp[0] = 1.0f / (temperature > 1e-5f ? temperature : 1e-5f);
+        h.samp[1] = top_p;
+    }
+    void sampling_defaults(float temperature, float top_p) {
+        def_temperature = temperature; def_top_p = top_p;
+        for (size_t i = 0; i < s.size(); ++i) set_sampling((int)i, temperature, top_p);
     }
 
     // ---- batch life cycle ----
@@ -163,6 +179,7 @@ struct SlotBook {
         h.ncontent = 0;
         h.last_pos = parked_position(slot, nspk);
         h.flag = flag;
+        set_sampling(slot, def_temperature, def_top_p);      // like a slot of a fresh batch (the caller uploads the pair)
     }
     // (its position is rewound when it would become due for a re-prefill: steady_step)
     void retire(int slot, int flag) {

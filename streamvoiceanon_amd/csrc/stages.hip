@@ -636,8 +636,7 @@ int ar_decode_frame_batch(sva_batch* b, int ci) {
     a.noise = b->noise_on_device ? nullptr : b->d_noise + (long)ci * nstride;
     a.noise_ld = (long)b->p.chunk_frames * nstride;
     a.forced = b->d_forced; a.use_forced = b->d_use_forced;
-    const float tclamp = b->p.temperature > 1e-5f ? b->p.temperature : 1e-5f;
-    a.inv_temp = 1.0f / tclamp; a.top_p = b->p.top_p; a.skip_semantic = b->p.skip_semantic;
+    a.samp = b->d_samp; a.skip_semantic = b->p.skip_semantic;
     a.vocab = c.ar_vocab; a.codebook_size = c.codebook_size;
     return launch_ar_batch(a, half ? 1 : 0, b->stream);
 }
@@ -669,8 +668,7 @@ int ar_decode_frame_mega(sva_batch* b, int ci, const long long* codes, int code_
     const int nstride = c.ar_vocab + c.num_codebooks * c.codebook_size;
     a.noise = b->noise_on_device ? nullptr : b->d_noise + (long)ci * nstride;
     a.forced = b->d_forced; a.use_forced = b->d_use_forced;
-    const float tclamp = b->p.temperature > 1e-5f ? b->p.temperature : 1e-5f;
-    a.inv_temp = 1.0f / tclamp; a.top_p = b->p.top_p; a.skip_semantic = b->p.skip_semantic;
+    a.samp = b->d_samp; a.skip_semantic = b->p.skip_semantic;
     a.vocab = c.ar_vocab; a.codebook_size = c.codebook_size;
     // on its own CU partition the kernel pads its LDS request so that the 96 workgroups land on 96 different CUs; on shared CUs it
     // keeps its small footprint so that the other stages' GEMM workgroups fit beside it
@@ -706,6 +704,8 @@ int ar_frame_tail(sva_batch* b, int ci, long hid_stride, long hid_off, const lon
     const float* noise = b->noise_on_device ? nullptr : b->d_noise + (long)ci * nstride;
     const int ldn = chunk * nstride;
     const bool fused = B <= 4;               // GEMV heads with the norm folded in
+    // the samplers below serve the B slots in order (row s = slot s), so they read the per-slot pairs of b->d_samp without a row_slot list;
+    // the scalar temperature / top_p they are handed are ignored then
     if (!b->p.skip_semantic) {
         if (fused) {
             Gemv hg;
@@ -723,7 +723,7 @@ int ar_frame_tail(sva_batch* b, int ci, long hid_stride, long hid_off, const lon
         if (b->edits_on && !b->edits_skip)
             SVA_TRY(launch_logit_edits(b->slow_logits, B, c.ar_vocab, c.ar_vocab, b->d_edit_prev, EDIT_CAP, b->d_edit_suppress, b->d_edit_params, st));
         SVA_TRY(launch_sampler(b->slow_logits, B, c.ar_vocab, c.ar_vocab, noise, ldn, b->d_seed, b->d_nframes, 0, 0, b->p.temperature,
-                               b->p.top_p, b->d_sem, 1, st));
+                               b->p.top_p, b->d_sem, 1, st, b->d_samp));
     }
     for (int cb = 0; cb < ncb; ++cb) {
         SVA_TRY(ar_layers_pass(b, e->ar_fast_layers, B, b->d_fast_slot, b->d_fast_pos + cb * B, e->rope_fast, (float*)b->kv_fast,
@@ -750,10 +750,10 @@ int ar_frame_tail(sva_batch* b, int ci, long hid_stride, long hid_off, const lon
         if (cbs <= 1024) {
             SVA_TRY(launch_sampler_small(lg, B, cbs, ncb * cbs, nz, ldn, b->d_seed, b->d_nframes, 1, cb * cbs, b->p.temperature, b->p.top_p,
                                          b->d_tok_raw + cb, b->d_tok + cb, ncb, b->d_forced + (long)cb * chunk + ci, ncb * chunk, b->d_use_forced,
-                                         cb + 1 < ncb ? e->fast_emb : nullptr, D, b->xf, D, st));
+                                         cb + 1 < ncb ? e->fast_emb : nullptr, D, b->xf, D, st, b->d_samp));
         } else {
             SVA_TRY(launch_sampler(lg, B, cbs, ncb * cbs, nz, ldn, b->d_seed, b->d_nframes, 1, cb * cbs, b->p.temperature, b->p.top_p,
-                                   b->d_tok_raw + cb, ncb, st));
+                                   b->d_tok_raw + cb, ncb, st, b->d_samp));
             SVA_TRY(launch_apply_forced(b->d_tok_raw, b->d_forced, b->d_use_forced, chunk, ci, cb, ncb, b->d_tok, B, st));
             if (cb + 1 < ncb) SVA_TRY(launch_gather_rows(e->fast_emb, b->d_tok + cb, ncb, 0, B, D, b->xf, D, st));
         }

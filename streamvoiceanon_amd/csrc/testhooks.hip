@@ -966,9 +966,8 @@ int run_logit_edits(float* d_rows, int rows, int V, int ldl, const EditArgs& e, 
     if (rc == -1) { *refused = 1; return 0; }
     return rc;
 }
-}  // namespace
-
-extern "C" int sva_test_sampler_launch(int device, const long long* d, const float* fpar, void* const* ptrs) {
+// the production sampler launchers on host operands; samp != null: n_pairs {inv_temp, top_p} pairs, row r reads pair row_slot[r] (null: r)
+int sampler_launch_impl(int device, const long long* d, const float* fpar, void* const* ptrs, const float* samp, int n_pairs, const int* row_slot) {
     SVA_HIP(hipSetDevice(device));
     const int small = (int)d[0], rows = (int)d[1], V = (int)d[2], ldl = (int)d[3], ldn = (int)d[6], kind = (int)d[9], noise_elem_off = (int)d[10];
     const int tok_stride = (int)d[11], forced_stride = (int)d[14], use_forced = (int)d[17], emb_rows = (int)d[18], D = (int)d[19], ldo = (int)d[20];
@@ -992,7 +991,16 @@ extern "C" int sva_test_sampler_launch(int device, const long long* d, const flo
         for (long i = 0; i < f_len; ++i) SVA_HOOK_CHECK(!emb_table || (forced[i] >= 0 && forced[i] < emb_rows), "sampler hook: forced code outside the table");
     }
     if (emb_table) SVA_HOOK_CHECK(tok && emb_out && emb_rows >= V && D >= 1 && ldo >= D && (long)(rows - 1) * ldo + D <= e_len, "sampler hook: embedding range");
-    DevBuf bl, bn, bs, bf, btr, bt, bfo, buf, bet, beo, bprev, bsup, bpar;
+    SVA_HOOK_CHECK(samp || !row_slot, "sampler hook: row_slot without pairs");
+    if (samp) {
+        SVA_HOOK_CHECK(n_pairs >= 1 && (row_slot || n_pairs >= rows), "sampler hook: fewer pairs than rows");
+        for (int r = 0; row_slot && r < rows; ++r) SVA_HOOK_CHECK(row_slot[r] >= 0 && row_slot[r] < n_pairs, "sampler hook: row_slot outside the pairs");
+    }
+    DevBuf bl, bn, bs, bf, btr, bt, bfo, buf, bet, beo, bprev, bsup, bpar, bsamp, brs;
+    if (samp) SVA_TRY(bsamp.put(samp, sizeof(float) * 2 * (size_t)n_pairs));
+    if (row_slot) SVA_TRY(brs.put(row_slot, sizeof(int) * (size_t)rows));
+    const float* dsamp = samp ? bsamp.as<float>() : nullptr;
+    const int* drs = row_slot ? brs.as<int>() : nullptr;
     SVA_TRY(btr.put(tok_raw, sizeof(int) * (size_t)t_len));
     if (tok) SVA_TRY(bt.put(tok, sizeof(int) * (size_t)t_len));
     if (emb_out) SVA_TRY(beo.put(emb_out, sizeof(float) * (size_t)e_len));          // (uploaded and handed over without a table too: nothing may be written then)
@@ -1012,10 +1020,10 @@ extern "C" int sva_test_sampler_launch(int device, const long long* d, const flo
     if (small)
         rc = launch_sampler_small(dl, rows, V, ldl, dn, ldn, seed ? bs.as<unsigned long long>() : nullptr, frame ? bf.as<int>() : nullptr, kind, noise_elem_off, fpar[0], fpar[1],
                                   btr.as<int>() + tok_off, tok ? bt.as<int>() + tok_off : nullptr, tok_stride, forced ? bfo.as<int>() + forced_off : nullptr, forced_stride,
-                                  use_forced >= 0 ? buf.as<int>() : nullptr, emb_table ? bet.as<float>() : nullptr, D, emb_out ? beo.as<float>() : nullptr, ldo, 0);
+                                  use_forced >= 0 ? buf.as<int>() : nullptr, emb_table ? bet.as<float>() : nullptr, D, emb_out ? beo.as<float>() : nullptr, ldo, 0, dsamp, drs);
     else
         rc = launch_sampler(dl, rows, V, ldl, dn, ldn, seed ? bs.as<unsigned long long>() : nullptr, frame ? bf.as<int>() : nullptr, kind, noise_elem_off, fpar[0], fpar[1],
-                            btr.as<int>() + tok_off, tok_stride, 0);
+                            btr.as<int>() + tok_off, tok_stride, 0, dsamp, drs);
     SVA_LAUNCH_OR_REFUSED(rc);
     SVA_HIP(hipDeviceSynchronize());
     SVA_TRY(bl.get(logits, sizeof(float) * (size_t)l_len));
@@ -1023,6 +1031,17 @@ extern "C" int sva_test_sampler_launch(int device, const long long* d, const flo
     if (tok) SVA_TRY(bt.get(tok, sizeof(int) * (size_t)t_len));
     if (emb_out) SVA_TRY(beo.get(emb_out, sizeof(float) * (size_t)e_len));
     return 0;
+}
+}  // namespace
+
+extern "C" int sva_test_sampler_launch(int device, const long long* d, const float* fpar, void* const* ptrs) {
+    return sampler_launch_impl(device, d, fpar, ptrs, nullptr, 0, nullptr);
+}
+// the operands of sva_test_sampler_launch + per-row sampling pairs: samp [n_pairs][2] = {inv_temp, top_p} (null: the scalars of fpar),
+// row_slot [rows] or null
+extern "C" int sva_test_sampler_rows(int device, const long long* d, const float* fpar, void* const* ptrs, const float* samp, int n_pairs,
+                                     const int* row_slot) {
+    return sampler_launch_impl(device, d, fpar, ptrs, samp, n_pairs, row_slot);
 }
 
 // ---- ar_device.h: nucleus_sample and gemv exactly as ar_decode.hip / ar_batch.hip instantiate them ----

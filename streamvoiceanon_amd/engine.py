@@ -77,6 +77,8 @@ def load_library():
     lib.sva_stream_restart.argtypes = [vp, i32, vp, vp, i32, vp, vp, C.c_uint64]
     lib.sva_stream_retire.argtypes = [vp, i32]
     lib.sva_stream_state.argtypes = [vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_long)]
+    lib.sva_stream_set_sampling.argtypes = [vp, i32, C.c_float, C.c_float]
+    lib.sva_stream_get_sampling.argtypes = [vp, i32, f32p, f32p]
     lib.sva_stream_activations.argtypes = [vp, C.POINTER(C.c_long), f32p]
     lib.sva_step.argtypes = [vp, vp, vp, vp, vp]
     lib.sva_step_device.argtypes = [vp, vp, vp]
@@ -128,6 +130,7 @@ def load_library():
     lib.sva_test_fsq.argtypes = [i32] * 6 + [vp, i64, i64, i64, i32, vp, vp, vp, i64, i64, i64]
     lib.sva_test_conv_post.argtypes = [i32] * 5 + [vp, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp]
     lib.sva_test_sampler_launch.argtypes = [i32, vp, vp, vp]
+    lib.sva_test_sampler_rows.argtypes = [i32, vp, vp, vp, vp, i32, vp]
     lib.sva_test_ar_device.argtypes = [i32, i32, vp, vp, vp]
     lib.sva_test_gemv.argtypes = [i32, vp, vp, vp]
     lib.sva_test_token_ops.argtypes = [i32, i32, vp, vp, vp]
@@ -145,12 +148,12 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "sva_last_error", "sva_config_default", "sva_stream_params_default", "sva_engine_create",
     "sva_engine_load_weight", "sva_engine_finalize", "sva_engine_destroy", "sva_batch_create", "sva_batch_destroy",
-    "sva_prefill_prompt", "sva_streams_begin", "sva_stream_restart", "sva_stream_retire", "sva_stream_state", "sva_stream_activations", "sva_step", "sva_step_device", "sva_step_device_on", "sva_join_stream", "sva_batch_uses_persistent_decode", "sva_test_force_ar_timeout", "sva_test_stream_overlap", "sva_debug_configure", "sva_sync", "sva_stream_chunks", "sva_encode_window", "sva_firefly_encode",
+    "sva_prefill_prompt", "sva_streams_begin", "sva_stream_restart", "sva_stream_retire", "sva_stream_state", "sva_stream_set_sampling", "sva_stream_get_sampling", "sva_stream_activations", "sva_step", "sva_step_device", "sva_step_device_on", "sva_join_stream", "sva_batch_uses_persistent_decode", "sva_test_force_ar_timeout", "sva_test_stream_overlap", "sva_debug_configure", "sva_sync", "sva_stream_chunks", "sva_encode_window", "sva_firefly_encode",
     "sva_vocode_window", "sva_vocode_stream", "sva_vocode_reset", "sva_quantizer_decode", "sva_vocoder_head", "sva_ar_delay_fill", "sva_ar_decode_one", "sva_generate", "sva_get_tap", "sva_get_timings",
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
     "sva_op_geglu", "sva_op_l2norm", "sva_ops_capture_begin", "sva_ops_capture_end", "sva_ops_graph_launch", "sva_ops_graph_free",
-    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_test_sampler_launch", "sva_test_ar_device", "sva_test_gemv", "sva_test_token_ops", "sva_test_step_ops", "sva_test_voc_level", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
+    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_test_sampler_launch", "sva_test_sampler_rows", "sva_test_ar_device", "sva_test_gemv", "sva_test_token_ops", "sva_test_step_ops", "sva_test_voc_level", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
 ]
 
 
@@ -314,9 +317,10 @@ class Batch:
     def begin(self):
         _check(self.lib.sva_streams_begin(self.h), "sva_streams_begin")
 
-    def restart(self, slot, ref_content_codes, ref_audio_codes, style, timbre, noise_seed=0):
+    def restart(self, slot, ref_content_codes, ref_audio_codes, style, timbre, noise_seed=0, temperature=None, top_p=None):
         """sva_stream_restart: a new utterance in `slot` of a begun batch (operands as prefill_prompt).  From the next step on the slot
-        behaves like a slot of a fresh batch -- `delay` chunks of zeros, then frame 0 -- and every other slot is unaffected."""
+        behaves like a slot of a fresh batch -- `delay` chunks of zeros, then frame 0 -- and every other slot is unaffected.  The slot's
+        sampling pair goes back to the batch's; temperature / top_p set it for the new utterance right after the restart."""
         cc = np.ascontiguousarray(ref_content_codes, dtype=np.int64).reshape(-1)
         ac = np.ascontiguousarray(ref_audio_codes, dtype=np.int32).reshape(8, -1)
         assert ac.shape[1] == cc.shape[0]
@@ -324,6 +328,21 @@ class Batch:
         tm = np.ascontiguousarray(timbre, dtype=np.float32)
         _check(self.lib.sva_stream_restart(self.h, int(slot), _ptr(cc), _ptr(ac), cc.shape[0], _ptr(st), _ptr(tm), int(noise_seed)),
                "sva_stream_restart")
+        if temperature is not None or top_p is not None:
+            self.set_sampling(slot, temperature, top_p)
+
+    def set_sampling(self, slot, temperature=None, top_p=None):
+        """sva_stream_set_sampling: the slot's sampler settings from its next decoded frame on (None = the batch's value).  The slot keeps
+        them until they are set again or the slot is restarted; the other slots are unaffected."""
+        t = self.p.temperature if temperature is None else temperature
+        tp = self.p.top_p if top_p is None else top_p
+        _check(self.lib.sva_stream_set_sampling(self.h, int(slot), float(t), float(tp)), "sva_stream_set_sampling")
+
+    def sampling(self, slot):
+        """sva_stream_get_sampling -> (temperature, top_p) of the slot"""
+        t, tp = C.c_float(), C.c_float()
+        _check(self.lib.sva_stream_get_sampling(self.h, int(slot), C.byref(t), C.byref(tp)), "sva_stream_get_sampling")
+        return float(t.value), float(tp.value)
 
     def retire(self, slot):
         """sva_stream_retire: the slot's input is no longer read and its output is zeros until restart()."""
@@ -770,7 +789,7 @@ def _i32(a):
 
 def test_sampler_launch(logits, rows, V, ldl, col_off=0, small=False, noise=None, ldn=0, noise_off=0, seed=None, frame=None, kind=0, noise_elem_off=0,
                         temperature=0.7, top_p=0.7, tok_raw=None, tok=None, tok_stride=1, tok_off=0, forced=None, forced_stride=0, forced_off=0,
-                        use_forced=None, emb_table=None, emb_out=None, ldo=0, edits=None, device=0):
+                        use_forced=None, emb_table=None, emb_out=None, ldo=0, edits=None, device=0, _hook=None):
     """launch_sampler / launch_sampler_small (small) over the flat float32 array `logits` (rows at col_off + r ldl; edited in place when
     edits = dict(prev, prev_cap, W, suppress, penalty) is given: launch_logit_edits runs first on the same device rows).  noise: flat array or None
     (device RNG from seed [rows] uint64, frame [rows]).  tok_raw / tok (int32, flat) and emb_out (float32, flat) are updated in place."""
@@ -787,9 +806,29 @@ def test_sampler_launch(logits, rows, V, ldl, col_off=0, small=False, noise=None
             tok_raw.size, forced_stride, forced_off, 0 if forced is None else forced.size, -1 if use_forced is None else int(use_forced),
             0 if emb_table is None else emb_table.shape[0], 0 if emb_table is None else emb_table.shape[1], ldo, 0 if emb_out is None else emb_out.size,
             int(edits is not None), e.get("W", prev.size), e.get("prev_cap", 4096), prev.size, e.get("n_suppress", sup.size), sup.size]
-    _hook_call(lib.sva_test_sampler_launch, "sva_test_sampler_launch", desc, [temperature, top_p, e.get("penalty", 1.5)],
+    _hook_call(_hook or lib.sva_test_sampler_launch, "sva_test_sampler_launch" if _hook is None else "sva_test_sampler_rows", desc,
+               [temperature, top_p, e.get("penalty", 1.5)],
                [logits, noise, seed, frame, tok_raw, tok, forced, emb_table, emb_out, prev if prev.size else None, sup if sup.size else None], device)
     return tok_raw
+
+
+def sampling_pairs(settings):
+    """[(temperature, top_p)] -> float32 [n][2] = {inv_temp, top_p} as the samplers read them: the quotient in float, temperature clamped at 1e-5"""
+    s = np.asarray(settings, np.float32).reshape(-1, 2)
+    return np.ascontiguousarray(np.stack([np.float32(1.0) / np.maximum(s[:, 0], np.float32(1e-5)), s[:, 1]], axis=1), dtype=np.float32)
+
+
+def test_sampler_rows(logits, rows, V, ldl, pairs=None, row_slot=None, **kw):
+    """test_sampler_launch through sva_test_sampler_rows: row r samples with pairs[row_slot[r]] (row_slot None: pairs[r]), pairs = [(temperature,
+    top_p)]; pairs None hands a null pointer over and the scalars temperature / top_p of `kw` apply"""
+    lib = load_library()
+    sp = None if pairs is None else sampling_pairs(pairs)
+    rs = _i32(row_slot)
+
+    def hook(device, d, f, ptrs):
+        return lib.sva_test_sampler_rows(device, d, f, ptrs, _ptr(sp), 0 if sp is None else sp.shape[0], _ptr(rs))
+
+    return test_sampler_launch(logits, rows, V, ldl, _hook=hook, **kw)
 
 
 AR_NUCLEUS_INSTS = {0: (4, 4, 1024), 1: (4, 32, 8192), 2: (8, 16, 8192), 3: (1, 16, 1024)}        # inst -> (NW, PER, largest V)

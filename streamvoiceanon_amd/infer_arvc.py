@@ -491,14 +491,18 @@ class InferenceWrapper:
 
 
     def stream_infer_many(self, sources, refs, n_slots, encode_window_frames=128, decode_window_frames=64, max_prompt_frames=256,
-                          max_seq_frames=768, buffer_frames=32, decode_chunk_frames=1, delay=None, noise_seeds=None, on_step=None, slot_priming=False):
+                          max_seq_frames=768, buffer_frames=32, decode_chunk_frames=1, delay=None, noise_seeds=None, on_step=None, slot_priming=False,
+                          sampling=None, temperature=None, top_p=None):
         """stream_infer over a queue of utterances of unequal length on ONE batch of `n_slots` streams (continuous batching): the first
         n_slots utterances start together, a slot takes the next utterance of the queue in the step after its own ends
         (Batch.restart), and slots are retired when the queue is empty.  sources[i]: wav path or float array at 44.1 kHz; refs[i]: the
         prompt of utterance i as (ref_audio_codes, ref_content_codes, style_vectors, timbre_latents) -- calculate_prompt(...)[:4] --
         or a reference wav path / array to compute it from.  -> list of per-utterance PCM, each padded and trimmed exactly as
         stream_infer returns it (the leading zero chunks of the delay stay).  slot_priming: the batch primes a restarted slot's vocoder in
-        a one-stream workspace (Batch(slot_priming=True)): same codes, PCM within the vocoder tolerance, a stall that does not grow with n_slots."""
+        a one-stream workspace (Batch(slot_priming=True)): same codes, PCM within the vocoder tolerance, a stall that does not grow with n_slots.
+        sampling: None, or one entry per utterance -- None or the sampling_kwargs {temperature, top_p} of that utterance (the reference's callers
+        vary them per call); the slot that carries the utterance samples with them, the others with their own (Batch.set_sampling).  temperature / top_p: the batch's
+        own values, which utterances without an entry use (None: the library's defaults)."""
         from . import stream_pool
 
         assert len(sources) == len(refs) and len(sources) >= 1
@@ -521,12 +525,12 @@ class InferenceWrapper:
         self.batch = E.Batch(self.engine, n_streams=n_slots, encode_window_frames=encode_window_frames,
                              decode_window_frames=decode_window_frames, chunk_frames=decode_chunk_frames, delay=self.delay,
                              max_seq_frames=max_seq_frames, buffer_frames=buffer_frames, max_prompt_frames=max_prompt_frames,
-                             slot_priming=slot_priming)
+                             slot_priming=slot_priming, **{k: float(v) for k, v in (("temperature", temperature), ("top_p", top_p)) if v is not None})
         for s in range(n_slots):
             ac, cc, st, tm = prompts[s]
             self.batch.prefill_prompt(s, cc, ac, st, tm, noise_seed=seeds[s])
         self.batch.begin()
-        return stream_pool.run_pool(self.batch, srcs, prompts, n_slots, n, noise_seeds=seeds, on_step=on_step)
+        return stream_pool.run_pool(self.batch, srcs, prompts, n_slots, n, noise_seeds=seeds, on_step=on_step, sampling=sampling)
 
 
 def main(argv=None, weights=None, style_vectors=None, timbre_latents=None):

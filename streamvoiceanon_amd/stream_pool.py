@@ -1,6 +1,7 @@
 """Continuous batching over a queue of utterances of unequal length: which utterance sits in which slot of a running batch, when a
 slot is restarted with the next one and when it is retired.  No GPU dependency: the batch is anything with `restart(slot, cc, ac, style,
-timbre, noise_seed)`, `retire(slot)` and `step(pcm_in) -> pcm_out` (engine.Batch, or a recording fake in the CPU tests).
+timbre, noise_seed)`, `retire(slot)` and `step(pcm_in) -> pcm_out` (engine.Batch, or a recording fake in the CPU tests); with per-utterance
+sampling also `set_sampling(slot, temperature, top_p)` and the same two keywords on `restart`.
 
 Timeline of a slot: its utterance of n chunks occupies n consecutive steps (the leading zero chunks of the delay included, as
 stream_infer returns them); in the step after the last one the slot carries the next utterance of the queue, or is retired when the
@@ -75,23 +76,42 @@ class SlotPool:
         return ended
 
 
-def run_pool(batch, sources, prompts, n_slots, samples_per_chunk, noise_seeds=None, on_step=None):
+def _sampling_entry(entry):
+    """None, or {temperature, top_p} of one utterance (through infer_arvc.check_sampling_kwargs) -> None or the keyword arguments of
+    Batch.set_sampling / Batch.restart; per-slot sampler edits do not exist"""
+    if entry is None:
+        return None
+    from .infer_arvc import check_sampling_kwargs
+
+    kw = check_sampling_kwargs(dict(entry))
+    if "edits" in kw:
+        raise ValueError("per-utterance sampling takes temperature / top_p only (sampler edits belong to the whole batch)")
+    return {"temperature": kw.get("temperature"), "top_p": kw.get("top_p")}
+
+
+def run_pool(batch, sources, prompts, n_slots, samples_per_chunk, noise_seeds=None, on_step=None, sampling=None):
     """Drive `batch` (already begun with the utterances of SlotPool.start() in their slots) over `sources` (float arrays, each a whole number
     of chunks) -> per-utterance PCM, each trimmed to its own chunks.  prompts[i] = (ac, cc, style, timbre) of utterance i.
-    on_step(step index, feeds) is called after every step (tests, reports)."""
+    on_step(step index, feeds) is called after every step (tests, reports).  sampling: None, or one entry per utterance -- None (the
+    batch's temperature / top_p) or a dict of the two: set on the slot that takes the utterance, before the first step (batch.set_sampling)
+    or with its restart (batch.restart(..., temperature=, top_p=)); a restart without an entry puts the batch's values back by itself."""
     n = int(samples_per_chunk)
     srcs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in sources]
     assert all(s.shape[0] % n == 0 and s.shape[0] >= n for s in srcs), "sources must be whole chunks"
     pool = SlotPool([s.shape[0] // n for s in srcs], n_slots)
     seeds = list(noise_seeds) if noise_seeds is not None else [0] * len(srcs)
     outs = [np.zeros_like(s) for s in srcs]
-    pool.start()
+    samp = [None] * len(srcs) if sampling is None else [_sampling_entry(e) for e in sampling]
+    assert len(samp) == len(srcs), "sampling: one entry per utterance"
+    for s, u in pool.start():
+        if samp[u] is not None:
+            batch.set_sampling(s, **samp[u])
     step = 0
     while not pool.done():
         restart, retire = pool.plan()
         for s, u in restart:
             ac, cc, style, timbre = prompts[u]
-            batch.restart(s, cc, ac, style, timbre, noise_seed=seeds[u])
+            batch.restart(s, cc, ac, style, timbre, noise_seed=seeds[u], **(samp[u] or {}))
         for s in retire:
             batch.retire(s)
         feeds = pool.feeds()
