@@ -226,6 +226,18 @@ int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float* noise, con
 int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* ref_ac, int R, const int64_t* src_cc, int S,
                  const float* style, const float* timbre, uint64_t noise_seed, const float* noise, int32_t* codes_out);
 
+/* ARVCWrapper.generate for every slot of a batch at once (chunk_frames == 1).  n == n_streams utterances; utterance i lives in slot i:
+ * ref_cc[i] int64[R[i]], ref_ac[i] int32[8][R[i]], src_cc[i] int64[S[i]], style float[n][192], timbre float[n][32][128], noise_seed[n];
+ * noise float[S_max][n][vocab + 8*codebook_size] (frame-major, S_max = max S[i]) or NULL = device RNG keyed per slot by noise_seed[i];
+ * codes_out[i] int32[8][S[i]]: exactly 8 * S[i] ints are written.
+ * Slot i gets what sva_generate computes for utterance i on a one-stream batch: frame 0 samples at temperature = top_p = 0.7, later frames with
+ * the slot's own pair (sva_stream_set_sampling); sampler edits apply from frame 1.  The prompts run as packed passes over the rows of several
+ * slots; a slot that has produced its S[i] frames rides along parked until the longest one ends.  Every argument is checked before any state
+ * changes: delay < S[i] < 4096, 33 + 2(R[i] + delay) + 1 + 2(S[i] - 1) <= 2048.  Afterwards sva_prefill_prompt + sva_streams_begin start streams afresh. */
+int sva_generate_many(sva_batch* b, int n, const int64_t* const* ref_cc, const int32_t* const* ref_ac, const int* R,
+                      const int64_t* const* src_cc, const int* S, const float* style, const float* timbre,
+                      const uint64_t* noise_seed, const float* noise, int32_t* const* codes_out);
+
 /* taps of the last step: "content_codes" int32[B][chunk], "audio_codes" int32[B][8][chunk] (as int32),
  * "slow_logits" float[B][vocab], "fast_logits" float[B][8][codebook_size], "hidden" float[B][dim],
  * "semantic" int32[B], "last_pos" int32[B], "mel" float[B][T][160] ... ; returns #bytes or <0 */
@@ -395,6 +407,16 @@ int sva_test_prefill_attention(int device, int M, int H, int pos0, int S, const 
 /* the same rows through the decode frame's paired attention kernel (rows 2 i, 2 i + 1 share one pass over the slot's K / V; M even) */
 int sva_test_pair_attention(int device, int M, int H, int pos0, int S, const float* q, const float* keys, const float* vals,
                                int half_kv, float* out_ref, float* out_mfma, int iters, float* us);
+/* The runs arm of the same kernel (launch_ar_prefill_attention_runs): a packed pass of total_rows rows q [total_rows][H*64] holding n_runs runs
+ * runs[r] = {slot, pos0, M, row0} against a cache [n_slots][2][H][S][64] (fp32, or rounded to fp16 when half_kv).  out [total_rows][H*64] is uploaded
+ * first, so a sentinel survives where nothing is stored.  single_out (or NULL) receives the single-run launcher called once per run on the same
+ * device data.  Returns 1 when the launcher refused (nothing written). */
+int sva_test_prefill_attention_runs(int device, int n_runs, const int* runs, int total_rows, int H, int S, int n_slots, int half_kv, const float* q,
+                                    const float* cache, float* out, float* single_out);
+/* The packing of sva_generate_many's prompt passes, no GPU needed: out = pass index and row0 of each of the n slots (2 n ints), then for every
+ * pass {number of tiles, then {run, q0} per tile} with run counted inside the pass; out_cap ints available.  Returns the number of passes,
+ * < 0 for an M outside 1 .. Mmax or a short out. */
+int sva_test_prefill_pack(const int* M, int n, int Mmax, int* out, int out_cap);
 
 /* Per-kernel hooks of the non-GEMM launchers (csrc/kernels.h), for tests/test_gpu_kernels.py: host arrays in, the production launcher with the
  * caller's arguments, host arrays out.  Output arrays are uploaded before the launch, so a sentinel the caller wrote survives wherever the

@@ -1087,7 +1087,7 @@ int steady_launches(sva_batch* b, bool timing_events) {
     SVA_TRY(b->enc_incremental ? encode_incremental(b, b->d_step, n, 1) : encode(b, b->d_step, n, 1));
     SVA_TRY(launch_append_content(b->d_codes, b->T2, chunk, b->d_content_hist, b->hist_cap, b->d_ncontent, b->d_step_content, B, b->d_step, st));
     if (timing_events) SVA_HIP(hipEventRecord(b->ev[1], st));
-    for (int ci = 0; ci < chunk; ++ci) SVA_TRY(ar_decode_frame(b, ci));          // :534-538
+    for (int ci = 0; ci < chunk; ++ci) SVA_TRY(ar_decode_frame(b, ci, b->d_codes, b->T2, b->T2 - chunk + ci));          // :534-538
     if (timing_events) SVA_HIP(hipEventRecord(b->ev[2], st));
     b->voc_codes = b->d_step_audio; b->voc_codes_bstride = (long)ncb * chunk; b->voc_codes_gstride = chunk;      // read in place
     const int vrc = vocode(b, chunk, true);
@@ -1243,7 +1243,7 @@ int steady_pipelined(sva_batch* b) {
         if (!b->pipe_graph_a[par]) {
             hipGraph_t graph = nullptr;
             SVA_HIP(hipStreamBeginCapture(sa, hipStreamCaptureModeThreadLocal));
-            for (int ci = 0; ci < chunk && !rc; ++ci) rc = ar_decode_frame(b, ci);
+            for (int ci = 0; ci < chunk && !rc; ++ci) rc = ar_decode_frame(b, ci, b->d_codes, b->T2, b->T2 - chunk + ci);
             const hipError_t ce = hipStreamEndCapture(sa, &graph);
             if (rc) { b->stream = se; return rc; }
             if (ce != hipSuccess || hipGraphInstantiate(&b->pipe_graph_a[par], graph, nullptr, nullptr, 0) != hipSuccess) {
@@ -1261,9 +1261,9 @@ int steady_pipelined(sva_batch* b) {
                 SVA_HIP(hipGraphLaunch(b->pipe_graph_a[par], sa));
                 rc = chain.finish();
             }
-        } else for (int ci = 0; ci < chunk && !rc; ++ci) rc = ar_decode_frame(b, ci);
+        } else for (int ci = 0; ci < chunk && !rc; ++ci) rc = ar_decode_frame(b, ci, b->d_codes, b->T2, b->T2 - chunk + ci);
     } else {
-        for (int ci = 0; ci < chunk && !rc; ++ci) rc = ar_decode_frame(b, ci);
+        for (int ci = 0; ci < chunk && !rc; ++ci) rc = ar_decode_frame(b, ci, b->d_codes, b->T2, b->T2 - chunk + ci);
     }
     if (rc) { b->stream = se; return rc; }
     if (stage_ev) SVA_HIP(hipEventRecord(b->ev[2], sa));
@@ -1891,7 +1891,7 @@ extern "C" int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float*
     SVA_TRY(h2d(b, b->d_use_forced, &uf, sizeof(int)));
     b->h_use_forced = uf;
     if (forced) SVA_TRY(h2d(b, b->d_forced, forced, sizeof(int) * (size_t)B * ncb));
-    SVA_TRY(ar_decode_frame(b, 0));
+    SVA_TRY(ar_decode_frame(b, 0, b->d_codes, b->T2, b->T2 - 1));
     for (int i = 0; i < B; ++i) b->slots.frame_decoded(i, 2);
     SVA_HIP(hipMemcpyAsync(codes_out, b->d_step_audio, sizeof(int) * (size_t)B * ncb, hipMemcpyDeviceToHost, st));
     if (pos_out) SVA_HIP(hipMemcpyAsync(pos_out, b->d_last_pos, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
@@ -1987,6 +1987,151 @@ extern "C" int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* 
     SVA_HIP(hipStreamSynchronize(st));
     for (int q = 0; q < ncb; ++q)
         SVA_HIP(hipMemcpy(codes_out + (size_t)q * S, b->d_pred_hist + (size_t)q * b->hist_cap, sizeof(int) * (size_t)S, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- offline batches: ARVCWrapper.generate for every slot of the batch at once.  Slot i gets what sva_generate computes for utterance i on a
+// one-stream batch (token layout, wait4end rows, the frame-0 rule, skip_semantic, batch-wide sampler edits from frame 1); the prompts run as
+// packed passes over the rows of several slots, the frames through the batch's normal decode choice, finished slots ride along parked ----
+extern "C" int sva_generate_many(sva_batch* b, int n, const int64_t* const* ref_cc, const int32_t* const* ref_ac, const int* R,
+                                 const int64_t* const* src_cc, const int* S, const float* style, const float* timbre,
+                                 const uint64_t* noise_seed, const float* noise, int32_t* const* codes_out) {
+    SVA_CHECK(b && ref_cc && ref_ac && R && src_cc && S && style && timbre && noise_seed && codes_out, "sva_generate_many: null argument");
+    SVA_CHECK(b->p.chunk_frames == 1 && n == b->B, "sva_generate_many: needs chunk_frames == 1 and one utterance per slot (n == n_streams)");
+    sva_engine* e = b->e;
+    const sva_config& c = e->cfg;
+    const int B = b->B, D = c.ar_dim, d = b->p.delay, ncb = c.num_codebooks, nspk = c.timbre_tokens + 1;
+    std::vector<int> Mi(B);
+    int Smax = 0;
+    for (int i = 0; i < B; ++i) {
+        SVA_CHECK(ref_cc[i] && ref_ac[i] && src_cc[i] && codes_out[i], "sva_generate_many: null argument");
+        SVA_CHECK(R[i] >= 1, "sva_generate_many: empty prompt");
+        SVA_CHECK(S[i] > d, "sva_generate_many: source length must exceed the delay");
+        SVA_CHECK(S[i] < b->hist_cap, "sva_generate_many: source longer than the prediction history (a finished slot parks in one spare column)");
+        Mi[i] = nspk + 2 * (R[i] + d) + 1;
+        SVA_CHECK(Mi[i] <= b->Mmax && R[i] + d <= b->Pmax, "sva_generate_many: prompt longer than the AR scratch");
+        SVA_CHECK(Mi[i] + 2 * (S[i] - 1) <= c.max_seq_len, "sva_generate_many: prompt + source exceed the 2048-position KV cache (the reference breaks there too)");
+        Smax = std::max(Smax, S[i]);
+    }
+    std::vector<int> pass_of, row0_of;
+    const int n_pass = prefill_pack(Mi.data(), B, b->Mmax, pass_of, row0_of);
+    SVA_CHECK(n_pass >= 1, "sva_generate_many: prompt longer than the AR scratch");
+    SVA_HIP(hipSetDevice(e->device));
+    (void)hipGetLastError();
+    SVA_TRY(quiesce(b));
+    hipStream_t st = b->stream;
+
+    // remaining_cond of every slot = [src_cond[d:], wait4end[:d]] (wait4end_j addressed as vocab + j), padded with a valid row
+    std::vector<long long> rem((size_t)B * Smax, 0);
+    for (int i = 0; i < B; ++i)
+        for (int f = 0; f < S[i]; ++f) rem[(size_t)i * Smax + f] = f < S[i] - d ? (long long)src_cc[i][d + f] : (long long)c.ar_vocab + (f - (S[i] - d));
+    // slots in the order they finish; the gather index of each slot's last prompt row inside its pass
+    std::vector<int> order(B), last_row(B), lp(B);
+    for (int i = 0; i < B; ++i) { order[i] = i; last_row[i] = row0_of[i] + Mi[i] - 1; lp[i] = Mi[i] - 1; }
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return S[x] < S[y]; });
+    // one device block for the call: run + tile tables (16-byte rows first) | rem | staging rows | order | last_row
+    PrefillTiles tt;
+    tt.max_runs = (size_t)B; tt.max_tiles = (size_t)b->Mmax / 16 + (size_t)B;
+    const size_t tab_bytes = sizeof(int) * (4 * tt.max_runs + 2 * tt.max_tiles), rem_bytes = sizeof(long long) * rem.size();
+    const size_t stage_bytes = sizeof(float) * (size_t)B * D;
+    struct DevGuard { char* p = nullptr; ~DevGuard() { if (p) (void)hipFree(p); } } guard;      // freed on every return path
+    SVA_HIP(hipMalloc((void**)&guard.p, tab_bytes + rem_bytes + stage_bytes + sizeof(int) * 2 * B));
+    tt.dev = (int*)guard.p;
+    long long* d_rem = (long long*)(guard.p + tab_bytes);
+    float* d_stage = (float*)(guard.p + tab_bytes + rem_bytes);
+    int* d_order = (int*)(guard.p + tab_bytes + rem_bytes + stage_bytes);
+    int* d_last_row = d_order + B;
+    SVA_HIP(hipMemcpyAsync(d_rem, rem.data(), rem_bytes, hipMemcpyHostToDevice, st));
+    SVA_HIP(hipMemcpyAsync(d_order, order.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
+    SVA_HIP(hipMemcpyAsync(d_last_row, last_row.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
+    SVA_HIP(hipMemcpyAsync(b->d_style, style, sizeof(float) * (size_t)B * c.style_dim, hipMemcpyHostToDevice, st));
+    SVA_HIP(hipMemcpyAsync(b->d_timbre, timbre, sizeof(float) * (size_t)B * c.timbre_tokens * c.timbre_dim, hipMemcpyHostToDevice, st));
+    SVA_HIP(hipMemcpyAsync(b->d_seed, noise_seed, sizeof(unsigned long long) * (size_t)B, hipMemcpyHostToDevice, st));
+    SVA_HIP(hipMemcpyAsync(b->d_last_pos, lp.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
+    SVA_HIP(hipMemsetAsync(b->d_nframes, 0, sizeof(int) * B, st));
+    SVA_HIP(hipStreamSynchronize(st));
+
+    // the prompts: as many whole slots per pass as fit Mmax rows, one ar_layers_pass per pack, the last prompt row of each slot gathered for frame 0
+    std::vector<int> hs(b->Mmax), hp(b->Mmax), runs;
+    for (int i0 = 0; i0 < B;) {
+        int i1 = i0, rows = 0;
+        runs.clear();
+        for (; i1 < B && pass_of[i1] == pass_of[i0]; ++i1) {
+            const int i = i1, Rp = R[i] + d, M = Mi[i], row0 = row0_of[i];
+            // prefill_cond = [ref_cond, src_cond[:d]] interleaved with [wait4start[:d], embed(ref_audio)]  (dual_ar_stream.py:711-715)
+            std::vector<int64_t> cc(ref_cc[i], ref_cc[i] + R[i]);
+            for (int k = 0; k < d; ++k) cc.push_back(src_cc[i][k]);
+            std::vector<int32_t> ac((size_t)ncb * Rp, 0);
+            for (int q = 0; q < ncb; ++q)
+                for (int k = 0; k < R[i]; ++k) ac[(size_t)q * Rp + k] = ref_ac[i][(size_t)q * R[i] + k];
+            SVA_TRY(stage_prompt(b, cc, ac, Rp));
+            SVA_TRY(gemm_call(b, b->d_timbre + (long)i * c.timbre_tokens * c.timbre_dim, (long)c.timbre_tokens * c.timbre_dim, 0, c.timbre_dim, 1, c.timbre_tokens,
+                              1, 1, 1, c.timbre_dim, e->context_in, b->spk, (long)nspk * D, 0, D));
+            SVA_TRY(gemm_call(b, b->d_style + (long)i * c.style_dim, c.style_dim, 0, c.style_dim, 1, 1, 1, 1, 1, c.style_dim, e->style_in,
+                              b->spk + (long)c.timbre_tokens * D, D, 0, D));
+            SVA_TRY(launch_build_prompt(b->spk, nspk, e->content_emb, e->codebook_emb, e->wait4start, b->d_prompt_cc, b->d_prompt_ac, b->Pmax, Rp, d, ncb,
+                                        c.codebook_size, D, b->ax + (long)row0 * D, M - 1, st));
+            SVA_TRY(launch_put_row(e->content_emb, rem[(size_t)i * Smax], D, b->ax + (long)(row0 + M - 1) * D, st));
+            for (int m = 0; m < M; ++m) { hs[row0 + m] = i; hp[row0 + m] = m; }
+            runs.insert(runs.end(), {i, 0, M, row0});
+            rows = row0 + M;
+        }
+        SVA_HIP(hipMemcpyAsync(b->d_slot, hs.data(), sizeof(int) * rows, hipMemcpyHostToDevice, st));
+        SVA_HIP(hipMemcpyAsync(b->d_pos, hp.data(), sizeof(int) * rows, hipMemcpyHostToDevice, st));
+        SVA_HIP(hipStreamSynchronize(st));            // (hs / hp are rewritten by the next pass)
+        const PassRuns pr{runs.data(), (int)runs.size() / 4, &tt};
+        SVA_TRY(ar_layers_pass(b, e->ar_layers, rows, b->d_slot, b->d_pos, e->rope_ar, (float*)b->kv_slow, b->kv_slow_layer, b->kv_slow_slot, c.max_seq_len,
+                               b->ax, -1, 0, &pr));
+        SVA_TRY(launch_gather_rows(b->ax, d_last_row + i0, 1, 0, i1 - i0, D, d_stage + (long)i0 * D, D, st));
+        SVA_HIP(hipStreamSynchronize(st));            // the pass is done: its tile table's host copy may go, b->ax may be rebuilt
+        tt.host.clear();
+        i0 = i1;
+    }
+    for (int i = 0; i < B; ++i) b->slots.offline_prefilled(i, lp[i]);
+    SVA_HIP(hipMemcpyAsync(b->ax, d_stage, stage_bytes, hipMemcpyDeviceToDevice, st));
+
+    const int nstride = c.ar_vocab + ncb * c.codebook_size;
+    const int zero = 0;
+    SVA_TRY(h2d(b, b->d_use_forced, &zero, sizeof(int)));
+    b->h_use_forced = 0;
+    b->noise_on_device = (noise == nullptr);
+    {   // frame 0 sits on the prefill's last row.  The prefill's decode ignores the caller's sampling settings (dual_ar_stream.py:722): temperature = top_p = 0.7,
+        // no previous_tokens / suppress_tokens -- written into every slot's device pair for this one frame; the slots' own pairs come back from the book
+        if (noise) SVA_TRY(h2d(b, b->d_noise, noise, sizeof(float) * (size_t)B * nstride));
+        std::vector<float> pairs((size_t)2 * B);
+        for (int i = 0; i < B; ++i) { pairs[2 * i] = 1.0f / 0.7f; pairs[2 * i + 1] = 0.7f; }
+        SVA_TRY(h2d(b, b->d_samp, pairs.data(), sizeof(float) * pairs.size()));
+        b->edits_skip = true;
+        const int rc0 = ar_frame_tail(b, 0, (long)D, 0, d_rem, Smax, 0, 0);
+        b->edits_skip = false;
+        for (int i = 0; i < B; ++i) { pairs[2 * i] = b->slots.s[i].samp[0]; pairs[2 * i + 1] = b->slots.s[i].samp[1]; }
+        const int rc1 = h2d(b, b->d_samp, pairs.data(), sizeof(float) * pairs.size());
+        SVA_TRY(rc0);
+        SVA_TRY(rc1);
+        for (int i = 0; i < B; ++i) b->slots.frame_decoded(i, 0);
+    }
+    // frames 1 .. Smax - 1 of every slot: tokens [embed(previous codes), rem[f]] at the next two positions (dual_ar_stream.py:735-760).  A slot that
+    // has produced its S[i] frames rides along parked: when it finishes, and after every throw-away frame, its position goes back by 2, so the
+    // frame rewrites the two KV positions of the slot's own last frame (never a position past the cache); after a throw-away frame its frame
+    // counter goes back by 1, so its codes land in ring column S[i], the spare one.  No launch while nobody has finished.
+    int n_done = 0;                                   // slots order[0 .. n_done) have finished before frame f
+    for (int f = 1; f < Smax; ++f) {
+        if (noise) SVA_TRY(h2d(b, b->d_noise, noise + (size_t)f * B * nstride, sizeof(float) * (size_t)B * nstride));
+        SVA_TRY(ar_decode_frame(b, 0, d_rem, Smax, f));
+        for (int i = 0; i < B; ++i) b->slots.frame_decoded(i, 2);
+        int n_now = n_done;
+        while (n_now < B && S[order[n_now]] <= f + 1) ++n_now;
+        if (f + 1 < Smax && n_now > 0) {
+            SVA_TRY(launch_add_list(b->d_last_pos, d_order, n_now, -2, st));
+            if (n_done > 0) SVA_TRY(launch_add_list(b->d_nframes, d_order, n_done, -1, st));
+            for (int k = 0; k < n_now; ++k) b->slots.offline_parked(order[k], 2, k < n_done ? 1 : 0);
+        }
+        n_done = n_now;
+    }
+    SVA_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < B; ++i)
+        for (int q = 0; q < ncb; ++q)
+            SVA_HIP(hipMemcpy(codes_out[i] + (size_t)q * S[i], b->d_pred_hist + ((size_t)i * ncb + q) * b->hist_cap, sizeof(int) * (size_t)S[i], hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -71,8 +71,15 @@ int enc_frontend_merged(sva_batch* b, const int* step_ptr, int n_chunk, int add,
 int enc_transformer(sva_batch* b, const Act& xin, int need_rows, int part = 0);
 int encode(sva_batch* b, const int* step_ptr, int n_chunk, int add);
 int encode_incremental(sva_batch* b, const int* step_ptr, int n_chunk, int add, bool transformer_too = true);
-int ar_layers_pass(sva_batch* b, std::vector<TrLayer>& layers, int M, const int* d_slot, const int* d_pos, const float* rope, float* kv, long kv_layer, long kv_slot, int S, float* x, int run_slot = -1, int run_pos0 = 0);
-int ar_decode_frame(sva_batch* b, int ci);
+// a packed pass over the prompt rows of several slots (launch_ar_prefill_attention_runs): its runs {slot, pos0, M, row0} and the tile table's buffers
+struct PassRuns {
+    const int* runs;
+    int n_runs;
+    PrefillTiles* tiles;
+};
+int ar_layers_pass(sva_batch* b, std::vector<TrLayer>& layers, int M, const int* d_slot, const int* d_pos, const float* rope, float* kv, long kv_layer, long kv_slot, int S, float* x, int run_slot = -1, int run_pos0 = 0, const PassRuns* runs = nullptr);
+// one decoded frame of every stream through the batch's decode choice; content code of slot s = codes[s * codes_ld + code_off]
+int ar_decode_frame(sva_batch* b, int ci, const long long* codes, int codes_ld, int code_off);
 // orders the persistent decode launches of different batches of one engine (stages.hip)
 struct PersistentChain {
     sva_batch* b;
@@ -84,7 +91,7 @@ struct PersistentChain {
     int finish();          // records the engine's event behind the launches enqueued since construction
 };
 int ar_decode_frame_batch(sva_batch* b, int ci);
-int ar_decode_frame_mega(sva_batch* b, int ci, const long long* codes, int code_off);
+int ar_decode_frame_mega(sva_batch* b, int ci, const long long* codes, int code_off, int codes_ld = 0);      // (codes_ld == 0: the encoder's table, T2)
 int ar_frame_tail(sva_batch* b, int ci, long hid_stride, long hid_off, const long long* codes, int codes_ld, int code_off, int last_pos_inc);
 int ar_prefill_slot(sva_batch* b, int slot, int R, bool tap_logits = false);
 int ar_delay_fill(sva_batch* b, const std::vector<int>& slots);

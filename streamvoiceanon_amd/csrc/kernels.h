@@ -2,6 +2,8 @@
 #pragma once
 #include "sva_common.h"
 
+#include <deque>
+
 namespace sva {
 
 // ---- content encoder -------------------------------------------------------------------
@@ -68,6 +70,26 @@ int launch_ar_attention_pairs(const float* qkv, int M, int H, int hd, const int*
 template <typename KV>
 int launch_ar_prefill_attention(const float* qkv, int M, int H, int hd, int slot0, int pos0, const KV* cache, long slot_stride, int S, float* out,
                                 hipStream_t st);
+// The same tile body for a PACKED pass holding the prompt rows of several slots (sva_generate_many): run r = runs[4 r ..] = {slot, pos0, M, row0},
+// rows row0 .. row0 + M - 1 of qkv / out at positions pos0 .. pos0 + M - 1 of `slot`; every run is cut into its own 16-row tiles.  Refuses
+// hd != 64, n_runs < 1, a run outside the cache (n_slots slots of S positions) or outside the pass's total_rows, and overlapping row ranges.
+// The run and tile tables go to tt.dev stream-ordered from a buffer appended to tt.host, which must live until the pass is synchronised;
+// with tt.ready set (the later layers of one pass, same runs) the table already enqueued is used again.
+struct PrefillTiles {
+    int* dev = nullptr;                     // [4 * max_runs + 2 * max_tiles]
+    size_t max_runs = 0, max_tiles = 0;
+    std::deque<std::vector<int>> host;
+    bool ready = false;
+    int n_tiles = 0;
+};
+template <typename KV>
+int launch_ar_prefill_attention_runs(const float* qkv, const int* runs, int n_runs, int total_rows, int H, int hd, const KV* cache, long slot_stride, int n_slots,
+                                     int S, float* out, PrefillTiles& tt, hipStream_t st);
+// {run, q0} pairs of the runs' tiles, in run order; returns their number
+int prefill_tile_table(const int* runs, int n_runs, std::vector<int>& tiles);
+// greedy packing of whole slots, in slot order, into passes of at most Mmax rows: pass_of[i], row0_of[i] (the prefix sum inside its pass);
+// returns the number of passes, -1 for an M[i] outside 1 .. Mmax
+int prefill_pack(const int* M, int n, int Mmax, std::vector<int>& pass_of, std::vector<int>& row0_of);
 // partial != null: split-key decode -- `splits` workgroups per (head, row) write unnormalised partials
 // partial[((m*H + h)*splits + s)*68 + {0..63: P.V, 64: max score, 65: exp-sum}] that gemv mode 4 merges
 

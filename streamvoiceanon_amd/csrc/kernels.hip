@@ -982,18 +982,32 @@ template <> __device__ __forceinline__ float4 ld_kv_f4<__half>(const __half* p) 
     return make_float4(__low2float(a), __high2float(a), __low2float(b), __high2float(b));
 }
 
-template <typename KV>
-__global__ __launch_bounds__(256) void ar_prefill_attention_kernel(const float* __restrict__ qkv, int M, int H, int pos0,
-                                                                   const KV* __restrict__ cache_slot, int S, float* __restrict__ out) {
+// RUNS: one launch serves a PACKED pass holding the prompt rows of several slots (the offline batch's prefill, sva_generate_many).  A run
+// {slot, pos0, M, row0} = rows row0 .. row0 + M - 1 of qkv / out at positions pos0 .. pos0 + M - 1 of `slot`; blockIdx.y indexes a tile table
+// {run, q0} in which every run is cut into its own 16-row tiles from its own row 0, so a tile never spans two runs.  The tile takes its
+// cache, pos0 and M from its run and moves qkv / out to the run's first row; everything below that is the one tile body (its tail clamp
+// min(q0 + fr, M - 1) stays inside the run: a clamped row never reads a neighbouring run's row).
+template <typename KV, bool RUNS>
+__global__ __launch_bounds__(256) void ar_prefill_attention_kernel(const float* __restrict__ qkv, int M_, int H, int pos0_,
+                                                                   const KV* __restrict__ cache_slot, int S, float* __restrict__ out,
+                                                                   const int4* __restrict__ runs, const int2* __restrict__ tiles, long slot_stride) {
     constexpr int HD = 64, KB = 64, LV = KB + 4;
     __shared__ __attribute__((aligned(16))) float Ps[4 * 16 * LV];        // per wave [row][key]
     __shared__ float Ms[4 * 16], Ls[4 * 16];                              // per wave row max / exp-sum
     __shared__ __attribute__((aligned(16))) float Os[4 * 16 * (HD + 4)];  // per wave unnormalised P.V
     const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fk = lane >> 4;
     const int D = H * HD;
+    int M = M_, pos0 = pos0_, q0 = blockIdx.y * 16;
+    if constexpr (RUNS) {
+        const int2 t = tiles[blockIdx.y];
+        const int4 r = runs[t.x];                                         // {slot, pos0, M, row0}
+        cache_slot += (long)r.x * slot_stride;
+        pos0 = r.y; M = r.z; q0 = t.y;
+        qkv += (long)r.w * 3 * D;
+        out += (long)r.w * D;
+    }
     const KV* kc = cache_slot + (long)h * S * HD;
     const KV* vc = kc + (long)H * S * HD;
-    const int q0 = blockIdx.y * 16;
     const int L = pos0 + M;                                               // keys of this pass: 0 .. L-1
     const int last_key = min(q0 + 15, M - 1) + pos0;                      // last key any row of the tile may see
     // Q fragments: lane (fr, fk) holds dims 16 blk + 4 fk .. +3 of row q0 + fr (RoPE already applied in place)
@@ -1122,10 +1136,62 @@ template <typename KV>
 int launch_ar_prefill_attention(const float* qkv, int M, int H, int hd, int slot0, int pos0, const KV* cache, long slot_stride, int S, float* out,
                                 hipStream_t st) {
     SVA_CHECK(hd == 64 && M >= 1 && pos0 >= 0 && pos0 + M <= S, "ar_prefill_attention: head_dim 64, rows inside the cache");
-    hipLaunchKernelGGL((ar_prefill_attention_kernel<KV>), dim3(H, (M + 15) / 16), dim3(256), 0, st, qkv, M, H, pos0, cache + (long)slot0 * slot_stride, S, out);
+    hipLaunchKernelGGL((ar_prefill_attention_kernel<KV, false>), dim3(H, (M + 15) / 16), dim3(256), 0, st, qkv, M, H, pos0, cache + (long)slot0 * slot_stride, S, out,
+                       (const int4*)nullptr, (const int2*)nullptr, 0L);
     SVA_HIP(hipGetLastError());
     return 0;
 }
+int prefill_tile_table(const int* runs, int n_runs, std::vector<int>& tiles) {
+    tiles.clear();
+    for (int r = 0; r < n_runs; ++r)
+        for (int q0 = 0; q0 < runs[4 * r + 2]; q0 += 16) { tiles.push_back(r); tiles.push_back(q0); }
+    return (int)tiles.size() / 2;
+}
+int prefill_pack(const int* M, int n, int Mmax, std::vector<int>& pass_of, std::vector<int>& row0_of) {
+    pass_of.assign((size_t)n, 0); row0_of.assign((size_t)n, 0);
+    int pass = 0, rows = 0;
+    for (int i = 0; i < n; ++i) {
+        if (M[i] < 1 || M[i] > Mmax) return -1;
+        if (rows + M[i] > Mmax) { ++pass; rows = 0; }
+        pass_of[i] = pass; row0_of[i] = rows;
+        rows += M[i];
+    }
+    return n ? pass + 1 : 0;
+}
+template <typename KV>
+int launch_ar_prefill_attention_runs(const float* qkv, const int* runs, int n_runs, int total_rows, int H, int hd, const KV* cache, long slot_stride, int n_slots,
+                                     int S, float* out, PrefillTiles& tt, hipStream_t st) {
+    SVA_CHECK(hd == 64 && runs && n_runs >= 1 && total_rows >= 1, "ar_prefill_attention_runs: head_dim 64, at least one run");
+    if (tt.ready) {     // the later layers of one pass: the table of its first layer is already on its way, in stream order
+        hipLaunchKernelGGL((ar_prefill_attention_kernel<KV, true>), dim3(H, tt.n_tiles), dim3(256), 0, st, qkv, 0, H, 0, cache, S, out,
+                           reinterpret_cast<const int4*>(tt.dev), reinterpret_cast<const int2*>(tt.dev + 4 * (size_t)n_runs), slot_stride);
+        SVA_HIP(hipGetLastError());
+        return 0;
+    }
+    for (int r = 0; r < n_runs; ++r) {
+        const int slot = runs[4 * r], pos0 = runs[4 * r + 1], M = runs[4 * r + 2], row0 = runs[4 * r + 3];
+        SVA_CHECK(slot >= 0 && slot < n_slots && pos0 >= 0 && M >= 1 && pos0 <= S - M, "ar_prefill_attention_runs: a run lies outside the cache");
+        SVA_CHECK(row0 >= 0 && row0 <= total_rows - M, "ar_prefill_attention_runs: a run lies outside the pass's rows");
+        for (int q = 0; q < r; ++q)
+            SVA_CHECK(row0 >= runs[4 * q + 3] + runs[4 * q + 2] || runs[4 * q + 3] >= row0 + M, "ar_prefill_attention_runs: the row ranges of two runs overlap");
+    }
+    // the table: [n_runs] int4 runs, then the {run, q0} tiles; uploaded stream-ordered from tt.host, which the caller keeps until the pass is synchronised
+    std::vector<int> tiles;
+    const int n_tiles = prefill_tile_table(runs, n_runs, tiles);
+    SVA_CHECK((size_t)n_runs <= tt.max_runs && (size_t)n_tiles <= tt.max_tiles && tt.dev, "ar_prefill_attention_runs: the tile table is too small for this pass");
+    tt.host.emplace_back(runs, runs + 4 * (size_t)n_runs);
+    std::vector<int>& hbuf = tt.host.back();
+    hbuf.insert(hbuf.end(), tiles.begin(), tiles.end());
+    SVA_HIP(hipMemcpyAsync(tt.dev, hbuf.data(), sizeof(int) * hbuf.size(), hipMemcpyHostToDevice, st));
+    const int4* d_runs = reinterpret_cast<const int4*>(tt.dev);
+    const int2* d_tiles = reinterpret_cast<const int2*>(tt.dev + 4 * (size_t)n_runs);
+    hipLaunchKernelGGL((ar_prefill_attention_kernel<KV, true>), dim3(H, n_tiles), dim3(256), 0, st, qkv, 0, H, 0, cache, S, out, d_runs, d_tiles, slot_stride);
+    SVA_HIP(hipGetLastError());
+    tt.ready = true; tt.n_tiles = n_tiles;
+    return 0;
+}
+template int launch_ar_prefill_attention_runs<float>(const float*, const int*, int, int, int, int, const float*, long, int, int, float*, PrefillTiles&, hipStream_t);
+template int launch_ar_prefill_attention_runs<__half>(const float*, const int*, int, int, int, int, const __half*, long, int, int, float*, PrefillTiles&, hipStream_t);
 template int launch_ar_prefill_attention<float>(const float*, int, int, int, int, int, const float*, long, int, float*, hipStream_t);
 template int launch_ar_prefill_attention<__half>(const float*, int, int, int, int, int, const __half*, long, int, float*, hipStream_t);
 

@@ -135,6 +135,9 @@ struct SlotBook {
     // one decoded frame outside the chunk step (sva_ar_decode_one: pos_inc 2; the offline loop's first frame sits on the prefill's last row: 0)
     void frame_decoded(int slot, int pos_inc) { s[slot].last_pos += pos_inc; s[slot].nframes += 1; }
     void offline_prefilled(int slot, int last_pos) { s[slot].last_pos = last_pos; s[slot].nframes = 0; }
+    // a finished slot of an offline batch rides along parked: its position is put back when it finishes and after every throw-away frame,
+    // its frame counter after every throw-away frame (sva_generate_many)
+    void offline_parked(int slot, int pos_back, int frames_back) { s[slot].last_pos -= pos_back; s[slot].nframes -= frames_back; }
     // a steady step decoded `chunk` frames for every slot (a parked slot's are thrown away).  Positions are deterministic, so the mirror decides
     // what is due without a device round trip; the rewinds are already applied to the mirror.
     StepPlan steady_step(int chunk, int max_seq_frames, int nspk) {

@@ -450,13 +450,19 @@ int encode_incremental(sva_batch* b, const int* step_ptr, int n_chunk, int add, 
 // rows [M, dim] in b->ax, slot/pos arrays on device; KV written at pos, attention over 0..pos
 // run_slot == -2: the rows are the decode frame's pairs (2 s, 2 s + 1) = positions (p, p + 1) of slot s: one attention workgroup per pair and head;
 // run_slot >= 0: the rows sit at CONSECUTIVE positions run_pos0 .. run_pos0 + M - 1 of that one slot (prompt prefill, re-prefill,
-// offline generate) -- their attention runs as the flash-style MFMA kernel instead of one workgroup per (head, row)
+// offline generate) -- their attention runs as the flash-style MFMA kernel instead of one workgroup per (head, row);
+// runs != null: the rows are the prompt rows of SEVERAL slots, each run at consecutive positions of its slot (the offline batch's packed
+// prefill): the runs arm of that kernel, one launch per layer for the whole pass
 int ar_layers_pass(sva_batch* b, std::vector<TrLayer>& layers, int M, const int* d_slot, const int* d_pos, const float* rope,
-                   float* kv, long kv_layer, long kv_slot, int S, float* x, int run_slot, int run_pos0) {
+                   float* kv, long kv_layer, long kv_slot, int S, float* x, int run_slot, int run_pos0, const PassRuns* runs) {
     const sva_config& c = b->e->cfg;
     const int D = c.ar_dim, I = c.ar_inter, H = c.ar_heads;
     hipStream_t st = b->stream;
     const bool half_kv = b->kv_half && S > 8;           // the slow cache of an ar_dtype = 1 batch (the fast cache stays fp32)
+    if (runs) {
+        SVA_CHECK(S > 8 && M > 4 && runs->tiles, "ar_layers_pass: runs are for a prompt pass over the slow cache");
+        runs->tiles->ready = false;                     // (a new pass: its first layer validates the runs and uploads the table)
+    }
     if (M <= 4 && !half_kv) {
         // decode at B <= 2: 5 launches per layer -- QKV GEMV (+RMSNorm, +RoPE, +KV write), attention, wo GEMV (+residual),
         // w1|w3 GEMV (+RMSNorm, +SwiGLU), w2 GEMV (+residual)
@@ -509,12 +515,14 @@ int ar_layers_pass(sva_batch* b, std::vector<TrLayer>& layers, int M, const int*
         } else if (half_kv) {
             __half* ch = reinterpret_cast<__half*>(kv) + (long)l * kv_layer;
             SVA_TRY(launch_rope_kvwrite<__half>(b->aqkv, M, H, 64, d_slot, d_pos, rope, ch, kv_slot, S, st));
-            if (run_slot >= 0 && M >= 96) SVA_TRY(launch_ar_prefill_attention<__half>(b->aqkv, M, H, 64, run_slot, run_pos0, ch, kv_slot, S, b->aatt, st));
+            if (runs) SVA_TRY(launch_ar_prefill_attention_runs<__half>(b->aqkv, runs->runs, runs->n_runs, M, H, 64, ch, kv_slot, b->B, S, b->aatt, *runs->tiles, st));
+            else if (run_slot >= 0 && M >= 96) SVA_TRY(launch_ar_prefill_attention<__half>(b->aqkv, M, H, 64, run_slot, run_pos0, ch, kv_slot, S, b->aatt, st));
             else if (run_slot == -2 && M % 2 == 0 && debug_options().ar_pairs) SVA_TRY(launch_ar_attention_pairs<__half>(b->aqkv, M, H, 64, d_slot, d_pos, ch, kv_slot, S, b->aatt, st));
             else SVA_TRY(launch_ar_attention<__half>(b->aqkv, M, H, 64, d_slot, d_pos, ch, kv_slot, S, b->aatt, st));
         } else {
             SVA_TRY(launch_rope_kvwrite<float>(b->aqkv, M, H, 64, d_slot, d_pos, rope, cache, kv_slot, S, st));
-            if (run_slot >= 0 && M >= 96) SVA_TRY(launch_ar_prefill_attention<float>(b->aqkv, M, H, 64, run_slot, run_pos0, cache, kv_slot, S, b->aatt, st));
+            if (runs) SVA_TRY(launch_ar_prefill_attention_runs<float>(b->aqkv, runs->runs, runs->n_runs, M, H, 64, cache, kv_slot, b->B, S, b->aatt, *runs->tiles, st));
+            else if (run_slot >= 0 && M >= 96) SVA_TRY(launch_ar_prefill_attention<float>(b->aqkv, M, H, 64, run_slot, run_pos0, cache, kv_slot, S, b->aatt, st));
             else if (run_slot == -2 && M % 2 == 0 && debug_options().ar_pairs) SVA_TRY(launch_ar_attention_pairs<float>(b->aqkv, M, H, 64, d_slot, d_pos, cache, kv_slot, S, b->aatt, st));
             else SVA_TRY(launch_ar_attention<float>(b->aqkv, M, H, 64, d_slot, d_pos, cache, kv_slot, S, b->aatt, st));
         }
@@ -542,7 +550,7 @@ int ar_layers_pass(sva_batch* b, std::vector<TrLayer>& layers, int M, const int*
 // one decoded frame for every stream (decode_one_token_ar, dual_ar_stream.py:1168-1219)
 int ar_frame_tail(sva_batch* b, int ci, long hid_stride, long hid_off, const long long* codes, int codes_ld, int code_off, int last_pos_inc);
 
-int ar_decode_frame_mega(sva_batch* b, int ci, const long long* codes, int code_off);
+int ar_decode_frame_mega(sva_batch* b, int ci, const long long* codes, int code_off, int codes_ld);
 int ar_decode_frame_batch(sva_batch* b, int ci);
 
 // Persistent decode kernels (ar_decode.hip, ar_batch.hip) need every workgroup of their grid resident at once: one 8-wave /
@@ -573,12 +581,11 @@ int PersistentChain::finish() {
     return 0;
 }
 
-int ar_decode_frame(sva_batch* b, int ci) {
+int ar_decode_frame(sva_batch* b, int ci, const long long* codes, int codes_ld, int code_off) {
     sva_engine* e = b->e;
     const sva_config& c = e->cfg;
     const int B = b->B, D = c.ar_dim, chunk = b->p.chunk_frames;
     hipStream_t st = b->stream;
-    const int code_off = b->T2 - chunk + ci;
     const bool persistent = (b->use_mega || b->use_abatch) && !b->edits_on;     // (sampler edits run on the multi-launch decode: same KV, positions and counters)
     if (persistent) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -586,19 +593,19 @@ int ar_decode_frame(sva_batch* b, int ci) {
         PersistentChain chain(b, st, eager);                                                                     //  the replay of a captured AR stage is chained as a whole, engine.hip)
         SVA_TRY(chain.rc);
         if (b->use_mega) {
-            SVA_TRY(ar_decode_frame_mega(b, ci, b->d_codes, code_off));
+            SVA_TRY(ar_decode_frame_mega(b, ci, codes, code_off, codes_ld));
         } else {
-            SVA_TRY(launch_ar_prepare_step(b->cached_audio_emb, e->content_emb, b->d_codes, b->T2, code_off, b->d_last_pos, D, b->ax, b->d_slot, b->d_pos,
+            SVA_TRY(launch_ar_prepare_step(b->cached_audio_emb, e->content_emb, codes, codes_ld, code_off, b->d_last_pos, D, b->ax, b->d_slot, b->d_pos,
                                            b->d_step_content, chunk, ci, B, st));
             SVA_TRY(ar_decode_frame_batch(b, ci));
         }
         return chain.finish();
     }
-    SVA_TRY(launch_ar_prepare_step(b->cached_audio_emb, e->content_emb, b->d_codes, b->T2, code_off, b->d_last_pos, D, b->ax, b->d_slot, b->d_pos,
+    SVA_TRY(launch_ar_prepare_step(b->cached_audio_emb, e->content_emb, codes, codes_ld, code_off, b->d_last_pos, D, b->ax, b->d_slot, b->d_pos,
                                    b->d_step_content, chunk, ci, B, st));
     SVA_TRY(ar_layers_pass(b, e->ar_layers, 2 * B, b->d_slot, b->d_pos, e->rope_ar, (float*)b->kv_slow, b->kv_slow_layer,
                            b->kv_slow_slot, c.max_seq_len, b->ax, -2));         // (-2: ar_prepare_step_kernel's row pairs)
-    return ar_frame_tail(b, ci, (long)2 * D, (long)D, b->d_codes, b->T2, code_off, 2);
+    return ar_frame_tail(b, ci, (long)2 * D, (long)D, codes, codes_ld, code_off, 2);
 }
 
 // one decoded frame of EVERY stream of the batch in one launch of the batched persistent kernel (ar_batch.hip); the frame's input
@@ -642,7 +649,7 @@ int ar_decode_frame_batch(sva_batch* b, int ci) {
 }
 
 // one decoded frame of a one-stream batch in ONE launch of the persistent kernel (ar_decode.hip)
-int ar_decode_frame_mega(sva_batch* b, int ci, const long long* codes, int code_off) {
+int ar_decode_frame_mega(sva_batch* b, int ci, const long long* codes, int code_off, int codes_ld) {
     sva_engine* e = b->e;
     const sva_config& c = e->cfg;
     ArDecodeArgs a;
@@ -674,7 +681,7 @@ int ar_decode_frame_mega(sva_batch* b, int ci, const long long* codes, int code_
     // keeps its small footprint so that the other stages' GEMM workgroups fit beside it
     {   // strides between the per-stream blocks (elements of each pointer's type)
         const int ncb = c.num_codebooks, D = c.ar_dim;
-        a.ss.codes = b->T2; a.ss.emb = D; a.ss.kv_slot = b->kv_slow_slot; a.ss.kv_fast = (long)AR_FAST_LAYERS * 8 * 2 * D;
+        a.ss.codes = codes_ld ? codes_ld : b->T2; a.ss.emb = D; a.ss.kv_slot = b->kv_slow_slot; a.ss.kv_fast = (long)AR_FAST_LAYERS * 8 * 2 * D;
         a.ss.gran = (long)ar_decode_granule_words(); a.ss.slow_logits = c.ar_vocab; a.ss.fast_logits = (long)ncb * c.codebook_size; a.ss.hidden = D;
         a.ss.tok = ncb; a.ss.step_audio = (long)ncb * b->p.chunk_frames; a.ss.pred_hist = (long)ncb * b->hist_cap;
         a.ss.step_content = b->p.chunk_frames; a.ss.noise = (long)b->p.chunk_frames * nstride; a.ss.forced = (long)ncb * b->p.chunk_frames;

@@ -203,6 +203,68 @@ extern "C" int sva_test_prefill_attention(int device, int M, int H, int pos0, in
                                           int half_kv, float* out_ref, float* out_mfma, int iters, float* us) {
     return test_attention_vs_per_row(device, false, M, H, pos0, S, q, keys, vals, half_kv, out_ref, out_mfma, iters, us);
 }
+extern "C" int sva_test_prefill_attention_runs(int device, int n_runs, const int* runs, int total_rows, int H, int S, int n_slots, int half_kv, const float* q,
+                                               const float* cache, float* out, float* single_out) {
+    SVA_CHECK(runs && q && cache && out && n_runs >= 0 && total_rows >= 1 && H >= 1 && S >= 1 && n_slots >= 1, "sva_test_prefill_attention_runs: bad arguments");
+    SVA_HIP(hipSetDevice(device));
+    const int D = H * 64;
+    const size_t slot_elems = (size_t)2 * H * S * 64, cache_elems = slot_elems * n_slots, out_elems = (size_t)total_rows * D;
+    std::vector<float> qkv((size_t)total_rows * 3 * D, 0.f);
+    for (int m = 0; m < total_rows; ++m) memcpy(&qkv[(size_t)m * 3 * D], q + (size_t)m * D, sizeof(float) * D);
+    DevBuf bq, bc, bo, bo1, bt;
+    SVA_TRY(bq.put(qkv.data(), sizeof(float) * qkv.size()));
+    if (half_kv) {
+        const std::vector<uint16_t> ch = to_half_bits(cache, cache_elems);
+        SVA_TRY(bc.put(ch.data(), 2 * cache_elems));
+    } else {
+        SVA_TRY(bc.put(cache, sizeof(float) * cache_elems));
+    }
+    SVA_TRY(bo.put(out, sizeof(float) * out_elems));
+    PrefillTiles tt;
+    tt.max_runs = (size_t)std::max(n_runs, 1); tt.max_tiles = (size_t)total_rows / 16 + tt.max_runs;
+    SVA_TRY(bt.alloc(sizeof(int) * (4 * tt.max_runs + 2 * tt.max_tiles)));
+    tt.dev = bt.as<int>();
+    const int rc = half_kv ? launch_ar_prefill_attention_runs<__half>(bq.as<float>(), runs, n_runs, total_rows, H, 64, bc.as<__half>(), (long)slot_elems, n_slots, S,
+                                                                      bo.as<float>(), tt, 0)
+                           : launch_ar_prefill_attention_runs<float>(bq.as<float>(), runs, n_runs, total_rows, H, 64, bc.as<float>(), (long)slot_elems, n_slots, S,
+                                                                     bo.as<float>(), tt, 0);
+    if (rc) return 1;                                 // refused: nothing was launched, the caller's arrays are as they were
+    SVA_HIP(hipDeviceSynchronize());
+    SVA_TRY(bo.get(out, sizeof(float) * out_elems));
+    if (single_out) {
+        SVA_TRY(bo1.put(single_out, sizeof(float) * out_elems));
+        for (int r = 0; r < n_runs; ++r) {
+            const int slot = runs[4 * r], pos0 = runs[4 * r + 1], M = runs[4 * r + 2], row0 = runs[4 * r + 3];
+            const float* qr = bq.as<float>() + (size_t)row0 * 3 * D;
+            float* orow = bo1.as<float>() + (size_t)row0 * D;
+            if (half_kv) SVA_TRY(launch_ar_prefill_attention<__half>(qr, M, H, 64, slot, pos0, bc.as<__half>(), (long)slot_elems, S, orow, 0));
+            else SVA_TRY(launch_ar_prefill_attention<float>(qr, M, H, 64, slot, pos0, bc.as<float>(), (long)slot_elems, S, orow, 0));
+        }
+        SVA_HIP(hipDeviceSynchronize());
+        SVA_TRY(bo1.get(single_out, sizeof(float) * out_elems));
+    }
+    return 0;
+}
+extern "C" int sva_test_prefill_pack(const int* M, int n, int Mmax, int* out, int out_cap) {
+    SVA_CHECK(M && out && n >= 1 && Mmax >= 1, "sva_test_prefill_pack: bad arguments");
+    std::vector<int> pass_of, row0_of;
+    const int n_pass = prefill_pack(M, n, Mmax, pass_of, row0_of);
+    SVA_CHECK(n_pass >= 1, "sva_test_prefill_pack: a slot's rows do not fit one pass (M outside 1 .. Mmax)");
+    std::vector<int> o;
+    for (int i = 0; i < n; ++i) { o.push_back(pass_of[i]); o.push_back(row0_of[i]); }
+    for (int i0 = 0; i0 < n;) {
+        std::vector<int> runs, tiles;
+        int i1 = i0;
+        for (; i1 < n && pass_of[i1] == pass_of[i0]; ++i1) runs.insert(runs.end(), {i1, 0, M[i1], row0_of[i1]});
+        const int nt = prefill_tile_table(runs.data(), (int)runs.size() / 4, tiles);
+        o.push_back(nt);
+        o.insert(o.end(), tiles.begin(), tiles.end());
+        i0 = i1;
+    }
+    SVA_CHECK((int)o.size() <= out_cap, "sva_test_prefill_pack: out is too short");
+    memcpy(out, o.data(), sizeof(int) * o.size());
+    return n_pass;
+}
 extern "C" int sva_test_pair_attention(int device, int M, int H, int pos0, int S, const float* q, const float* keys, const float* vals,
                                        int half_kv, float* out_ref, float* out_mfma, int iters, float* us) {
     SVA_CHECK(M % 2 == 0, "sva_test_pair_attention: an even number of rows");

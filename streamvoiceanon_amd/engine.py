@@ -100,6 +100,9 @@ def load_library():
     lib.sva_firefly_encode.argtypes = [vp, vp, vp]
     lib.sva_stream_chunks.argtypes = [vp, vp, vp, i32]
     lib.sva_generate.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, C.c_uint64, vp, vp]
+    lib.sva_generate_many.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.sva_test_prefill_attention_runs.argtypes = [i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.sva_test_prefill_pack.argtypes = [vp, i32, i32, vp, i32]
     lib.sva_get_tap.argtypes = [vp, C.c_char_p, vp, C.c_long]
     lib.sva_get_tap.restype = C.c_long
     lib.sva_get_timings.argtypes = [vp, f32p]
@@ -149,11 +152,11 @@ EXPORTED_SYMBOLS = [
     "sva_last_error", "sva_config_default", "sva_stream_params_default", "sva_engine_create",
     "sva_engine_load_weight", "sva_engine_finalize", "sva_engine_destroy", "sva_batch_create", "sva_batch_destroy",
     "sva_prefill_prompt", "sva_streams_begin", "sva_stream_restart", "sva_stream_retire", "sva_stream_state", "sva_stream_set_sampling", "sva_stream_get_sampling", "sva_stream_activations", "sva_step", "sva_step_device", "sva_step_device_on", "sva_join_stream", "sva_batch_uses_persistent_decode", "sva_test_force_ar_timeout", "sva_test_stream_overlap", "sva_debug_configure", "sva_sync", "sva_stream_chunks", "sva_encode_window", "sva_firefly_encode",
-    "sva_vocode_window", "sva_vocode_stream", "sva_vocode_reset", "sva_quantizer_decode", "sva_vocoder_head", "sva_ar_delay_fill", "sva_ar_decode_one", "sva_generate", "sva_get_tap", "sva_get_timings",
+    "sva_vocode_window", "sva_vocode_stream", "sva_vocode_reset", "sva_quantizer_decode", "sva_vocoder_head", "sva_ar_delay_fill", "sva_ar_decode_one", "sva_generate", "sva_generate_many", "sva_get_tap", "sva_get_timings",
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
     "sva_op_geglu", "sva_op_l2norm", "sva_ops_capture_begin", "sva_ops_capture_end", "sva_ops_graph_launch", "sva_ops_graph_free",
-    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_test_sampler_launch", "sva_test_sampler_rows", "sva_test_ar_device", "sva_test_gemv", "sva_test_token_ops", "sva_test_step_ops", "sva_test_voc_level", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
+    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_prefill_attention_runs", "sva_test_prefill_pack", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_test_sampler_launch", "sva_test_sampler_rows", "sva_test_ar_device", "sva_test_gemv", "sva_test_token_ops", "sva_test_step_ops", "sva_test_voc_level", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
 ]
 
 
@@ -454,6 +457,30 @@ class Batch:
         _check(self.lib.sva_generate(self.h, _ptr(cc), _ptr(ac), cc.shape[0], _ptr(src), src.shape[0], _ptr(st), _ptr(tm), int(noise_seed),
                                      _ptr(nz), _ptr(out)), "sva_generate")
         return out
+
+    def generate_many(self, prompts, sources, noise_seeds=None, noise=None):
+        """offline ARVCWrapper.generate for every slot of the batch at once (sva_generate_many): utterance i in slot i, len(prompts) ==
+        len(sources) == n_streams.  prompts: (ref_content_codes, ref_audio_codes, style, timbre) per utterance; sources: content codes [S_i];
+        noise: [S_max, n, vocab + 8 * codebook_size] frame-major or None (device RNG keyed by noise_seeds[i]) -> list of int32 [8, S_i]"""
+        n = len(sources)
+        assert len(prompts) == n, "one prompt per source"
+        ccs = [np.ascontiguousarray(p[0], dtype=np.int64).reshape(-1) for p in prompts]
+        acs = [np.ascontiguousarray(p[1], dtype=np.int32).reshape(8, -1) for p in prompts]
+        for cc, ac in zip(ccs, acs):
+            assert ac.shape[1] == cc.shape[0], "ref_audio_codes must be [8, R] for ref_content_codes [R]"
+        srcs = [np.ascontiguousarray(s, dtype=np.int64).reshape(-1) for s in sources]
+        st = np.ascontiguousarray(np.stack([np.asarray(_as_np(p[2]), dtype=np.float32).reshape(-1) for p in prompts]) if n else np.zeros((0, 192), np.float32))
+        tm = np.ascontiguousarray(np.stack([np.asarray(_as_np(p[3]), dtype=np.float32).reshape(32, 128) for p in prompts]) if n else np.zeros((0, 32, 128), np.float32))
+        R = np.array([c.shape[0] for c in ccs], dtype=np.int32)
+        S = np.array([s.shape[0] for s in srcs], dtype=np.int32)
+        seeds = np.ascontiguousarray(np.zeros(n) if noise_seeds is None else noise_seeds, dtype=np.uint64).reshape(n)
+        s_max = int(S.max()) if n else 0
+        nz = None if noise is None else np.ascontiguousarray(noise, dtype=np.float32).reshape(s_max, n, self.noise_stride)
+        outs = [np.empty((8, int(s)), dtype=np.int32) for s in S]
+        ptrs = lambda arrs: (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        _check(self.lib.sva_generate_many(self.h, n, ptrs(ccs), ptrs(acs), _ptr(R), ptrs(srcs), _ptr(S), _ptr(st), _ptr(tm), _ptr(seeds), _ptr(nz), ptrs(outs)),
+               "sva_generate_many")
+        return outs
 
     def vocode_reset(self):
         _check(self.lib.sva_vocode_reset(self.h), "sva_vocode_reset")
@@ -1018,6 +1045,41 @@ def test_conv_gemm(members, plan=None, repeat=False, device=0):
     if rc not in (0, 1):
         _check(rc, "sva_test_conv_gemm")
     return dict(refused=rc == 1, kind=int(out[0]), identical=None if out[1] < 0 else bool(out[1]))
+
+
+def test_prefill_attention_runs(runs, total_rows, H, S, n_slots, half_kv, q, cache, out, single_out=None, device=0):
+    """launch_ar_prefill_attention_runs on caller-chosen runs (include/sva.h: sva_test_prefill_attention_runs); out / single_out are written in
+    place.  Returns True when the launcher refused."""
+    r = np.ascontiguousarray(runs, dtype=np.int32).reshape(-1, 4)
+    assert q.dtype == np.float32 and q.shape == (total_rows, H * 64) and q.flags.c_contiguous
+    assert cache.dtype == np.float32 and cache.size == n_slots * 2 * H * S * 64 and cache.flags.c_contiguous
+    for o in (out, single_out):
+        assert o is None or (o.dtype == np.float32 and o.shape == (total_rows, H * 64) and o.flags.c_contiguous)
+    rc = load_library().sva_test_prefill_attention_runs(device, r.shape[0], _ptr(r), int(total_rows), int(H), int(S), int(n_slots), int(bool(half_kv)), _ptr(q),
+                                                        _ptr(cache), _ptr(out), _ptr(single_out))
+    if rc == 1:
+        return True
+    _check(rc, "sva_test_prefill_attention_runs")
+    return False
+
+
+def test_prefill_pack(M, Mmax):
+    """the packing of sva_generate_many's prompt passes (include/sva.h: sva_test_prefill_pack), no GPU needed ->
+    (pass_of [n], row0_of [n], tiles: per pass a list of (run inside the pass, q0))"""
+    m = np.ascontiguousarray(M, dtype=np.int32).reshape(-1)
+    n = m.shape[0]
+    cap = 2 * n + n + 2 * (int(np.maximum(m, 0).sum()) // 16 + n) + 8
+    out = np.zeros(cap, dtype=np.int32)
+    n_pass = load_library().sva_test_prefill_pack(_ptr(m), n, int(Mmax), _ptr(out), cap)
+    if n_pass < 0:
+        _check(n_pass, "sva_test_prefill_pack")
+    head = out[:2 * n].reshape(n, 2)
+    tiles, k = [], 2 * n
+    for _ in range(n_pass):
+        nt = int(out[k])
+        tiles.append([(int(a), int(b)) for a, b in out[k + 1:k + 1 + 2 * nt].reshape(nt, 2)])
+        k += 1 + 2 * nt
+    return head[:, 0].copy(), head[:, 1].copy(), tiles
 
 
 def test_slot_book(cfg, ops):

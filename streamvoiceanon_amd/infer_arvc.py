@@ -450,6 +450,71 @@ class InferenceWrapper:
             self._save(wav, src_path, ref_path, out_dir, output_path)
         return wav
 
+    def infer_many(self, sources, refs=None, prompts=None, n_slots=8, delay=None, alpha=1.0, spk_emb_collate_type="concat_mel", noise_seeds=None,
+                   **sampling_kwargs):
+        """`infer` for a list of utterances, `n_slots` at a time: the utterances are sorted into waves of similar length
+        (stream_pool.plan_offline_waves) and each wave runs on one batch (kept across waves of the same size) -- one encode_window over the zero-padded sources (causal encoder:
+        padding leaves earlier codes alone), Batch.generate_many, one vocode_window over the zero-padded codes, every waveform cut to
+        2048 * S_i.  `prompts[i]` = (ref_audio_codes, ref_content_codes, style, timbre) as calculate_prompt returns them, or `refs[i]` = the
+        reference waveforms of utterance i (calculate_prompt per utterance, as infer computes them).  -> list of waveforms in input order."""
+        from .stream_pool import plan_offline_waves
+        n = len(sources)
+        if prompts is None:
+            assert refs is not None and len(refs) == n, "infer_many needs one prompt or one list of reference waveforms per source"
+            prompts = [self.calculate_prompt(r, alpha=alpha, spk_emb_collate_type=spk_emb_collate_type) for r in refs]
+        assert len(prompts) == n, "one prompt per source"
+        seeds = [0] * n if noise_seeds is None else [int(x) for x in noise_seeds]
+        assert len(seeds) == n, "one noise seed per source"
+        d = 2 if delay is None else int(delay)
+        kw = check_sampling_kwargs(sampling_kwargs)
+        edits = kw.pop("edits", None)
+        wavs = [np.asarray(self._load_src(s)[0], dtype=np.float32).reshape(-1) for s in sources]
+        S = [w.shape[0] // self.SAMPLES_PER_FRAME for w in wavs]
+        out = [None] * n
+        # The waves come longest first, so the batch of the first wave (its window and vocoder lengths) also holds every later wave of the same
+        # size: it is kept across them -- creating and freeing the workspaces of 64 slots x 10 s costs seconds -- and only a smaller last wave
+        # gets a smaller batch of its own.  encode_window and vocode_window have window semantics and generate_many starts from the prompts,
+        # so nothing of a wave reaches the next one.
+        b, shape = None, None
+        try:
+            for wave in plan_offline_waves(S, int(n_slots)):
+                s_max = max(S[i] for i in wave)
+                if b is None or shape[0] != len(wave):
+                    if b is not None:
+                        b.close()
+                        b = None
+                    Wp = ((s_max + 3) // 4) * 4
+                    if Wp > 2048:
+                        raise ValueError(f"utterance of {s_max} frames: the tokenizer's transformer has rotary tables for 2048 positions (95 s)")
+                    try:
+                        b = E.Batch(self.engine, n_streams=len(wave), encode_window_frames=Wp, voc_max_frames=s_max, delay=d, **kw)
+                    except RuntimeError as err:
+                        raise RuntimeError(f"infer_many: a batch of {len(wave)} utterances of up to {s_max} frames could not be allocated; "
+                                           f"lower n_slots (now {n_slots}): {err}") from err
+                    shape = (len(wave), Wp)
+                    if edits:
+                        b.set_sampler_edits(**edits)
+                Wp = shape[1]
+                buf = np.zeros((len(wave), Wp * self.SAMPLES_PER_FRAME), np.float32)
+                for k, i in enumerate(wave):
+                    buf[k, :S[i] * self.SAMPLES_PER_FRAME] = wavs[i][:S[i] * self.SAMPLES_PER_FRAME]
+                src_codes = b.encode_window(buf)
+                pr = []
+                for i in wave:
+                    ac, cc, st, tm = [np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x) for x in prompts[i][:4]]
+                    pr.append((cc.reshape(-1), ac.reshape(8, -1), st.reshape(-1), tm.reshape(32, -1)))
+                codes = b.generate_many(pr, [src_codes[k, :S[i]] for k, i in enumerate(wave)], noise_seeds=[seeds[i] for i in wave])
+                padded = np.zeros((len(wave), 8, s_max), np.int32)
+                for k, c in enumerate(codes):
+                    padded[k, :, :c.shape[1]] = c
+                pcm = b.vocode_window(padded)
+                for k, i in enumerate(wave):
+                    out[i] = pcm[k, :S[i] * self.SAMPLES_PER_FRAME].copy()
+        finally:
+            if b is not None:
+                b.close()
+        return out
+
     # ---- per chunk ---------------------------------------------------------------------------------------
     def process_one_chunk(self, src_wav_chunk, pitch_shift=0.0):
         """src_wav_chunk [1, 2048*c] (torch or numpy) -> same type/shape (:492-596): zeros for the first `delay` chunks."""

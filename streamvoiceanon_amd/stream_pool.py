@@ -12,6 +12,16 @@ from __future__ import annotations
 import numpy as np
 
 
+def plan_offline_waves(lengths, n_slots):
+    """Offline batches (Batch.generate_many): every slot of a wave starts together and the wave lasts as long as its longest utterance, so
+    the utterances are sorted by length, longest first (ties in input order), and cut into waves of at most `n_slots` -- neighbours in
+    length share a wave and the frames a finished slot spends parked are as few as a cut into consecutive groups allows.
+    -> per wave, the original indices of its utterances."""
+    assert n_slots >= 1
+    order = sorted(range(len(lengths)), key=lambda i: (-int(lengths[i]), i))
+    return [order[k:k + n_slots] for k in range(0, len(order), int(n_slots))]
+
+
 class SlotPool:
     """Slot assignment for `lengths[i]` chunks per utterance (all >= 1) over `n_slots` slots, in queue order."""
 
