@@ -213,7 +213,10 @@ int sva_stream_activations(sva_batch* b, long counts[2], float* last_ms);
 /* AR seams with caller-supplied content codes (chunk_frames == 1):
  *   ARVCWrapper.prefill_src_condition4delay (modules/arvc_wrapper.py:114-119): codes int64[B][delay]
  *   ARVCWrapper.decode_one (:121-126 -> dual_ar_stream.py:817-837): code int64[B] -> codes_out int32[B][8],
- *   pos_out int32[B] (kv_pos[-1]); noise float[B][vocab + 8*codebook_size] or NULL; forced int32[B][8] or NULL */
+ *   pos_out int32[B] (kv_pos[-1]); noise float[B][vocab + 8*codebook_size] or NULL; forced int32[B][8] or NULL
+ * Both refuse, before anything is uploaded or launched, a call whose rows would leave the KV cache: sva_ar_decode_one when any slot has
+ * last_pos + 2 >= max_seq_len, sva_ar_delay_fill when last_pos + 2 * delay - 1 >= max_seq_len.  The error names the cache; positions and cache
+ * rows are unchanged and the batch stays usable (sva_prefill_prompt + sva_streams_begin start the slot afresh). */
 int sva_ar_delay_fill(sva_batch* b, const int64_t* codes);
 int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float* noise, const int32_t* forced, int32_t* codes_out,
                       int32_t* pos_out);
@@ -240,7 +243,8 @@ int sva_generate_many(sva_batch* b, int n, const int64_t* const* ref_cc, const i
 
 /* taps of the last step: "content_codes" int32[B][chunk], "audio_codes" int32[B][8][chunk] (as int32),
  * "slow_logits" float[B][vocab], "fast_logits" float[B][8][codebook_size], "hidden" float[B][dim],
- * "semantic" int32[B], "last_pos" int32[B], "mel" float[B][T][160] ... ; returns #bytes or <0 */
+ * "semantic" int32[B], "last_pos" int32[B], "cached_audio_emb" float[B][dim] (the embedding of the last decoded frame's codes: the
+ * audio row of the next frame), "mel" float[B][T][160] ... ; returns #bytes or <0 */
 long sva_get_tap(sva_batch* b, const char* what, void* out, long out_bytes);
 /* the stream state `pred_codes[..., -n:]` of evaluations/infer_arvc.py:520-523 for one slot: the last n predicted frames
  * (n <= frames decoded so far, n <= 4096 = the device ring), int32 codes_out[8][n].  Drains the batch's streams first.
@@ -316,6 +320,10 @@ int sva_batch_uses_persistent_decode(sva_batch* b);
  * environment input -- listed in csrc/sva_common.h: ar_timing, pipe_trace, concurrency, ar_persistent, voc_fused_mask, autotune,
  * tune_log, tune_table, tune_dump).  Profiling and test switches; batches created afterwards see the change. */
 int sva_debug_configure(const char* kv);
+/* test hook, read-only: rows pos0 .. pos0 + n - 1 of one slot's slow-AR KV cache as float out[ar_layers][2 (k, v)][ar_heads][n][64]; an fp16
+ * cache (ar_dtype = 1) is widened exactly.  Drains the batch's streams first.  Fails for a slot outside the batch or rows outside the cache
+ * (slot < 0, slot >= n_streams, pos0 < 0, n < 1, pos0 + n > max_seq_len). */
+int sva_test_kv_rows(sva_batch* b, int slot, int pos0, int n, float* out);
 /* test hook: set the persistent kernel's device-side timeout word, as a launch with non-resident workgroups would */
 int sva_test_force_ar_timeout(sva_batch* b);
 /* test hook: do the four chain streams of a pipelined batch -- main, encoder side, AR, vocoder -- run concurrently, i.e. sit on four

@@ -1858,6 +1858,9 @@ extern "C" int sva_sync(sva_batch* b) {
 // ---- AR seams: DualARWrapper.prefill_src_condition4delay / decode_one driven with caller-supplied content codes ----
 extern "C" int sva_ar_delay_fill(sva_batch* b, const int64_t* codes) {
     SVA_CHECK(b && codes && b->begun, "sva_ar_delay_fill: bad argument");
+    // the 2 * delay - 1 rows land on last_pos + 1 ..: refused before anything is uploaded or launched (the positions are the book's mirror)
+    for (int i = 0; i < b->B; ++i)
+        SVA_CHECK(b->slots.s[i].last_pos + 2 * b->p.delay - 1 < b->e->cfg.max_seq_len, "sva_ar_delay_fill: a slot's delay rows would run past the KV cache (max_seq_len)");
     SVA_HIP(hipSetDevice(b->e->device));
     (void)hipGetLastError();
     SVA_TRY(quiesce(b));
@@ -1875,6 +1878,10 @@ extern "C" int sva_ar_delay_fill(sva_batch* b, const int64_t* codes) {
 extern "C" int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float* noise, const int32_t* forced, int32_t* codes_out, int32_t* pos_out) {
     SVA_CHECK(b && code && codes_out && b->begun && b->slots.delay_filled, "sva_ar_decode_one: bad argument / delay not filled");
     SVA_CHECK(b->p.chunk_frames == 1, "sva_ar_decode_one needs chunk_frames == 1");
+    // a frame writes the rows last_pos + 1, last_pos + 2 of every slot: refused before anything is uploaded or launched, the batch stays as it was
+    // (sva_generate / sva_generate_many check the same bound on their whole run)
+    for (int i = 0; i < b->B; ++i)
+        SVA_CHECK(b->slots.s[i].last_pos + 2 < b->e->cfg.max_seq_len, "sva_ar_decode_one: a slot's frame would run past the KV cache (max_seq_len): re-prefill it first");
     SVA_HIP(hipSetDevice(b->e->device));
     (void)hipGetLastError();
     SVA_TRY(quiesce(b));
@@ -2198,6 +2205,7 @@ extern "C" long sva_get_tap(sva_batch* b, const char* what, void* out, long out_
     else if (w == "hidden") { src = b->hidden; bytes = sizeof(float) * (long)B * c.ar_dim; }
     else if (w == "semantic") { src = b->d_sem; bytes = sizeof(int) * (long)B; }
     else if (w == "last_pos") { src = b->d_last_pos; bytes = sizeof(int) * (long)B; }
+    else if (w == "cached_audio_emb") { src = b->cached_audio_emb; bytes = sizeof(float) * (long)B * c.ar_dim; }
     else if (w == "window_codes") { src = b->d_codes; bytes = sizeof(long long) * (long)B * b->T2; }
     else if (w == "u") { src = b->d_u; bytes = sizeof(float) * (long)B * b->T2 * c.bsq_bits; }
     else if (w == "mel") { src = b->mel.p; bytes = sizeof(float) * (long)B * b->mel.bstride; }

@@ -2079,3 +2079,27 @@ extern "C" int sva_test_conv_gemm(int device, int n, const long long* desc, cons
     }
     return 0;
 }
+
+// Read-only seam of the whole-frame tests (include/sva.h): rows pos0 .. pos0 + n - 1 of one slot's slow KV cache, every layer, as float
+// out[layers][2 (k, v)][H][n][64].  An fp16 cache (ar_dtype = 1) is widened on the host, exactly.  No kernel: one strided copy per layer.
+extern "C" int sva_test_kv_rows(sva_batch* b, int slot, int pos0, int n, float* out) {
+    SVA_CHECK(b && out && b->kv_slow, "sva_test_kv_rows: null argument");
+    const sva_config& c = b->e->cfg;
+    const int S = c.max_seq_len, H = c.ar_heads;
+    SVA_CHECK(slot >= 0 && slot < b->B, "sva_test_kv_rows: slot outside the batch");
+    SVA_CHECK(n >= 1 && n <= S && pos0 >= 0 && pos0 <= S - n, "sva_test_kv_rows: rows outside the KV cache");
+    SVA_HIP(hipSetDevice(b->e->device));
+    std::vector<int> lp((size_t)b->B);
+    if (sva_get_tap(b, "last_pos", lp.data(), (long)(sizeof(int) * lp.size())) < 0) return -2;      // drains the batch's streams
+    const size_t esz = b->kv_half ? 2 : 4, per_layer = (size_t)2 * H * n * 64;
+    std::vector<uint16_t> hb(b->kv_half ? per_layer : 0);
+    for (int l = 0; l < c.ar_layers; ++l) {
+        const size_t off = (size_t)l * b->kv_slow_layer + (size_t)slot * b->kv_slow_slot + (size_t)pos0 * 64;       // (k, v) x head = 2 H planes of S rows
+        float* dst = out + (size_t)l * per_layer;
+        SVA_HIP(hipMemcpy2D(b->kv_half ? (void*)hb.data() : (void*)dst, (size_t)n * 64 * esz, (const char*)b->kv_slow + off * esz, (size_t)S * 64 * esz,
+                            (size_t)n * 64 * esz, (size_t)2 * H, hipMemcpyDeviceToHost));
+        if (b->kv_half)
+            for (size_t i = 0; i < per_layer; ++i) { _Float16 h; memcpy(&h, &hb[i], 2); dst[i] = (float)h; }
+    }
+    return 0;
+}

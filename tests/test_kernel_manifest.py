@@ -18,9 +18,9 @@ MANIFEST = {
         "finish_reprefill", "copy_rows", "copy_rows2", "broadcast_row", "fill_rows", "inc", "add_list", "add_vec", "set_slot_i32", "history_rows_copy",
         "history_rows_move", "put_row", "prepare_offline_step", "mean3", "copy_tokens")},
     "voc_level_kernel": (STEP, "test_voc_level"),
-    # the persistent decode kernels: whole frames inside the engine, against the reference's fixtures and the multi-launch decode
-    "ar_decode_kernel": (PAR, "test_stream_vs_reference_golden", IN_SITU),
-    "ar_batch_kernel": (PAR, "test_batched_persistent_decode_equals_multi_launch", IN_SITU),
+    # the persistent decode kernels: whole frames inside the engine, every output against the float64 frame of ar_frame_ref.py
+    "ar_decode_kernel": ("test_gpu_ar_frame.py", "test_decode_frames_match_fp64", IN_SITU),
+    "ar_batch_kernel": ("test_gpu_ar_frame.py", "test_decode_frames_match_fp64", IN_SITU),
     # csrc/kernels.hip
     "ring_write_kernel": (TAIL, "test_ring_write"),
     "fill_i32_kernel": (PAR, "host_launch_cost", IN_SITU),
