@@ -539,6 +539,21 @@ int sva_test_step_ops(int device, int kind, const long long* desc, const float* 
  *   ptrs X (xH history rows, then Tl rows per stream), Y3[0], Y3[1], Y3[2] (io, len(Y) each), the 18 weights back to back in (branch, conv) order
  *        ([C][k C], k = 3 / 7 / 11 per branch), bias [18][C], int [1] (out): the tile height the launcher chose.  rc 1: the launcher refused. */
 int sva_test_voc_level(int device, const long long* desc, const float* fpar, void* const* ptrs);
+/* sva_test_voc_conv: launch_voc_conv (voc_conv_kernel: one conv stage of 1..3 ResBlock branches of a narrow HiFiGAN level, C = 16 / 32, over
+ * row-major operand planes) once, with the operands made as the engine makes them.
+ *   desc 8 ints {C, mode (1 = H3, 2 = H1), B, T (output rows per stream), n members, cu_limit (0 = the device), repeat, 0}, then 16 ints per member
+ *        {taps, dil, a_rows_b, a_row0, c_bstride, c_off, len(Cf), r_bstride, r_off, len(res), c_rows_b, c_row0, conv (0: Ap is used as handed in;
+ *         1 / 2: rows [conv_row0, conv_row0 + conv_T) of every stream of A are first split into Ap by launch_to_planes_act's row-major arm, 2: of
+ *         silu(A)), conv_row0, conv_T, drop (bit 0: the launcher gets no Ap, bit 1: no Wp)}
+ *   ptrs {ovf int [1] (io, optional), int [1] (out): 1 when the repeated launch was bit-identical}, then 8 per member
+ *        {A fp32 [B][a_rows_b][C] (with conv), Ap uint16 [planes][B a_rows_b C] (io: caller-filled, comes back as the kernel read it), W fp32 [C][taps C]
+ *         (K index = tap C + channel), Wp uint16 [planes][C Kp] (out: the packed weight planes, K-blocked; Kp = taps C, at C = 16 padded to whole
+ *         32-k blocks), bias [C], res [len(res)] (io), Cf [len(Cf)] (io), Cp uint16 [planes][B c_rows_b C] (io)}; bias, res, Cf, Cp may be NULL = absent
+ *   repeat != 0: the launch runs a second time from the same initial Cf / Cp.
+ * Returns 0 when it ran; 1 when a row of the launch would lie outside an array (for every stream a_row0 >= 0 and a_row0 + T + (taps - 1) dil <=
+ * a_rows_b, likewise the Cf, Cp, res and converted rows) -- nothing was launched -- or when launch_voc_conv itself refused; no array is written back
+ * then.  -2 on a HIP error, -4 on arguments the hook cannot lay out. */
+int sva_test_voc_conv(int device, const long long* desc, const float* fpar, void* const* ptrs);
 
 /* host cost (microseconds) of enqueueing one kernel from the calling thread, measured over `iters` launches of a one-element
  * kernel into an idle stream.  A synchronous single-stream step is ~170 launches (a pipelined one: four graph launches + the persistent

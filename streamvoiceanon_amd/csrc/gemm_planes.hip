@@ -1125,4 +1125,24 @@ int make_weight_planes(const float* dW, int N, int K, float max_abs, int mode, u
     return launch_to_planes(dW, N, K, K, dst, (long)N * K, mode, ldexpf(1.f, e), 0, st);
 }
 
+// The same for the narrow levels' voc_conv_kernel: K = k * C padded with zero columns to whole 32-k blocks (C = 16 with an odd k: the second
+// tap of the last K step reads a clamped row, which must meet zero weights).  dst holds planes_count(mode) * N * padded_weight_k(K) elements.
+int make_weight_planes_padded(const float* dW, int N, int K, int mode, unsigned short* dst, float* inv) {
+    const int Kp = padded_weight_k(K);
+    std::vector<float> host((size_t)N * K);
+    SVA_HIP(hipMemcpy(host.data(), dW, sizeof(float) * host.size(), hipMemcpyDeviceToHost));
+    std::vector<float> pad((size_t)N * Kp, 0.f);
+    float mx = 0.f;
+    for (int r = 0; r < N; ++r)
+        for (int k = 0; k < K; ++k) { const float v = host[(size_t)r * K + k]; pad[(size_t)r * Kp + k] = v; mx = std::max(mx, fabsf(v)); }
+    float* tmp = nullptr;
+    SVA_HIP(hipMalloc((void**)&tmp, sizeof(float) * pad.size()));
+    int rc = -2;
+    if (hipMemcpy(tmp, pad.data(), sizeof(float) * pad.size(), hipMemcpyHostToDevice) == hipSuccess) rc = make_weight_planes(tmp, N, Kp, mx, mode, dst, inv, 0);
+    else set_error("make_weight_planes_padded: upload of the padded matrix failed");
+    (void)hipDeviceSynchronize();
+    (void)hipFree(tmp);
+    return rc;
+}
+
 }  // namespace sva

@@ -518,23 +518,9 @@ extern "C" int sva_engine_finalize(sva_engine* e) {
         // (narrow levels: K = k * C padded with zero columns to whole 32-k blocks)
         auto planes_padded = [&](const Lin& l, int mode, unsigned short** out, float* inv, int* Kq) -> int {
             if (mode < 0 || !l.W) return 0;
-            const int Kp = (l.K + 31) / 32 * 32;
-            *Kq = Kp;
-            const long n = (long)l.N * l.K;
-            host.resize(n);
-            SVA_HIP(hipMemcpy(host.data(), l.W, sizeof(float) * n, hipMemcpyDeviceToHost));
-            std::vector<float> pad((size_t)l.N * Kp, 0.f);
-            float mx = 0.f;
-            for (int r = 0; r < l.N; ++r)
-                for (int k = 0; k < l.K; ++k) { const float v = host[(long)r * l.K + k]; pad[(size_t)r * Kp + k] = v; mx = std::max(mx, fabsf(v)); }
-            float* tmp = nullptr;
-            SVA_HIP(hipMalloc((void**)&tmp, sizeof(float) * pad.size()));
-            SVA_HIP(hipMemcpy(tmp, pad.data(), sizeof(float) * pad.size(), hipMemcpyHostToDevice));
-            SVA_TRY(dev_alloc(e->allocs, out, (size_t)planes_count(mode) * pad.size(), false));
-            int rc = make_weight_planes(tmp, l.N, Kp, mx, mode, *out, inv, 0);
-            (void)hipDeviceSynchronize();
-            (void)hipFree(tmp);
-            return rc;
+            *Kq = padded_weight_k(l.K);
+            SVA_TRY(dev_alloc(e->allocs, out, (size_t)planes_count(mode) * l.N * *Kq, false));
+            return make_weight_planes_padded(l.W, l.N, l.K, mode, *out, inv);
         };
         SVA_TRY(front(e->tokf, tok_mode, c.enc_dtype == 1));
         SVA_TRY(front(e->vocf, enc_mode));           // firefly.encode of the prompt produces FSQ indices: encoder grade

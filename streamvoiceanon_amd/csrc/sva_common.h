@@ -251,6 +251,10 @@ int launch_to_planes(const float* src, long rows, int K, long ld, unsigned short
 // (blocked = 0: row-major planes [plane][rows][K], the layout of voc_conv_kernel)
 int launch_to_planes_act(const float* src, int nb, long rows_b, long row0, int T, int K, unsigned short* dst, long pstride, int mode, int silu, hipStream_t st, int blocked = 1);
 int make_weight_planes(const float* dW, int N, int K, float max_abs, int mode, unsigned short* dst, float* inv, hipStream_t st);
+// planes of W [N][K] with K padded by zero columns to whole 32-k blocks (the weights of voc_conv_kernel at C = 16); synchronises the device.
+// dst: planes_count(mode) * N * padded_weight_k(K) elements
+inline int padded_weight_k(int K) { return (K + 31) / 32 * 32; }
+int make_weight_planes_padded(const float* dW, int N, int K, int mode, unsigned short* dst, float* inv);
 // gemm_f16w.hip: fp16 weights on the f16 matrix pipes (fp32 activations split hi + lo), plain linear layers of the AR chain
 bool f16w_gemm_supported(const ConvGemm& g);
 bool f16w_gemm_validated_compiler();      // built with the compiler the kernel's workarounds were validated with

@@ -1752,6 +1752,150 @@ extern "C" int sva_test_voc_level(int device, const long long* d, const float* f
     return 0;
 }
 
+// launch_voc_conv (gemm_planes.hip: voc_conv_kernel -- one conv stage of 1..3 ResBlock branches of a narrow HiFiGAN level) from host arrays, the
+// operands made the way the engine makes them: input planes by the row-major arm of launch_to_planes_act over caller-given rows of caller-filled
+// planes (or handed in ready: one launch's Cp as the next one's Ap), weight planes by make_weight_planes (C = 32) / make_weight_planes_padded
+// (C = 16).  Descriptor and array order: include/sva.h.  Every row the launch may touch is checked against the arrays first -- a failed check
+// returns 1 and nothing is launched; what launch_voc_conv itself refuses returns 1 as well.  After a refusal no array is written back.
+namespace {
+enum { VC_C, VC_MODE, VC_B, VC_T, VC_N, VC_CU_LIMIT, VC_REPEAT, VC_NH = 8 };
+enum { VM_TAPS, VM_DIL, VM_A_ROWS_B, VM_A_ROW0, VM_C_BSTRIDE, VM_C_OFF, VM_F_LEN, VM_R_BSTRIDE, VM_R_OFF, VM_R_LEN, VM_C_ROWS_B, VM_C_ROW0, VM_CONV, VM_CONV_ROW0,
+       VM_CONV_T, VM_DROP, VM_ND = 16 };
+enum { VP_A, VP_AP, VP_W, VP_WP, VP_BIAS, VP_RES, VP_CF, VP_CP, VP_NP = 8 };
+struct VocMember {
+    DevBuf A, Ap, W, Wp, bias, res, Cf, Cp;
+    size_t ap_elems = 0, wp_elems = 0, f_len = 0, r_len = 0, cp_elems = 0;
+    std::vector<float> cf0;             // Cf as the caller handed it in
+    std::vector<uint16_t> cp0;          // Cp likewise
+};
+}  // namespace
+
+extern "C" int sva_test_voc_conv(int device, const long long* d, const float* fpar, void* const* ptrs) {
+    (void)fpar;
+    SVA_CHECK(d && ptrs, "sva_test_voc_conv: null argument");
+    const long C = d[VC_C], B = d[VC_B], T = d[VC_T], n = d[VC_N], cu_limit = d[VC_CU_LIMIT];
+    const int mode = (int)d[VC_MODE];
+    const bool repeat = d[VC_REPEAT] != 0;
+    SVA_HOOK_CHECK((C == 16 || C == 32 || C == 64) && B >= 1 && B <= 64 && T >= 1 && T <= (1 << 16) && n >= 0 && n <= 4 && cu_limit >= 0 && cu_limit <= 1024 &&
+                   d[VC_MODE] >= 0 && d[VC_MODE] <= 2, "voc_conv hook: sizes");
+    SVA_HOOK_CHECK(!repeat || ptrs[1], "voc_conv hook: a repeated launch needs the verdict word");
+    const bool fp16 = mode == PLANES_H3 || mode == PLANES_H1;          // (another format reaches the launcher with operands nobody made: it refuses)
+    const int npl = planes_count(mode), nm = (int)std::min(n, 3L);     // (n = 4 reaches the launcher with three members built: it refuses)
+    // ---- every member's geometry against its arrays, before anything is uploaded ----
+    for (int i = 0; i < nm; ++i) {
+        const long long* m = d + VC_NH + VM_ND * i;
+        void* const* pp = ptrs + 2 + VP_NP * i;
+        const long taps = m[VM_TAPS], dil = m[VM_DIL], a_rows_b = m[VM_A_ROWS_B], a_row0 = m[VM_A_ROW0], c_bs = m[VM_C_BSTRIDE], c_off = m[VM_C_OFF], f_len = m[VM_F_LEN],
+                   r_bs = m[VM_R_BSTRIDE], r_off = m[VM_R_OFF], r_len = m[VM_R_LEN], c_rows_b = m[VM_C_ROWS_B], c_row0 = m[VM_C_ROW0], conv = m[VM_CONV],
+                   conv_row0 = m[VM_CONV_ROW0], conv_T = m[VM_CONV_T];
+        SVA_HOOK_CHECK(taps >= 1 && taps <= 64 && dil >= 1 && dil <= 64 && a_rows_b >= 1 && a_rows_b <= (1 << 20) && c_rows_b >= 0 && c_rows_b <= (1 << 20) && f_len >= 0 &&
+                       f_len <= kStepMax && r_len >= 0 && r_len <= kStepMax && conv >= 0 && conv <= 2 && m[VM_DROP] >= 0 && m[VM_DROP] <= 3, "voc_conv hook: member sizes");
+        SVA_HOOK_CHECK(pp[VP_AP] && pp[VP_W] && pp[VP_WP] && (!conv || pp[VP_A]), "voc_conv hook: Ap, W and Wp are required, A with a conversion");
+        SVA_HOOK_CHECK((!pp[VP_CF] || f_len >= 1) && (!pp[VP_RES] || r_len >= 1) && (!pp[VP_CP] || c_rows_b >= 1), "voc_conv hook: an output array without its length");
+        SVA_HOOK_REFUSE(a_row0 >= 0 && a_row0 + T + (taps - 1) * dil <= a_rows_b, "voc_conv hook: input rows outside the planes");
+        SVA_HOOK_REFUSE(!conv || (conv_row0 >= 0 && conv_T >= 1 && conv_row0 + conv_T <= a_rows_b), "voc_conv hook: converted rows outside the planes");
+        SVA_HOOK_REFUSE(!pp[VP_CF] || (c_off >= 0 && c_bs >= 0 && c_off % 4 == 0 && c_bs % 4 == 0 && (B - 1) * c_bs + c_off + T * C <= f_len), "voc_conv hook: Cf rows outside the array");
+        SVA_HOOK_REFUSE(!pp[VP_RES] || (r_off >= 0 && r_bs >= 0 && r_off % 4 == 0 && r_bs % 4 == 0 && (B - 1) * r_bs + r_off + T * C <= r_len), "voc_conv hook: res rows outside the array");
+        SVA_HOOK_REFUSE(!pp[VP_CP] || (c_row0 >= 0 && c_row0 + T <= c_rows_b), "voc_conv hook: Cp rows outside the planes");
+    }
+    SVA_HIP(hipSetDevice(device));
+    VocConvGroup gg;
+    gg.n = (int)n; gg.B = (int)B; gg.T = (int)T;
+    VocMember mem[3];
+    DevBuf bovf;
+    if (ptrs[0]) { SVA_TRY(bovf.put(ptrs[0], sizeof(int))); gg.ovf = bovf.as<int>(); }
+    for (int i = 0; i < nm; ++i) {
+        const long long* m = d + VC_NH + VM_ND * i;
+        void* const* pp = ptrs + 2 + VP_NP * i;
+        VocMember& M = mem[i];
+        VocConv& g = gg.g[i];
+        const long taps = m[VM_TAPS], a_rows_b = m[VM_A_ROWS_B], K = taps * C, Kp = C == 16 ? padded_weight_k((int)K) : K;
+        const long a_rows = B * a_rows_b;
+        M.ap_elems = (size_t)npl * a_rows * C;
+        SVA_TRY(M.Ap.put(pp[VP_AP], 2 * M.ap_elems));
+        if (m[VM_CONV] && fp16) {
+            SVA_TRY(M.A.put(pp[VP_A], sizeof(float) * a_rows * C));
+            SVA_LAUNCH_OR_REFUSED(launch_to_planes_act(M.A.as<float>(), (int)B, a_rows_b, m[VM_CONV_ROW0], (int)m[VM_CONV_T], (int)C, M.Ap.as<unsigned short>(), a_rows * C, mode,
+                                                       m[VM_CONV] == 2 ? 1 : 0, 0, 0));
+        }
+        SVA_TRY(M.W.put(pp[VP_W], sizeof(float) * C * K));
+        M.wp_elems = (size_t)npl * C * Kp;
+        SVA_TRY(M.Wp.alloc(2 * M.wp_elems));
+        SVA_HIP(hipMemset(M.Wp.p, 0, 2 * M.wp_elems));
+        if (fp16 && C == 16) {              // weight planes as sva_engine_finalize makes them
+            SVA_TRY(make_weight_planes_padded(M.W.as<float>(), (int)C, (int)K, mode, M.Wp.as<unsigned short>(), &g.wp_inv));
+        } else if (fp16) {
+            const float* W = (const float*)pp[VP_W];
+            float mx = 0.f;
+            for (long k = 0; k < C * K; ++k) mx = std::max(mx, fabsf(W[k]));
+            SVA_TRY(make_weight_planes(M.W.as<float>(), (int)C, (int)K, mx, mode, M.Wp.as<unsigned short>(), &g.wp_inv, 0));
+        }
+        g.Ap = (m[VM_DROP] & 1) ? nullptr : M.Ap.as<unsigned short>();
+        g.ap_pstride = a_rows * C; g.a_rows_b = a_rows_b; g.a_row0 = m[VM_A_ROW0]; g.a_rows_total = a_rows;
+        g.Wp = (m[VM_DROP] & 2) ? nullptr : M.Wp.as<unsigned short>();
+        g.wp_pstride = C * Kp;
+        g.taps = (int)taps; g.dil = (int)m[VM_DIL];
+        if (pp[VP_BIAS]) { SVA_TRY(M.bias.put(pp[VP_BIAS], sizeof(float) * C)); g.bias = M.bias.as<float>(); }
+        if (pp[VP_RES]) {
+            M.r_len = (size_t)m[VM_R_LEN];
+            SVA_TRY(M.res.put(pp[VP_RES], sizeof(float) * M.r_len));
+            g.res = M.res.as<float>(); g.r_bstride = m[VM_R_BSTRIDE]; g.r_off = m[VM_R_OFF];
+        }
+        if (pp[VP_CF]) {
+            M.f_len = (size_t)m[VM_F_LEN];
+            M.cf0.assign((const float*)pp[VP_CF], (const float*)pp[VP_CF] + M.f_len);
+            SVA_TRY(M.Cf.put(M.cf0.data(), sizeof(float) * M.f_len));
+            g.Cf = M.Cf.as<float>(); g.c_bstride = m[VM_C_BSTRIDE]; g.c_off = m[VM_C_OFF];
+        }
+        if (pp[VP_CP]) {
+            M.cp_elems = (size_t)npl * B * m[VM_C_ROWS_B] * C;
+            M.cp0.assign((const uint16_t*)pp[VP_CP], (const uint16_t*)pp[VP_CP] + M.cp_elems);
+            SVA_TRY(M.Cp.put(M.cp0.data(), 2 * M.cp_elems));
+            g.Cp = M.Cp.as<unsigned short>(); g.cp_pstride = B * m[VM_C_ROWS_B] * C; g.c_rows_b = m[VM_C_ROWS_B]; g.c_row0 = m[VM_C_ROW0];
+        }
+    }
+    SVA_HIP(hipDeviceSynchronize());
+    auto run = [&]() -> int {
+        SVA_LAUNCH_OR_REFUSED(launch_voc_conv(gg, (int)C, mode, (int)cu_limit, 0));
+        SVA_HIP(hipDeviceSynchronize());
+        return 0;
+    };
+    SVA_TRY(run());             // (refused: 1, and the caller's arrays stay as they are)
+    for (int i = 0; i < nm; ++i) {
+        void* const* pp = ptrs + 2 + VP_NP * i;
+        VocMember& M = mem[i];
+        SVA_TRY(M.Ap.get(pp[VP_AP], 2 * M.ap_elems));
+        SVA_TRY(M.Wp.get(pp[VP_WP], 2 * M.wp_elems));
+        if (pp[VP_RES]) SVA_TRY(M.res.get(pp[VP_RES], sizeof(float) * M.r_len));
+        if (pp[VP_CF]) SVA_TRY(M.Cf.get(pp[VP_CF], sizeof(float) * M.f_len));
+        if (pp[VP_CP]) SVA_TRY(M.Cp.get(pp[VP_CP], 2 * M.cp_elems));
+    }
+    if (ptrs[0]) SVA_TRY(bovf.get(ptrs[0], sizeof(int)));
+    if (repeat) {               // the same launch again from the same initial Cf / Cp: the tile walk has no order that may change a bit
+        for (int i = 0; i < nm; ++i) {
+            if (mem[i].f_len) SVA_HIP(hipMemcpy(mem[i].Cf.p, mem[i].cf0.data(), sizeof(float) * mem[i].f_len, hipMemcpyHostToDevice));
+            if (mem[i].cp_elems) SVA_HIP(hipMemcpy(mem[i].Cp.p, mem[i].cp0.data(), 2 * mem[i].cp_elems, hipMemcpyHostToDevice));
+        }
+        SVA_TRY(run());
+        bool same = true;
+        for (int i = 0; i < nm; ++i) {
+            void* const* pp = ptrs + 2 + VP_NP * i;
+            if (mem[i].f_len) {
+                std::vector<float> c2(mem[i].f_len);
+                SVA_TRY(mem[i].Cf.get(c2.data(), sizeof(float) * mem[i].f_len));
+                same = same && memcmp(c2.data(), pp[VP_CF], sizeof(float) * mem[i].f_len) == 0;
+            }
+            if (mem[i].cp_elems) {
+                std::vector<uint16_t> p2(mem[i].cp_elems);
+                SVA_TRY(mem[i].Cp.get(p2.data(), 2 * mem[i].cp_elems));
+                same = same && memcmp(p2.data(), pp[VP_CP], 2 * mem[i].cp_elems) == 0;
+            }
+        }
+        *(int*)ptrs[1] = same ? 1 : 0;
+    }
+    return 0;
+}
+
 // Do the four chain streams of a pipelined batch (main, encoder side stream, AR, vocoder) each have a hardware queue of their own?  For
 // every unordered pair (X, Y), in the order (main, aux0) (main, sa) (main, sv) (aux0, sa) (aux0, sv) (sa, sv): a bounded waiter kernel on
 // X and, enqueued after it, a setter kernel on Y (stream_overlap.h); pair_ok[k] = 1 when the waiter saw the setter's store, 0 when it ran

@@ -140,6 +140,7 @@ def load_library():
     lib.sva_test_token_ops.argtypes = [i32, i32, vp, vp, vp]
     lib.sva_test_step_ops.argtypes = [i32, i32, vp, vp, vp]
     lib.sva_test_voc_level.argtypes = [i32, vp, vp, vp]
+    lib.sva_test_voc_conv.argtypes = [i32, vp, vp, vp]
     lib.sva_test_gemm_f16w.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp]
     lib.sva_test_gemm_planes.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.sva_test_gemm_h16.argtypes = [i32] * 8 + [vp] * 5 + [i32] * 4 + [vp, i32, vp]
@@ -157,7 +158,7 @@ EXPORTED_SYMBOLS = [
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
     "sva_op_geglu", "sva_op_l2norm", "sva_ops_capture_begin", "sva_ops_capture_end", "sva_ops_graph_launch", "sva_ops_graph_free",
-    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_prefill_attention_runs", "sva_test_prefill_pack", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_test_sampler_launch", "sva_test_sampler_rows", "sva_test_ar_device", "sva_test_gemv", "sva_test_token_ops", "sva_test_step_ops", "sva_test_voc_level", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
+    "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_prefill_attention_runs", "sva_test_prefill_pack", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_test_sampler_launch", "sva_test_sampler_rows", "sva_test_ar_device", "sva_test_gemv", "sva_test_token_ops", "sva_test_step_ops", "sva_test_voc_level", "sva_test_voc_conv", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
 ]
 
 
@@ -935,6 +936,45 @@ def test_voc_level(X, Y3, W, bias, C, B, Tl, xH, x_bstride, y_bstride, dil, rows
     _hook_call(load_library().sva_test_voc_level, "sva_test_voc_level",
                [C, B, Tl, xH, x_bstride, X.size, y_bstride, Y3[0].size, dil[0], dil[1], dil[2], rows_per_frame, frames_done], [], [X, Y3[0], Y3[1], Y3[2], W, bias, tr], device)
     return int(tr[0])
+
+
+_VOC_CONV_INTS = ("taps", "dil", "a_rows_b", "a_row0", "c_bstride", "c_off", "f_len", "r_bstride", "r_off", "r_len", "c_rows_b", "c_row0", "conv", "conv_row0",
+                  "conv_T", "drop")
+_VOC_CONV_PTRS = ("A", "Ap", "W", "Wp", "bias", "res", "Cf", "Cp")
+_VOID_P = C.c_void_p          # (test_voc_conv names the channel count C)
+
+
+def test_voc_conv(members, C, mode, B, T, cu_limit=0, repeat=False, ovf=None, n=None, device=0):
+    """launch_voc_conv on one group of 1..3 members (include/sva.h: sva_test_voc_conv).  A member is a dict of the descriptor fields by name (taps, dil,
+    a_rows_b, a_row0; c_bstride, c_off with Cf; r_bstride, r_off with res; c_rows_b, c_row0 with Cp; conv = 0 | 1 | 2 with conv_row0, conv_T and A;
+    drop) and of its arrays: Ap uint16 (in and out), W float32 [C, taps C], Wp uint16 (out), optional A, bias, res, Cf (float32, flat) and Cp (uint16);
+    res, Cf and Cp come back whole.  ovf: int32 [1] or None; n: the group's member count where it is not len(members).
+    -> dict(refused, identical): refused = a row outside an array or the launcher's own refusal (no array was written), identical = the repeat verdict"""
+    lib = load_library()
+    nm = len(members)
+    assert 1 <= nm <= 3
+    desc = np.zeros(8 + 16 * nm, np.int64)
+    desc[:7] = [C, mode, B, T, nm if n is None else n, cu_limit, int(bool(repeat))]
+    same = np.full(1, -1, np.int32)
+    ptrs = (_VOID_P * (2 + 8 * nm))()
+    assert ovf is None or (ovf.dtype == np.int32 and ovf.size == 1)
+    ptrs[0], ptrs[1] = None if ovf is None else ovf.ctypes.data, same.ctypes.data
+    for i, m in enumerate(members):
+        m = dict(m)
+        for name, dt in (("A", np.float32), ("Ap", np.uint16), ("W", np.float32), ("Wp", np.uint16), ("bias", np.float32), ("res", np.float32), ("Cf", np.float32),
+                         ("Cp", np.uint16)):
+            a = m.get(name)
+            assert a is None or (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous), name
+            ptrs[2 + 8 * i + _VOC_CONV_PTRS.index(name)] = None if a is None else a.ctypes.data
+        m["f_len"] = 0 if m.get("Cf") is None else m["Cf"].size
+        m["r_len"] = 0 if m.get("res") is None else m["res"].size
+        for j, name in enumerate(_VOC_CONV_INTS):
+            desc[8 + 16 * i + j] = int(m.get(name, 0))
+    fpar = np.zeros(1, np.float32)
+    rc = lib.sva_test_voc_conv(device, _ptr(desc), _ptr(fpar), ptrs)
+    if rc not in (0, 1):
+        _check(rc, "sva_test_voc_conv")
+    return dict(refused=rc == 1, identical=None if same[0] < 0 else bool(same[0]))
 
 
 def test_logit_edits(logits, rows, V, ldl, prev, suppress, penalty, W=None, prev_cap=4096, device=0):

@@ -619,3 +619,25 @@ def voc_level(x_hist_and_new, W, bias, dil, frames_before, dt=np.float64, hist=N
             y = (t + y).astype(dt)
         out.append(y[:, hist:])
     return np.stack(out)
+
+
+# ---- one conv stage of a narrow HiFiGAN level over dense rows (csrc/gemm_planes.hip: voc_conv_kernel; csrc/sva_common.h: VocConv) -----------
+def voc_conv_ref(rows, W, bias, res, taps, dil, a_row0=0, T=None, dt=np.float64):
+    """rows [B, a_rows, C]: the dense input rows of every stream AS THE CONV READS THEM (SiLU is the producer's: the planes hold silu(.)), history in
+    front; W [N, taps C] with column j C + c = tap j, input channel c; bias [N] or None; res [B, T, N] or None.  The causal dilated conv
+        v[b, t] = sum_j rows[b, a_row0 + t + j dil] @ W[:, j C:(j + 1) C].T + bias (+ res[b, t]),  t = 0 .. T - 1
+    (output row t sits at input row a_row0 + t + (taps - 1) dil: the last tap reads the row itself, the first one (taps - 1) dil rows back)
+    -> (v, silu(v)), both [B, T, N]: the fp32 output and what the kernel's output planes hold.
+    float32: one rank-1 update per k = j C + c in ascending order, then the bias, then the residual"""
+    rows = np.asarray(rows, dt)
+    B, n_rows, C = rows.shape
+    T = n_rows - a_row0 - (taps - 1) * dil if T is None else T
+    assert a_row0 >= 0 and T >= 1 and a_row0 + T + (taps - 1) * dil <= n_rows and np.shape(W) == (np.shape(W)[0], taps * C)
+    a = np.concatenate([rows[:, a_row0 + j * dil:a_row0 + j * dil + T] for j in range(taps)], axis=-1)          # [B, T, taps C]
+    v = _matmul(a, np.asarray(W, dt).T, dt)
+    if bias is not None:
+        v = v + np.asarray(bias, dt)
+    if res is not None:
+        v = v + np.asarray(res, dt)
+    v = v.astype(dt)
+    return v, silu(v, dt)

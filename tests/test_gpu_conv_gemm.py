@@ -14,6 +14,9 @@ test_planes_gemm_every_mode_vs_fp64: it caps the derived one.
 Exact: every element of C (and Cp) outside the stored ones -- pad columns, the c_off prefix, skipped rows, the tails between items -- keeps the
 value it went in with; a refused plan returns the hook's "refused" code and leaves C alone; a repeated launch is bit-identical.
 
+The activation pass that makes the A planes (to_planes_act_kernel) is reached here in its K-blocked arm only (blocked = 1, one stream, row 0); its
+row-major arm, several streams and a first row > 0 are test_gpu_voc_conv.py: test_to_planes_act_row_major_arm.
+
 With SVA_CONV_GEMM_PARITY_TABLE=<path> the run writes its table there (profiles/conv_gemm_parity.txt): one row per (family, shape, form) with
 the family's worst plan; every plan's own error, bound and ratio are printed by the run and recorded as pytest properties."""
 import os

@@ -8,7 +8,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "streamvoiceanon_amd", "csrc")
 
 STEP, TAIL, KERN, PAR, CONV = "test_gpu_step_ops.py", "test_gpu_decode_tail.py", "test_gpu_kernels.py", "test_gpu_parity.py", "test_gpu_conv_gemm.py"
-IN_SITU = "in situ"          # reached only inside the engine's own step: the named test runs it and checks what it computes
+VOC = "test_gpu_voc_conv.py"
+ROW_MAJOR_ARM = (VOC, "test_to_planes_act_row_major_arm")          # to_planes_act_kernel with blocked = 0, the layout voc_conv_kernel reads
+IN_SITU = "in situ"         # reached only inside the engine's own step: the named test runs it and checks what it computes
 
 # kernel -> (test file, hook or entry point named in that file[, IN_SITU])
 MANIFEST = {
@@ -59,8 +61,8 @@ MANIFEST = {
     "planes_gemm_kernel": (CONV, "test_conv_gemm"),
     "planes_dma_kernel": (CONV, "test_conv_gemm"),
     "to_planes_kernel": (PAR, "test_gemm_planes"),
-    "to_planes_act_kernel": (CONV, "test_conv_gemm"),
-    "voc_conv_kernel": (PAR, "voc_dma=1", IN_SITU),
+    "to_planes_act_kernel": (CONV, "test_conv_gemm"),            # (its row-major arm: ROW_MAJOR_ARM below)
+    "voc_conv_kernel": (VOC, "test_voc_conv"),
     "f16w_gemm_kernel": (PAR, "test_gemm_f16w"),
     "stream_h_gemm_kernel": ("test_gpu_enc_fp16.py", "test_gemm_h16"),
     # csrc/prompt_ops.hip: the sva_op_* entry points
@@ -115,6 +117,10 @@ def test_every_kernel_has_a_test_that_names_its_hook():
         with open(path) as f:
             assert entry[1] in f.read(), "%s: %s does not name %s" % (k, entry[0], entry[1])
         assert len(entry) == 2 or entry[2] == IN_SITU
+    # to_planes_act_kernel has two arms: the conv-GEMM hook reaches only the K-blocked one, the row-major one has its own case
+    for fn in (ROW_MAJOR_ARM[0], MANIFEST["to_planes_act_kernel"][0]):
+        with open(os.path.join(ROOT, "tests", fn)) as f:
+            assert ROW_MAJOR_ARM[1] in f.read(), "%s does not name the row-major case of to_planes_act_kernel" % fn
 
 
 def test_step_ops_hook_covers_every_kernel_of_engine_kernels():

@@ -706,6 +706,76 @@ def test_voc_level_matches_the_oracles_resblock_loop(C):
     _close(got1, R.voc_level(first, W, bias, S.DIL, 0, dt=np.float32), "voc_level f32 restatement")
 
 
+@pytest.mark.parametrize("C", [16, 32])
+def test_voc_conv_ref_matches_conv1d_and_the_oracles_resblock_step(C):
+    """voc_conv_ref over dense rows with its history in front against torch's conv1d in float64 over the left-padded stream, for every (taps,
+    dilation) of the engine and the edge forms of the GPU test; then c1 and c2 chained with the residual against one ResBlock1 step of the oracle
+    (causal_conv1d(silu(.)) twice, + y)"""
+    rng = np.random.default_rng(40 + C)
+    B, T = 2, 70
+    for taps, dil in [(3, 1), (7, 3), (11, 5), (1, 2), (2, 7), (6, 10)]:
+        padL, a_row0 = (taps - 1) * dil, 4
+        x = rng.standard_normal((B, T, C))
+        W = rng.standard_normal((C, taps * C)) / np.sqrt(taps * C)
+        bias, res = rng.standard_normal(C), rng.standard_normal((B, T, C))
+        rows = np.concatenate([np.full((B, a_row0, C), np.nan), np.zeros((B, padL, C)), x, np.full((B, 3, C), np.nan)], axis=1)     # zero history = the left pad
+        v, s = R.voc_conv_ref(rows, W, bias, res, taps, dil, a_row0=a_row0, T=T)
+        w_t = torch.from_numpy(W).reshape(C, taps, C).permute(0, 2, 1).contiguous()                                                # [Cout, Cin, k]
+        want = F.conv1d(F.pad(torch.from_numpy(x).permute(0, 2, 1), (padL, 0)), w_t, torch.from_numpy(bias), dilation=dil).permute(0, 2, 1).numpy() + res
+        assert np.abs(v - want).max() <= 1e-12 * np.abs(want).max(), (taps, dil)
+        assert np.abs(s - F.silu(torch.from_numpy(want)).numpy()).max() <= 1e-12 * np.abs(want).max()
+        v32, s32 = R.voc_conv_ref(rows, W, bias, res, taps, dil, a_row0=a_row0, T=T, dt=np.float32)
+        assert v32.dtype == np.float32 and s32.dtype == np.float32
+        _close(v, v32, "voc_conv_ref f32 restatement")
+        _close(s, s32, "voc_conv_ref silu f32 restatement")
+    # one ResBlock1 step: t = c1(silu(y)); y' = c2(silu(t)) + y.  History rows are zero = the oracle's left pad (silu(0) = 0)
+    taps, dil = 7, 3
+    padL = (taps - 1) * dil
+    y = rng.standard_normal((B, T, C)).astype(np.float32)
+    W1, W2 = (rng.standard_normal((C, taps * C)).astype(np.float32) / np.float32(np.sqrt(taps * C)) for _ in range(2))
+    b1, b2 = (rng.standard_normal(C).astype(np.float32) for _ in range(2))
+    hist = np.zeros((B, padL, C))
+    _, st = R.voc_conv_ref(np.concatenate([hist, R.silu(y)], axis=1), W1, b1, None, taps, dil)
+    v, _ = R.voc_conv_ref(np.concatenate([hist, st], axis=1), W2, b2, y, taps, dil)
+    y_ct = _t(y).permute(0, 2, 1)
+    w1, w2 = (_t(w).reshape(C, taps, C).permute(0, 2, 1).contiguous() for w in (W1, W2))
+    t_o = O.causal_conv1d(F.silu(y_ct), w1, _t(b1), dilation=dil)
+    want = (O.causal_conv1d(F.silu(t_o), w2, _t(b2), dilation=dil) + y_ct).permute(0, 2, 1).numpy()
+    _close(v, want, "voc_conv_ref chained = one ResBlock1 step of the oracle")
+
+
+@pytest.mark.parametrize("mname", ["H3", "H1"])
+@pytest.mark.parametrize("C", [16, 32])
+def test_voc_conv_rule_bites_on_deliberate_errors(C, mname):
+    """the comparison rule of tests/test_gpu_voc_conv.py (voc_conv_cases.rule / bound_of) on reference-versus-mutated-reference, at the GPU test's
+    shapes and operands as the planes hold them: a reversed tap order, a dilation off by one, a first input row off by one (both ways), the residual
+    of the wrong stream and -- C = 16 -- the last odd tap counted twice each exceed the bound of the fp32 rows AND of the SiLU'd planes; the
+    float32 restatement itself passes"""
+    import voc_conv_cases as V
+    mode, B, T = V.MODES[mname], 3, V.TILE[C]
+    for m in V.group(900 + C, C, B, T, V.RES_K, V.RES_D, "c2"):
+        a, alo, w, wlo = V.cpu_operands(m, mode)
+        q = V.rule(m, mode, a, alo, w, wlo)
+        bv, bs = V.bound_of(q["v64"], q["v32"], q["extra"], q["ceiling"]), V.bound_of(q["s64"], q["s32"], q["extra_p"], q["ceiling_p"])
+        assert np.abs(q["v32"] - q["v64"]).max() <= bv and np.abs(q["s32"] - q["s64"]).max() <= bs
+        taps, Cc = m["taps"], m["C"]
+        w_rev = w.reshape(Cc, taps, Cc)[:, ::-1].reshape(Cc, -1)
+        w_twice = w.copy()
+        w_twice[:, (taps - 1) * Cc:] *= 2.0
+        res = V.res_rows(m)
+        mutants = {"tap order reversed": dict(w=w_rev), "dilation off by one": dict(dil=m["dil"] - 1 if m["dil"] > 1 else 2),
+                   "first row one early": dict(a_row0=m["a_row0"] - 1), "first row one late": dict(a_row0=m["a_row0"] + 1),
+                   "residual of the wrong stream": dict(res=np.roll(res, 1, axis=0))}
+        if C == 16:
+            assert taps % 2 == 1
+            mutants["last odd tap counted twice"] = dict(w=w_twice)
+        for what, mut in mutants.items():
+            mut = dict(mut)
+            v64, s64, _, _ = V.reference(m, a, mut.pop("w", w), res=mut.pop("res", None), **mut)
+            assert np.abs(v64 - q["v64"]).max() > bv, (what, taps, "fp32 rows")
+            assert np.abs(s64 - q["s64"]).max() > bs, (what, taps, "SiLU'd planes")
+
+
 def test_ring_wrap_runs_straddle_the_capacity_on_the_oracles_trace(monkeypatch):
     """test_gpu_parity.py replays max_seq_frames = 160 / buffer_frames = 16 streams at hist_cap = 32 through every decode path.  On the oracle's own
     state machine (StreamSession; the transformer stubbed out -- positions do not depend on it) every such run has a re-prefill whose na-frame window
