@@ -324,6 +324,10 @@ int sva_debug_configure(const char* kv);
  * cache (ar_dtype = 1) is widened exactly.  Drains the batch's streams first.  Fails for a slot outside the batch or rows outside the cache
  * (slot < 0, slot >= n_streams, pos0 < 0, n < 1, pos0 + n > max_seq_len). */
 int sva_test_kv_rows(sva_batch* b, int slot, int pos0, int n, float* out);
+/* test hook, read-only: rows row0 .. row0 + n - 1 of the engine's table of fast layer 0 (RMSNorm + wqkv of every fast_embeddings row, before
+ * RoPE, in the engine's AR element type; csrc/ar_decode.h) as float out[n][3 * ar_dim].  Fails when the engine has no table (sizes the
+ * persistent decode kernel is not built for) or for rows outside it (row0 < 0, n < 1, row0 + n > codebook_size). */
+int sva_test_fast_qkv0(sva_engine* e, int row0, int n, float* out);
 /* test hook: set the persistent kernel's device-side timeout word, as a launch with non-resident workgroups would */
 int sva_test_force_ar_timeout(sva_batch* b);
 /* test hook: do the four chain streams of a pipelined batch -- main, encoder side, AR, vocoder -- run concurrently, i.e. sit on four

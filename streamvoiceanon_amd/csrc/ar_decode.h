@@ -26,6 +26,11 @@ struct ArDecodeArgs {
     const void* fast_out_w;       // [codebook_size][768]
     const float* fast_norm;
     const float *content_emb, *codebook_emb, *fast_emb, *rope_slow, *rope_fast;
+    // [codebook_size][2304] fast layer 0's RMSNorm + wqkv of every row of fast_emb, before RoPE: what phase FA would compute for codebooks
+    // 1..7, whose input is fast_emb[token].  fill_qkv0 != 0: this launch (grid 96 x 1) only writes the table -- every wave keeps its six
+    // wqkv rows in registers and walks the rows of fast_emb; it touches no stream state, hands nothing off and waits for nothing
+    float* fast_qkv0;
+    int fill_qkv0;
     // stream state (slot 0 of a one-stream batch)
     const long long* codes;       // content code of this frame = codes[code_off]
     int code_off;

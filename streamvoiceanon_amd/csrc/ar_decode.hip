@@ -3,7 +3,8 @@
 // decode_one_token_ar (modules/dual_ar_stream.py:1168-1219) at batch 1 is a chain of ~200 tiny matrix-vector products
 // (12 slow layers on 2 tokens, then 8 x [4 fast layers + codebook head + nucleus sample]); every one needs the whole
 // output vector of its predecessor, so as separate kernels each costs a launch boundary plus a cold start of its weight
-// stream (5-9 us per kernel measured, 1.5 ms per frame) although the frame only moves 0.5 GB (fp32) / 0.26 GB (fp16).
+// stream (5-9 us per kernel measured, 1.5 ms per frame) although the frame only moves 1.3 GB (fp32) / 0.66 GB (fp16): 368 MB of slow
+// weights once and 8 passes over the fast layers and the codebook head (tools/ar_timing.py prints the sum).
 // Here 96 workgroups (one per CU of the AR stream's partition) stay resident for the whole frame and hand the
 // activation vectors to each other in-launch:
 //   * every wave owns fixed output rows of every weight matrix and keeps the whole K extent of its rows in registers
@@ -17,7 +18,17 @@
 //     p + 1, when every workgroup has provably finished reading it (it published its phase-p output after the read);
 //   * the nucleus sampler of a codebook runs redundantly in every wave (one wave, 16 logits per lane, sort-free
 //     threshold search with DPP reductions only), so the sampled token needs no broadcast edge;
-//   * fast-AR K/V of the 8 codebook positions go through a small global scratch with agent-scope stores / loads.
+//   * fast-AR K/V of the 8 codebook positions go through a small global scratch with agent-scope stores / loads;
+//   * fast layer 0 of codebooks 1..7 is a function of the sampled token alone (its input is fast_emb[token]): RMSNorm + wqkv of all
+//     codebook_size rows are tabulated once per engine (fast_qkv0, 9.2 MB, filled by this kernel's own fill mode -- same device
+//     function, same lanes, same bits), and the frame loads row `token` beside the embedding, applies RoPE and goes straight to the
+//     attention: no phase FA, no all-gather of q | k | v, 7 x 7 MB of wqkv less per frame;
+//   * the fast attention has two forms.  Codebook 0 has one key: the softmax weight and the normaliser are exactly 1, the output is V,
+//     so FB gathers only the V third and feeds it to wo.  Codebooks 1..7: one head per 16-lane row (wave w: heads 3w .. 3w + 2, the
+//     fourth row idles), 4 dimensions of q, of every key and of every value per lane; scores are row reductions, the maximum, the
+//     exponentials and the denominator stay in registers (summed in the order of the wave-wide reduction they replace, so the bits
+//     are the same: tests/test_fast_attention_order_cpu.py).
+// In-kernel marks, one stream, fp32 (profiles/ar_fast_path_report.txt): 813 -> 760 us per frame; the kernel trace 826 -> 775 us.
 // All spins are bounded (a timeout sets *fail and lets the kernel run to its end with garbage instead of hanging).
 #include "ar_decode.h"
 #include "device_util.h"
@@ -116,6 +127,23 @@ __global__ __launch_bounds__(256, 1) void ar_decode_kernel(const ArDecodeArgs a)
     float* ropef = scr + 16 * 68;             // [8][32][2] RoPE table of the codebook positions
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wg = blockIdx.x, gw = wg * 4 + wave;
     // this kernel is a latency chain that shares its CUs with the encoder's / vocoder's throughput kernels: its waves go first
+    if (a.fill_qkv0) {
+        // table of fast layer 0 (ar_decode.h): phase FA's own product on every row of fast_emb, stored before RoPE -- the same device
+        // function, lane layout and wave_sum as in the frame, hence the same bits.  No stream state, no hand-off, no poll.
+        WFrag<WT, D> w[6];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) w[r].load(a.fast[0].wqkv, 6L * gw + r, lane);
+        for (int row = 0; row < a.codebook_size; ++row) {
+            float o[1][6];
+            gemv<WT, D, 6, 1, true>(w, a.fast_emb + (long)row * D, D, a.fast[0].attn_norm, 1e-5f, lane, o);
+            float mine = 0.f;
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+                if (lane == r) mine = o[0][r];
+            if (lane < 6) a.fast_qkv0[(long)row * I + 6 * gw + lane] = mine;
+        }
+        return;
+    }
     __builtin_amdgcn_s_setprio(3);
     unsigned ep = *s_epoch;
     int nmark = 0;
@@ -393,24 +421,17 @@ __global__ __launch_bounds__(256, 1) void ar_decode_kernel(const ArDecodeArgs a)
     // ======================================= fast AR: 8 codebooks x 4 layers on M = 1 row =======================================
     __shared__ int toks[NCB];                  // the frame's codes (every workgroup samples the same token)
     int tprev = 0;
-    WFrag<WT, D> wq0[6];                       // wqkv rows of fast layer 0: requested a phase early (before the sampler of the previous codebook)
-#pragma unroll
-    for (int r = 0; r < 6; ++r) wq0[r].load(a.fast[0].wqkv, 6L * gw + r, lane);
     for (int cb = 0; cb < NCB; ++cb) {
-        if (cb > 0) {
-            for (int i = tid; i < D; i += 256) xs[i] = a.fast_emb[(long)tprev * D + i];
-            __syncthreads();
-        }
         for (int l = 0; l < AR_FAST_LAYERS; ++l) {
             const ArLayerW& L = a.fast[l];
             float* kvg = s_kv_fast + (long)l * NCB * 2 * D;             // [8][k 768 | v 768]
-            {   // ---- FA: RMSNorm + wqkv + RoPE (position = codebook index) ----
+            // layer 0 of codebooks 1..7: the input is fast_emb[token], so RMSNorm + wqkv is row `token` of the table fast_qkv0.  Phase FA
+            // and its all-gather do not exist there (no publish: the epoch does not advance); FB loads the row itself.
+            const bool tab = l == 0 && cb > 0;
+            if (!tab) {   // ---- FA: RMSNorm + wqkv + RoPE (position = codebook index) ----
                 WFrag<WT, D> w[6];
 #pragma unroll
-                for (int r = 0; r < 6; ++r) {
-                    if (l > 0) w[r].load(L.wqkv, 6L * gw + r, lane);
-                    else w[r] = wq0[r];
-                }
+                for (int r = 0; r < 6; ++r) w[r].load(L.wqkv, 6L * gw + r, lane);
                 asm volatile("" ::: "memory");
                 if (l > 0) gather<3>(s_gx, D, ep, xs, a.fail, 7);
                 AR_MARK();
@@ -421,10 +442,7 @@ __global__ __launch_bounds__(256, 1) void ar_decode_kernel(const ArDecodeArgs a)
 #pragma unroll
                     for (int pr = 0; pr < 3; ++pr) {
                         const int d = (n0 + 2 * pr) & 63;
-                        const float c = ropef[(cb * 32 + (d >> 1)) * 2], sn = ropef[(cb * 32 + (d >> 1)) * 2 + 1];
-                        const float x0 = o[0][2 * pr], x1 = o[0][2 * pr + 1];
-                        o[0][2 * pr] = x0 * c - x1 * sn;
-                        o[0][2 * pr + 1] = x1 * c + x0 * sn;
+                        rope_pair(o[0][2 * pr], o[0][2 * pr + 1], ropef[(cb * 32 + (d >> 1)) * 2], ropef[(cb * 32 + (d >> 1)) * 2 + 1]);
                     }
                 }
                 AR_MARK();
@@ -440,68 +458,108 @@ __global__ __launch_bounds__(256, 1) void ar_decode_kernel(const ArDecodeArgs a)
                 }
             }
             {   // ---- FB: attention over <= 8 positions (every workgroup computes all heads: wave w takes heads 3w..3w+2), wo + residual ----
+                // the token's rows of fast_emb and of the table: the only loads of this phase that depend on the sampler, so they go first
+                float4 tq[3], tx;
+                if (tab) {
+                    const float4* qr = reinterpret_cast<const float4*>(a.fast_qkv0 + (long)tprev * I);
+#pragma unroll
+                    for (int j = 0; j < 3; ++j)
+                        if (tid + 256 * j < I / 4) tq[j] = qr[tid + 256 * j];
+                    if (tid < D / 4) tx = reinterpret_cast<const float4*>(a.fast_emb + (long)tprev * D)[tid];
+                }
                 WFrag<WT, D> w[2];
 #pragma unroll
                 for (int r = 0; r < 2; ++r) w[r].load(L.wo, 2L * gw + r, lane);
-                // K | V of the earlier positions (written through at least one whole codebook step ago).  Scores: one key per 16-lane
-                // row, 4 dimensions per lane (two rounds cover the 8 positions: 2 row reductions per head instead of 8 wave reductions);
-                // P.V: lane = head dimension
+                // K | V of the earlier positions (written through at least one whole codebook step ago).  One head per 16-lane row: row g
+                // of the wave (g < 3) serves head 3w + g, lane i of the row holds dimensions 4i .. 4i + 3 of q, of every key and of every
+                // value; the fourth row shadows the third and stores nothing
                 const int kg = lane >> 4, kli = lane & 15;
-                u64 pk[3][2][2];
-                float pv[3][7];
+                const int hb = (wave * 3 + (kg < 3 ? kg : 2)) * 64 + 4 * kli;
+                u64 pk[7][2], pv[7][2];
 #pragma unroll
-                for (int hh = 0; hh < 3; ++hh) {
-                    const int hb = (wave * 3 + hh) * 64;
-#pragma unroll
-                    for (int rnd = 0; rnd < 2; ++rnd) {
-                        const int t = kg + 4 * rnd;
-                        if (t < cb) {
-                            const u64* src = reinterpret_cast<const u64*>(kvg + (long)t * 2 * D + hb + 4 * kli);
-                            pk[hh][rnd][0] = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            pk[hh][rnd][1] = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
+                for (int t = 0; t < 7; ++t)
+                    if (t < cb) {
+                        const u64* src = reinterpret_cast<const u64*>(kvg + (long)t * 2 * D + hb);
+                        pk[t][0] = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        pk[t][1] = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        pv[t][0] = __hip_atomic_load(src + D / 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        pv[t][1] = __hip_atomic_load(src + D / 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
-#pragma unroll
-                    for (int t = 0; t < 7; ++t)
-                        if (t < cb) pv[hh][t] = __hip_atomic_load(kvg + (long)t * 2 * D + D + hb + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
                 asm volatile("" ::: "memory");
-                gather<9>(s_gbig, I, ep, big, a.fail, 8);
-                AR_MARK();
+                if (tab) {
+                    // q | k | v of this position from the table row: RoPE on the q and k regions, the row into `big`, the token's
+                    // embedding into `xs` (both last read before the sampler's closing barrier)
 #pragma unroll
-                for (int hh = 0; hh < 3; ++hh) {
-                    const int hb = (wave * 3 + hh) * 64;
-                    const float4 q4 = *reinterpret_cast<const float4*>(big + hb + 4 * kli);
-                    float sc2[2];
-#pragma unroll
-                    for (int rnd = 0; rnd < 2; ++rnd) {
-                        const int t = kg + 4 * rnd;
-                        float4 k4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (t < cb) {
-                            k4 = make_float4(__uint_as_float((unsigned)pk[hh][rnd][0]), __uint_as_float((unsigned)(pk[hh][rnd][0] >> 32)),
-                                             __uint_as_float((unsigned)pk[hh][rnd][1]), __uint_as_float((unsigned)(pk[hh][rnd][1] >> 32)));
-                        } else if (t == cb) {
-                            k4 = *reinterpret_cast<const float4*>(big + D + hb + 4 * kli);
+                    for (int j = 0; j < 3; ++j) {
+                        const int f = tid + 256 * j;                // float4 index: elements 4f .. 4f + 3, two adjacent pairs of one head
+                        if (f < I / 4) {
+                            float4 v = tq[j];
+                            if (f < 2 * D / 4) {
+                                const float* cs = ropef + (cb * 32 + (((4 * f) & 63) >> 1)) * 2;
+                                rope_pair(v.x, v.y, cs[0], cs[1]);
+                                rope_pair(v.z, v.w, cs[2], cs[3]);
+                            }
+                            *reinterpret_cast<float4*>(big + 4 * f) = v;
+                            // K | V of this codebook position for the later positions of this frame: every workgroup holds the whole row,
+                            // workgroup g writes elements 16g .. 16g + 15 of the 1536
+                            if (f >= D / 4 && ((f - D / 4) >> 2) == wg) {
+                                float* dst = kvg + (long)cb * 2 * D + (4 * f - D);
+                                __hip_atomic_store(dst, v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                __hip_atomic_store(dst + 1, v.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                __hip_atomic_store(dst + 2, v.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                __hip_atomic_store(dst + 3, v.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            }
                         }
-                        const float dot = row16_sum(q4.x * k4.x + q4.y * k4.y + q4.z * k4.z + q4.w * k4.w) * 0.125f;
-                        sc2[rnd] = t <= cb ? dot : -INFINITY;
                     }
-                    const float mx = wave_max(fmaxf(sc2[0], sc2[1]));
-                    const float e0 = sc2[0] > -INFINITY ? expf(sc2[0] - mx) : 0.f, e1 = sc2[1] > -INFINITY ? expf(sc2[1] - mx) : 0.f;
-                    const float inv = 16.f / wave_sum(e0 + e1);                  // every row holds its value 16 times
-                    float acc = 0.f;
+                    if (tid < D / 4) *reinterpret_cast<float4*>(xs + 4 * tid) = tx;
+                    // What gather() ends with, in its place: the relaxed write-through stores of the K | V elements above (and everything
+                    // older this wave issued) have completed before this workgroup publishes FB's output below.  A later reader of those
+                    // elements -- FB of a later codebook -- is ordered behind that publish (it has gathered vectors that depend on it),
+                    // hence behind the completed stores: no tag or fence on the rows themselves is needed.
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __syncthreads();
+                } else if (cb == 0) {
+                    gather<3>(s_gbig + 2 * D, D, ep, big + 2 * D, a.fail, 8);      // one key: the attention is V (below)
+                } else {
+                    gather<9>(s_gbig, I, ep, big, a.fail, 8);
+                }
+                AR_MARK();
+                const float* ao = av;
+                if (cb == 0) {
+                    // position 0 attends to itself alone: the softmax weight is exactly 1 and the normaliser exactly 1, fmaf(1, v, 0) * 1 == v
+                    // bit for bit.  wo reads the gathered V third; q and k of FA are not even waited for.
+                    ao = big + 2 * D;
+                } else {
+                    const float4 q4 = *reinterpret_cast<const float4*>(big + hb);
+                    const float4 kc = *reinterpret_cast<const float4*>(big + D + hb), vc = *reinterpret_cast<const float4*>(big + 2 * D + hb);
+                    float e[NCB], mx = -INFINITY;
 #pragma unroll
                     for (int t = 0; t < NCB; ++t) {
-                        // probability of position t: held by row t & 3 in round t >> 2
-                        const float e = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, (t >> 2) ? e1 : e0), (t & 3) * 16));
-                        const float vd = t < cb ? (t < 7 ? pv[hh][t < 7 ? t : 0] : 0.f) : big[2 * D + hb + lane];
-                        if (t <= cb) acc = fmaf(e, vd, acc);
+                        e[t] = -INFINITY;
+                        if (t <= cb) {
+                            const float4 k4 = t < cb ? f4_from_u64(pk[t < 7 ? t : 0][0], pk[t < 7 ? t : 0][1]) : kc;
+                            e[t] = row16_sum(dot4(q4, k4)) * 0.125f;
+                            mx = fmaxf(mx, e[t]);
+                        }
                     }
-                    av[hb + lane] = acc * inv;
+#pragma unroll
+                    for (int t = 0; t < NCB; ++t) e[t] = t <= cb ? expf(e[t] - mx) : 0.f;
+                    // the denominator in the order of the wave-wide sum this replaces (16 lanes of row r held e[r] + e[r + 4]; row_bcast15
+                    // formed rows 1 + 0 and 3 + 2, row_bcast31 added the former to the latter; the in-row steps only doubled)
+                    const float inv = 1.f / (((e[3] + e[7]) + (e[2] + e[6])) + ((e[1] + e[5]) + (e[0] + e[4])));
+                    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                    for (int t = 0; t < NCB; ++t)
+                        if (t <= cb) {
+                            const float4 v4 = t < cb ? f4_from_u64(pv[t < 7 ? t : 0][0], pv[t < 7 ? t : 0][1]) : vc;
+                            acc.x = fmaf(e[t], v4.x, acc.x); acc.y = fmaf(e[t], v4.y, acc.y);
+                            acc.z = fmaf(e[t], v4.z, acc.z); acc.w = fmaf(e[t], v4.w, acc.w);
+                        }
+                    if (kg < 3) *reinterpret_cast<float4*>(av + hb) = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
+                    __syncthreads();
                 }
-                __syncthreads();
                 float o[1][2];
-                gemv<WT, D, 2, 1, false>(w, av, D, nullptr, 0.f, lane, o);
+                gemv<WT, D, 2, 1, false>(w, ao, D, nullptr, 0.f, lane, o);
                 AR_MARK();
                 ++ep;
                 if (lane < 2) {
@@ -571,11 +629,6 @@ __global__ __launch_bounds__(256, 1) void ar_decode_kernel(const ArDecodeArgs a)
         }
         {   // ---- FS: nucleus sample, redundantly in every workgroup (4 waves x 4 logits per lane) ----
             const int V = a.codebook_size;
-            if (cb + 1 < NCB) {
-#pragma unroll
-                for (int r = 0; r < 6; ++r) wq0[r].load(a.fast[0].wqkv, 6L * gw + r, lane);
-                asm volatile("" ::: "memory");
-            }
             gather<4>(s_glog, V, ep, lg, a.fail, 12);
             AR_MARK();
             float l[4];
@@ -589,7 +642,7 @@ __global__ __launch_bounds__(256, 1) void ar_decode_kernel(const ArDecodeArgs a)
             tprev = t;
             if (tid == 0) toks[cb] = t;
             if (wg == 0 && tid == 0) { s_tok_raw[cb] = raw; s_tok[cb] = t; }
-            __syncthreads();          // lg / xs are rewritten by the next codebook step
+            __syncthreads();          // lg / xs / big are rewritten by the next codebook step
         }
     }
 

@@ -141,6 +141,24 @@ __device__ __forceinline__ float row16_sum(float v) {        // sum over the 16 
     return v;
 }
 
+// RoPE of one adjacent (even, odd) pair, (x0, x1) -> (x0 c - x1 s, x1 c + x0 s), with the products and the fused steps spelt out: the forms
+// the compiler contracts the plain expressions to.  Phase FA and the table path of fast layer 0 both go through here, so that the two
+// cannot be contracted differently.
+__device__ __forceinline__ void rope_pair(float& x0, float& x1, float c, float sn) {
+    const float a = x0, b = x1;
+    x0 = fmaf(a, c, -(b * sn));
+    x1 = fmaf(b, c, a * sn);
+}
+
+// the 4-term partial of a 64-dimension dot product that one lane of a 16-lane row holds (sum: row16_sum)
+__device__ __forceinline__ float dot4(const float4& q, const float4& k) {
+    return fmaf(q.w, k.w, fmaf(q.z, k.z, fmaf(q.x, k.x, q.y * k.y)));
+}
+
+__device__ __forceinline__ float4 f4_from_u64(u64 lo, u64 hi) {
+    return make_float4(__uint_as_float((unsigned)lo), __uint_as_float((unsigned)(lo >> 32)), __uint_as_float((unsigned)hi), __uint_as_float((unsigned)(hi >> 32)));
+}
+
 __device__ __forceinline__ unsigned umax_wave(unsigned v) {
     v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true));
     v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true));

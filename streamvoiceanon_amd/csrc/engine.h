@@ -156,6 +156,7 @@ struct sva_engine {
     sva::Lin ar_output, ar_fast_output, context_in, style_in;
     float *rope_ar = nullptr, *rope_fast = nullptr;
     void *m_output = nullptr, *m_fast_output = nullptr;     // heads in the persistent decode kernel's element type
+    float* fast_qkv0 = nullptr;            // [codebook_size][2304] fast layer 0's RMSNorm + wqkv of every fast_emb row, before RoPE (ar_decode.h; mega_ok only)
     bool mega_ok = false;                  // layer counts / sizes match what ar_decode.hip is built for
     // the front-end's steady response to silence (what sva_streams_begin initialises the per-layer histories and the token cache
     // with), computed once per (streams, chunk) configuration by streaming zeros and reused by later batches: one row per history

@@ -399,6 +399,15 @@ extern "C" int sva_engine_finalize(sva_engine* e) {
             SVA_TRY(P.mega_copy(m + "output", e->ar_output, &e->m_output));
             SVA_TRY(P.mega_copy(m + "fast_output", e->ar_fast_output, &e->m_fast_output));
             if (c.ar_dtype == 1) { e->ar_output.Wh = e->m_output; e->ar_fast_output.Wh = e->m_fast_output; }
+            // fast layer 0 as a function of the token (codebooks 1..7 feed it fast_emb[token]): tabulated once, by the decode kernel's own
+            // fill mode in the engine's AR element type, so that a row carries the bits phase FA would compute
+            SVA_TRY(dev_alloc(e->allocs, &e->fast_qkv0, (size_t)c.codebook_size * 3 * D));
+            ArDecodeArgs fa;
+            memset(&fa, 0, sizeof(fa));
+            const TrLayer& L0 = e->ar_fast_layers[0];
+            fa.fast[0] = ArLayerW{L0.m_wqkv, L0.m_wo, L0.m_w13, L0.m_w2, L0.attn_norm, L0.ffn_norm};
+            fa.fast_emb = e->fast_emb; fa.fast_qkv0 = e->fast_qkv0; fa.fill_qkv0 = 1; fa.codebook_size = c.codebook_size;
+            SVA_TRY(launch_ar_decode(fa, c.ar_dtype == 1, 0, false, 0, 1));
         }
         SVA_TRY(P.linear("arvc.context_in", e->context_in, D, c.timbre_dim));
         SVA_TRY(P.linear("arvc.style_in", e->style_in, D, c.style_dim));

@@ -664,6 +664,7 @@ int ar_decode_frame_mega(sva_batch* b, int ci, const long long* codes, int code_
     }
     a.out_w = e->m_output; a.out_norm = e->ar_norm; a.fast_out_w = e->m_fast_output; a.fast_norm = e->ar_fast_norm;
     a.content_emb = e->content_emb; a.codebook_emb = e->codebook_emb; a.fast_emb = e->fast_emb; a.rope_slow = e->rope_ar; a.rope_fast = e->rope_fast;
+    a.fast_qkv0 = e->fast_qkv0;
     a.codes = codes; a.code_off = code_off;
     a.cached_audio_emb = b->cached_audio_emb; a.last_pos = b->d_last_pos; a.nframes = b->d_nframes; a.seed = b->d_seed;
     a.kv_slow = b->kv_slow; a.kv_layer_stride = b->kv_slow_layer; a.S = c.max_seq_len; a.kv_fast = b->kv_fast_mega;

@@ -2224,6 +2224,19 @@ extern "C" int sva_test_conv_gemm(int device, int n, const long long* desc, cons
     return 0;
 }
 
+// Read-only seam of the fast-path tests (include/sva.h): rows of the engine's fast-layer-0 table.  No kernel: one copy.
+extern "C" int sva_test_fast_qkv0(sva_engine* e, int row0, int n, float* out) {
+    SVA_CHECK(e && out, "sva_test_fast_qkv0: null argument");
+    SVA_CHECK(e->fast_qkv0, "sva_test_fast_qkv0: this engine has no table (sizes the persistent decode kernel is not built for)");
+    const sva_config& c = e->cfg;
+    SVA_CHECK(n >= 1 && row0 >= 0 && n <= c.codebook_size && row0 <= c.codebook_size - n, "sva_test_fast_qkv0: rows outside the table");
+    SVA_HIP(hipSetDevice(e->device));
+    SVA_HIP(hipDeviceSynchronize());
+    const size_t ld = (size_t)3 * c.ar_dim;
+    SVA_HIP(hipMemcpy(out, e->fast_qkv0 + (size_t)row0 * ld, sizeof(float) * ld * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // Read-only seam of the whole-frame tests (include/sva.h): rows pos0 .. pos0 + n - 1 of one slot's slow KV cache, every layer, as float
 // out[layers][2 (k, v)][H][n][64].  An fp16 cache (ar_dtype = 1) is widened on the host, exactly.  No kernel: one strided copy per layer.
 extern "C" int sva_test_kv_rows(sva_batch* b, int slot, int pos0, int n, float* out) {

@@ -87,6 +87,7 @@ def load_library():
     lib.sva_batch_uses_persistent_decode.argtypes = [vp]
     lib.sva_test_force_ar_timeout.argtypes = [vp]
     lib.sva_test_kv_rows.argtypes = [vp, i32, i32, i32, vp]
+    lib.sva_test_fast_qkv0.argtypes = [vp, i32, i32, vp]
     lib.sva_test_stream_overlap.argtypes = [vp, C.POINTER(C.c_int)]
     lib.sva_debug_configure.argtypes = [C.c_char_p]
     lib.sva_sync.argtypes = [vp]
@@ -153,7 +154,7 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "sva_last_error", "sva_config_default", "sva_stream_params_default", "sva_engine_create",
     "sva_engine_load_weight", "sva_engine_finalize", "sva_engine_destroy", "sva_batch_create", "sva_batch_destroy",
-    "sva_prefill_prompt", "sva_streams_begin", "sva_stream_restart", "sva_stream_retire", "sva_stream_state", "sva_stream_set_sampling", "sva_stream_get_sampling", "sva_stream_activations", "sva_step", "sva_step_device", "sva_step_device_on", "sva_join_stream", "sva_batch_uses_persistent_decode", "sva_test_force_ar_timeout", "sva_test_kv_rows", "sva_test_stream_overlap", "sva_debug_configure", "sva_sync", "sva_stream_chunks", "sva_encode_window", "sva_firefly_encode",
+    "sva_prefill_prompt", "sva_streams_begin", "sva_stream_restart", "sva_stream_retire", "sva_stream_state", "sva_stream_set_sampling", "sva_stream_get_sampling", "sva_stream_activations", "sva_step", "sva_step_device", "sva_step_device_on", "sva_join_stream", "sva_batch_uses_persistent_decode", "sva_test_force_ar_timeout", "sva_test_kv_rows", "sva_test_fast_qkv0", "sva_test_stream_overlap", "sva_debug_configure", "sva_sync", "sva_stream_chunks", "sva_encode_window", "sva_firefly_encode",
     "sva_vocode_window", "sva_vocode_stream", "sva_vocode_reset", "sva_quantizer_decode", "sva_vocoder_head", "sva_ar_delay_fill", "sva_ar_decode_one", "sva_generate", "sva_generate_many", "sva_get_tap", "sva_get_timings",
     "sva_dev_alloc", "sva_dev_free", "sva_dev_upload", "sva_dev_download", "sva_op_conv", "sva_op_affine", "sva_op_unary", "sva_op_colstats",
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
@@ -259,6 +260,13 @@ class Engine:
         _check(self.lib.sva_engine_finalize(self.h), "sva_engine_finalize")
         self._batches = weakref.WeakSet()
         self.ops_lock = threading.RLock()      # serialises users of the engine's ops stream (prompt_encoders.py: recording / capture / replay)
+
+    def fast_qkv0_rows(self, row0, n=1):
+        """sva_test_fast_qkv0: rows row0 .. row0 + n - 1 of the table of fast layer 0 (RMSNorm + wqkv of fast_embeddings rows, before RoPE)
+        -> float32 [n, 3 * ar_dim].  Read-only."""
+        out = np.empty((int(n), 3 * self.cfg.ar_dim), dtype=np.float32)
+        _check(self.lib.sva_test_fast_qkv0(self.h, int(row0), int(n), _ptr(out)), "sva_test_fast_qkv0")
+        return out
 
     def close(self):
         if self.h:

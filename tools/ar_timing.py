@@ -29,6 +29,8 @@ if not v2:
 for cb in range(8):
     for l in range(4):
         for ph in ("FA", "FB", "FC", "FD"):
+            if ph == "FA" and l == 0 and cb > 0 and not v2:
+                continue        # fast layer 0 of codebooks 1..7 is a row of the fast_qkv0 table: no phase FA, the sampler's span ends at FB.in
             ph2 = "FSA" if (v2 and ph == "FA" and l == 0 and cb > 0) else ph
             labels += [f"f{cb}.{l}.{ph2}.in", f"f{cb}.{l}.{ph2}.out"]
     labels += [f"f{cb}.FH.in", f"f{cb}.FH.out"] + ([] if v2 else [f"f{cb}.FS.in"])
@@ -53,6 +55,16 @@ for k in range(len(acc)):
 print(f"ar_dtype={ar_dtype}  frame span (first mark -> last mark): {acc.sum():.1f} us   fail={b.tap('ar_fail', (1,), np.int32)[0]}")
 for key, v in kinds.items():
     print(f"  {key:24s} n={len(v):3d} mean {np.mean(v):6.2f} us  min {np.min(v):6.2f}  max {np.max(v):6.2f}  sum {np.sum(v):7.1f}")
+# the fast AR by codebook: codebook 0 has one key (its attention is V and FB gathers only the V third), codebooks 1..7 take layer 0 from the table
+by = {}
+for k in range(len(acc)):
+    p = labels[k].split(".")
+    if p[0][0] == "f" and p[0][1:].isdigit():
+        a, bb = p[-2:], labels[k + 1].split(".")[-2:]
+        by.setdefault((f"{a[0]}.{a[1]} -> {bb[0]}.{bb[1]}", "codebook 0" if p[0] == "f0" else "codebooks 1-7"), []).append(acc[k])
+print("fast AR by codebook:")
+for (key, grp), v in by.items():
+    print(f"  {key:24s} {grp:13s} n={len(v):3d} mean {np.mean(v):6.2f} us  sum {np.sum(v):7.1f}")
 if not v2:
     ns = b.tap("ar_timing", (1024,), np.int64)[900:908].astype(np.float64)
     print("sampler raw marks (us from entry: softmax done, [search done], ties done, final softmax done, argmax done, back in kernel):",
@@ -78,7 +90,7 @@ if not v2:
                     (w_, MB[w_], MB[w_] / mean)) if w_ else "edge; no weights in front of the polls (KV prefetch / partial merge / logits)"
             rows.append(("edge", key, n_, mean, sm, note))
         elif a.startswith("FS") or a.startswith("hidden"):
-            rows.append(("sampler" if a.startswith("FS") else "semantic head", key, n_, mean, sm, "nucleus sampler (threshold search ~6 us) + embedding of the token" if a.startswith("FS") else "semantic head rows + fast-AR input"))
+            rows.append(("sampler" if a.startswith("FS") else "semantic head", key, n_, mean, sm, "nucleus sampler (threshold search ~6 us) + the token's rows of fast_emb and of the fast_qkv0 table + RoPE" if a.startswith("FS") else "semantic head rows + fast-AR input"))
         else:
             rows.append(("phase", key, n_, mean, sm, "products + RoPE / attention / epilogue of the phase"))
     print("critical path (kind, span, count, mean us, sum us):")
@@ -89,6 +101,6 @@ if not v2:
             for r in sub:
                 print("      %-24s x%3d  %5.2f us  = %6.1f us   %s" % (r[1], r[2], r[3], r[4], r[5]))
     slow_mb = 12 * (MB["wqkv"] + MB["wo"] + MB["w13"] + MB["w2"])
-    fast_mb = 32 * (MB["wqkv"] + MB["wo"] + MB["w13"] + MB["w2"]) + 8 * MB["head"]
-    print("  sum %.1f us; weight bytes per frame %.0f MB (slow %.0f once, fast %.0f = 8 passes over 4 layers + heads) -> %.2f TB/s over the frame; "
+    fast_mb = 32 * (MB["wo"] + MB["w13"] + MB["w2"]) + 25 * MB["wqkv"] + 8 * MB["head"]       # (layer 0 of codebooks 1..7: a 9 KB table row, no wqkv)
+    print("  sum %.1f us; weight bytes per frame %.0f MB (slow %.0f once, fast %.0f = 8 passes over 4 layers less 7 wqkv of layer 0 + heads) -> %.2f TB/s over the frame; "
           "at the ~4.8 TB/s the 96 CUs pull (50 GB/s each) the stream alone is %.0f us of the span" % (tot, slow_mb + fast_mb, slow_mb, fast_mb, (slow_mb + fast_mb) / tot, (slow_mb + fast_mb) / 4.8))
