@@ -225,6 +225,7 @@ int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float* noise, con
  * on a batch created with n_streams = 1, chunk_frames = 1: one prefill of 33 + 2(R+delay) + 1 tokens, then S-1 decode steps
  * (the last `delay` frames are driven by the wait4end embeddings).  ref_cc int64[R], ref_ac int32[8][R], src_cc int64[S],
  * noise float[S][vocab + 8*codebook_size] or NULL (device RNG keyed by noise_seed); codes_out int32[8][S].
+ * This is the one-utterance call of the code behind sva_generate_many (same checks, same rules, same kernels).
  * Follow with sva_vocode_window(codes, S) for code2wav_fn (evaluations/infer_arvc.py:349-360). */
 int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* ref_ac, int R, const int64_t* src_cc, int S,
                  const float* style, const float* timbre, uint64_t noise_seed, const float* noise, int32_t* codes_out);
@@ -233,10 +234,10 @@ int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* ref_ac, int
  * ref_cc[i] int64[R[i]], ref_ac[i] int32[8][R[i]], src_cc[i] int64[S[i]], style float[n][192], timbre float[n][32][128], noise_seed[n];
  * noise float[S_max][n][vocab + 8*codebook_size] (frame-major, S_max = max S[i]) or NULL = device RNG keyed per slot by noise_seed[i];
  * codes_out[i] int32[8][S[i]]: exactly 8 * S[i] ints are written.
- * Slot i gets what sva_generate computes for utterance i on a one-stream batch: frame 0 samples at temperature = top_p = 0.7, later frames with
+ * Every slot follows the rules of generate on its own: frame 0 samples at temperature = top_p = 0.7, later frames with
  * the slot's own pair (sva_stream_set_sampling); sampler edits apply from frame 1.  The prompts run as packed passes over the rows of several
  * slots; a slot that has produced its S[i] frames rides along parked until the longest one ends.  Every argument is checked before any state
- * changes: delay < S[i] < 4096, 33 + 2(R[i] + delay) + 1 + 2(S[i] - 1) <= 2048.  Afterwards sva_prefill_prompt + sva_streams_begin start streams afresh. */
+ * changes: delay < S[i] <= 4096, 33 + 2(R[i] + delay) + 1 + 2(S[i] - 1) <= 2048.  Afterwards sva_prefill_prompt + sva_streams_begin start streams afresh. */
 int sva_generate_many(sva_batch* b, int n, const int64_t* const* ref_cc, const int32_t* const* ref_ac, const int* R,
                       const int64_t* const* src_cc, const int* S, const float* style, const float* timbre,
                       const uint64_t* noise_seed, const float* noise, int32_t* const* codes_out);
@@ -534,9 +535,8 @@ int sva_test_token_ops(int device, int kind, const long long* desc, const float*
  *                             ptrs buf (io), save (io)
  *   kind 18 history_rows_move desc n_desc, slot, len(src), len(dst), then (source offset, destination offset, destination bstride, H, C) per descriptor; ptrs src, dst (io)
  *   kind 19 put_row           desc table rows, code, D; ptrs table, dst [D] (io)
- *   kind 20 prepare_offline_step  desc D, step, len(rem), content rows; ptrs cached_audio_emb [D], content_emb, rem, last_pos [1], x [2][D] (io), slot [2] (io), pos [2] (io)
- *   kind 21 mean3             desc B, y_bstride, len(y), o_bstride, o_off, len(out), n4; ptrs y0, y1, y2, out (io)
- *   kind 22 copy_tokens       desc B, Ht, gap, c, T2, D, tok_bstride, len(tok), d_bstride, len(d2c); ptrs tok, d2c (io) */
+ *   kind 20 mean3             desc B, y_bstride, len(y), o_bstride, o_off, len(out), n4; ptrs y0, y1, y2, out (io)
+ *   kind 21 copy_tokens     desc B, Ht, gap, c, T2, D, tok_bstride, len(tok), d_bstride, len(d2c); ptrs tok, d2c (io) */
 int sva_test_step_ops(int device, int kind, const long long* desc, const float* fpar, void* const* ptrs);
 /* sva_test_voc_level: launch_voc_level (the fused HiFiGAN level, C = 16 / 32) with the caller's arguments.
  *   desc C, B, Tl, xH, x_bstride, len(X), y_bstride, len(Y), dil0, dil1, dil2, rows_per_frame, frames_done

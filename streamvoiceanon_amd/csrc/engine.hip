@@ -1906,123 +1906,29 @@ extern "C" int sva_ar_decode_one(sva_batch* b, const int64_t* code, const float*
     return 0;
 }
 
-// ---- offline ARVCWrapper.generate (modules/arvc_wrapper.py:82-98 + DualARWrapper.generate, dual_ar_stream.py:698-762) ----
-extern "C" int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* ref_ac, int R, const int64_t* src_cc, int S,
-                            const float* style, const float* timbre, uint64_t noise_seed, const float* noise, int32_t* codes_out) {
-    SVA_CHECK(b && ref_cc && ref_ac && src_cc && style && timbre && codes_out, "sva_generate: null argument");
-    SVA_CHECK(b->B == 1 && b->p.chunk_frames == 1, "sva_generate: the offline path is batch 1 / chunk 1 like the reference");
-    SVA_HIP(hipSetDevice(b->e->device));
-    (void)hipGetLastError();
-    SVA_TRY(quiesce(b));
-    sva_engine* e = b->e;
-    const sva_config& c = e->cfg;
-    const int D = c.ar_dim, d = b->p.delay, ncb = c.num_codebooks, nspk = c.timbre_tokens + 1;
-    hipStream_t st = b->stream;
-    SVA_CHECK(S > d && S <= b->hist_cap, "sva_generate: source length must exceed the delay");
-    const int Rp = R + d, M = nspk + 2 * Rp + 1;
-    SVA_CHECK(M + 2 * (S - 1) <= c.max_seq_len && M <= b->Mmax, "sva_generate: prompt + source exceed the 2048-position KV cache (the reference breaks there too)");
-    SVA_TRY(h2d(b, b->d_style, style, sizeof(float) * c.style_dim));
-    SVA_TRY(h2d(b, b->d_timbre, timbre, sizeof(float) * c.timbre_tokens * c.timbre_dim));
-    unsigned long long sd = noise_seed;
-    SVA_TRY(h2d(b, b->d_seed, &sd, sizeof(sd)));
-    SVA_HIP(hipMemsetAsync(b->d_nframes, 0, sizeof(int), st));
-    // prefill_cond = [ref_cond, src_cond[:d]] interleaved with [wait4start[:d], embed(ref_audio)]  (:711-715)
-    std::vector<int64_t> cc(ref_cc, ref_cc + R);
-    for (int i = 0; i < d; ++i) cc.push_back(src_cc[i]);
-    std::vector<int32_t> ac((size_t)ncb * Rp, 0);
-    for (int q = 0; q < ncb; ++q)
-        for (int i = 0; i < R; ++i) ac[(size_t)q * Rp + i] = ref_ac[(size_t)q * R + i];
-    SVA_TRY(stage_prompt(b, cc, ac, Rp));
-    // remaining_cond = [src_cond[d:], wait4end[:d]]  (:716), wait4end_j addressed as vocab + j in the extended table
-    std::vector<int64_t> rem(S);
-    for (int i = 0; i < S; ++i) rem[i] = i < S - d ? src_cc[d + i] : (int64_t)c.ar_vocab + (i - (S - d));
-    struct DevGuard { long long* p = nullptr; ~DevGuard() { if (p) (void)hipFree(p); } } remq_guard;      // freed on every return path
-    SVA_HIP(hipMalloc((void**)&remq_guard.p, sizeof(long long) * (size_t)S));
-    long long* d_remq = remq_guard.p;
-    SVA_HIP(hipMemcpyAsync(d_remq, rem.data(), sizeof(long long) * (size_t)S, hipMemcpyHostToDevice, st));
-    SVA_HIP(hipStreamSynchronize(st));
-    // speaker prefix + prompt rows, then remaining_cond[0] as the last row
-    SVA_TRY(gemm_call(b, b->d_timbre, (long)c.timbre_tokens * c.timbre_dim, 0, c.timbre_dim, 1, c.timbre_tokens, 1, 1, 1, c.timbre_dim, e->context_in,
-                      b->spk, (long)nspk * D, 0, D));
-    SVA_TRY(gemm_call(b, b->d_style, c.style_dim, 0, c.style_dim, 1, 1, 1, 1, 1, c.style_dim, e->style_in, b->spk + (long)c.timbre_tokens * D, D, 0, D));
-    SVA_TRY(launch_build_prompt(b->spk, nspk, e->content_emb, e->codebook_emb, e->wait4start, b->d_prompt_cc, b->d_prompt_ac, b->Pmax, Rp, d, ncb, c.codebook_size,
-                                D, b->ax, M - 1, st));
-    SVA_TRY(launch_put_row(e->content_emb, (long long)rem[0], D, b->ax + (long)(M - 1) * D, st));
-    std::vector<int> hs(M, 0), hp(M);
-    for (int i = 0; i < M; ++i) hp[i] = i;
-    SVA_HIP(hipMemcpyAsync(b->d_slot, hs.data(), sizeof(int) * M, hipMemcpyHostToDevice, st));
-    SVA_HIP(hipMemcpyAsync(b->d_pos, hp.data(), sizeof(int) * M, hipMemcpyHostToDevice, st));
-    SVA_HIP(hipStreamSynchronize(st));
-    SVA_TRY(ar_layers_pass(b, e->ar_layers, M, b->d_slot, b->d_pos, e->rope_ar, (float*)b->kv_slow, b->kv_slow_layer, b->kv_slow_slot,
-                           c.max_seq_len, b->ax, 0, 0));
-    const int lp = M - 1;
-    SVA_TRY(h2d(b, b->d_last_pos, &lp, sizeof(int)));
-    b->slots.offline_prefilled(0, lp);
-    const int nstride = c.ar_vocab + ncb * c.codebook_size;
-    const int zero = 0;
-    SVA_TRY(h2d(b, b->d_use_forced, &zero, sizeof(int)));
-    b->h_use_forced = 0;
-    b->noise_on_device = (noise == nullptr);
-    for (int i = 0; i < S; ++i) {
-        if (noise) SVA_TRY(h2d(b, b->d_noise, noise + (size_t)i * nstride, sizeof(float) * nstride));
-        if (i == 0) {
-            // the prefill's decode ignores the caller's sampling_kwargs: generate() calls decode_one_token_ar without them
-            // (dual_ar_stream.py:722), i.e. with temperature = top_p = 0.7
-            // -- written into slot 0's device pair for this one frame; the slot's own pair comes back from the book
-            const float quirk[2] = {1.0f / 0.7f, 0.7f};
-            SVA_TRY(h2d(b, b->d_samp, quirk, sizeof(quirk)));
-            b->edits_skip = true;                     // ... and without previous_tokens / suppress_tokens
-            const int rc0 = ar_frame_tail(b, 0, 0, (long)(M - 1) * D, d_remq, S, 0, 0);
-            b->edits_skip = false;
-            const int rc1 = h2d(b, b->d_samp, b->slots.s[0].samp, sizeof(float) * 2);
-            SVA_TRY(rc0);
-            SVA_TRY(rc1);
-            b->slots.frame_decoded(0, 0);
-        } else if (b->use_mega && !b->edits_on) {
-            // decode steps of the offline loop (dual_ar_stream.py:735-760) through the persistent kernel: the same two tokens
-            // [embed(previous codes), cond_i] at the next two positions, one launch per frame instead of ~200
-            SVA_TRY(ar_decode_frame_mega(b, 0, d_remq, i));
-            b->slots.frame_decoded(0, 2);
-        } else {
-            SVA_TRY(launch_prepare_offline_step(b->cached_audio_emb, e->content_emb, d_remq, i, b->d_last_pos, D, b->ax, b->d_slot, b->d_pos, st));
-            SVA_TRY(ar_layers_pass(b, e->ar_layers, 2, b->d_slot, b->d_pos, e->rope_ar, (float*)b->kv_slow, b->kv_slow_layer, b->kv_slow_slot,
-                                   c.max_seq_len, b->ax));
-            SVA_TRY(ar_frame_tail(b, 0, (long)2 * D, (long)D, d_remq, S, i, 2));
-            b->slots.frame_decoded(0, 2);
-        }
-    }
-    SVA_HIP(hipStreamSynchronize(st));
-    for (int q = 0; q < ncb; ++q)
-        SVA_HIP(hipMemcpy(codes_out + (size_t)q * S, b->d_pred_hist + (size_t)q * b->hist_cap, sizeof(int) * (size_t)S, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// ---- offline batches: ARVCWrapper.generate for every slot of the batch at once.  Slot i gets what sva_generate computes for utterance i on a
-// one-stream batch (token layout, wait4end rows, the frame-0 rule, skip_semantic, batch-wide sampler edits from frame 1); the prompts run as
+// ---- offline ARVCWrapper.generate (modules/arvc_wrapper.py:82-98 + DualARWrapper.generate, dual_ar_stream.py:698-762) for every slot of the
+// batch at once: utterance i in slot i, one utterance per slot (the entries below check that and their own pointers).  The prompts run as
 // packed passes over the rows of several slots, the frames through the batch's normal decode choice, finished slots ride along parked ----
-extern "C" int sva_generate_many(sva_batch* b, int n, const int64_t* const* ref_cc, const int32_t* const* ref_ac, const int* R,
-                                 const int64_t* const* src_cc, const int* S, const float* style, const float* timbre,
-                                 const uint64_t* noise_seed, const float* noise, int32_t* const* codes_out) {
-    SVA_CHECK(b && ref_cc && ref_ac && R && src_cc && S && style && timbre && noise_seed && codes_out, "sva_generate_many: null argument");
-    SVA_CHECK(b->p.chunk_frames == 1 && n == b->B, "sva_generate_many: needs chunk_frames == 1 and one utterance per slot (n == n_streams)");
+static int offline_generate(sva_batch* b, const int64_t* const* ref_cc, const int32_t* const* ref_ac, const int* R, const int64_t* const* src_cc,
+                            const int* S, const float* style, const float* timbre, const uint64_t* noise_seed, const float* noise,
+                            int32_t* const* codes_out) {
     sva_engine* e = b->e;
     const sva_config& c = e->cfg;
     const int B = b->B, D = c.ar_dim, d = b->p.delay, ncb = c.num_codebooks, nspk = c.timbre_tokens + 1;
     std::vector<int> Mi(B);
     int Smax = 0;
     for (int i = 0; i < B; ++i) {
-        SVA_CHECK(ref_cc[i] && ref_ac[i] && src_cc[i] && codes_out[i], "sva_generate_many: null argument");
-        SVA_CHECK(R[i] >= 1, "sva_generate_many: empty prompt");
-        SVA_CHECK(S[i] > d, "sva_generate_many: source length must exceed the delay");
-        SVA_CHECK(S[i] < b->hist_cap, "sva_generate_many: source longer than the prediction history (a finished slot parks in one spare column)");
+        SVA_CHECK(S[i] > d, "offline generate: source length must exceed the delay");
+        // (a slot parks in ring column S[i] only while a longer one still runs: S[i] < Smax <= hist_cap, so that column exists)
+        SVA_CHECK(S[i] <= b->hist_cap, "offline generate: source longer than the prediction history");
         Mi[i] = nspk + 2 * (R[i] + d) + 1;
-        SVA_CHECK(Mi[i] <= b->Mmax && R[i] + d <= b->Pmax, "sva_generate_many: prompt longer than the AR scratch");
-        SVA_CHECK(Mi[i] + 2 * (S[i] - 1) <= c.max_seq_len, "sva_generate_many: prompt + source exceed the 2048-position KV cache (the reference breaks there too)");
+        SVA_CHECK(Mi[i] <= b->Mmax && R[i] + d <= b->Pmax, "offline generate: prompt longer than the AR scratch");
+        SVA_CHECK(Mi[i] + 2 * (S[i] - 1) <= c.max_seq_len, "offline generate: prompt + source exceed the 2048-position KV cache (the reference breaks there too)");
         Smax = std::max(Smax, S[i]);
     }
     std::vector<int> pass_of, row0_of;
     const int n_pass = prefill_pack(Mi.data(), B, b->Mmax, pass_of, row0_of);
-    SVA_CHECK(n_pass >= 1, "sva_generate_many: prompt longer than the AR scratch");
+    SVA_CHECK(n_pass >= 1, "offline generate: prompt longer than the AR scratch");
     SVA_HIP(hipSetDevice(e->device));
     (void)hipGetLastError();
     SVA_TRY(quiesce(b));
@@ -2072,12 +1978,8 @@ extern "C" int sva_generate_many(sva_batch* b, int n, const int64_t* const* ref_
             for (int q = 0; q < ncb; ++q)
                 for (int k = 0; k < R[i]; ++k) ac[(size_t)q * Rp + k] = ref_ac[i][(size_t)q * R[i] + k];
             SVA_TRY(stage_prompt(b, cc, ac, Rp));
-            SVA_TRY(gemm_call(b, b->d_timbre + (long)i * c.timbre_tokens * c.timbre_dim, (long)c.timbre_tokens * c.timbre_dim, 0, c.timbre_dim, 1, c.timbre_tokens,
-                              1, 1, 1, c.timbre_dim, e->context_in, b->spk, (long)nspk * D, 0, D));
-            SVA_TRY(gemm_call(b, b->d_style + (long)i * c.style_dim, c.style_dim, 0, c.style_dim, 1, 1, 1, 1, 1, c.style_dim, e->style_in,
-                              b->spk + (long)c.timbre_tokens * D, D, 0, D));
-            SVA_TRY(launch_build_prompt(b->spk, nspk, e->content_emb, e->codebook_emb, e->wait4start, b->d_prompt_cc, b->d_prompt_ac, b->Pmax, Rp, d, ncb,
-                                        c.codebook_size, D, b->ax + (long)row0 * D, M - 1, st));
+            // speaker prefix + prompt rows, then remaining_cond[0] as the last row
+            SVA_TRY(ar_build_prompt_rows(b, i, Rp, b->ax + (long)row0 * D, M - 1));
             SVA_TRY(launch_put_row(e->content_emb, rem[(size_t)i * Smax], D, b->ax + (long)(row0 + M - 1) * D, st));
             for (int m = 0; m < M; ++m) { hs[row0 + m] = i; hp[row0 + m] = m; }
             runs.insert(runs.end(), {i, 0, M, row0});
@@ -2140,6 +2042,26 @@ extern "C" int sva_generate_many(sva_batch* b, int n, const int64_t* const* ref_
         for (int q = 0; q < ncb; ++q)
             SVA_HIP(hipMemcpy(codes_out[i] + (size_t)q * S[i], b->d_pred_hist + ((size_t)i * ncb + q) * b->hist_cap, sizeof(int) * (size_t)S[i], hipMemcpyDeviceToHost));
     return 0;
+}
+
+// one utterance on a one-stream batch: the n = 1 call of offline_generate
+extern "C" int sva_generate(sva_batch* b, const int64_t* ref_cc, const int32_t* ref_ac, int R, const int64_t* src_cc, int S,
+                            const float* style, const float* timbre, uint64_t noise_seed, const float* noise, int32_t* codes_out) {
+    SVA_CHECK(b && ref_cc && ref_ac && src_cc && style && timbre && codes_out, "sva_generate: null argument");
+    SVA_CHECK(b->B == 1 && b->p.chunk_frames == 1, "sva_generate: the offline path is batch 1 / chunk 1 like the reference");
+    return offline_generate(b, &ref_cc, &ref_ac, &R, &src_cc, &S, style, timbre, &noise_seed, noise, &codes_out);
+}
+
+extern "C" int sva_generate_many(sva_batch* b, int n, const int64_t* const* ref_cc, const int32_t* const* ref_ac, const int* R,
+                                 const int64_t* const* src_cc, const int* S, const float* style, const float* timbre,
+                                 const uint64_t* noise_seed, const float* noise, int32_t* const* codes_out) {
+    SVA_CHECK(b && ref_cc && ref_ac && R && src_cc && S && style && timbre && noise_seed && codes_out, "sva_generate_many: null argument");
+    SVA_CHECK(b->p.chunk_frames == 1 && n == b->B, "sva_generate_many: needs chunk_frames == 1 and one utterance per slot (n == n_streams)");
+    for (int i = 0; i < n; ++i) {
+        SVA_CHECK(ref_cc[i] && ref_ac[i] && src_cc[i] && codes_out[i], "sva_generate_many: null argument");
+        SVA_CHECK(R[i] >= 1, "sva_generate_many: empty prompt");
+    }
+    return offline_generate(b, ref_cc, ref_ac, R, src_cc, S, style, timbre, noise_seed, noise, codes_out);
 }
 
 extern "C" int sva_encode_window(sva_batch* b, const float* audio, int64_t* codes_out, float* u_out) {

@@ -93,6 +93,7 @@ struct PersistentChain {
 int ar_decode_frame_batch(sva_batch* b, int ci);
 int ar_decode_frame_mega(sva_batch* b, int ci, const long long* codes, int code_off, int codes_ld = 0);      // (codes_ld == 0: the encoder's table, T2)
 int ar_frame_tail(sva_batch* b, int ci, long hid_stride, long hid_off, const long long* codes, int codes_ld, int code_off, int last_pos_inc);
+int ar_build_prompt_rows(sva_batch* b, int slot, int R, float* x, int rows);
 int ar_prefill_slot(sva_batch* b, int slot, int R, bool tap_logits = false);
 int ar_delay_fill(sva_batch* b, const std::vector<int>& slots);
 int ar_delay_fill(sva_batch* b);

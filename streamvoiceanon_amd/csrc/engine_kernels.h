@@ -42,9 +42,6 @@ int launch_finish_reprefill(const ReprefillArgs& a, const float* codebook_emb, c
                             int d, int ncb, int cbsize, int D, int nspk, float* cached_ref_emb, int* last_pos, hipStream_t st);
 // dst [D] = table[code]
 int launch_put_row(const float* table, long long code, int D, float* dst, hipStream_t st);
-// the offline loop's frame input (one stream): x = [cached_audio_emb, content_emb[rem[step]]] at last_pos[0] + 1, + 2
-int launch_prepare_offline_step(const float* cached_audio_emb, const float* content_emb, const long long* rem, int step, const int* last_pos, int D,
-                                float* x, int* slot, int* pos, hipStream_t st);
 
 // ---- copies ----
 // dst[r] = src[r * src_stride + src_off ..] for r < rows (D floats)

@@ -270,16 +270,6 @@ __global__ void put_codes_kernel(const long long* __restrict__ src, int n_per, l
 __global__ void put_row_kernel(const float* __restrict__ table, long long code, int D, float* __restrict__ dst) {
     for (int i = threadIdx.x; i < D; i += blockDim.x) dst[i] = table[code * D + i];
 }
-__global__ void prepare_offline_step_kernel(const float* __restrict__ cached_audio_emb, const float* __restrict__ content_emb,
-                                            const long long* __restrict__ rem, int step, const int* __restrict__ last_pos, int D,
-                                            float* __restrict__ x, int* __restrict__ slot, int* __restrict__ pos) {
-    const long long code = rem[step];
-    for (int i = threadIdx.x; i < D; i += blockDim.x) {
-        x[i] = cached_audio_emb[i];
-        x[D + i] = content_emb[code * D + i];
-    }
-    if (threadIdx.x == 0) { slot[0] = 0; slot[1] = 0; pos[0] = last_pos[0] + 1; pos[1] = last_pos[0] + 2; }
-}
 
 __global__ void mean3_kernel(const float* __restrict__ y0, const float* __restrict__ y1, const float* __restrict__ y2, long y_bstride,
                              float* __restrict__ out, long o_bstride, long o_off, long n4) {
@@ -400,13 +390,6 @@ int launch_finish_reprefill(const ReprefillArgs& a, const float* codebook_emb, c
 int launch_put_row(const float* table, long long code, int D, float* dst, hipStream_t st) {
     SVA_CHECK(code >= 0 && D >= 1, "put_row: bad arguments");
     hipLaunchKernelGGL(put_row_kernel, dim3(1), dim3(256), 0, st, table, code, D, dst);
-    SVA_HIP(hipGetLastError());
-    return 0;
-}
-int launch_prepare_offline_step(const float* cached_audio_emb, const float* content_emb, const long long* rem, int step, const int* last_pos, int D,
-                                float* x, int* slot, int* pos, hipStream_t st) {
-    SVA_CHECK(step >= 0 && D >= 1, "prepare_offline_step: bad arguments");
-    hipLaunchKernelGGL(prepare_offline_step_kernel, dim3(1), dim3(256), 0, st, cached_audio_emb, content_emb, rem, step, last_pos, D, x, slot, pos);
     SVA_HIP(hipGetLastError());
     return 0;
 }

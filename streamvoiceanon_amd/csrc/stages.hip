@@ -449,8 +449,8 @@ int encode_incremental(sva_batch* b, const int* step_ptr, int n_chunk, int add, 
 // ---- A: slow / fast transformer passes ------------------------------------------------------------
 // rows [M, dim] in b->ax, slot/pos arrays on device; KV written at pos, attention over 0..pos
 // run_slot == -2: the rows are the decode frame's pairs (2 s, 2 s + 1) = positions (p, p + 1) of slot s: one attention workgroup per pair and head;
-// run_slot >= 0: the rows sit at CONSECUTIVE positions run_pos0 .. run_pos0 + M - 1 of that one slot (prompt prefill, re-prefill,
-// offline generate) -- their attention runs as the flash-style MFMA kernel instead of one workgroup per (head, row);
+// run_slot >= 0: the rows sit at CONSECUTIVE positions run_pos0 .. run_pos0 + M - 1 of that one slot (prompt prefill, re-prefill)
+// -- their attention runs as the flash-style MFMA kernel instead of one workgroup per (head, row);
 // runs != null: the rows are the prompt rows of SEVERAL slots, each run at consecutive positions of its slot (the offline batch's packed
 // prefill): the runs arm of that kernel, one launch per layer for the whole pass
 int ar_layers_pass(sva_batch* b, std::vector<TrLayer>& layers, int M, const int* d_slot, const int* d_pos, const float* rope,
@@ -771,6 +771,20 @@ int ar_frame_tail(sva_batch* b, int ci, long hid_stride, long hid_off, const lon
     return launch_ar_finish_frame(b->d_tok, ncb, b->d_last_pos, b->d_nframes, b->d_pred_hist, b->hist_cap, b->d_step_audio, chunk, ci, B, last_pos_inc, st);
 }
 
+// the first `rows` prompt rows of ONE slot into x: the slot's speaker prefix, then the R frames staged in d_prompt_cc / d_prompt_ac
+int ar_build_prompt_rows(sva_batch* b, int slot, int R, float* x, int rows) {
+    sva_engine* e = b->e;
+    const sva_config& c = e->cfg;
+    const int D = c.ar_dim, nspk = c.timbre_tokens + 1;
+    // speaker prefix: cat[context_in(timbre) (32 tok), style_in(style) (1 tok)]  (arvc_wrapper.py:108-109)
+    SVA_TRY(gemm_call(b, b->d_timbre + (long)slot * c.timbre_tokens * c.timbre_dim, (long)c.timbre_tokens * c.timbre_dim, 0, c.timbre_dim, 1,
+                      c.timbre_tokens, 1, 1, 1, c.timbre_dim, e->context_in, b->spk, (long)nspk * D, 0, D));
+    SVA_TRY(gemm_call(b, b->d_style + (long)slot * c.style_dim, c.style_dim, 0, c.style_dim, 1, 1, 1, 1, 1, c.style_dim, e->style_in,
+                      b->spk + (long)c.timbre_tokens * D, D, 0, D));
+    return launch_build_prompt(b->spk, nspk, e->content_emb, e->codebook_emb, e->wait4start, b->d_prompt_cc, b->d_prompt_ac, b->Pmax, R, b->p.delay,
+                               c.num_codebooks, c.codebook_size, D, x, rows, b->stream);
+}
+
 // prefill of ONE slot from prompt codes already staged in d_prompt_cc / d_prompt_ac (R frames)
 int ar_prefill_slot(sva_batch* b, int slot, int R, bool tap_logits) {
     sva_engine* e = b->e;
@@ -780,13 +794,7 @@ int ar_prefill_slot(sva_batch* b, int slot, int R, bool tap_logits) {
     const int M = nspk + 2 * R;
     SVA_CHECK(M <= b->Mmax && M <= c.max_seq_len, "prompt too long for the KV cache");
     SVA_CHECK(R > d, "prompt must be longer than the delay");
-    // speaker prefix: cat[context_in(timbre) (32 tok), style_in(style) (1 tok)]  (arvc_wrapper.py:108-109)
-    SVA_TRY(gemm_call(b, b->d_timbre + (long)slot * c.timbre_tokens * c.timbre_dim, (long)c.timbre_tokens * c.timbre_dim, 0, c.timbre_dim, 1,
-                      c.timbre_tokens, 1, 1, 1, c.timbre_dim, e->context_in, b->spk, (long)nspk * D, 0, D));
-    SVA_TRY(gemm_call(b, b->d_style + (long)slot * c.style_dim, c.style_dim, 0, c.style_dim, 1, 1, 1, 1, 1, c.style_dim, e->style_in,
-                      b->spk + (long)c.timbre_tokens * D, D, 0, D));
-    SVA_TRY(launch_build_prompt(b->spk, nspk, e->content_emb, e->codebook_emb, e->wait4start, b->d_prompt_cc, b->d_prompt_ac, b->Pmax, R, d, c.num_codebooks,
-                                c.codebook_size, D, b->ax, M, st));
+    SVA_TRY(ar_build_prompt_rows(b, slot, R, b->ax, M));
     // positions 0..M-1, all rows in this slot
     std::vector<int> hs(M, slot), hp(M);
     for (int i = 0; i < M; ++i) hp[i] = i;

@@ -1682,19 +1682,7 @@ extern "C" int sva_test_step_ops(int device, int kind, const long long* d, const
         SVA_HIP(hipDeviceSynchronize());
         return s.down(1, F * D);
     }
-    if (kind == 20) {          // prepare_offline_step
-        const long D = d[0], step = d[1], n_rem = d[2], n_rows = d[3];
-        SVA_HOOK_CHECK(D >= 1 && D <= 8192 && n_rem >= 1 && n_rem <= kStepMax && n_rows >= 1 && n_rows * D <= kStepMax && ptrs[2], "prepare_offline_step hook: sizes");
-        SVA_HOOK_REFUSE(step >= 0 && step < n_rem && all_in64((const long long*)ptrs[2], (size_t)n_rem, 0, n_rows), "prepare_offline_step hook: step / code outside their arrays");
-        SVA_TRY(s.up(4, F * 2 * D)); SVA_TRY(s.up(5, I * 2)); SVA_TRY(s.up(6, I * 2));
-        SVA_TRY(s.up(0, F * D)); SVA_TRY(s.up(1, F * n_rows * D)); SVA_TRY(s.up(2, L * n_rem)); SVA_TRY(s.up(3, I));
-        SVA_LAUNCH_OR_REFUSED(launch_prepare_offline_step(s.at<float>(0), s.at<float>(1), s.at<long long>(2), (int)step, s.at<int>(3), (int)D, s.at<float>(4), s.at<int>(5),
-                                                          s.at<int>(6), 0));
-        SVA_HIP(hipDeviceSynchronize());
-        SVA_TRY(s.down(4, F * 2 * D)); SVA_TRY(s.down(5, I * 2));
-        return s.down(6, I * 2);
-    }
-    if (kind == 21) {          // mean3
+    if (kind == 20) {          // mean3
         const long B = d[0], ybs = d[1], y_len = d[2], obs = d[3], o_off = d[4], o_len = d[5], n4 = d[6];
         SVA_HOOK_CHECK(B >= 1 && B <= 4096 && y_len >= 1 && y_len <= kStepMax && o_len >= 1 && o_len <= kStepMax, "mean3 hook: sizes");
         SVA_HOOK_REFUSE(n4 >= 1 && ybs >= 0 && obs >= 0 && o_off >= 0 && (B - 1) * ybs + 4 * n4 <= y_len && (B - 1) * obs + o_off + 4 * n4 <= o_len, "mean3 hook: lanes outside the arrays");
@@ -1703,7 +1691,7 @@ extern "C" int sva_test_step_ops(int device, int kind, const long long* d, const
         SVA_HIP(hipDeviceSynchronize());
         return s.down(3, F * o_len);
     }
-    SVA_HOOK_CHECK(kind == 22, "step ops hook: kind 0 .. 22");          // copy_tokens
+    SVA_HOOK_CHECK(kind == 21, "step ops hook: kind 0 .. 21");          // copy_tokens
     const long B = d[0], Ht = d[1], gap = d[2], c = d[3], T2 = d[4], D = d[5], tbs = d[6], t_len = d[7], dbs = d[8], d_len = d[9];
     SVA_HOOK_CHECK(B >= 1 && B <= 4096 && D >= 1 && D <= 8192 && t_len >= 1 && t_len <= kStepMax && d_len >= 1 && d_len <= kStepMax, "copy_tokens hook: sizes");
     SVA_HOOK_REFUSE(Ht >= 0 && gap >= 0 && c >= 1 && T2 >= Ht + c && Ht + c <= 65535 && tbs >= 0 && dbs >= 0 && (B - 1) * tbs + (Ht + gap + c) * D <= t_len && (B - 1) * dbs + T2 * D <= d_len,

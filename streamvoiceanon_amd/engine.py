@@ -926,8 +926,7 @@ def test_gemv(W, Y, M, N, K, X=None, ldx=None, ldy=None, y_off=0, norm_w=None, b
 
 STEP_OPS = {"ar_prepare_step": 0, "apply_forced": 1, "ar_finish_frame": 2, "append_content": 3, "put_codes": 4, "build_prompt": 5, "build_delayfill": 6,
             "build_reprefill": 7, "finish_reprefill": 8, "copy_rows": 9, "copy_rows2": 10, "broadcast_row": 11, "fill_rows": 12, "inc": 13, "add_list": 14,
-            "add_vec": 15, "set_slot_i32": 16, "history_rows_copy": 17, "history_rows_move": 18, "put_row": 19, "prepare_offline_step": 20, "mean3": 21,
-            "copy_tokens": 22}          # kernel of csrc/engine_kernels.hip -> kind of sva_test_step_ops
+            "add_vec": 15, "set_slot_i32": 16, "history_rows_copy": 17, "history_rows_move": 18, "put_row": 19, "mean3": 20, "copy_tokens": 21}          # kernel of csrc/engine_kernels.hip -> kind of sva_test_step_ops
 
 
 def test_step_op(name, desc, arrays, device=0):

@@ -29,7 +29,6 @@ ARRAYS = {
     "copy_rows": ("src", "dst"), "copy_rows2": ("src", "dst1", "dst2"), "broadcast_row": ("p",), "fill_rows": ("p", "src"),
     "inc": ("p",), "add_list": ("p", "list"), "add_vec": ("p",), "set_slot_i32": ("p",),
     "history_rows_copy": ("live", "save"), "history_rows_move": ("src", "dst"), "put_row": ("table", "dst"),
-    "prepare_offline_step": ("cached_audio_emb", "content_emb", "rem", "last_pos", "x", "slot", "pos"),
     "mean3": ("y0", "y1", "y2", "out"), "copy_tokens": ("tok", "d2c"),
 }
 
@@ -171,7 +170,7 @@ def reprefill_cases():
 
 
 def frame_cases():
-    """ar_prepare_step, apply_forced, put_row, prepare_offline_step"""
+    """ar_prepare_step, apply_forced, put_row"""
     out = []
     for B, D, chunk, ci in [(1, 1024, 1, 0), (3, 300, 3, 2), (65, 257, 2, 1)]:
         rng = np.random.default_rng(300 + B)
@@ -194,9 +193,6 @@ def frame_cases():
         rng = np.random.default_rng(D)
         ce = _tables(rng, D, 1)[0]
         out.append(_case("put_row", "D %d code %d" % (D, code), [NC, code, D], [ce, np.full(D, SENT, F32)], (1,), {1: ce[code]}))
-        rem, lp, cae = rng.integers(0, NC, 5).astype(I64), np.array([77], I32), rng.standard_normal(D).astype(F32)
-        out.append(_case("prepare_offline_step", "D %d step 3" % D, [D, 3, 5, NC], [cae, ce, rem, lp, np.full((2, D), SENT, F32), np.full(2, ISENT, I32), np.full(2, ISENT, I32)],
-                         (4, 5, 6), {4: np.stack([cae, ce[rem[3]]]), 5: [0, 0], 6: [78, 79]}))
     return out
 
 
@@ -350,8 +346,6 @@ def validate(c):
         assert ncb <= 8 and 0 <= cb < ncb and 0 <= ci < chunk and a[1].shape == (B, ncb, chunk)
     elif op == "put_row":
         assert 0 <= d[1] < d[0] and a[0].shape == (d[0], d[2])
-    elif op == "prepare_offline_step":
-        assert 0 <= d[1] < d[2] and _within(a[2], 0, d[3])
     elif op in ("copy_rows", "copy_rows2"):
         rows, D, stride, off, n = d
         assert off + (rows - 1) * stride + D <= n == a[0].size

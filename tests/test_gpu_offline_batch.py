@@ -329,7 +329,61 @@ def test_refusals_change_nothing(eng, weights0):
         np.testing.assert_array_equal(after[k], first[k])
 
 
-# ---- 7. infer_many end to end -------------------------------------------------------------------------------------------------------------
+# ---- 7. a source as long as the prediction history ----------------------------------------------------------------------------------------
+def _batch_with_hist_cap(engine, B, cap):
+    """a batch whose history rings hold `cap` frames (SVA_DEBUG hist_cap, read at batch creation; the default is back before anything runs);
+    with buffer_frames = 16 the batch's own rule buffer_frames + delay + chunk < hist_cap admits no ring below 32"""
+    from streamvoiceanon_amd import engine as E
+
+    lib = E.load_library()
+    assert lib.sva_debug_configure(("hist_cap=%d" % cap).encode()) == 0
+    try:
+        return E.Batch(engine, n_streams=B, delay=DELAY, buffer_frames=16)
+    finally:
+        lib.sva_debug_configure(b"hist_cap=4096")
+
+
+def test_source_as_long_as_the_history(eng):
+    """S == hist_cap is legal for both entries (a slot parks in column S_i only while a longer one runs, and S_max <= hist_cap): a 32-frame source
+    on 32-column rings, alone and next to a 5-frame slot that parks beside the full ring, gives the codes of the default rings; 33 frames are
+    refused by both entries and change nothing"""
+    CAP = 32
+    prompts = [_prompt(2301, 24), _prompt(2314, 24)]
+    useeds = [881, 894]
+    sources = [_src_codes(CAP), _src_codes(5)]
+    too_long = _src_codes(CAP + 1)
+    noise = _noise_block(useeds, CAP + 1)
+    cc, ac, style, timbre = prompts[0]
+    got = {}
+    for cap in (4096, CAP):
+        b = _batch_with_hist_cap(eng, 1, cap)
+        try:
+            one = b.generate(cc, ac, sources[0], style, timbre, noise=noise[:CAP, 0])
+            if cap == CAP:
+                with pytest.raises(RuntimeError, match="prediction history"):
+                    b.generate(cc, ac, too_long, style, timbre, noise=noise[:, 0])
+                np.testing.assert_array_equal(b.generate(cc, ac, sources[0], style, timbre, noise=noise[:CAP, 0]), one)
+        finally:
+            b.close()
+        b = _batch_with_hist_cap(eng, 2, cap)
+        try:
+            many = b.generate_many(prompts, sources, noise_seeds=useeds, noise=noise[:CAP])
+            if cap == CAP:
+                with pytest.raises(RuntimeError, match="prediction history"):
+                    b.generate_many(prompts, [too_long, sources[1]], noise_seeds=useeds, noise=noise)
+                again = b.generate_many(prompts, sources, noise_seeds=useeds, noise=noise[:CAP])
+                for k in range(2):
+                    np.testing.assert_array_equal(again[k], many[k], err_msg="slot %d after the refusal" % k)
+        finally:
+            b.close()
+        got[cap] = (one, many)
+    assert got[CAP][0].shape == (8, CAP) and got[CAP][1][0].shape == (8, CAP) and got[CAP][1][1].shape == (8, 5)
+    np.testing.assert_array_equal(got[CAP][0], got[4096][0])
+    for k in range(2):
+        np.testing.assert_array_equal(got[CAP][1][k], got[4096][1][k], err_msg="slot %d" % k)
+
+
+# ---- 8. infer_many end to end -------------------------------------------------------------------------------------------------------------
 def test_infer_many_equals_infer_alone(wrap, record_property):
     from streamvoiceanon_amd import engine as E
     from streamvoiceanon_amd.stream_pool import plan_offline_waves

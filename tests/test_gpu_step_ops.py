@@ -1,4 +1,4 @@
-"""The glue of the chunk step, kernel by kernel: the 23 bookkeeping kernels of csrc/engine_kernels.hip through their launchers (hook
+"""The glue of the chunk step, kernel by kernel: the 22 bookkeeping kernels of csrc/engine_kernels.hip through their launchers (hook
 sva_test_step_ops: the grid and block size the engine uses) and the fused HiFiGAN level voc_level_kernel<16 | 32> through launch_voc_level (hook
 sva_test_voc_level), against the references of tests/kernel_refs.py, which tests/test_kernel_refs.py pins to the oracle on the CPU.
 

@@ -18,7 +18,7 @@ MANIFEST = {
     **{k + "_kernel": (STEP, "test_step_op") for k in (
         "ar_prepare_step", "apply_forced", "ar_finish_frame", "append_content", "put_codes", "build_prompt", "build_delayfill", "build_reprefill",
         "finish_reprefill", "copy_rows", "copy_rows2", "broadcast_row", "fill_rows", "inc", "add_list", "add_vec", "set_slot_i32", "history_rows_copy",
-        "history_rows_move", "put_row", "prepare_offline_step", "mean3", "copy_tokens")},
+        "history_rows_move", "put_row", "mean3", "copy_tokens")},
     "voc_level_kernel": (STEP, "test_voc_level"),
     # the persistent decode kernels: whole frames inside the engine, every output against the float64 frame of ar_frame_ref.py
     "ar_decode_kernel": ("test_gpu_ar_frame.py", "test_decode_frames_match_fp64", IN_SITU),
@@ -124,7 +124,7 @@ def test_every_kernel_has_a_test_that_names_its_hook():
 
 
 def test_step_ops_hook_covers_every_kernel_of_engine_kernels():
-    """the 23 kernels of engine_kernels.hip are the kinds of sva_test_step_ops, one launcher each, and no other file launches them"""
+    """the 22 kernels of engine_kernels.hip are the kinds of sva_test_step_ops, one launcher each, and no other file launches them"""
     from streamvoiceanon_amd import engine as E
     found = kernels_in_source()
     mine = sorted(k[:-len("_kernel")] for k, fn in found.items() if fn == "engine_kernels.hip")
