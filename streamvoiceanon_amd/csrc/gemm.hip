@@ -10,6 +10,8 @@
 // next tile's global loads are issued before the current tile's MFMAs and written to the other
 // LDS buffer after them (one barrier per K tile).
 #include "sva_common.h"
+#include "gemm_epilogue.h"
+#include "gemm_stream_common.h"
 #include <mutex>
 #include <unordered_map>
 
@@ -18,9 +20,6 @@ namespace sva {
 constexpr int KS_ERR_WORD = (1 << 16) - 1;      // last word of a stream's split-K arrival counters: set when a partial never arrived
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float silu_f(float x) { return x / (1.f + __expf(-x)); }
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 
 template <int BM, int BN, int WM, int WN, int BK>
 __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_kernel(const ConvGemmGroup gg) {
@@ -98,7 +97,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_kernel(const ConvGemmG
         for (int i = 0; i < A_LD; ++i)
             if (a_on[i]) {
                 float4 v = ra[i];
-                if (g.a_silu) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
+                if (g.a_silu) v = epi::silu_of(v);
                 *reinterpret_cast<float4*>(As + ((buf * BM + lrow + i * RPP) * LS + kq * 4)) = v;
             }
 #pragma unroll
@@ -148,71 +147,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_kernel(const ConvGemmG
         __syncthreads();
     }
 
-    // ---- epilogue ----
-    // The accumulators (C/D layout of the 16x16 MFMA: col = lane & 15, row = (lane >> 4) * 4 + reg) are staged
-    // through LDS so that bias / residual reads and the C stores are whole 16-byte, row-contiguous accesses
-    // (a lane-per-element epilogue touches a 64-byte segment per row per instruction and costs up to 30 % of a
-    // K = 512 GEMM).  The last loop iteration ended with a barrier, so the A/B buffers are free to reuse.
-    constexpr int CS = BN + 4;
-    float* Cs = smem;                              // [BM][CS]
-    const int col = lane & 15, rq = (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Cs[(wm * TM + i * 16 + rq + r) * CS + wn * TN + j * 16 + col] = acc[i][j][r];
-    __syncthreads();
-    if (g.w13) {
-        // SwiGLU: tile columns alternate 16 x w1 | 16 x w3; output column (n0 >> 1) + c
-        constexpr int OC4 = BN / 8;                // float4 chunks of output per row
-        for (int idx = tid; idx < BM * OC4; idx += NTH) {
-            const int row = idx / OC4, q = idx - row * OC4;
-            const int m = bm0 + row;
-            const int grp = q >> 2, c4 = (q & 3) * 4;       // 16-wide group, offset inside it
-            const int n = bn0 + grp * 32 + c4;              // w1 column
-            if (m >= g.M || n >= g.N) continue;
-            const int b = m / g.T, t = m - b * g.T;
-            if (t >= g.skip_lo && t < g.skip_hi) continue;
-            const float4 a = *reinterpret_cast<const float4*>(&Cs[row * CS + grp * 32 + c4]);
-            const float4 w = *reinterpret_cast<const float4*>(&Cs[row * CS + grp * 32 + 16 + c4]);
-            float4 o;
-            o.x = silu_f(a.x) * w.x; o.y = silu_f(a.y) * w.y; o.z = silu_f(a.z) * w.z; o.w = silu_f(a.w) * w.w;
-            float* crow = g.C + (long)b * g.c_bstride + g.c_off + (long)t * g.ldc;
-            *reinterpret_cast<float4*>(crow + ((bn0 + grp * 32) >> 1) + c4) = o;
-        }
-        return;
-    }
-    constexpr int C4 = BN / 4;
-    for (int idx = tid; idx < BM * C4; idx += NTH) {
-        const int row = idx / C4, c4 = (idx - row * C4) * 4;
-        const int m = bm0 + row, n = bn0 + c4;
-        if (m >= g.M || n >= g.N) continue;
-        const int b = m / g.T, t = m - b * g.T;
-        if (t >= g.skip_lo && t < g.skip_hi) continue;
-        float4 v = *reinterpret_cast<const float4*>(&Cs[row * CS + c4]);
-        if (g.bias) {
-            const float4 bb = *reinterpret_cast<const float4*>(g.bias + n);
-            v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
-        }
-        if (g.act == ACT_GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
-        else if (g.act == ACT_LOGCLAMP) { v.x = __logf(fmaxf(v.x, 1e-5f)); v.y = __logf(fmaxf(v.y, 1e-5f)); v.z = __logf(fmaxf(v.z, 1e-5f)); v.w = __logf(fmaxf(v.w, 1e-5f)); }
-        if (g.gamma) {
-            const float4 gg = *reinterpret_cast<const float4*>(g.gamma + n);
-            v.x *= gg.x; v.y *= gg.y; v.z *= gg.z; v.w *= gg.w;
-        }
-        if (g.res) {
-            const float4 rr = *reinterpret_cast<const float4*>(g.res + (long)b * g.r_bstride + g.r_off + (long)t * g.ldr + n);
-            v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
-        }
-        v.x *= g.scale; v.y *= g.scale; v.z *= g.scale; v.w *= g.scale;
-        float* cp = g.C + (long)b * g.c_bstride + g.c_off + (long)t * g.ldc + n;
-        if (g.accumulate) {
-            const float4 cc = *reinterpret_cast<const float4*>(cp);
-            v.x += cc.x; v.y += cc.y; v.z += cc.z; v.w += cc.w;
-        }
-        *reinterpret_cast<float4*>(cp) = v;
-    }
+    // ---- epilogue: staged through LDS (gemm_epilogue.h); the last loop iteration ended with a barrier, so the A/B buffers are free to reuse ----
+    epi::tile_epilogue<BM, BN, NTH>(g, smem, acc, true, wm * TM, wn * TN, bm0, bn0, [](float x) { return x; }, [](int) { return 1.f; }, epi::Store16{g.C});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -312,9 +248,8 @@ __global__ __launch_bounds__(64 * KW) void skinny_gemm_kernel(const ConvGemmGrou
     // hipcc drain vmcnt(0) at the join): out-of-range blocks re-load the wave's last valid block and are masked.
     // this workgroup's share of the K blocks (grid-level split), interleaved over its waves
     const int kb_lo = (int)((long)ks * nk / Z), kb_hi = (int)((long)(ks + 1) * nk / Z);
-    const int nk_loc = kb_hi - kb_lo;
-    const int my_n = nk_loc > wave ? (nk_loc - wave + KW - 1) / KW : 0;          // K blocks owned by this wave
-    const int last_kb = my_n > 0 ? kb_lo + wave + (my_n - 1) * KW : kb_lo;
+    int my_n, last_kb;                                                           // K blocks owned by this wave
+    wstream::wave_blocks<KW>(kb_lo, kb_hi, wave, my_n, last_kb);
     auto kbq = [&](int q) { return kb_lo + wave + q * KW; };
     float4 wv[D][NT], av[D][MT], nv[D];
     float ssq[MT];
@@ -350,7 +285,7 @@ __global__ __launch_bounds__(64 * KW) void skinny_gemm_kernel(const ConvGemmGrou
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 a[i] = av[d][i];
-                if (SILU) { a[i].x = silu_f(a[i].x); a[i].y = silu_f(a[i].y); a[i].z = silu_f(a[i].z); a[i].w = silu_f(a[i].w); }
+                if (SILU) a[i] = epi::silu_of(a[i]);
                 a[i].x *= keep; a[i].y *= keep; a[i].z *= keep; a[i].w *= keep;
                 if (RMS) {
                     // explicit sequential fmas: under -ffp-contract the pairwise form was fused differently per unrolled row tile (gemm_stream.hip), so a row's statistic depended on its position
@@ -403,18 +338,16 @@ __global__ __launch_bounds__(64 * KW) void skinny_gemm_kernel(const ConvGemmGrou
     auto epilogue = [&](int i, f32x4 (&t)[NT]) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int m = m_base + i * 16 + rq + r;
-            if (m >= g.M) continue;
-            const int b = m / g.T, tt = m - b * g.T;
-            if (tt >= g.skip_lo && tt < g.skip_hi) continue;
-            float* crow = g.C + (long)b * g.c_bstride + g.c_off + (long)tt * g.ldc;
-            const float* rrow = g.res ? g.res + (long)b * g.r_bstride + g.r_off + (long)tt * g.ldr : nullptr;
+            int b, tt;
+            if (!epi::out_row(g, m_base + i * 16 + rq + r, b, tt)) continue;
+            float* crow = g.C + epi::c_row(g, b, tt);
+            const float* rrow = g.res ? g.res + epi::r_row(g, b, tt) : nullptr;
             if (g.w13) {
                 if constexpr (NT % 2 == 0) {          // column tiles come in (gate, up) pairs
 #pragma unroll
                     for (int jp = 0; jp < NT / 2; ++jp) {
                         const int n = n0 + jp * 32 + col;
-                        if (n < g.N) crow[(n0 >> 1) + jp * 16 + col] = silu_f(t[2 * jp][r]) * t[2 * jp + 1][r];
+                        if (n < g.N) crow[(n0 >> 1) + jp * 16 + col] = epi::swiglu(t[2 * jp][r], t[2 * jp + 1][r]);
                     }
                 }
             } else {
@@ -422,15 +355,8 @@ __global__ __launch_bounds__(64 * KW) void skinny_gemm_kernel(const ConvGemmGrou
                 for (int j = 0; j < NT; ++j) {
                     const int n = n0 + j * 16 + col;
                     if (n >= g.N) continue;
-                    float v = t[j][r];
-                    if (g.bias) v += g.bias[n];
-                    if (g.act == ACT_GELU) v = gelu_erf(v);
-                    else if (g.act == ACT_LOGCLAMP) v = __logf(fmaxf(v, 1e-5f));
-                    if (g.gamma) v *= g.gamma[n];
-                    if (rrow) v += rrow[n];
-                    v *= g.scale;
-                    if (g.accumulate) v += crow[n];
-                    crow[n] = v;
+                    crow[n] = epi::value<false>(t[j][r], g.act, g.scale, g.bias != nullptr, [&] { return g.bias[n]; }, g.gamma != nullptr, [&] { return g.gamma[n]; },
+                                                rrow != nullptr, [&] { return rrow[n]; }, g.accumulate != 0, [&] { return crow[n]; });
                 }
             }
         }
@@ -440,10 +366,7 @@ __global__ __launch_bounds__(64 * KW) void skinny_gemm_kernel(const ConvGemmGrou
         f32x4 t[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            f32x4 s = *reinterpret_cast<const f32x4*>(&red[((i * NT + j) * 64 + lane) * 4]);
-#pragma unroll
-            for (int w = 1; w < KW; ++w) s += *reinterpret_cast<const f32x4*>(&red[((w * (MT * NT) + i * NT + j) * 64 + lane) * 4]);
-            t[j] = s;
+            t[j] = wstream::tile_sum<MT, NT, KW, KW>(red, i, j, lane);
         }
         if (RMS) {
 #pragma unroll
@@ -588,10 +511,7 @@ static int launch_skinny_op(const ConvGemmGroup& gin, int z, hipStream_t st) {
         grid.z = Z;
     }
     static DeviceOnce attr;
-    if (attr.needed() && smem > 48 * 1024) {
-        SVA_HIP(hipFuncSetAttribute((const void*)skinny_gemm_kernel<MT, NT, KW, D, AOP>, hipFuncAttributeMaxDynamicSharedMemorySize, 132 * 1024));
-        attr.done();
-    }
+    if (smem > 48 * 1024) SVA_TRY_RC(attr.max_dynamic_lds((const void*)skinny_gemm_kernel<MT, NT, KW, D, AOP>, 132 * 1024));
     hipLaunchKernelGGL((skinny_gemm_kernel<MT, NT, KW, D, AOP>), grid, dim3(64 * KW), smem, st, gg);
     return 0;
 }
@@ -649,10 +569,7 @@ static int launch_t(const ConvGemmGroup& gin, hipStream_t st) {
     constexpr size_t smem_c = (size_t)BM * (BN + 4) * sizeof(float);          // epilogue staging tile reuses the buffers
     constexpr size_t smem = smem_ab > smem_c ? smem_ab : smem_c;
     static DeviceOnce attr_set;
-    if (attr_set.needed() && smem > 48 * 1024) {
-        SVA_HIP(hipFuncSetAttribute((const void*)conv_gemm_kernel<BM, BN, WM, WN, BK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set.done();
-    }
+    if (smem > 48 * 1024) SVA_TRY_RC(attr_set.max_dynamic_lds((const void*)conv_gemm_kernel<BM, BN, WM, WN, BK>, 160 * 1024));
     ConvGemmGroup gg = gin;
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, gg.n);
     gg.xcd_swz = xcd_swizzle_for(grid.x, grid.y);

@@ -12,6 +12,7 @@
 // Prologue: RMSNorm of the A rows folded in (weight into the operand, 1 / rms applied to the accumulators).  Epilogues: residual
 // add, SwiGLU over (gate, up) column-tile pairs, bias.
 #include "sva_common.h"
+#include "gemm_epilogue.h"
 
 namespace sva {
 namespace {
@@ -19,8 +20,6 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float silu_f(float x) { return x / (1.f + __expf(-x)); }
 
 // eight fp32 -> (hi, lo) fp16 fragments with hi + lo == x to 2^-22 relative (RNE conversions, exact fp32 residuals)
 __device__ __forceinline__ void split8(const float4& a, const float4& b, f16x8& hi, f16x8& lo) {
@@ -197,7 +196,7 @@ __global__ __launch_bounds__(64 * KW) void f16w_gemm_kernel(const ConvGemm g, co
 #pragma unroll
                     for (int jp = 0; jp < NT / 2; ++jp) {
                         const int n = n0 + jp * 32 + col;
-                        if (n < g.N) crow[(n0 >> 1) + jp * 16 + col] = silu_f(t[2 * jp][r]) * t[2 * jp + 1][r];
+                        if (n < g.N) crow[(n0 >> 1) + jp * 16 + col] = epi::swiglu(t[2 * jp][r], t[2 * jp + 1][r]);
                     }
                 }
             } else {

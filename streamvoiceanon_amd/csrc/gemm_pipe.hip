@@ -14,15 +14,13 @@
 // the other kernels -- touch 16 distinct chunk positions per 16 lanes: conflict-free.
 #include "sva_common.h"
 #include "device_util.h"
+#include "gemm_epilogue.h"
 
 namespace sva {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ __forceinline__ float silu_p(float x) { return x / (1.f + __expf(-x)); }
-__device__ __forceinline__ float gelu_p(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 
 template <int BM, int BN, int RS, int PRO>
 __global__ __launch_bounds__(256) void pipe_gemm_kernel(const ConvGemmGroup gg) {
@@ -110,7 +108,7 @@ __global__ __launch_bounds__(256) void pipe_gemm_kernel(const ConvGemmGroup gg) 
             for (int j = 0; j < NI; ++j) bf[j] = *reinterpret_cast<const float4*>(Bb + j * 16 * BK + pos);
             if constexpr (PRO == 1) {
 #pragma unroll
-                for (int i = 0; i < MI; ++i) { af[i].x = silu_p(af[i].x); af[i].y = silu_p(af[i].y); af[i].z = silu_p(af[i].z); af[i].w = silu_p(af[i].w); }
+                for (int i = 0; i < MI; ++i) af[i] = epi::silu_of(af[i]);
             }
             if constexpr (PRO == 2) {         // fused RMSNorm (taps == 1): row statistics of the raw rows, weight folded into the operand
                 const float4 nw = *reinterpret_cast<const float4*>(nws + kc + kb * 16 + 4 * fk);
@@ -178,17 +176,8 @@ __global__ __launch_bounds__(256) void pipe_gemm_kernel(const ConvGemmGroup gg) 
 #undef PIPE_LOAD
     __syncthreads();                 // all fragment reads done: the ring is reused as the epilogue staging tile
 
-    // ---- epilogue (same as conv_gemm_kernel: accumulators staged through LDS, 16-byte row-contiguous stores) ----
-    constexpr int CS = BN + 4;
-    float* Cs = smem;                              // [BM][CS]
-    float* rs = smem + BM * CS;                    // [BM] row sums of squares (fused RMSNorm)
-    const int col = lane & 15, rq = (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Cs[(wm * TM + i * 16 + rq + r) * CS + wn * TN + j * 16 + col] = acc[i][j][r];
+    // ---- epilogue: staged through LDS (gemm_epilogue.h), with the row factor of the fused RMSNorm ----
+    float* rs = smem + BM * (BN + 4);              // [BM] row sums of squares, behind the staging tile
     if (PRO == 2 && wn == 0) {
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
@@ -198,64 +187,11 @@ __global__ __launch_bounds__(256) void pipe_gemm_kernel(const ConvGemmGroup gg) 
             if (fk == 0) rs[wm * TM + i * 16 + fr] = v;
         }
     }
-    __syncthreads();
-    if (g.w13) {
-        constexpr int OC4 = BN / 8;
-        for (int idx = tid; idx < BM * OC4; idx += 256) {
-            const int row = idx / OC4, q = idx - row * OC4;
-            const int m = bm0 + row;
-            const int grp = q >> 2, c4 = (q & 3) * 4;
-            const int n = bn0 + grp * 32 + c4;
-            if (m >= g.M || n >= g.N) continue;
-            const int b = m / g.T, t = m - b * g.T;
-            if (t >= g.skip_lo && t < g.skip_hi) continue;
-            float4 a = *reinterpret_cast<const float4*>(&Cs[row * CS + grp * 32 + c4]);
-            float4 w = *reinterpret_cast<const float4*>(&Cs[row * CS + grp * 32 + 16 + c4]);
-            if constexpr (PRO == 2) {
-                const float inv = 1.f / sqrtf(rs[row] / (float)Kt + g.rms_eps);
-                a.x *= inv; a.y *= inv; a.z *= inv; a.w *= inv; w.x *= inv; w.y *= inv; w.z *= inv; w.w *= inv;
-            }
-            float4 o;
-            o.x = silu_p(a.x) * w.x; o.y = silu_p(a.y) * w.y; o.z = silu_p(a.z) * w.z; o.w = silu_p(a.w) * w.w;
-            float* crow = g.C + (long)b * g.c_bstride + g.c_off + (long)t * g.ldc;
-            *reinterpret_cast<float4*>(crow + ((bn0 + grp * 32) >> 1) + c4) = o;
-        }
-        return;
-    }
-    constexpr int C4 = BN / 4;
-    for (int idx = tid; idx < BM * C4; idx += 256) {
-        const int row = idx / C4, c4 = (idx - row * C4) * 4;
-        const int m = bm0 + row, n = bn0 + c4;
-        if (m >= g.M || n >= g.N) continue;
-        const int b = m / g.T, t = m - b * g.T;
-        if (t >= g.skip_lo && t < g.skip_hi) continue;
-        float4 v = *reinterpret_cast<const float4*>(&Cs[row * CS + c4]);
-        if constexpr (PRO == 2) {
-            const float inv = 1.f / sqrtf(rs[row] / (float)Kt + g.rms_eps);
-            v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv;
-        }
-        if (g.bias) {
-            const float4 bb = *reinterpret_cast<const float4*>(g.bias + n);
-            v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
-        }
-        if (g.act == ACT_GELU) { v.x = gelu_p(v.x); v.y = gelu_p(v.y); v.z = gelu_p(v.z); v.w = gelu_p(v.w); }
-        else if (g.act == ACT_LOGCLAMP) { v.x = __logf(fmaxf(v.x, 1e-5f)); v.y = __logf(fmaxf(v.y, 1e-5f)); v.z = __logf(fmaxf(v.z, 1e-5f)); v.w = __logf(fmaxf(v.w, 1e-5f)); }
-        if (g.gamma) {
-            const float4 gm = *reinterpret_cast<const float4*>(g.gamma + n);
-            v.x *= gm.x; v.y *= gm.y; v.z *= gm.z; v.w *= gm.w;
-        }
-        if (g.res) {
-            const float4 rr = *reinterpret_cast<const float4*>(g.res + (long)b * g.r_bstride + g.r_off + (long)t * g.ldr + n);
-            v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
-        }
-        v.x *= g.scale; v.y *= g.scale; v.z *= g.scale; v.w *= g.scale;
-        float* cp = g.C + (long)b * g.c_bstride + g.c_off + (long)t * g.ldc + n;
-        if (g.accumulate) {
-            const float4 cc = *reinterpret_cast<const float4*>(cp);
-            v.x += cc.x; v.y += cc.y; v.z += cc.z; v.w += cc.w;
-        }
-        *reinterpret_cast<float4*>(cp) = v;
-    }
+    auto row_scale = [&](int row) {
+        if constexpr (PRO == 2) return 1.f / sqrtf(rs[row] / (float)Kt + g.rms_eps);
+        else return 1.f;
+    };
+    epi::tile_epilogue<BM, BN, 256>(g, smem, acc, true, wm * TM, wn * TN, bm0, bn0, [](float x) { return x; }, row_scale, epi::Store16{g.C});
 }
 
 template <int BM, int BN, int RS, int PRO>
@@ -266,10 +202,7 @@ int launch_pipe_p(const ConvGemmGroup& gg_in, hipStream_t st) {
     constexpr size_t smem = ring > epi ? ring : epi;
     static_assert(smem <= 160 * 1024, "LDS");
     static DeviceOnce attr;
-    if (attr.needed()) {
-        SVA_HIP(hipFuncSetAttribute((const void*)pipe_gemm_kernel<BM, BN, RS, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr.done();
-    }
+    SVA_TRY_RC(attr.max_dynamic_lds((const void*)pipe_gemm_kernel<BM, BN, RS, PRO>, smem));
     const ConvGemm& g = gg.g[0];
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, gg.n);
     gg.xcd_swz = xcd_swizzle_for(grid.x, grid.y);

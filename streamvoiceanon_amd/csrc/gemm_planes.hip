@@ -35,6 +35,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "gemm_epilogue.h"
 #include "planes_split.h"
 #include "sva_common.h"
 
@@ -50,9 +51,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float silu_f(float x) { return x / (1.f + __expf(-x)); }
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 
 template <int MODE> struct PM;
 template <> struct PM<PLANES_H3> { static constexpr int NPL = 2; };
@@ -193,8 +191,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 && BM > 128) ? 1 : 2) vo
                 } else {
                     f32x4 v0 = __builtin_bit_cast(f32x4, r.a[kb][i][0]), v1 = __builtin_bit_cast(f32x4, r.a[kb][i][1]);
                     if (g_silu) {
-                        v0.x = silu_f(v0.x); v0.y = silu_f(v0.y); v0.z = silu_f(v0.z); v0.w = silu_f(v0.w);
-                        v1.x = silu_f(v1.x); v1.y = silu_f(v1.y); v1.z = silu_f(v1.z); v1.w = silu_f(v1.w);
+                        v0 = epi::silu_of(v0);
+                        v1 = epi::silu_of(v1);
                     }
                     split8<MODE>(v0, v1, o);
                 }
@@ -269,26 +267,14 @@ k_done:
     __syncthreads();
 
     if (dbg & 8) { if (acc[0][0][0] == 123.456f) g.C[0] = 1.f; return; }
-    // ---- epilogue (as conv_gemm_kernel / split_gemm_kernel: accumulators staged through LDS for whole 16-byte row accesses) ----
-    constexpr int CS = BN + 4;
-    float* Cs = smem;                              // [BM][CS]
-    const int col = lane & 15, rq = (lane >> 4) * 4;
+    // ---- epilogue: staged through LDS (gemm_epilogue.h) with the weights' 2^-e; the store also writes the output's planes ----
     const float winv = g.wp_inv;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Cs[(wm * TM + i * 16 + rq + r) * CS + wn * TN + j * 16 + col] = acc[i][j][r] * winv;
-    __syncthreads();
     const long c_rows_b = g.ldc ? g.c_bstride / g.ldc : 0, c_row0 = g.ldc ? g.c_off / g.ldc : 0;
-    auto store4 = [&](const float4& v, long idx, int b_, int t_, int n_) {
-        {
-            // fp16 parts have fp16's range: an operand beyond +-65504 turns into inf and the output into inf / nan.  The reference
-            // (torch.autocast(fp16)) has the same limit; here it is REPORTED (sva_sync fails, naming mm_mode = 0) instead of propagating
-            if (g.ovf && !(fabsf(v.x) + fabsf(v.y) + fabsf(v.z) + fabsf(v.w) < INFINITY)) *reinterpret_cast<volatile int*>(g.ovf) = 1;
-        }
-        if (g.C) *reinterpret_cast<float4*>(g.C + idx) = v;
+    auto store4 = [&](const f32x4& v, long idx, int b_, int t_, int n_) {
+        // fp16 parts have fp16's range: an operand beyond +-65504 turns into inf and the output into inf / nan.  The reference
+        // (torch.autocast(fp16)) has the same limit; here it is REPORTED (sva_sync fails, naming mm_mode = 0) instead of propagating
+        if (g.ovf && !(fabsf(v.x) + fabsf(v.y) + fabsf(v.z) + fabsf(v.w) < INFINITY)) *reinterpret_cast<volatile int*>(g.ovf) = 1;
+        if (g.C) *reinterpret_cast<f32x4*>(g.C + idx) = v;
         if (g.Cp) {
             unsigned p0[NPL], p1[NPL];
             split_pair<MODE>(v.x, v.y, p0);
@@ -298,59 +284,7 @@ k_done:
             for (int p = 0; p < NPL; ++p) *reinterpret_cast<u32x2*>(g.Cp + (long)p * g.cp_pstride + po) = (u32x2){p0[p], p1[p]};
         }
     };
-    if (g.w13) {
-        // SwiGLU: tile columns alternate 16 x w1 | 16 x w3; output column (n0 >> 1) + c
-        constexpr int OC4 = BN / 8;                // float4 chunks of output per row
-        const int eb0w = bm0 / g.T, et0w = bm0 - eb0w * g.T;
-        for (int idx = tid; idx < BM * OC4; idx += NTH) {
-            const int row = idx / OC4, q = idx - row * OC4;
-            const int m = bm0 + row;
-            const int grp = q >> 2, c4 = (q & 3) * 4;       // 16-wide group, offset inside it
-            const int n = bn0 + grp * 32 + c4;              // w1 column
-            if (m >= g.M || n >= g.N) continue;
-            int b = eb0w, t = et0w + row;
-            if (t >= g.T) { t -= g.T; ++b; if (t >= g.T) { b += t / g.T; t %= g.T; } }
-            if (t >= g.skip_lo && t < g.skip_hi) continue;
-            const float4 a = *reinterpret_cast<const float4*>(&Cs[row * CS + grp * 32 + c4]);
-            const float4 w = *reinterpret_cast<const float4*>(&Cs[row * CS + grp * 32 + 16 + c4]);
-            float4 o;
-            o.x = silu_f(a.x) * w.x; o.y = silu_f(a.y) * w.y; o.z = silu_f(a.z) * w.z; o.w = silu_f(a.w) * w.w;
-            store4(o, (long)b * g.c_bstride + g.c_off + (long)t * g.ldc + ((bn0 + grp * 32) >> 1) + c4, b, t, ((bn0 + grp * 32) >> 1) + c4);
-        }
-        return;
-    }
-    constexpr int C4 = BN / 4;
-    const int eb0 = bm0 / g.T, et0 = bm0 - eb0 * g.T;          // (one division per workgroup; a tile rarely spans more than two batch items)
-    for (int idx = tid; idx < BM * C4; idx += NTH) {
-        const int row = idx / C4, c4 = (idx - row * C4) * 4;
-        const int m = bm0 + row, n = bn0 + c4;
-        if (m >= g.M || n >= g.N) continue;
-        int b = eb0, t = et0 + row;
-        if (t >= g.T) { t -= g.T; ++b; if (t >= g.T) { b += t / g.T; t %= g.T; } }
-        if (t >= g.skip_lo && t < g.skip_hi) continue;
-        float4 v = *reinterpret_cast<const float4*>(&Cs[row * CS + c4]);
-        if (g.bias) {
-            const float4 bb = *reinterpret_cast<const float4*>(g.bias + n);
-            v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
-        }
-        if (g.act == ACT_GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
-        else if (g.act == ACT_LOGCLAMP) { v.x = __logf(fmaxf(v.x, 1e-5f)); v.y = __logf(fmaxf(v.y, 1e-5f)); v.z = __logf(fmaxf(v.z, 1e-5f)); v.w = __logf(fmaxf(v.w, 1e-5f)); }
-        if (g.gamma) {
-            const float4 gm = *reinterpret_cast<const float4*>(g.gamma + n);
-            v.x *= gm.x; v.y *= gm.y; v.z *= gm.z; v.w *= gm.w;
-        }
-        if (g.res) {
-            const float4 rr = *reinterpret_cast<const float4*>(g.res + (long)b * g.r_bstride + g.r_off + (long)t * g.ldr + n);
-            v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
-        }
-        v.x *= g.scale; v.y *= g.scale; v.z *= g.scale; v.w *= g.scale;
-        const long ci = (long)b * g.c_bstride + g.c_off + (long)t * g.ldc + n;
-        if (g.accumulate) {
-            const float4 cc = *reinterpret_cast<const float4*>(g.C + ci);
-            v.x += cc.x; v.y += cc.y; v.z += cc.z; v.w += cc.w;
-        }
-        store4(v, ci, b, t, n);
-    }
+    epi::tile_epilogue<BM, BN, NTH>(g, smem, acc, true, wm * TM, wn * TN, bm0, bn0, [&](float x) { return x * winv; }, [](int) { return 1.f; }, store4);
 }
 
 template <int MODE, int BM, int BN, int KB, bool APL, int WM = 2, int WN = 2>
@@ -362,10 +296,7 @@ int launch_planes_t(const ConvGemmGroup& gg_in, hipStream_t st) {
     constexpr size_t smem = smem_ab > smem_c ? smem_ab : smem_c;
     static_assert(smem <= 160 * 1024, "LDS of one CU");
     static DeviceOnce attr_set;
-    if (attr_set.needed() && smem > 48 * 1024) {
-        SVA_HIP(hipFuncSetAttribute((const void*)planes_gemm_kernel<MODE, BM, BN, KB, APL, WM, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set.done();
-    }
+    if (smem > 48 * 1024) SVA_TRY_RC(attr_set.max_dynamic_lds((const void*)planes_gemm_kernel<MODE, BM, BN, KB, APL, WM, WN>, smem));
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, gg.n);
     gg.xcd_swz = xcd_swizzle_for(grid.x, grid.y) | (debug_options().planes_dbg << 8);
     hipLaunchKernelGGL((planes_gemm_kernel<MODE, BM, BN, KB, APL, WM, WN>), grid, dim3(64 * WM * WN), smem, st, gg);
@@ -584,7 +515,7 @@ __global__ __launch_bounds__(64 * (NW + LW), (LW > 0 ? 3 : DmaCfg<MODE, BM, BN, 
             if (g.C) *reinterpret_cast<f32x4*>(g.C + idx) = v;
             if (g.Cp) {
                 f32x4 w = v;
-                if (CONV && g.cp_silu) { w.x = silu_f(v.x); w.y = silu_f(v.y); w.z = silu_f(v.z); w.w = silu_f(v.w); }      // the consumer conv reads silu(.) (HiFiGAN)
+                if (CONV && g.cp_silu) { w.x = epi::silu(v.x); w.y = epi::silu(v.y); w.z = epi::silu(v.z); w.w = epi::silu(v.w); }      // the consumer conv reads silu(.) (HiFiGAN)
                 unsigned p0[NPL], p1[NPL];
                 split_pair<MODE>(w.x, w.y, p0);
                 split_pair<MODE>(w.z, w.w, p1);
@@ -609,7 +540,7 @@ __global__ __launch_bounds__(64 * (NW + LW), (LW > 0 ? 3 : DmaCfg<MODE, BM, BN, 
                     if (!row_ok || n >= g.N) continue;
                     const f32x4 a = acc[i][j] * winv, w = acc[i][j + 1] * winv;
                     f32x4 o;
-                    o.x = silu_f(a.x) * w.x; o.y = silu_f(a.y) * w.y; o.z = silu_f(a.z) * w.z; o.w = silu_f(a.w) * w.w;
+                    o.x = epi::silu(a.x) * w.x; o.y = epi::silu(a.y) * w.y; o.z = epi::silu(a.z) * w.z; o.w = epi::silu(a.w) * w.w;
                     store4(o, (long)b * g.c_bstride + g.c_off + (long)t * g.ldc + (n >> 1) + nq, b, t, (n >> 1) + nq);
                 }
                 continue;
@@ -620,8 +551,7 @@ __global__ __launch_bounds__(64 * (NW + LW), (LW > 0 ? 3 : DmaCfg<MODE, BM, BN, 
                 if (!row_ok || n >= g.N) continue;
                 f32x4 v = acc[i][j] * winv;
                 if (g.bias) v += *reinterpret_cast<const f32x4*>(g.bias + n);
-                if (g.act == ACT_GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
-                else if (g.act == ACT_LOGCLAMP) { v.x = __logf(fmaxf(v.x, 1e-5f)); v.y = __logf(fmaxf(v.y, 1e-5f)); v.z = __logf(fmaxf(v.z, 1e-5f)); v.w = __logf(fmaxf(v.w, 1e-5f)); }
+                v = epi::act(g.act, v);
                 if (g.gamma) v *= *reinterpret_cast<const f32x4*>(g.gamma + n);
                 if (g.res) v += *reinterpret_cast<const f32x4*>(g.res + (long)b * g.r_bstride + g.r_off + (long)t * g.ldr + n);
                 v *= g.scale;
@@ -771,12 +701,9 @@ int launch_planes_dma_t(const ConvGemmGroup& gg, hipStream_t st) {
     constexpr size_t smem = DmaCfg<MODE, BM, BN, NST, NW>::smem;
     constexpr int WG_PER_CU = LW > 0 ? 1 : DmaCfg<MODE, BM, BN, NST, NW>::WG_PER_CU;
     static_assert(smem <= 160 * 1024 && WG_PER_CU >= 1, "LDS of one CU");
-    static DeviceOnce attr_set;
-    if (attr_set.needed()) {
-        SVA_HIP(hipFuncSetAttribute((const void*)planes_dma_kernel<MODE, BM, NST, false, BN, NW, CONV, LW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        if (MODE == PLANES_H3) SVA_HIP(hipFuncSetAttribute((const void*)planes_dma_kernel<PLANES_H3, BM, NST, true, BN, NW, CONV, LW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set.done();
-    }
+    static DeviceOnce attr_set, attr_set_x;
+    SVA_TRY_RC(attr_set.max_dynamic_lds((const void*)planes_dma_kernel<MODE, BM, NST, false, BN, NW, CONV, LW>, smem));
+    if (MODE == PLANES_H3) SVA_TRY_RC(attr_set_x.max_dynamic_lds((const void*)planes_dma_kernel<PLANES_H3, BM, NST, true, BN, NW, CONV, LW>, smem));
     int cus = g.cu_limit > 0 ? g.cu_limit : g_dma_cu_limit;
     if (cus <= 0) {
         static int dev_cus = 0;
@@ -859,8 +786,8 @@ __global__ void to_planes_kernel(const float* __restrict__ src, long rows, int K
         f32x4 v0 = *reinterpret_cast<const f32x4*>(src + row * ld + k), v1 = *reinterpret_cast<const f32x4*>(src + row * ld + k + 4);
         v0 *= scale; v1 *= scale;
         if (silu) {
-            v0.x = silu_f(v0.x); v0.y = silu_f(v0.y); v0.z = silu_f(v0.z); v0.w = silu_f(v0.w);
-            v1.x = silu_f(v1.x); v1.y = silu_f(v1.y); v1.z = silu_f(v1.z); v1.w = silu_f(v1.w);
+            v0 = epi::silu_of(v0);
+            v1 = epi::silu_of(v1);
         }
         u32x4 o[NPL];
         split8<MODE>(v0, v1, o);
@@ -882,8 +809,8 @@ __global__ void to_planes_act_kernel(const float* __restrict__ src, int nb, long
         const long b = m / T, row = b * rows_b + row0 + (m - b * T);
         f32x4 v0 = *reinterpret_cast<const f32x4*>(src + row * K + k), v1 = *reinterpret_cast<const f32x4*>(src + row * K + k + 4);
         if (silu) {
-            v0.x = silu_f(v0.x); v0.y = silu_f(v0.y); v0.z = silu_f(v0.z); v0.w = silu_f(v0.w);
-            v1.x = silu_f(v1.x); v1.y = silu_f(v1.y); v1.z = silu_f(v1.z); v1.w = silu_f(v1.w);
+            v0 = epi::silu_of(v0);
+            v1 = epi::silu_of(v1);
         }
         u32x4 o[NPL];
         split8<MODE>(v0, v1, o);
@@ -1000,8 +927,8 @@ __global__ __launch_bounds__(256, C == 16 ? 4 : 2) void voc_conv_kernel(const Vo
                 if (g.Cf) *reinterpret_cast<f32x4*>(g.Cf + (long)b * g.c_bstride + g.c_off + (long)t * C + n) = v;
                 if (g.Cp) {
                     unsigned p0[NPL], p1[NPL];
-                    split_pair<MODE>(silu_f(v.x), silu_f(v.y), p0);
-                    split_pair<MODE>(silu_f(v.z), silu_f(v.w), p1);
+                    split_pair<MODE>(epi::silu(v.x), epi::silu(v.y), p0);
+                    split_pair<MODE>(epi::silu(v.z), epi::silu(v.w), p1);
                     const long po = ((long)b * g.c_rows_b + g.c_row0 + t) * C + n;
 #pragma unroll
                     for (int p = 0; p < NPL; ++p) *reinterpret_cast<u32x2*>(g.Cp + (long)p * g.cp_pstride + po) = (u32x2){p0[p], p1[p]};
@@ -1018,10 +945,7 @@ int launch_voc_conv_t(VocConvGroup& gg, int cus, hipStream_t st) {
     constexpr int WG_PER_CU = C == 16 ? 4 : 2;
     static_assert(smem * WG_PER_CU <= 160 * 1024, "LDS of one CU");
     static DeviceOnce attr_set;
-    if (attr_set.needed()) {
-        SVA_HIP(hipFuncSetAttribute((const void*)voc_conv_kernel<MODE, C, BM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set.done();
-    }
+    SVA_TRY_RC(attr_set.max_dynamic_lds((const void*)voc_conv_kernel<MODE, C, BM>, smem));
     const int n_tiles = gg.B * (gg.T / BM);
     // longest K first; workgroups in proportion to the members' taps (each member's tiles are equally many), at most one per tile
     std::stable_sort(gg.g, gg.g + gg.n, [](const VocConv& a, const VocConv& b_) { return a.taps > b_.taps; });

@@ -4,7 +4,7 @@
 // v_mfma_f32_16x16x32_bf16.  The three dropped products are below 2^-24 relative -- one fp32 rounding -- so the result is
 // fp32-grade (measured on the encoder: max |du| 1.1e-6 against the exact fp32 formulation, BSQ indices identical;
 // tools/bf16split_feasibility.py), while six 16-cycle MFMAs replace eight 32-cycle v_mfma_f32_16x16x4_f32 per 32 k: 2.7x less
-// matrix-pipe time.  Same problem description (ConvGemm: taps, SiLU prologue, fused epilogues, groups) as conv_gemm_kernel.
+// matrix-pipe time.  The ConvGemm contract (taps, SiLU prologue, groups; epilogue: gemm_epilogue.h).
 //
 // LDS: one buffer of 3 planes per operand, [rows][32 bf16] with a 96-byte row stride (16-byte fragment reads, the lanes of every
 // ds_read_b128 lane group on distinct banks); global -> registers prefetch of the next K tile runs under the MFMAs; two workgroups per CU.
@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "sva_common.h"
+#include "gemm_epilogue.h"
 
 namespace sva {
 namespace {
@@ -21,9 +22,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float silu_f(float x) { return x / (1.f + __expf(-x)); }
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 
 // two fp32 -> packed (hi, mid, lo) bf16 pairs; RNE conversions (v_cvt_pk_bf16_f32), residuals exact in fp32
 __device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
@@ -101,7 +99,7 @@ __global__ __launch_bounds__(256) void split_gemm_kernel(const ConvGemmGroup gg)
 #pragma unroll
         for (int i = 0; i < A_LD; ++i) {
             f32x4 v = ra[i];
-            if (g.a_silu) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
+            if (g.a_silu) v = epi::silu_of(v);
             unsigned h0, m0, l0, h1, m1, l1;
             split2(v.x, v.y, h0, m0, l0);
             split2(v.z, v.w, h1, m1, l1);
@@ -161,71 +159,8 @@ __global__ __launch_bounds__(256) void split_gemm_kernel(const ConvGemmGroup gg)
         __syncthreads();
     }
 
-    // ---- epilogue ----
-    // The accumulators (C/D layout of the 16x16 MFMA: col = lane & 15, row = (lane >> 4) * 4 + reg) are staged
-    // through LDS so that bias / residual reads and the C stores are whole 16-byte, row-contiguous accesses
-    // (a lane-per-element epilogue touches a 64-byte segment per row per instruction and costs up to 30 % of a
-    // K = 512 GEMM).  The last loop iteration ended with a barrier, so the A/B buffers are free to reuse.
-    constexpr int CS = BN + 4;
-    float* Cs = smem;                              // [BM][CS]
-    const int col = lane & 15, rq = (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Cs[(wm * TM + i * 16 + rq + r) * CS + wn * TN + j * 16 + col] = acc[i][j][r];
-    __syncthreads();
-    if (g.w13) {
-        // SwiGLU: tile columns alternate 16 x w1 | 16 x w3; output column (n0 >> 1) + c
-        constexpr int OC4 = BN / 8;                // float4 chunks of output per row
-        for (int idx = tid; idx < BM * OC4; idx += NTH) {
-            const int row = idx / OC4, q = idx - row * OC4;
-            const int m = bm0 + row;
-            const int grp = q >> 2, c4 = (q & 3) * 4;       // 16-wide group, offset inside it
-            const int n = bn0 + grp * 32 + c4;              // w1 column
-            if (m >= g.M || n >= g.N) continue;
-            const int b = m / g.T, t = m - b * g.T;
-            if (t >= g.skip_lo && t < g.skip_hi) continue;
-            const float4 a = *reinterpret_cast<const float4*>(&Cs[row * CS + grp * 32 + c4]);
-            const float4 w = *reinterpret_cast<const float4*>(&Cs[row * CS + grp * 32 + 16 + c4]);
-            float4 o;
-            o.x = silu_f(a.x) * w.x; o.y = silu_f(a.y) * w.y; o.z = silu_f(a.z) * w.z; o.w = silu_f(a.w) * w.w;
-            float* crow = g.C + (long)b * g.c_bstride + g.c_off + (long)t * g.ldc;
-            *reinterpret_cast<float4*>(crow + ((bn0 + grp * 32) >> 1) + c4) = o;
-        }
-        return;
-    }
-    constexpr int C4 = BN / 4;
-    for (int idx = tid; idx < BM * C4; idx += NTH) {
-        const int row = idx / C4, c4 = (idx - row * C4) * 4;
-        const int m = bm0 + row, n = bn0 + c4;
-        if (m >= g.M || n >= g.N) continue;
-        const int b = m / g.T, t = m - b * g.T;
-        if (t >= g.skip_lo && t < g.skip_hi) continue;
-        float4 v = *reinterpret_cast<const float4*>(&Cs[row * CS + c4]);
-        if (g.bias) {
-            const float4 bb = *reinterpret_cast<const float4*>(g.bias + n);
-            v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
-        }
-        if (g.act == ACT_GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
-        else if (g.act == ACT_LOGCLAMP) { v.x = __logf(fmaxf(v.x, 1e-5f)); v.y = __logf(fmaxf(v.y, 1e-5f)); v.z = __logf(fmaxf(v.z, 1e-5f)); v.w = __logf(fmaxf(v.w, 1e-5f)); }
-        if (g.gamma) {
-            const float4 gg = *reinterpret_cast<const float4*>(g.gamma + n);
-            v.x *= gg.x; v.y *= gg.y; v.z *= gg.z; v.w *= gg.w;
-        }
-        if (g.res) {
-            const float4 rr = *reinterpret_cast<const float4*>(g.res + (long)b * g.r_bstride + g.r_off + (long)t * g.ldr + n);
-            v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
-        }
-        v.x *= g.scale; v.y *= g.scale; v.z *= g.scale; v.w *= g.scale;
-        float* cp = g.C + (long)b * g.c_bstride + g.c_off + (long)t * g.ldc + n;
-        if (g.accumulate) {
-            const float4 cc = *reinterpret_cast<const float4*>(cp);
-            v.x += cc.x; v.y += cc.y; v.z += cc.z; v.w += cc.w;
-        }
-        *reinterpret_cast<float4*>(cp) = v;
-    }
+    // ---- epilogue: staged through LDS (gemm_epilogue.h); the last loop iteration ended with a barrier, so the A/B buffers are free to reuse ----
+    epi::tile_epilogue<BM, BN, NTH>(g, smem, acc, true, wm * TM, wn * TN, bm0, bn0, [](float x) { return x; }, [](int) { return 1.f; }, epi::Store16{g.C});
 }
 
 // Wave-specialised form (512 threads): waves 0..3 are CONSUMERS (fragment reads + MFMAs, 64 x 64 each of a 128 x 128 tile), waves
@@ -302,7 +237,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int i = 0; i < A_LD; ++i) {
                 f32x4 v = xa[i];
-                if (g.a_silu) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
+                if (g.a_silu) v = epi::silu_of(v);
                 unsigned h0, m0, l0, h1, m1, l1;
                 split2(v.x, v.y, h0, m0, l0);
                 split2(v.z, v.w, h1, m1, l1);
@@ -383,73 +318,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
     }
 
-    // ---- epilogue ----
-    // The accumulators (C/D layout of the 16x16 MFMA: col = lane & 15, row = (lane >> 4) * 4 + reg) are staged
-    // through LDS so that bias / residual reads and the C stores are whole 16-byte, row-contiguous accesses
-    // (a lane-per-element epilogue touches a 64-byte segment per row per instruction and costs up to 30 % of a
-    // K = 512 GEMM).  The last loop iteration ended with a barrier, so the A/B buffers are free to reuse.
-    constexpr int CS = BN + 4;
-    float* Cs = smem;                              // [BM][CS]
-    const int col = lane & 15, rq = (lane >> 4) * 4;
-    if (!producer) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Cs[(wm * TM + i * 16 + rq + r) * CS + wn * TN + j * 16 + col] = acc[i][j][r];
-    }
-    __syncthreads();
-    if (g.w13) {
-        // SwiGLU: tile columns alternate 16 x w1 | 16 x w3; output column (n0 >> 1) + c
-        constexpr int OC4 = BN / 8;                // float4 chunks of output per row
-        for (int idx = tid; idx < BM * OC4; idx += NTH) {
-            const int row = idx / OC4, q = idx - row * OC4;
-            const int m = bm0 + row;
-            const int grp = q >> 2, c4 = (q & 3) * 4;       // 16-wide group, offset inside it
-            const int n = bn0 + grp * 32 + c4;              // w1 column
-            if (m >= g.M || n >= g.N) continue;
-            const int b = m / g.T, t = m - b * g.T;
-            if (t >= g.skip_lo && t < g.skip_hi) continue;
-            const float4 a = *reinterpret_cast<const float4*>(&Cs[row * CS + grp * 32 + c4]);
-            const float4 w = *reinterpret_cast<const float4*>(&Cs[row * CS + grp * 32 + 16 + c4]);
-            float4 o;
-            o.x = silu_f(a.x) * w.x; o.y = silu_f(a.y) * w.y; o.z = silu_f(a.z) * w.z; o.w = silu_f(a.w) * w.w;
-            float* crow = g.C + (long)b * g.c_bstride + g.c_off + (long)t * g.ldc;
-            *reinterpret_cast<float4*>(crow + ((bn0 + grp * 32) >> 1) + c4) = o;
-        }
-        return;
-    }
-    constexpr int C4 = BN / 4;
-    for (int idx = tid; idx < BM * C4; idx += NTH) {
-        const int row = idx / C4, c4 = (idx - row * C4) * 4;
-        const int m = bm0 + row, n = bn0 + c4;
-        if (m >= g.M || n >= g.N) continue;
-        const int b = m / g.T, t = m - b * g.T;
-        if (t >= g.skip_lo && t < g.skip_hi) continue;
-        float4 v = *reinterpret_cast<const float4*>(&Cs[row * CS + c4]);
-        if (g.bias) {
-            const float4 bb = *reinterpret_cast<const float4*>(g.bias + n);
-            v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
-        }
-        if (g.act == ACT_GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
-        else if (g.act == ACT_LOGCLAMP) { v.x = __logf(fmaxf(v.x, 1e-5f)); v.y = __logf(fmaxf(v.y, 1e-5f)); v.z = __logf(fmaxf(v.z, 1e-5f)); v.w = __logf(fmaxf(v.w, 1e-5f)); }
-        if (g.gamma) {
-            const float4 gg = *reinterpret_cast<const float4*>(g.gamma + n);
-            v.x *= gg.x; v.y *= gg.y; v.z *= gg.z; v.w *= gg.w;
-        }
-        if (g.res) {
-            const float4 rr = *reinterpret_cast<const float4*>(g.res + (long)b * g.r_bstride + g.r_off + (long)t * g.ldr + n);
-            v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
-        }
-        v.x *= g.scale; v.y *= g.scale; v.z *= g.scale; v.w *= g.scale;
-        float* cp = g.C + (long)b * g.c_bstride + g.c_off + (long)t * g.ldc + n;
-        if (g.accumulate) {
-            const float4 cc = *reinterpret_cast<const float4*>(cp);
-            v.x += cc.x; v.y += cc.y; v.z += cc.z; v.w += cc.w;
-        }
-        *reinterpret_cast<float4*>(cp) = v;
-    }
+    // ---- epilogue: the consumer waves stage their accumulators, all 512 threads store (gemm_epilogue.h) ----
+    epi::tile_epilogue<BM, BN, NTH>(g, smem, acc, !producer, wm * TM, wn * TN, bm0, bn0, [](float x) { return x; }, [](int) { return 1.f; }, epi::Store16{g.C});
 }
 
 template <int BM, int BN>
@@ -460,10 +330,7 @@ int launch_split_ws(const ConvGemmGroup& gg_in, hipStream_t st) {
     constexpr size_t smem_c = (size_t)BM * (BN + 4) * sizeof(float);
     constexpr size_t smem = smem_ab > smem_c ? smem_ab : smem_c;
     static DeviceOnce attr_set;
-    if (attr_set.needed()) {
-        SVA_HIP(hipFuncSetAttribute((const void*)split_ws_kernel<BM, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set.done();
-    }
+    SVA_TRY_RC(attr_set.max_dynamic_lds((const void*)split_ws_kernel<BM, BN>, smem));
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, gg.n);
     gg.xcd_swz = xcd_swizzle_for(grid.x, grid.y);
     hipLaunchKernelGGL((split_ws_kernel<BM, BN>), grid, dim3(512), smem, st, gg);
@@ -478,10 +345,7 @@ int launch_split_t(const ConvGemmGroup& gg_in, hipStream_t st) {
     constexpr size_t smem_c = (size_t)BM * (BN + 4) * sizeof(float);
     constexpr size_t smem = smem_ab > smem_c ? smem_ab : smem_c;
     static DeviceOnce attr_set;
-    if (attr_set.needed() && smem > 48 * 1024) {
-        SVA_HIP(hipFuncSetAttribute((const void*)split_gemm_kernel<BM, BN, WM, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set.done();
-    }
+    if (smem > 48 * 1024) SVA_TRY_RC(attr_set.max_dynamic_lds((const void*)split_gemm_kernel<BM, BN, WM, WN>, smem));
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, gg.n);
     gg.xcd_swz = xcd_swizzle_for(grid.x, grid.y);
     hipLaunchKernelGGL((split_gemm_kernel<BM, BN, WM, WN>), grid, dim3(256), smem, st, gg);

@@ -15,19 +15,18 @@
 //     tail to MT waves).
 // Operand mapping as in gemm.hip: lane l supplies, for MFMA step j of block kb, W[n0 + (l & 15)][16 kb + 4 (l >> 4) + j] and the same k of
 // A[m0 + (l & 15)] -- a permutation of k inside the block, identical on both operands.
-// Same ConvGemm semantics as the other kernels (taps over shifted rows, SiLU / RMSNorm prologues, bias / act / gamma / residual / scale /
-// accumulate / SwiGLU epilogues, skipped history rows); every output element is the fixed-order sum wave 0 .. KW - 1 of fixed-order block sums.
+// The ConvGemm contract (taps over shifted rows, SiLU / RMSNorm prologues; epilogue: gemm_epilogue.h); every output element is the
+// fixed-order sum wave 0 .. KW - 1 of fixed-order block sums.  Everything that does not depend on the operand format is shared with the
+// fp16 kernel of gemm_stream_h.hip: gemm_stream_common.h.
 #include "sva_common.h"
 #include "device_util.h"
+#include "gemm_stream_common.h"
 
 namespace sva {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ __forceinline__ float silu_s(float x) { return x / (1.f + __expf(-x)); }
-__device__ __forceinline__ float gelu_s(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 
 struct StreamArgs {
     const float* A; long a_bstride, a_off; int lda, T, M, stride, dil, taps, Cin;
@@ -53,15 +52,8 @@ __global__ __launch_bounds__(64 * KW) void stream_gemm_kernel(const StreamArgs g
     constexpr bool SILU = AOP == 1, RMS = AOP == 2;
     extern __shared__ __attribute__((aligned(16))) float red[];      // [KW][MT*NT][64] f32x4 (+ [KW][MT][16] row sums of squares)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // XCD x owns the x-th contiguous eighth of the tile sequence (row tiles fastest)
-    int V;
-    {
-        const int Tn = g.m_tiles * g.n_tiles, L = blockIdx.x;
-        const int xcd = L & 7, idx = L >> 3, q = Tn >> 3, r = Tn & 7;
-        V = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int tn = V / g.m_tiles, tm = V - tn * g.m_tiles;
-    const int n0 = tn * (16 * NT), m_base = tm * (16 * MT);
+    int n0, m_base;
+    wstream::tile_origin<MT, NT>(g, n0, m_base);
     const int fr = lane & 15, fg = lane >> 4;
     const long Kt = (long)g.nkb * 16;
     const int kc_tiles = g.Cin >> 4;
@@ -87,22 +79,16 @@ __global__ __launch_bounds__(64 * KW) void stream_gemm_kernel(const StreamArgs g
         const int b = m / g.T, t = m - b * g.T;
         ap[i] = g.A + (long)b * g.a_bstride + g.a_off + (long)t * g.stride * g.lda + 4 * fg;
     }
-    const int my_n = g.nkb > wave ? (g.nkb - wave + KW - 1) / KW : 0;           // blocks of this wave: wave, wave + KW, ...
-    const int last_kb = my_n > 0 ? wave + (my_n - 1) * KW : 0;
+    int my_n, last_kb;                           // blocks of this wave: wave, wave + KW, ...
+    wstream::wave_blocks<KW>(0, g.nkb, wave, my_n, last_kb);
 
     f32x4 wv[KB][NT], av[KB][MT], nv[KB];
     auto issue_w = [&](f32x4 (&w)[NT], int kb) {
         kb = kb < g.nkb ? kb : last_kb;
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            const f32x4* p;
-            if constexpr (WP) p = reinterpret_cast<const f32x4*>(wp[j] + (long)kb * 256);
-            else {
-                const int tap = kb / kc_tiles;           // (W's K axis is the taps back to back: block kb sits at 16 kb)
-                (void)tap;
-                p = reinterpret_cast<const f32x4*>(wp[j] + (long)kb * 16);
-            }
-            w[j] = *p;
+            // (row-major W: its K axis is the taps back to back, block kb sits at 16 kb)
+            w[j] = *reinterpret_cast<const f32x4*>(wp[j] + (long)kb * (WP ? 256 : 16));
         }
     };
     auto issue_a = [&](f32x4 (&a)[MT], f32x4& nw, int kb) {
@@ -114,7 +100,10 @@ __global__ __launch_bounds__(64 * KW) void stream_gemm_kernel(const StreamArgs g
         for (int i = 0; i < MT; ++i) a[i] = *reinterpret_cast<const f32x4*>(ap[i] + aoff);
         if constexpr (RMS) nw = *reinterpret_cast<const f32x4*>(g.rms_w + kc + 4 * fg);
     };
-    // epilogue operands of this thread's output units, requested first (unit u = (row tile i, column tile j, lane slot l): see the tail)
+    // epilogue operands of this thread's output units, requested first (unit u = (row tile i, column tile j, lane slot l): see the tail).
+    // This request and the tail below are the text of wstream::EpiOperands / wstream::unit_tail, which the fp16 kernel calls: called from
+    // here they moved 2-3 registers and cost 17 of this kernel's 984 instances an occupancy step, so this kernel keeps its own copy
+    // (the stage sequence itself is epi::value)
     constexpr int UNITS = (MT * NT + KW - 1) / KW;
     const bool w13 = g.w13 != 0;
     float e_bias[UNITS], e_gamma[UNITS], e_res[UNITS][4];
@@ -177,7 +166,7 @@ __global__ __launch_bounds__(64 * KW) void stream_gemm_kernel(const StreamArgs g
             if (it + d < my_n) {                     // wave-uniform; no load inside
 #pragma unroll
                 for (int i = 0; i < MT; ++i) {
-                    if constexpr (SILU) { a[i].x = silu_s(a[i].x); a[i].y = silu_s(a[i].y); a[i].z = silu_s(a[i].z); a[i].w = silu_s(a[i].w); }
+                    if constexpr (SILU) a[i] = epi::silu_of(a[i]);
                     if constexpr (RMS) {
                         // explicit, sequential fmas: left to -ffp-contract the sum of squares was fused differently per unrolled row tile (fma(x, x, y * y)
                         // here, two products and an add there), which made a row's statistic -- and every logit after it -- depend on the row's position
@@ -206,7 +195,7 @@ __global__ __launch_bounds__(64 * KW) void stream_gemm_kernel(const StreamArgs g
             }
         }
     }
-    // the KW partial tiles meet in LDS
+    // the KW partial tiles meet in LDS (a store of the kernel's own: handed to a shared function it cost registers and an occupancy step in some instances)
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -259,7 +248,7 @@ __global__ __launch_bounds__(64 * KW) void stream_gemm_kernel(const StreamArgs g
                 const int b = m / g.T, tt = m - b * g.T;
                 if (tt >= g.skip_lo && tt < g.skip_hi) continue;
                 float* crow = g.C + (long)b * g.c_bstride + g.c_off + (long)tt * g.ldc;
-                crow[(n0 >> 1) + jj * 16 + col] = silu_s(ga[r]) * up[r];
+                crow[(n0 >> 1) + jj * 16 + col] = epi::swiglu(ga[r], up[r]);
             }
             continue;
         }
@@ -273,14 +262,8 @@ __global__ __launch_bounds__(64 * KW) void stream_gemm_kernel(const StreamArgs g
             const int b = m / g.T, tt = m - b * g.T;
             if (tt >= g.skip_lo && tt < g.skip_hi) continue;
             float* cp = g.C + (long)b * g.c_bstride + g.c_off + (long)tt * g.ldc + n;
-            float v = s[r] + e_bias[k];
-            if (g.act == ACT_GELU) v = gelu_s(v);
-            else if (g.act == ACT_LOGCLAMP) v = __logf(fmaxf(v, 1e-5f));
-            v *= e_gamma[k];
-            v += e_res[k][r];
-            v *= g.scale;
-            if (g.accumulate) v += *cp;
-            *cp = v;
+            *cp = epi::value<true>(s[r], g.act, g.scale, true, [&] { return e_bias[k]; }, true, [&] { return e_gamma[k]; }, true, [&] { return e_res[k][r]; },
+                                   g.accumulate != 0, [&] { return *cp; });
         }
     }
 }
@@ -288,39 +271,21 @@ __global__ __launch_bounds__(64 * KW) void stream_gemm_kernel(const StreamArgs g
 template <int MT, int NT, int KW, int KB, int AOP, bool WP, int PROBE, bool LOOP>
 int launch_stream_kl(const ConvGemm& g, const float* Wsrc, hipStream_t st) {
     StreamArgs a;
-    a.A = g.A; a.a_bstride = g.a_bstride; a.a_off = g.a_off; a.lda = g.lda; a.T = g.T; a.M = g.M; a.stride = g.stride; a.dil = g.dil;
-    a.taps = g.taps; a.Cin = g.Cin; a.W = Wsrc; a.N = g.N; a.nkb = g.taps * g.Cin / 16;
-    a.bias = g.bias; a.gamma = g.gamma; a.res = g.res; a.r_bstride = g.r_bstride; a.r_off = g.r_off; a.ldr = g.ldr;
-    a.C = g.C; a.c_bstride = g.c_bstride; a.c_off = g.c_off; a.ldc = g.ldc; a.scale = g.scale; a.skip_lo = g.skip_lo; a.skip_hi = g.skip_hi;
-    a.act = g.act; a.accumulate = g.accumulate; a.w13 = g.w13; a.rms_w = g.rms_w; a.rms_eps = g.rms_eps;
-    a.m_tiles = (g.M + 16 * MT - 1) / (16 * MT); a.n_tiles = (g.N + 16 * NT - 1) / (16 * NT);
+    wstream::fill_front(a, g, 16, MT, NT);
+    a.W = Wsrc; a.scale = g.scale; a.accumulate = g.accumulate; a.rms_w = g.rms_w; a.rms_eps = g.rms_eps;
     const size_t smem = ((size_t)KW * MT * NT * 256 + (AOP == 2 ? KW * MT * 16 : 0)) * sizeof(float);
     static DeviceOnce attr;
-    if (attr.needed() && smem > 48 * 1024) {
-        SVA_HIP(hipFuncSetAttribute((const void*)stream_gemm_kernel<MT, NT, KW, KB, AOP, WP, PROBE, LOOP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr.done();
-    }
-    hipLaunchKernelGGL((stream_gemm_kernel<MT, NT, KW, KB, AOP, WP, PROBE, LOOP>), dim3(a.m_tiles * a.n_tiles), dim3(64 * KW), smem, st, a);
-    return 0;
+    return wstream::launch_tiles(stream_gemm_kernel<MT, NT, KW, KB, AOP, WP, PROBE, LOOP>, a, KW, smem, attr, st);
 }
 
-// registers in flight: 4 (MT + NT [+ 1 with the fused RMSNorm]) KB per lane -- at most ~200 load registers per wave (a 16-wave workgroup's
-// waves own 128 registers; the looping form keeps a second copy of the block it is consuming)
-template <int MT, int NT, int KW, int AOP, bool LOOP>
-constexpr int kb_for() {
-    constexpr int per = 4 * (MT + NT + (AOP == 2 ? 1 : 0));
-    constexpr int budget = KW == 16 ? (LOOP ? 44 : 64) : (LOOP ? 136 : 200);
-    return budget / per > 24 ? 24 : (budget / per < 2 ? 2 : budget / per);
-}
-
+// registers in flight: 4 (MT + NT [+ 1 with the fused RMSNorm]) KB per lane
 template <int MT, int NT, int KW, int AOP, bool WP, int PROBE>
 int launch_stream_k(const ConvGemm& g, const float* Wsrc, hipStream_t st) {
     const int nkb = g.taps * g.Cin / 16, need = (nkb + KW - 1) / KW;
-    constexpr int KB0 = kb_for<MT, NT, KW, AOP, false>(), KB1 = kb_for<MT, NT, KW, AOP, true>();
-#define SVA_KB(KBv) \
-    if constexpr (KBv <= KB0) { if (need <= KBv) return launch_stream_kl<MT, NT, KW, KBv, AOP, WP, PROBE, false>(g, Wsrc, st); }
-    SVA_KB(1) SVA_KB(2) SVA_KB(3) SVA_KB(4) SVA_KB(6) SVA_KB(8) SVA_KB(12) SVA_KB(16) SVA_KB(24)
-#undef SVA_KB
+    constexpr int PER = 4 * (MT + NT + (AOP == 2 ? 1 : 0));
+    constexpr int KB0 = wstream::kb_for<PER, KW, false, 24>(), KB1 = wstream::kb_for<PER, KW, true, 24>();
+    int rc = 0;
+    if (wstream::kb_ladder<KB0>(need, rc, [&](auto kb) { return launch_stream_kl<MT, NT, KW, decltype(kb)::value, AOP, WP, PROBE, false>(g, Wsrc, st); })) return rc;
     if constexpr (PROBE == 0) return launch_stream_kl<MT, NT, KW, KB1, AOP, WP, 0, true>(g, Wsrc, st);
     set_error("stream_gemm: probes are single-round only");
     return -1;
@@ -355,15 +320,10 @@ bool stream_gemm_supported(const ConvGemm& g) {
 int launch_stream_gemm(const ConvGemm& g, const float* Wsrc, int mt, int nt, int kw, int wmode, int probe, hipStream_t st) {
     SVA_CHECK(stream_gemm_supported(g), "stream_gemm: unsupported problem");
     SVA_CHECK(!(g.w13 && nt != 2), "stream_gemm: SwiGLU needs column-tile pairs (nt = 2)");
-#define SVA_SG(MTv, NTv, KWv) \
-    if (mt == MTv && nt == NTv && kw == KWv) return launch_stream_w<MTv, NTv, KWv>(g, Wsrc, wmode, probe, st);
-    SVA_SG(1, 1, 4) SVA_SG(1, 1, 8) SVA_SG(1, 1, 16)
-    SVA_SG(2, 1, 4) SVA_SG(2, 1, 8) SVA_SG(2, 1, 16)
-    SVA_SG(4, 1, 4) SVA_SG(4, 1, 8)
-    SVA_SG(1, 2, 4) SVA_SG(1, 2, 8) SVA_SG(1, 2, 16)
-    SVA_SG(2, 2, 4) SVA_SG(2, 2, 8)
-    SVA_SG(4, 2, 4) SVA_SG(4, 2, 8)
-#undef SVA_SG
+    int rc = 0;
+    if (wstream::config_ladder(mt, nt, kw, rc, [&](auto MTc, auto NTc, auto KWc) {
+            return launch_stream_w<decltype(MTc)::value, decltype(NTc)::value, decltype(KWc)::value>(g, Wsrc, wmode, probe, st);
+        })) return rc;
     set_error("stream_gemm: bad configuration");
     return -1;
 }

@@ -1,13 +1,8 @@
 // Weight-streaming fp16-MFMA conv-GEMM for few rows: the content encoder's GEMMs of 1-9 streams when sva_config.enc_dtype = 1.  The
-// fp16-operand sibling of gemm_stream.hip, same structure:
-//   * a workgroup owns a (16 MT) x (16 NT) output tile for the WHOLE K axis, its KW waves take the 32-k blocks round-robin, and every wave
-//     requests ALL its operand fragments before it multiplies the first one (KB blocks = (4 NT + 8 MT) KB registers in flight per lane;
-//     problems with more blocks per wave re-request a block as soon as one is consumed).  Straight-line code, no load under a branch;
-//   * the weight fragments are requested first (HBM / MALL), then the activation rows (L2); the epilogue's operands (bias, gamma, residual)
-//     before anything else, so the tail is arithmetic and stores only;
-//   * tiles are numbered so that XCD x owns a contiguous band of column tiles with all their row tiles;
-//   * the KW partial tiles meet in LDS once, summed in the fixed order wave 0 .. KW - 1, and every thread stores its share of the tile.
-// What differs:
+// skeleton of gemm_stream.hip on fp16 operands; what the two share is gemm_stream_common.h (tile numbering, the waves' K-block schedule,
+// the early request of the epilogue operands, the meeting in LDS summed in the fixed order wave 0 .. KW - 1, the unit-per-thread tail),
+// KB blocks = (4 NT + 8 MT) KB registers in flight per lane.
+// What is this kernel's own:
 //   * the product is v_mfma_f32_16x16x32_f16: BOTH operands rounded once, to nearest even, to fp16; products exact, accumulation fp32.  Lane l
 //     supplies k = 8 (l >> 4) + j, j < 8, of row / column l & 15 of a 32-k block on both operands; the accumulator holds column l & 15, rows
 //     4 (l >> 4) + reg;
@@ -23,6 +18,7 @@
 // not depend on the tile or slot it sits in.
 #include "sva_common.h"
 #include "device_util.h"
+#include "gemm_stream_common.h"
 
 #include <cstring>
 #include <vector>
@@ -33,9 +29,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
-
-__device__ __forceinline__ float silu_s(float x) { return x / (1.f + __expf(-x)); }
-__device__ __forceinline__ float gelu_s(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 
 struct StreamHArgs {
     const float* A; long a_bstride, a_off; int lda, T, M, stride, dil, taps, Cin;
@@ -64,15 +57,8 @@ __global__ __launch_bounds__(64 * KW) void stream_h_gemm_kernel(const StreamHArg
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) float red[];      // [KW][MT*NT][64] f32x4
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // XCD x owns the x-th contiguous eighth of the tile sequence (row tiles fastest)
-    int V;
-    {
-        const int Tn = g.m_tiles * g.n_tiles, L = blockIdx.x;
-        const int xcd = L & 7, idx = L >> 3, q = Tn >> 3, r = Tn & 7;
-        V = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int tn = V / g.m_tiles, tm = V - tn * g.m_tiles;
-    const int n0 = tn * (16 * NT), m_base = tm * (16 * MT);
+    int n0, m_base;
+    wstream::tile_origin<MT, NT>(g, n0, m_base);
     const int fr = lane & 15, fg = lane >> 4;
     const int kc_tiles = g.Cin >> 5;
     const _Float16* wp[NT];
@@ -91,8 +77,8 @@ __global__ __launch_bounds__(64 * KW) void stream_h_gemm_kernel(const StreamHArg
         const int b = m / g.T, t = m - b * g.T;
         ap[i] = g.A + (long)b * g.a_bstride + g.a_off + (long)t * g.stride * g.lda + 8 * fg;
     }
-    const int my_n = g.nkb > wave ? (g.nkb - wave + KW - 1) / KW : 0;           // blocks of this wave: wave, wave + KW, ...
-    const int last_kb = my_n > 0 ? wave + (my_n - 1) * KW : 0;
+    int my_n, last_kb;                           // blocks of this wave: wave, wave + KW, ...
+    wstream::wave_blocks<KW>(0, g.nkb, wave, my_n, last_kb);
 
     f16x8 wv[KB][NT];
     f32x4 av[KB][MT][2];
@@ -112,37 +98,9 @@ __global__ __launch_bounds__(64 * KW) void stream_h_gemm_kernel(const StreamHArg
             a[i][1] = *reinterpret_cast<const f32x4*>(ap[i] + aoff + 4);
         }
     };
-    // epilogue operands of this thread's output units, requested first (unit u = (row tile i, column tile j, lane slot l): see the tail)
-    constexpr int UNITS = (MT * NT + KW - 1) / KW;
-    const bool w13 = g.w13 != 0;
-    float e_bias[UNITS], e_gamma[UNITS], e_res[UNITS][4];
-#pragma unroll
-    for (int k = 0; k < UNITS; ++k) {
-        e_bias[k] = 0.f; e_gamma[k] = 1.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) e_res[k][r] = 0.f;
-    }
-    if (!w13) {
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k) {
-            int u = tid + k * 64 * KW;
-            if (u > MT * NT * 64 - 1) u = MT * NT * 64 - 1;
-            const int l = u & 63, ij = u >> 6, i = ij / NT, jj = ij - i * NT;
-            int n = n0 + jj * 16 + (l & 15);
-            if (n > g.N - 1) n = g.N - 1;
-            if (g.bias) e_bias[k] = g.bias[n];
-            if (g.gamma) e_gamma[k] = g.gamma[n];
-            if (g.res) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    int m = m_base + i * 16 + (l >> 4) * 4 + r;
-                    if (m > g.M - 1) m = g.M - 1;
-                    const int b = m / g.T, tt = m - b * g.T;
-                    e_res[k][r] = g.res[(long)b * g.r_bstride + g.r_off + (long)tt * g.ldr + n];
-                }
-            }
-        }
-    }
+    // epilogue operands of this thread's output units, requested first
+    wstream::EpiOperands<MT, NT, KW> e;
+    e.request(g, tid, n0, m_base);
     // everything this wave needs (or its first KB blocks) is requested here, weights first
 #pragma unroll
     for (int d = 0; d < KB; ++d) issue_w(wv[d], wave + d * KW);
@@ -176,64 +134,17 @@ __global__ __launch_bounds__(64 * KW) void stream_h_gemm_kernel(const StreamHArg
             }
         }
     }
-    // the KW partial tiles meet in LDS
+    // the KW partial tiles meet in LDS (a store of the kernel's own: handed to a shared function it cost registers and an occupancy step in some
+    // instances); every thread sums and stores its share (no scale, no accumulate: stream_h_gemm_supported)
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
             *reinterpret_cast<f32x4*>(&red[((wave * (MT * NT) + i * NT + j) * 64 + lane) * 4]) = acc[i][j];
     __syncthreads();
-    // every thread sums and stores its share: unit u = (row tile i, column tile j [pair for SwiGLU], lane slot l)
-    const int jt = w13 ? NT / 2 : NT;
-    const int units = MT * jt * 64;
     bool bad = false;
-#pragma unroll
-    for (int k = 0; k < UNITS; ++k) {
-        const int u = tid + k * 64 * KW;
-        if (u >= units) break;
-        const int l = u & 63, ij = u >> 6;
-        const int i = ij / jt, jj = ij - i * jt;
-        const int col = l & 15, rq = (l >> 4) * 4;
-        auto tile_sum = [&](int j) {
-            f32x4 s = *reinterpret_cast<const f32x4*>(&red[((i * NT + j) * 64 + l) * 4]);
-#pragma unroll 4
-            for (int w = 1; w < KW; ++w) s += *reinterpret_cast<const f32x4*>(&red[((w * (MT * NT) + i * NT + j) * 64 + l) * 4]);
-            return s;
-        };
-        if (w13) {
-            const f32x4 ga = tile_sum(2 * jj), up = tile_sum(2 * jj + 1);
-            const int n = n0 + jj * 32 + col;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m_base + i * 16 + rq + r;
-                if (m >= g.M || n >= g.N) continue;
-                const int b = m / g.T, tt = m - b * g.T;
-                if (tt >= g.skip_lo && tt < g.skip_hi) continue;
-                float* crow = g.C + (long)b * g.c_bstride + g.c_off + (long)tt * g.ldc;
-                const float v = silu_s(ga[r]) * up[r];
-                bad = bad || !(fabsf(v) < INFINITY);
-                crow[(n0 >> 1) + jj * 16 + col] = v;
-            }
-            continue;
-        }
-        const f32x4 s = tile_sum(jj);
-        const int n = n0 + jj * 16 + col;
-        if (n >= g.N) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = m_base + i * 16 + rq + r;
-            if (m >= g.M) continue;
-            const int b = m / g.T, tt = m - b * g.T;
-            if (tt >= g.skip_lo && tt < g.skip_hi) continue;
-            float* cp = g.C + (long)b * g.c_bstride + g.c_off + (long)tt * g.ldc + n;
-            float v = s[r] + e_bias[k];
-            if (g.act == ACT_GELU) v = gelu_s(v);
-            v *= e_gamma[k];
-            v += e_res[k][r];
-            bad = bad || !(fabsf(v) < INFINITY);
-            *cp = v;
-        }
-    }
+    wstream::unit_tail<MT, NT, KW>(g, red, tid, n0, m_base, e, 1.f, false, [](int, int) { return (f32x4){1.f, 1.f, 1.f, 1.f}; },
+                                   [&](float v) { bad = bad || !(fabsf(v) < INFINITY); });
     // range report: an ordinary store from the lanes that saw a non-finite output
     if (bad && g.ovf) *reinterpret_cast<volatile int*>(g.ovf) = 1;
 }
@@ -241,38 +152,20 @@ __global__ __launch_bounds__(64 * KW) void stream_h_gemm_kernel(const StreamHArg
 template <int MT, int NT, int KW, int KB, bool LOOP>
 int launch_stream_h_kl(const ConvGemm& g, hipStream_t st) {
     StreamHArgs a;
-    a.A = g.A; a.a_bstride = g.a_bstride; a.a_off = g.a_off; a.lda = g.lda; a.T = g.T; a.M = g.M; a.stride = g.stride; a.dil = g.dil;
-    a.taps = g.taps; a.Cin = g.Cin; a.W = reinterpret_cast<const _Float16*>(g.Wkh); a.N = g.N; a.nkb = g.taps * g.Cin / 32;
-    a.bias = g.bias; a.gamma = g.gamma; a.res = g.res; a.r_bstride = g.r_bstride; a.r_off = g.r_off; a.ldr = g.ldr;
-    a.C = g.C; a.c_bstride = g.c_bstride; a.c_off = g.c_off; a.ldc = g.ldc; a.skip_lo = g.skip_lo; a.skip_hi = g.skip_hi;
-    a.act = g.act; a.w13 = g.w13; a.ovf = g.ovf;
-    a.m_tiles = (g.M + 16 * MT - 1) / (16 * MT); a.n_tiles = (g.N + 16 * NT - 1) / (16 * NT);
-    const size_t smem = (size_t)KW * MT * NT * 256 * sizeof(float);
+    wstream::fill_front(a, g, 32, MT, NT);
+    a.W = reinterpret_cast<const _Float16*>(g.Wkh); a.ovf = g.ovf;
     static DeviceOnce attr;
-    if (attr.needed() && smem > 48 * 1024) {
-        SVA_HIP(hipFuncSetAttribute((const void*)stream_h_gemm_kernel<MT, NT, KW, KB, LOOP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr.done();
-    }
-    hipLaunchKernelGGL((stream_h_gemm_kernel<MT, NT, KW, KB, LOOP>), dim3(a.m_tiles * a.n_tiles), dim3(64 * KW), smem, st, a);
-    return 0;
+    return wstream::launch_tiles(stream_h_gemm_kernel<MT, NT, KW, KB, LOOP>, a, KW, (size_t)KW * MT * NT * 256 * sizeof(float), attr, st);
 }
 
-// registers in flight: (4 NT + 8 MT) KB per lane (weights as 8 halves, activations as 8 floats) -- the budgets of gemm_stream.hip
-template <int MT, int NT, int KW, bool LOOP>
-constexpr int kb_for() {
-    constexpr int per = 4 * NT + 8 * MT;
-    constexpr int budget = KW == 16 ? (LOOP ? 44 : 64) : (LOOP ? 136 : 200);
-    return budget / per > 16 ? 16 : (budget / per < 2 ? 2 : budget / per);
-}
-
+// registers in flight: (4 NT + 8 MT) KB per lane (weights as 8 halves, activations as 8 floats)
 template <int MT, int NT, int KW>
 int launch_stream_h_k(const ConvGemm& g, hipStream_t st) {
     const int nkb = g.taps * g.Cin / 32, need = (nkb + KW - 1) / KW;
-    constexpr int KB0 = kb_for<MT, NT, KW, false>(), KB1 = kb_for<MT, NT, KW, true>();
-#define SVA_KB(KBv) \
-    if constexpr (KBv <= KB0) { if (need <= KBv) return launch_stream_h_kl<MT, NT, KW, KBv, false>(g, st); }
-    SVA_KB(1) SVA_KB(2) SVA_KB(3) SVA_KB(4) SVA_KB(6) SVA_KB(8) SVA_KB(12) SVA_KB(16)
-#undef SVA_KB
+    constexpr int PER = 4 * NT + 8 * MT;
+    constexpr int KB0 = wstream::kb_for<PER, KW, false, 16>(), KB1 = wstream::kb_for<PER, KW, true, 16>();
+    int rc = 0;
+    if (wstream::kb_ladder<KB0>(need, rc, [&](auto kb) { return launch_stream_h_kl<MT, NT, KW, decltype(kb)::value, false>(g, st); })) return rc;
     return launch_stream_h_kl<MT, NT, KW, KB1, true>(g, st);
 }
 
@@ -321,15 +214,10 @@ int launch_stream_h_gemm(const ConvGemm& g, int mt, int nt, int kw, hipStream_t 
     SVA_CHECK(stream_h_gemm_supported(g), "stream_h_gemm: unsupported problem");
     if (mt == 0) stream_h_config(g, &mt, &nt, &kw);
     SVA_CHECK(!(g.w13 && nt != 2), "stream_h_gemm: SwiGLU needs column-tile pairs (nt = 2)");
-#define SVA_SG(MTv, NTv, KWv) \
-    if (mt == MTv && nt == NTv && kw == KWv) return launch_stream_h_k<MTv, NTv, KWv>(g, st);
-    SVA_SG(1, 1, 4) SVA_SG(1, 1, 8) SVA_SG(1, 1, 16)
-    SVA_SG(2, 1, 4) SVA_SG(2, 1, 8) SVA_SG(2, 1, 16)
-    SVA_SG(4, 1, 4) SVA_SG(4, 1, 8)
-    SVA_SG(1, 2, 4) SVA_SG(1, 2, 8) SVA_SG(1, 2, 16)
-    SVA_SG(2, 2, 4) SVA_SG(2, 2, 8)
-    SVA_SG(4, 2, 4) SVA_SG(4, 2, 8)
-#undef SVA_SG
+    int rc = 0;
+    if (wstream::config_ladder(mt, nt, kw, rc, [&](auto MTc, auto NTc, auto KWc) {
+            return launch_stream_h_k<decltype(MTc)::value, decltype(NTc)::value, decltype(KWc)::value>(g, st);
+        })) return rc;
     set_error("stream_h_gemm: bad configuration");
     return -1;
 }

@@ -67,6 +67,8 @@ struct DeviceOnce {
         int dev = 0;
         if (hipGetDevice(&dev) == hipSuccess) mask.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
     }
+    // the one use in the GEMM launchers: raise a kernel's dynamic-LDS limit, once per device (whether at all is the call site's condition)
+    int max_dynamic_lds(const void* kernel, size_t bytes);
 };
 
 #define SVA_HIP(expr)                                                                        \
@@ -78,6 +80,13 @@ struct DeviceOnce {
             return -2;                                                                       \
         }                                                                                    \
     } while (0)
+
+inline int DeviceOnce::max_dynamic_lds(const void* kernel, size_t bytes) {
+    if (!needed()) return 0;
+    SVA_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done();
+    return 0;
+}
 
 #define SVA_TRY_RC(expr)     \
     do {                     \
@@ -101,6 +110,8 @@ struct DeviceOnce {
 // every tensor, so a causal Conv1d is a GEMM whose K axis is split into taps that read
 // shifted rows (no im2col, no bounds checks).  ConvTranspose1d (k = 2*stride or k = stride)
 // is the same GEMM with N = stride*Cout and 2 (or 1) taps -- see DESIGN.md.
+//   epi(v) = (act(v + bias) * gamma + residual) * scale (+ old C); w13: C[., n / 2] = silu(w1 column) * (w3 column); rows t in
+//   [skip_lo, skip_hi) are not stored.  The device code of this contract is gemm_epilogue.h, once for all families.
 // ---------------------------------------------------------------------------------------
 enum ActKind : int { ACT_NONE = 0, ACT_GELU = 1, ACT_LOGCLAMP = 2 };
 // operand-plane formats of gemm_planes.hip: H3 = 2 fp16 planes / three products (fp32-grade inside the fp16 range; sva_config::mm_mode = 1),
@@ -185,11 +196,14 @@ struct ConvGemmGroup {
 inline int xcd_swizzle_for(unsigned nx, unsigned ny) {
     return nx >= 2 && ny >= 16 ? 1 : 0;
 }
+// position of workgroup L of T in that band order (also the tile numbering of the weight-streaming kernels: gemm_stream_common.h)
+__device__ __forceinline__ int xcd_band_index(int L, int T) {
+    const int xcd = L & 7, idx = L >> 3, q = T >> 3, r = T & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
 __device__ __forceinline__ void xcd_tile(int swz, int nx, int ny, int& bx, int& by) {
     if (!(swz & 1)) return;
-    const int T = nx * ny, L = by * nx + bx;
-    const int xcd = L & 7, idx = L >> 3, q = T >> 3, r = T & 7;
-    const int V = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int V = xcd_band_index(by * nx + bx, nx * ny);
     by = V / nx; bx = V - by * nx;
 }
 
@@ -264,7 +278,7 @@ int launch_f16w_gemm(const ConvGemm& g, hipStream_t st);
 // bit 1 = Wsrc is the fragment-major packing of g.W ([N / 16][K / 16][64][4]); probe != 0: timing diagnostics
 bool stream_gemm_supported(const ConvGemm& g);
 int launch_stream_gemm(const ConvGemm& g, const float* Wsrc, int mt, int nt, int kw, int wmode, int probe, hipStream_t st);
-// gemm_stream_h.hip: its fp16-operand sibling (v_mfma_f32_16x16x32_f16 on g.Wkh, activations converted in registers, round to nearest even); the
+// gemm_stream_h.hip: the same skeleton (gemm_stream_common.h) on fp16 operands (v_mfma_f32_16x16x32_f16 on g.Wkh, activations converted in registers, round to nearest even); the
 // encoder's GEMMs below the planes kernel's scale when sva_config.enc_dtype = 1.  mt = 0: (mt, nt, kw) from stream_h_config
 bool stream_h_gemm_supported(const ConvGemm& g);
 void stream_h_config(const ConvGemm& g, int* mt, int* nt, int* kw);

@@ -16,6 +16,7 @@ import torch
 from conftest import load_golden
 from enc_fp16_ref import ENC_FP16_YARDSTICK as Y, agreement, emulated_encode_window
 from kernel_refs import round_f16
+from test_gpu_kernels import digest
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -62,6 +63,7 @@ def _case(rng, B, T, N, Cin, taps=1, dil=1, stride=1, bias=True, gelu=False, gam
     sentinel = np.full((B, T, Nout), 777.0, np.float32)
     out, _ = E.test_gemm_h16(A, W, B, T, taps=taps, dil=dil, stride=stride, bias=b, gamma=gm, res=rs, gelu=gelu, swiglu=swiglu,
                              skip_rows=skip_rows, padded=padded, config=config, out=sentinel)
+    digest("stream_h_gemm", (B, T, N, Cin, taps, dil, stride, bias, gelu, gamma_res, swiglu, skip_rows, padded, config), out)
     a16, w16 = round_f16(A).astype(np.float64), round_f16(W).astype(np.float64)
     acc, mag = np.zeros((B, T, N)), np.zeros((B, T, N))
     for tap in range(taps):

@@ -9,6 +9,7 @@ Exact where the operation is exact: indices, untouched rows / cache entries (a s
 No attention output may exceed the 2e-5 of test_prefill_attention_mfma_vs_fp64 (same input scale); no BSQ u the 2e-5 of the module docstring.
 
 With SVA_KERNEL_PARITY_TABLE=<path> the run writes its table (kernel, shape, error, bound, ratio) there (profiles/kernel_parity.txt)."""
+import hashlib
 import os
 import time
 
@@ -42,9 +43,19 @@ def _E():
     return E
 
 
+def digest(kernel, tag, got):
+    """bit identity between two builds of the library: with SVA_KERNEL_DIGESTS=PATH every compared output appends
+    `kernel, tag, sha1(its bytes)` to that file; run the same tests under both builds (SVA_LIB_PATH) and compare the sorted files"""
+    path = os.environ.get("SVA_KERNEL_DIGESTS")
+    if path:
+        with open(path, "a") as f:
+            f.write("%s, %s, %s\n" % (kernel, tag, hashlib.sha1(np.ascontiguousarray(got).tobytes()).hexdigest()))
+
+
 def _check(record_property, kernel, shape, got, f64, f32=None, extra=0.0, ceiling=None, e32=None):
     """the one floating comparison of this file: err <= min(4 e32 + 4 ulp32(max |ref|) + extra, ceiling); e32 from the float32 restatement
     `f32` of the same elements, or handed in when it was taken on a sub-tensor"""
+    digest(kernel, shape, got)
     got, f64 = np.asarray(got, F64), np.asarray(f64, F64)
     assert got.shape == f64.shape, (kernel, shape, got.shape, f64.shape)
     e32 = R.e32_of(f32, f64) if e32 is None else e32

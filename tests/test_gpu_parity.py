@@ -21,6 +21,27 @@ PCM_TOL = 5e-5
 LOGIT_TOL = 2e-3
 
 
+@pytest.fixture(autouse=True)
+def _gemm_hook_digests(request, monkeypatch):
+    """with SVA_KERNEL_DIGESTS set, every output of the GEMM test hooks called by a test of this file leaves its digest line
+    (test_gpu_kernels.digest): bit identity between two builds of the library"""
+    import os
+
+    if not os.environ.get("SVA_KERNEL_DIGESTS"):
+        return
+    from streamvoiceanon_amd import engine as E
+    from test_gpu_kernels import digest
+
+    calls = [0]
+    for name in ("test_gemm_choice", "test_gemm_planes", "test_gemm_f16w"):
+        def hook(*a, _fn=getattr(E, name), _name=name, **kw):
+            out = _fn(*a, **kw)
+            calls[0] += 1
+            digest(_name, "%s #%d" % (request.node.name, calls[0]), out[0] if isinstance(out, tuple) else out)
+            return out
+        monkeypatch.setattr(E, name, hook)
+
+
 @pytest.fixture(scope="module")
 def eng(weights0):
     from streamvoiceanon_amd import engine as E
