@@ -122,6 +122,52 @@ struct ResConv {
     int Kq = 0;
 };
 
+// How a HiFiGAN level (ParallelBlock) runs: a static choice per batch (engine.hip, voc_level_form), since the level's history lives in one form
+enum class VocForm {
+    Rows,          // fp32 rows, SiLU on load: one grouped conv-GEMM launch per conv stage
+    Fused,         // narrow level as one LDS-resident launch (voc_fused.hip): the input's history is its only streaming state
+    PlanesDma,     // K-blocked operand planes + the LDS-DMA GEMM's conv form (C >= 64)
+    PlanesHalo,    // row-major operand planes + voc_conv_kernel (C = 16 / 32)
+};
+inline bool voc_form_planes(VocForm f) { return f == VocForm::PlanesDma || f == VocForm::PlanesHalo; }
+
+struct VocLevel {
+    Act X;                                 // resblock input
+    Act tb[3][3];                          // [branch][stage] c1 outputs
+    Act yb[3][2];                          // y_{b,1}, y_{b,2}
+    Act y3[3];                             // y_{b,3}: branch outputs before the ParallelBlock mean (no history)
+    // planes forms: the conv inputs silu(X), silu(tb), silu(yb) live as operand planes over the same dense rows as the fp32 tensors above
+    // (history rows included: they are the streaming state of such a level; the fp32 tensors are read as residuals only)
+    unsigned short* XP = nullptr;
+    unsigned short* tbP[3][3] = {};
+    unsigned short* ybP[3][2] = {};
+    int rpf = 0;                           // rows per code frame
+    VocForm form = VocForm::Rows;
+};
+
+// Everything vocode() (stages.hip) reads and writes besides the launch context (streams, B, CU limit, overflow flag, GEMM counters) of its batch
+struct VocWorkspace {
+    int Tv = 0;                            // max code frames per call
+    Act zq;                                // [B][Tv][512]
+    Act u0, v0, u1, pin;                   // upsample stack, conv_pre input
+    float *vh1 = nullptr, *vh2 = nullptr;  // ConvNeXt scratch
+    Act S[6];                              // S[i] = input of ups.i (i<5); S[5] = conv_post input
+    VocLevel lv[5];
+    int pmode = -1;                        // PlanesMode of the levels in a planes form
+    int* d_frames = nullptr;               // code frames the streaming vocoder has consumed since its last reset
+    float* d_pcm = nullptr;                // [B][2048*Tv]
+    int* d_vcodes = nullptr;               // [B][8][Tv]
+    std::vector<ShiftDesc> shift_host;     // history rows of the streaming state, in the order of for_each_voc_state (engine_internal.h)
+    ShiftDesc* d_shift = nullptr;
+    // per-step redirections of the device-buffer step (no staging copies): PCM destination, codes source
+    float* pcm_dst = nullptr;              // conv_post_tanh writes straight into the caller's buffer ([B][2048*chunk])
+    long pcm_dst_bstride = 0;
+    bool pcm_direct_done = false;
+    const int* codes = nullptr;            // FSQ decode reads the step's audio codes in place
+    long codes_bstride = 0, codes_gstride = 0;
+    hipEvent_t codes_event = nullptr;      // recorded right after the FSQ decode has been enqueued (pipelined hand-off)
+};
+
 }  // namespace sva
 
 struct sva_engine {
@@ -305,43 +351,16 @@ struct sva_batch {
     long voc_save_bstride = 0;
     long* d_voc_save_offs = nullptr;       // [shift_host.size()] offset of each desc's rows inside a slot's block
     float* prime_pcm = nullptr;            // [B][2048 * chunk] PCM sink of the priming run (the step's own PCM stays where it is)
-    // slot-local priming (p.slot_priming): a one-stream, vocoder-only workspace owned by this batch.  Only the fields vocode() reads are
-    // set up in it; every level keeps the form of this batch, so its ShiftDesc table is parallel to this one's (same count, same H / C
-    // per entry) and one kernel moves slot 0 of it into a slot of this batch.  Not a stream batch: no encoder, AR or KV memory, not
-    // counted in persistent_batches.
+    // slot-local priming (p.slot_priming): a one-stream vocoder owned by this batch.  An sva_batch of which two things are set up: the launch
+    // context (B = 1, this batch's streams, CU limit and overflow flag) and `voc`, allocated with every level in the form of this batch's `voc`,
+    // so its ShiftDesc table is parallel to this one's (same count, same H / C per entry) and one kernel moves slot 0 of it into a slot of
+    // this batch.  Not a stream batch: no encoder, AR or KV memory, not counted in persistent_batches.
     sva_batch* prime_ws = nullptr;
     long n_act_local = 0, n_act_whole = 0; // activations primed through the workspace / through the whole-batch run
     float last_act_ms = 0.f;               // host wall time of the last activate_slot, taken after its final synchronise
 
-    // ---- vocoder workspace ----
-    int Tv = 0;                            // max code frames per call
-    sva::Act zq;                           // [B][Tv][512]
-    sva::Act u0, v0, u1, pin;              // upsample stack, conv_pre input
-    float *vh1 = nullptr, *vh2 = nullptr;  // ConvNeXt scratch
-    sva::Act S[6];                         // S[i] = input of ups.i (i<5); S[5] = conv_post input
-    sva::Act X[5];                         // resblock inputs
-    sva::Act tb[5][3][3];                  // c1 outputs
-    sva::Act yb[5][3][2];                  // y_{b,1}, y_{b,2}
-    sva::Act y3[5][3];                     // y_{b,3}: branch outputs before the ParallelBlock mean (no history)
-    // wide levels on the LDS-DMA planes kernel (stages.hip, vocode): the conv inputs silu(X), silu(tb), silu(yb) live as K-blocked operand
-    // planes over the same dense rows as the fp32 tensors above (history rows included: they are the streaming state of such a level)
-    int voc_dma[5] = {0, 0, 0, 0, 0};        // 1: K-blocked planes + the LDS-DMA GEMM's conv form (C >= 64); 2: row-major planes + voc_conv_kernel (C = 16 / 32)
-    int voc_pmode = -1;
-    unsigned short* XP[5] = {};
-    unsigned short* tbP[5][3][3] = {};
-    unsigned short* ybP[5][3][2] = {};
-    float* d_pcm = nullptr;                // [B][2048*Tv]
-    // per-step redirections of the device-buffer step (no staging copies): chunk source, PCM destination, codes source
-    const float* step_src = nullptr;       // ring_write reads the caller's chunk directly
-    float* pcm_dst = nullptr;              // conv_post_tanh writes straight into the caller's buffer ([B][2048*chunk])
-    long pcm_dst_bstride = 0;
-    const int* voc_codes = nullptr;        // FSQ decode reads the step's audio codes in place
-    long voc_codes_bstride = 0, voc_codes_gstride = 0;
-    hipEvent_t voc_codes_event = nullptr;  // recorded right after the FSQ decode has been enqueued (pipelined hand-off)
-    bool pcm_direct_done = false;
-    int* d_vcodes = nullptr;               // [B][8][Tv]
-    std::vector<sva::ShiftDesc> shift_host;
-    sva::ShiftDesc* d_shift = nullptr;
+    sva::VocWorkspace voc;
+    const float* step_src = nullptr;       // device-buffer step: ring_write reads the caller's chunk directly (no staging copy)
 
     // pinned staging
     float *hp_in = nullptr, *hp_out = nullptr;
@@ -368,10 +387,6 @@ struct sva_batch {
     hipGraphExec_t gEm[2] = {nullptr, nullptr}, gEs[2] = {nullptr, nullptr};      // front-end cut behind the backbone: main part / side part, per parity
     hipEvent_t pipe_evFeat[2] = {nullptr, nullptr};
     int* step_bump = nullptr;              // set around a front-end call whose last kernel should also advance this counter
-    int voc_fused_mask = -1;               // -1: default policy; else bit 0: the C = 16 level, bit 1: the C = 32 level
-    bool voc_fused = true;                 // narrow vocoder levels (C <= 32) as one fused launch (voc_fused.hip)
-    int* d_voc_frames = nullptr;           // code frames the streaming vocoder has consumed since its last reset
-    int voc_rpf[5] = {0, 0, 0, 0, 0};      // rows of level i per code frame
     hipGraphExec_t gT0 = nullptr, gT1[2] = {nullptr, nullptr}, gV = nullptr;
     bool graph_ready = false;
     bool graph_step = false;       // last step ran through the graph (no per-stage events)

@@ -234,113 +234,107 @@ static bool abatch_serves(int B, int ar_dtype, bool pipelined, int chunk) {
     return r ? r->decode == 2 : B <= 32;
 }
 
-// The vocoder workspace of a batch: activations with their history rows, operand planes, the ShiftDesc table, code and PCM buffers for up to
-// Tv code frames per call.  The FORM of every HiFiGAN level -- fp32 rows, the fused C = 16 level, K-blocked planes, row-major planes -- is a
-// static choice per batch, derived here from its streams and Tv (forms == nullptr), or taken over from the batch `forms` that owns this one as
-// its priming workspace: the history rows of the two must be the same rows in the same layout, whatever B = 1 and its Tv would have chosen.
-static int alloc_vocoder(sva_batch* b, int Tv, const sva_batch* forms) {
+// The form of HiFiGAN level `level` (C = ch, rpf rows per code frame) of a batch of B streams and Tv code frames per call.
+// Fused (voc_fused.hip): measured on MI355X (profiles/r02_voc_fused.txt), the C = 16 level takes 27-33 us fused against 7 launches / ~70 us at
+// one stream and breaks even around 4-8 streams; from there on, and for C = 32 at any batch, the tap-split GEMM formulation is faster (the fused
+// kernel recomputes an 18 (k - 1)-row halo per tile and runs one workgroup per CU), so the default fuses C = 16 for <= 4 streams.
+// SVA_DEBUG=voc_fused_mask=M (bit 0: C = 16, bit 1: C = 32) / sva_debug_configure override it for the parity tests.
+// Planes: every other level of a batch with enough rows per step runs its 18 ResBlock convs on operand planes, three branches per launch, the
+// activations between them as planes (history included).  From 10 code frames per step over the batch (streams x voc_max_frames): +4.7 / +5.7 /
+// +6.7 / +5.2 / +3.9 % frames/s at 16 / 24 / 32 / 48 / 128 streams, +2 % and a 6 % shorter synchronous step at 10 / 12, even at 8
+// (profiles/r05_voc_dma_sweep.txt).  C = 16 / 32: row-major planes + voc_conv_kernel (the input rows of a tile and the branch's whole weight
+// resident in LDS); wider: K-blocked planes + the LDS-DMA GEMM's conv form.  A level whose weights lack the planes of its form stays on fp32 rows.
+static int voc_planes_mode(const sva_config& c) { return c.voc_dtype == 1 ? PLANES_H1 : (c.mm_mode == 1 ? PLANES_H3 : -1); }
+static VocForm voc_level_form(const sva_engine* e, int level, int ch, int rpf, int B, int Tv) {
+    const DebugOptions& o = debug_options();
+    if (voc_level_supported(ch) && (o.voc_fused_mask >= 0 ? (o.voc_fused_mask & (ch == 16 ? 1 : 2)) != 0 : ch == 16 && B <= 4)) return VocForm::Fused;
+    const int pm = voc_planes_mode(e->cfg);
+    if (!(ch % 16 == 0 && pm >= 0 && o.planes_dma != 0 && o.voc_dma != 0 && (o.voc_dma == 1 || (long)B * Tv >= 10))) return VocForm::Rows;
+    const bool halo = ch <= 32 && voc_conv_supported(ch, rpf, pm);
+    for (const auto& branch : e->res[level])
+        for (const ResConv& rcv : branch)
+            if (halo ? !(rcv.q1 && rcv.q2) : !(ch % 64 == 0 && rcv.c1.Wp && rcv.c2.Wp && rcv.c1.pmode == pm && rcv.c2.pmode == pm)) return VocForm::Rows;
+    return halo ? VocForm::PlanesHalo : VocForm::PlanesDma;
+}
+
+// The vocoder workspace of batch b: activations with their history rows, operand planes, the ShiftDesc table, code and PCM buffers for up to
+// Tv code frames per call.  Every level's form is derived from the batch (owner == nullptr), or taken over from the workspace `owner` of the
+// batch that owns b as its priming workspace: the history rows of the two must be the same rows in the same layout, whatever B = 1 and its Tv
+// would have chosen.
+static int alloc_vocoder(sva_batch* b, int Tv, const VocWorkspace* owner) {
     sva_engine* e = b->e;
     const sva_config& c = e->cfg;
     auto& A = b->allocs;
+    VocWorkspace& v = b->voc;
     const int B = b->B, V = c.voc_dim, ncb = c.num_codebooks;
-    b->Tv = Tv;
-    if (forms) {
-        b->voc_fused = forms->voc_fused;
-        b->voc_fused_mask = (voc_level_is_fused(forms, 16) ? 1 : 0) | (voc_level_is_fused(forms, 32) ? 2 : 0);
-    } else if (debug_options().voc_fused_mask >= 0) b->voc_fused_mask = debug_options().voc_fused_mask;
-    SVA_TRY(dev_alloc(A, &b->d_voc_frames, 1));
-    SVA_HIP(hipMemset(b->d_voc_frames, 0, sizeof(int)));
-    SVA_TRY(alloc_act(A, b->zq, B, 0, Tv, V));
-    SVA_TRY(alloc_act(A, b->u0, B, 6, 2L * Tv, V));
-    SVA_TRY(alloc_act(A, b->v0, B, 0, 2L * Tv, V));
-    SVA_TRY(alloc_act(A, b->u1, B, 6, 4L * Tv, V));
-    SVA_TRY(alloc_act(A, b->pin, B, e->pre_k - 1, 4L * Tv, V));
-    SVA_TRY(dev_alloc(A, &b->vh1, (size_t)B * 4 * Tv * V));
-    SVA_TRY(dev_alloc(A, &b->vh2, (size_t)B * 4 * Tv * 4 * V));
-    SVA_TRY(alloc_act(A, b->S[0], B, 1, 4L * Tv, V));
-    SVA_TRY(register_shift(b, b->u0, 2));
-    SVA_TRY(register_shift(b, b->u1, 4));
-    SVA_TRY(register_shift(b, b->pin, 4));
-    SVA_TRY(register_shift(b, b->S[0], 4));
+    v.Tv = Tv;
+    SVA_TRY(dev_alloc(A, &v.d_frames, 1));
+    SVA_TRY(alloc_act(A, v.zq, B, 0, Tv, V));
+    SVA_TRY(alloc_act(A, v.u0, B, 6, 2L * Tv, V));
+    SVA_TRY(alloc_act(A, v.v0, B, 0, 2L * Tv, V));
+    SVA_TRY(alloc_act(A, v.u1, B, 6, 4L * Tv, V));
+    SVA_TRY(alloc_act(A, v.pin, B, e->pre_k - 1, 4L * Tv, V));
+    SVA_TRY(dev_alloc(A, &v.vh1, (size_t)B * 4 * Tv * V));
+    SVA_TRY(dev_alloc(A, &v.vh2, (size_t)B * 4 * Tv * 4 * V));
+    SVA_TRY(alloc_act(A, v.S[0], B, 1, 4L * Tv, V));
     long rows = 4L * Tv;
     int rpf = 4;
     int ch = V;
     for (int i = 0; i < 5; ++i) {
+        VocLevel& l = v.lv[i];
         rows *= e->ups_s[i];
         rpf *= e->ups_s[i];
         ch /= 2;
-        b->voc_rpf[i] = rpf;
-        const bool fused_level = voc_level_is_fused(b, ch);
-        // Every level of a batch with enough rows per step: the 18 ResBlock convs on operand planes, three branches per launch (C >= 64: the LDS-DMA
-        // planes kernel's conv form; C = 16 / 32: voc_conv_kernel), the activations between them as planes (history included).  A static choice per
-        // batch -- the history lives in one form.  From 10 code frames per step over the batch (streams x voc_max_frames): +4.7 / +5.7 / +6.7 / +5.2 /
-        // +3.9 % frames/s at 16 / 24 / 32 / 48 / 128 streams, +2 % and a 6 % shorter synchronous step at 10 / 12, even at 8 (profiles/r05_voc_dma_sweep.txt)
-        const int voc_pm = c.voc_dtype == 1 ? PLANES_H1 : (c.mm_mode == 1 ? PLANES_H3 : -1);
-        bool dma_level = forms ? forms->voc_dma[i] != 0
-                               : !fused_level && ch % 16 == 0 && voc_pm >= 0 && debug_options().planes_dma != 0 && debug_options().voc_dma != 0 &&
-                                     (debug_options().voc_dma == 1 || (long)B * Tv >= 10);
-        // C = 16 / 32: row-major planes + voc_conv_kernel (the input rows of a tile and the branch's whole weight resident in LDS); wider: K-blocked planes +
-        // the LDS-DMA GEMM's conv form
-        const bool halo_level = forms ? forms->voc_dma[i] == 2 : dma_level && ch <= 32 && voc_conv_supported(ch, rpf, voc_pm);
-        for (int br = 0; br < 3 && dma_level && !forms; ++br)
-            for (int j = 0; j < 3; ++j) {
-                const ResConv& rcv = e->res[i][br][j];
-                if (halo_level) dma_level = dma_level && rcv.q1 && rcv.q2;
-                else dma_level = dma_level && ch % 64 == 0 && rcv.c1.Wp && rcv.c2.Wp && rcv.c1.pmode == voc_pm && rcv.c2.pmode == voc_pm;
-            }
-        if (dma_level) b->voc_pmode = voc_pm;
-        b->voc_dma[i] = dma_level ? (halo_level ? 2 : 1) : 0;
-        auto alloc_planes = [&](const Act& a, unsigned short** P) -> int {
-            const int npl = planes_count(b->voc_pmode);
-            const size_t n = (size_t)npl * B * a.bstride;
-            SVA_TRY(dev_alloc(A, P, n));
-            if (a.H == 0) return 0;
-            for (int p = 0; p < npl; ++p) {
-                if (halo_level) {       // row-major plane: a [B][rows][C / 2 floats] tensor
-                    ShiftDesc d;
-                    d.ptr = reinterpret_cast<float*>(*P + (size_t)p * B * a.bstride);
-                    d.bstride = a.rows * (a.C / 2); d.H = a.H; d.T = 0; d.C = a.C / 2; d.pad = rpf;
-                    b->shift_host.push_back(d);
-                    continue;
-                }
-                // K-blocked: the history rows of every (plane, 32-channel block) shift like a [B][rows][16 floats] tensor of its own
-                for (int kb = 0; kb < a.C / 32; ++kb) {
-                    ShiftDesc d;
-                    d.ptr = reinterpret_cast<float*>(*P + (size_t)p * B * a.bstride + (size_t)kb * B * a.rows * 32);
-                    d.bstride = a.rows * 16; d.H = a.H; d.T = 0; d.C = 16; d.pad = rpf;
-                    b->shift_host.push_back(d);
-                }
-            }
-            return 0;
+        l.rpf = rpf;
+        l.form = owner ? owner->lv[i].form : voc_level_form(e, i, ch, rpf, B, Tv);
+        if (voc_form_planes(l.form)) v.pmode = voc_planes_mode(c);
+        // every streaming tensor of the level, in a planes form followed by its operand planes.  The allocation keeps a loop of its own beside
+        // for_each_voc_state: the stateless tensors (zq, v0, y3, the scratch) lie between the streaming ones, and the order in the arena is part
+        // of the measured behaviour (all streaming tensors first: -0.3 % frames/s at one stream, profiles/voc_workspace_refactor_ab.txt)
+        auto alloc = [&](Act& a, unsigned short*& P, int H) -> int {
+            SVA_TRY(alloc_act(A, a, B, H, rows, ch));
+            return voc_form_planes(l.form) ? dev_alloc(A, &P, (size_t)planes_count(v.pmode) * B * a.bstride) : 0;
         };
         // fused levels keep the receptive field of the whole six-conv chain as input history (their only streaming state)
-        SVA_TRY(alloc_act(A, b->X[i], B, fused_level ? (kResK[2] - 1) * 2 * (kResD[0] + kResD[1] + kResD[2]) : (kResK[2] - 1) * kResD[0], rows, ch));
-        if (dma_level) SVA_TRY(alloc_planes(b->X[i], &b->XP[i]));        // (the fp32 tensors of such a level are read as residuals only: current rows)
-        else SVA_TRY(register_shift(b, b->X[i], rpf));
+        SVA_TRY(alloc(l.X, l.XP, l.form == VocForm::Fused ? (kResK[2] - 1) * 2 * (kResD[0] + kResD[1] + kResD[2]) : (kResK[2] - 1) * kResD[0]));
         for (int br = 0; br < 3; ++br)
             for (int j = 0; j < 3; ++j) {
-                SVA_TRY(alloc_act(A, b->tb[i][br][j], B, (kResK[br] - 1) * kResD[j], rows, ch));
-                if (dma_level) SVA_TRY(alloc_planes(b->tb[i][br][j], &b->tbP[i][br][j]));
-                else SVA_TRY(register_shift(b, b->tb[i][br][j], rpf));
-                if (j < 2) {
-                    SVA_TRY(alloc_act(A, b->yb[i][br][j], B, (kResK[br] - 1) * kResD[j + 1], rows, ch));
-                    if (dma_level) SVA_TRY(alloc_planes(b->yb[i][br][j], &b->ybP[i][br][j]));
-                    else SVA_TRY(register_shift(b, b->yb[i][br][j], rpf));
-                }
+                SVA_TRY(alloc(l.tb[br][j], l.tbP[br][j], (kResK[br] - 1) * kResD[j]));
+                if (j < 2) SVA_TRY(alloc(l.yb[br][j], l.ybP[br][j], (kResK[br] - 1) * kResD[j + 1]));
             }
-        for (int br = 0; br < 3; ++br) SVA_TRY(alloc_act(A, b->y3[i][br], B, 0, rows, ch));
-        SVA_TRY(alloc_act(A, b->S[i + 1], B, i < 4 ? 1 : e->post_k - 1, rows, ch));
-        SVA_TRY(register_shift(b, b->S[i + 1], rpf));
+        for (int br = 0; br < 3; ++br) SVA_TRY(alloc_act(A, l.y3[br], B, 0, rows, ch));
+        SVA_TRY(alloc_act(A, v.S[i + 1], B, i < 4 ? 1 : e->post_k - 1, rows, ch));
     }
-    SVA_TRY(dev_alloc(A, &b->d_pcm, (size_t)B * 2048 * Tv));
-    SVA_TRY(dev_alloc(A, &b->d_vcodes, (size_t)B * ncb * Tv));
-    SVA_TRY(dev_alloc(A, &b->d_shift, b->shift_host.size()));
+    // the ShiftDesc table: the fp32 rows themselves, or in a planes form the tensor's operand planes
+    SVA_TRY(for_each_voc_state(v, [&](Act& a, unsigned short*& P, int rpf, VocForm form) -> int {
+        if (!voc_form_planes(form)) return register_shift(b, a, rpf);
+        for (int p = 0; p < planes_count(v.pmode) && a.H > 0; ++p) {
+            ShiftDesc d;
+            d.H = a.H; d.T = 0; d.pad = rpf;
+            if (form == VocForm::PlanesHalo) {       // row-major plane: a [B][rows][C / 2 floats] tensor
+                d.ptr = reinterpret_cast<float*>(P + (size_t)p * B * a.bstride);
+                d.bstride = a.rows * (a.C / 2); d.C = a.C / 2;
+                v.shift_host.push_back(d);
+                continue;
+            }
+            // K-blocked: the history rows of every (plane, 32-channel block) shift like a [B][rows][16 floats] tensor of its own
+            for (int kb = 0; kb < a.C / 32; ++kb) {
+                d.ptr = reinterpret_cast<float*>(P + (size_t)p * B * a.bstride + (size_t)kb * B * a.rows * 32);
+                d.bstride = a.rows * 16; d.C = 16;
+                v.shift_host.push_back(d);
+            }
+        }
+        return 0;
+    }));
+    SVA_TRY(dev_alloc(A, &v.d_pcm, (size_t)B * 2048 * Tv));
+    SVA_TRY(dev_alloc(A, &v.d_vcodes, (size_t)B * ncb * Tv));
+    SVA_TRY(dev_alloc(A, &v.d_shift, v.shift_host.size()));
     return 0;
 }
 
-// Slot-local activation (sva_stream_params.slot_priming): the one-stream vocoder workspace a restarted slot's state is primed in.  An internal
-// sva_batch on which only what vocode() reads is set up; it runs on the owner's stream with the owner's CU limit and reports fp16-range
-// overflows through the owner's flag.  Allocated with the owner so that no activating step allocates; freed by sva_batch_destroy(owner).
+// Slot-local activation (sva_stream_params.slot_priming): the one-stream vocoder a restarted slot's state is primed in.  An internal sva_batch
+// = a launch context (the owner's stream, CU limit and fp16-range overflow flag, B = 1) + a vocoder workspace in the owner's forms.  Allocated
+// with the owner so that no activating step allocates; freed by sva_batch_destroy(owner).
 static int create_priming_workspace(sva_batch* b) {
     const int chunk = b->p.chunk_frames;
     const int Tv = ((b->p.decode_window_frames - 1) / chunk) * chunk;
@@ -360,16 +354,19 @@ static int create_priming_workspace(sva_batch* b) {
     w->enc_cus = b->enc_cus;
     w->d_mm_ovf = b->d_mm_ovf;              // (h_mm_ovf stays null here: the owner polls and frees the flag)
     for (int i = 0; i < 64; ++i) SVA_HIP(hipEventCreateWithFlags(&w->evpool[i], hipEventDisableTiming));
-    SVA_TRY(alloc_vocoder(w, Tv, b));
-    // the move kernel walks the two tables in parallel: refuse anything else here, not in an activating step
-    bool parallel = w->shift_host.size() == b->shift_host.size() && w->voc_pmode == b->voc_pmode;
-    for (size_t i = 0; parallel && i < w->shift_host.size(); ++i) {
-        const ShiftDesc &x = w->shift_host[i], &y = b->shift_host[i];
-        parallel = x.H == y.H && x.C == y.C && x.pad == y.pad && (long)y.H * y.C <= y.bstride && (long)x.H * x.C <= x.bstride;
-    }
-    for (int i = 0; i < 5; ++i) parallel = parallel && w->voc_dma[i] == b->voc_dma[i] && w->voc_rpf[i] == b->voc_rpf[i];
-    SVA_CHECK(parallel, "slot_priming: the priming workspace's vocoder state is not in the form of the batch's (history descriptors differ)");
-    SVA_HIP(hipMemcpy(w->d_shift, w->shift_host.data(), sizeof(ShiftDesc) * w->shift_host.size(), hipMemcpyHostToDevice));
+    SVA_TRY(alloc_vocoder(w, Tv, &b->voc));
+    // the move kernel walks the two ShiftDesc tables in parallel: refuse anything but the same state in the same form here, not in an activating step
+    auto state = [](VocWorkspace& v) {
+        std::vector<std::array<int, 5>> s;
+        for_each_voc_state(v, [&](Act& a, unsigned short*& P, int rpf, VocForm form) -> int {
+            s.push_back({a.H, a.C, rpf, (int)form, P != nullptr});
+            return 0;
+        });
+        return s;
+    };
+    SVA_CHECK(state(w->voc) == state(b->voc) && w->voc.pmode == b->voc.pmode && w->voc.shift_host.size() == b->voc.shift_host.size(),
+              "slot_priming: the priming workspace's vocoder state is not in the form of the batch's (history descriptors differ)");
+    SVA_HIP(hipMemcpy(w->voc.d_shift, w->voc.shift_host.data(), sizeof(ShiftDesc) * w->voc.shift_host.size(), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -816,30 +813,12 @@ extern "C" int sva_vocode_reset(sva_batch* b) {
     SVA_HIP(hipSetDevice(b->e->device));
     (void)hipGetLastError();
     SVA_TRY(quiesce(b));
-    auto zero = [&](Act& a) -> int {
+    SVA_HIP(hipMemsetAsync(b->voc.d_frames, 0, sizeof(int), b->stream));
+    SVA_TRY(for_each_voc_state(b->voc, [&](Act& a, unsigned short*& P, int, VocForm) -> int {
         SVA_HIP(hipMemsetAsync(a.p, 0, sizeof(float) * (size_t)b->B * a.bstride, b->stream));
+        if (P) SVA_HIP(hipMemsetAsync(P, 0, sizeof(unsigned short) * (size_t)planes_count(b->voc.pmode) * b->B * a.bstride, b->stream));
         return 0;
-    };
-    SVA_TRY(zero(b->u0)); SVA_TRY(zero(b->u1)); SVA_TRY(zero(b->pin));
-    SVA_HIP(hipMemsetAsync(b->d_voc_frames, 0, sizeof(int), b->stream));
-    for (int i = 0; i < 6; ++i) SVA_TRY(zero(b->S[i]));
-    auto zero_planes = [&](const Act& a, unsigned short* P) -> int {
-        if (P) SVA_HIP(hipMemsetAsync(P, 0, sizeof(unsigned short) * (size_t)planes_count(b->voc_pmode) * b->B * a.bstride, b->stream));
-        return 0;
-    };
-    for (int i = 0; i < 5; ++i) {
-        SVA_TRY(zero(b->X[i]));
-        SVA_TRY(zero_planes(b->X[i], b->XP[i]));
-        for (int br = 0; br < 3; ++br)
-            for (int j = 0; j < 3; ++j) {
-                SVA_TRY(zero(b->tb[i][br][j]));
-                SVA_TRY(zero_planes(b->tb[i][br][j], b->tbP[i][br][j]));
-                if (j < 2) {
-                    SVA_TRY(zero(b->yb[i][br][j]));
-                    SVA_TRY(zero_planes(b->yb[i][br][j], b->ybP[i][br][j]));
-                }
-            }
-    }
+    }));
     SVA_HIP(hipStreamSynchronize(b->stream));
     return 0;
 }
@@ -848,12 +827,12 @@ namespace {
 int upload_vcodes(sva_batch* b, const int32_t* codes, int T) {
     // host codes [B][8][T] -> d_vcodes [B][8][Tv]
     const int ncb = b->e->cfg.num_codebooks;
-    SVA_HIP(hipMemcpy2DAsync(b->d_vcodes, sizeof(int) * b->Tv, codes, sizeof(int) * T, sizeof(int) * T, (size_t)b->B * ncb,
+    SVA_HIP(hipMemcpy2DAsync(b->voc.d_vcodes, sizeof(int) * b->voc.Tv, codes, sizeof(int) * T, sizeof(int) * T, (size_t)b->B * ncb,
                              hipMemcpyHostToDevice, b->stream));
     return 0;
 }
 int download_pcm(sva_batch* b, int T, float* pcm_out) {
-    SVA_HIP(hipMemcpy2DAsync(pcm_out, sizeof(float) * 2048 * T, b->d_pcm, sizeof(float) * 2048 * b->Tv, sizeof(float) * 2048 * T, b->B,
+    SVA_HIP(hipMemcpy2DAsync(pcm_out, sizeof(float) * 2048 * T, b->voc.d_pcm, sizeof(float) * 2048 * b->voc.Tv, sizeof(float) * 2048 * T, b->B,
                              hipMemcpyDeviceToHost, b->stream));
     SVA_HIP(hipStreamSynchronize(b->stream));
     return 0;
@@ -862,7 +841,7 @@ int download_pcm(sva_batch* b, int T, float* pcm_out) {
 
 extern "C" int sva_vocode_stream(sva_batch* b, const int32_t* codes, int T, float* pcm_out) {
     SVA_CHECK(b && codes && pcm_out, "null argument");
-    SVA_CHECK(T >= 1 && T <= b->Tv, "vocode: T out of range (1 .. voc_max_frames)");
+    SVA_CHECK(T >= 1 && T <= b->voc.Tv, "vocode: T out of range (1 .. voc_max_frames)");
     SVA_HIP(hipSetDevice(b->e->device));
     (void)hipGetLastError();
     SVA_TRY(quiesce(b));
@@ -873,7 +852,7 @@ extern "C" int sva_vocode_stream(sva_batch* b, const int32_t* codes, int T, floa
 
 extern "C" int sva_vocode_window(sva_batch* b, const int32_t* codes, int T, float* pcm_out) {
     SVA_CHECK(b && codes && pcm_out, "null argument");
-    SVA_CHECK(T >= 1 && T <= b->Tv, "vocode: T out of range (1 .. voc_max_frames)");
+    SVA_CHECK(T >= 1 && T <= b->voc.Tv, "vocode: T out of range (1 .. voc_max_frames)");
     SVA_TRY(sva_vocode_reset(b));
     SVA_TRY(sva_vocode_stream(b, codes, T, pcm_out));
     return sva_vocode_reset(b);
@@ -883,12 +862,12 @@ extern "C" int sva_vocode_window(sva_batch* b, const int32_t* codes, int T, floa
 // (channel-last; the reference tensor is [B, 512, 4T]), window semantics (zero history) like sva_vocode_window
 extern "C" int sva_quantizer_decode(sva_batch* b, const int32_t* codes, int T, float* z_out) {
     SVA_CHECK(b && codes && z_out, "null argument");
-    SVA_CHECK(T >= 1 && T <= b->Tv, "quantizer_decode: T out of range (1 .. voc_max_frames)");
+    SVA_CHECK(T >= 1 && T <= b->voc.Tv, "quantizer_decode: T out of range (1 .. voc_max_frames)");
     SVA_TRY(sva_vocode_reset(b));
     SVA_TRY(upload_vcodes(b, codes, T));
-    SVA_TRY(vocode(b, T, false, 1));
+    SVA_TRY(vocode(b, T, false, VocPart::QuantizerDecode));
     const int V = b->e->cfg.voc_dim;
-    SVA_HIP(hipMemcpy2DAsync(z_out, sizeof(float) * 4 * T * V, b->pin.p + (long)b->pin.H * V, sizeof(float) * b->pin.bstride, sizeof(float) * 4 * T * V, b->B,
+    SVA_HIP(hipMemcpy2DAsync(z_out, sizeof(float) * 4 * T * V, b->voc.pin.p + (long)b->voc.pin.H * V, sizeof(float) * b->voc.pin.bstride, sizeof(float) * 4 * T * V, b->B,
                              hipMemcpyDeviceToHost, b->stream));
     SVA_HIP(hipStreamSynchronize(b->stream));
     return sva_vocode_reset(b);
@@ -897,12 +876,12 @@ extern "C" int sva_quantizer_decode(sva_batch* b, const int32_t* codes, int T, f
 // firefly.head (HiFiGANGenerator.forward, firefly.py:280-293) as a seam of its own: z float[B][4T][512] -> pcm float[B][2048 T]
 extern "C" int sva_vocoder_head(sva_batch* b, const float* z, int T, float* pcm_out) {
     SVA_CHECK(b && z && pcm_out, "null argument");
-    SVA_CHECK(T >= 1 && T <= b->Tv, "vocoder_head: T out of range (1 .. voc_max_frames)");
+    SVA_CHECK(T >= 1 && T <= b->voc.Tv, "vocoder_head: T out of range (1 .. voc_max_frames)");
     SVA_TRY(sva_vocode_reset(b));
     const int V = b->e->cfg.voc_dim;
-    SVA_HIP(hipMemcpy2DAsync(b->pin.p + (long)b->pin.H * V, sizeof(float) * b->pin.bstride, z, sizeof(float) * 4 * T * V, sizeof(float) * 4 * T * V, b->B,
+    SVA_HIP(hipMemcpy2DAsync(b->voc.pin.p + (long)b->voc.pin.H * V, sizeof(float) * b->voc.pin.bstride, z, sizeof(float) * 4 * T * V, sizeof(float) * 4 * T * V, b->B,
                              hipMemcpyHostToDevice, b->stream));
-    SVA_TRY(vocode(b, T, false, 2));
+    SVA_TRY(vocode(b, T, false, VocPart::Head));
     SVA_TRY(download_pcm(b, T, pcm_out));
     return sva_vocode_reset(b);
 }
@@ -1089,9 +1068,9 @@ int steady_launches(sva_batch* b, bool timing_events) {
     if (timing_events) SVA_HIP(hipEventRecord(b->ev[1], st));
     for (int ci = 0; ci < chunk; ++ci) SVA_TRY(ar_decode_frame(b, ci, b->d_codes, b->T2, b->T2 - chunk + ci));          // :534-538
     if (timing_events) SVA_HIP(hipEventRecord(b->ev[2], st));
-    b->voc_codes = b->d_step_audio; b->voc_codes_bstride = (long)ncb * chunk; b->voc_codes_gstride = chunk;      // read in place
+    b->voc.codes = b->d_step_audio; b->voc.codes_bstride = (long)ncb * chunk; b->voc.codes_gstride = chunk;      // read in place
     const int vrc = vocode(b, chunk, true);
-    b->voc_codes = nullptr;
+    b->voc.codes = nullptr;
     if (vrc) return vrc;
     if (timing_events) SVA_HIP(hipEventRecord(b->ev[3], st));
     return 0;
@@ -1275,17 +1254,17 @@ int steady_pipelined(sva_batch* b) {
     SVA_HIP(hipStreamWaitEvent(sv, evA, 0));
     b->stream = sv;
     SVA_TRY(mark(7, sv));
-    b->voc_codes = b->d_step_audio; b->voc_codes_bstride = (long)ncb * chunk; b->voc_codes_gstride = chunk;      // read in place ...
+    b->voc.codes = b->d_step_audio; b->voc.codes_bstride = (long)ncb * chunk; b->voc.codes_gstride = chunk;      // read in place ...
     b->pipe_evVc[par] = next_event(b);
-    b->voc_codes_event = b->pipe_evVc[par];       // ... and A(n+1) may overwrite them once the FSQ decode has run
-    if (b->stage_graphs && !b->pcm_dst) {
-        rc = vocode(b, chunk, true, 3);           // FSQ decode (reads this parity's code buffer) + the release event, eagerly
-        b->voc_codes_event = nullptr;
-        if (!rc) rc = stage_graph(b, &b->gV, sv, [&]() -> int { b->stream = sv; return vocode(b, chunk, true, 4); });
+    b->voc.codes_event = b->pipe_evVc[par];       // ... and A(n+1) may overwrite them once the FSQ decode has run
+    if (b->stage_graphs && !b->voc.pcm_dst) {
+        rc = vocode(b, chunk, true, VocPart::FsqOnly);           // FSQ decode (reads this parity's code buffer) + the release event, eagerly
+        b->voc.codes_event = nullptr;
+        if (!rc) rc = stage_graph(b, &b->gV, sv, [&]() -> int { b->stream = sv; return vocode(b, chunk, true, VocPart::AfterFsq); });
     } else {
         rc = vocode(b, chunk, true);
     }
-    b->voc_codes = nullptr; b->voc_codes_event = nullptr;
+    b->voc.codes = nullptr; b->voc.codes_event = nullptr;
     b->stream = se;
     if (rc) return rc;
     if (stage_ev) SVA_HIP(hipEventRecord(b->ev[3], sv));
@@ -1352,12 +1331,12 @@ int restart_encoder_state(sva_batch* b, int slot) {
 // vocoder steps (tools/stream_restart_report.py measures it).
 int prime_vocoder_slot(sva_batch* b, int slot) {
     const int B = b->B, c = b->p.chunk_frames, ncb = b->e->cfg.num_codebooks;
-    const int nd = (int)b->shift_host.size();
+    const int nd = (int)b->voc.shift_host.size();
     hipStream_t st = b->stream;
     if (!b->voc_save) {
         std::vector<long> offs(nd);
         long tot = 0;
-        for (int i = 0; i < nd; ++i) { offs[i] = tot; tot += (long)b->shift_host[i].H * b->shift_host[i].C; }
+        for (int i = 0; i < nd; ++i) { offs[i] = tot; tot += (long)b->voc.shift_host[i].H * b->voc.shift_host[i].C; }
         b->voc_save_bstride = tot;
         SVA_TRY(dev_alloc(b->allocs, &b->d_voc_save_offs, (size_t)nd));
         SVA_HIP(hipMemcpy(b->d_voc_save_offs, offs.data(), sizeof(long) * nd, hipMemcpyHostToDevice));
@@ -1366,15 +1345,15 @@ int prime_vocoder_slot(sva_batch* b, int slot) {
     }
     const int P = b->slots.priming_frames(slot, b->p.decode_window_frames, c);
     int frames_kept = 0;
-    SVA_HIP(hipMemcpy(&frames_kept, b->d_voc_frames, sizeof(int), hipMemcpyDeviceToHost));
-    SVA_TRY(launch_history_rows_copy(b->d_shift, nd, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, 0, B, 0, st));
+    SVA_HIP(hipMemcpy(&frames_kept, b->voc.d_frames, sizeof(int), hipMemcpyDeviceToHost));
+    SVA_TRY(launch_history_rows_copy(b->voc.d_shift, nd, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, 0, B, 0, st));
     SVA_TRY(sva_vocode_reset(b));
     // the step that activates the slot may hold its PCM in d_pcm or in the caller's buffer: the priming run writes its own sink
     struct Keep {
         sva_batch* b; float* dst; long bs; bool done; double fl, by; long ln;
-        ~Keep() { b->pcm_dst = dst; b->pcm_dst_bstride = bs; b->pcm_direct_done = done; b->gemm_flops = fl; b->gemm_bytes = by; b->gemm_launches = ln; }
-    } keep{b, b->pcm_dst, b->pcm_dst_bstride, b->pcm_direct_done, b->gemm_flops, b->gemm_bytes, b->gemm_launches};
-    b->pcm_dst = b->prime_pcm; b->pcm_dst_bstride = 2048L * c;
+        ~Keep() { b->voc.pcm_dst = dst; b->voc.pcm_dst_bstride = bs; b->voc.pcm_direct_done = done; b->gemm_flops = fl; b->gemm_bytes = by; b->gemm_launches = ln; }
+    } keep{b, b->voc.pcm_dst, b->voc.pcm_dst_bstride, b->voc.pcm_direct_done, b->gemm_flops, b->gemm_bytes, b->gemm_launches};
+    b->voc.pcm_dst = b->prime_pcm; b->voc.pcm_dst_bstride = 2048L * c;
     std::vector<int32_t> codes((size_t)(P / c) * B * ncb * c);       // (alive until the copies have landed)
     for (int f = 0; f < P; f += c) {
         int32_t* cf = codes.data() + (size_t)(f / c) * B * ncb * c;
@@ -1382,24 +1361,24 @@ int prime_vocoder_slot(sva_batch* b, int slot) {
         SVA_TRY(upload_vcodes(b, cf, c));
         SVA_TRY(vocode(b, c, true));
     }
-    SVA_TRY(launch_history_rows_copy(b->d_shift, nd, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, slot, 1, 0, st));
-    SVA_TRY(launch_history_rows_copy(b->d_shift, nd, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, 0, B, 1, st));
-    SVA_HIP(hipMemcpyAsync(b->d_voc_frames, &frames_kept, sizeof(int), hipMemcpyHostToDevice, st));
+    SVA_TRY(launch_history_rows_copy(b->voc.d_shift, nd, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, slot, 1, 0, st));
+    SVA_TRY(launch_history_rows_copy(b->voc.d_shift, nd, b->d_voc_save_offs, b->voc_save, b->voc_save_bstride, 0, B, 1, st));
+    SVA_HIP(hipMemcpyAsync(b->voc.d_frames, &frames_kept, sizeof(int), hipMemcpyHostToDevice, st));
     SVA_HIP(hipStreamSynchronize(st));
     return 0;
 }
 
 // Slot-local form of the above (sva_stream_params.slot_priming): the same state -- zero state, then the last P frames of the prompt -- built in
 // the batch's one-stream workspace in ONE T = P pass, then moved into the slot by one kernel.  Nothing of the batch but the slot's history rows
-// is written (d_voc_frames, the other slots, the PCM sinks and the GEMM counters stay), and the cost does not depend on the batch size.  The
+// is written (voc.d_frames, the other slots, the PCM sinks and the GEMM counters stay), and the cost does not depend on the batch size.  The
 // rows differ from the chunk-by-chunk ones by the rounding of other GEMM tilings only.  Runs on the batch's drained stream, never beside its steps.
 int prime_vocoder_slot_local(sva_batch* b, int slot) {
     sva_batch* w = b->prime_ws;
     SVA_CHECK(w, "slot-local priming without a workspace");
-    const int ncb = b->e->cfg.num_codebooks, nd = (int)b->shift_host.size();
+    const int ncb = b->e->cfg.num_codebooks, nd = (int)b->voc.shift_host.size();
     SVA_CHECK(slot >= 0 && slot < b->B, "slot-local priming: slot out of range");
     const int P = b->slots.priming_frames(slot, b->p.decode_window_frames, b->p.chunk_frames);
-    SVA_CHECK(P <= w->Tv, "slot-local priming: prompt tail longer than the workspace");
+    SVA_CHECK(P <= w->voc.Tv, "slot-local priming: prompt tail longer than the workspace");
     hipStream_t st = b->stream;
     w->stream = st;
     SVA_TRY(sva_vocode_reset(w));
@@ -1409,7 +1388,7 @@ int prime_vocoder_slot_local(sva_batch* b, int slot) {
         SVA_TRY(upload_vcodes(w, codes.data(), P));
         SVA_TRY(vocode(w, P, true));
     }
-    SVA_TRY(launch_history_rows_move(w->d_shift, b->d_shift, nd, slot, st));
+    SVA_TRY(launch_history_rows_move(w->voc.d_shift, b->voc.d_shift, nd, slot, st));
     SVA_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -1530,7 +1509,7 @@ int step_body(sva_batch* b) {
     // sva_streams_begin nothing is left to fill in lock step.
     if (b->slots.warmup_step(chunk, d)) SVA_TRY(ar_delay_fill(b));
     SVA_HIP(hipEventRecord(b->ev[2], st));
-    SVA_HIP(hipMemsetAsync(b->d_pcm, 0, sizeof(float) * (size_t)B * 2048 * b->Tv, st));
+    SVA_HIP(hipMemsetAsync(b->voc.d_pcm, 0, sizeof(float) * (size_t)B * 2048 * b->voc.Tv, st));
     SVA_HIP(hipEventRecord(b->ev[3], st));
     return activate_due_slots(b);
 }
@@ -1655,7 +1634,7 @@ extern "C" int sva_step(sva_batch* b, const float* pcm_in, float* pcm_out, const
     SVA_HIP(hipStreamSynchronize(st));
     b->gemm_flops = 0; b->gemm_launches = 0; b->gemm_bytes = 0;
     SVA_TRY(step_body(b));
-    SVA_HIP(hipMemcpy2DAsync(b->hp_out, sizeof(float) * n, b->d_pcm, sizeof(float) * 2048 * b->Tv, sizeof(float) * n, B, hipMemcpyDeviceToHost, st));
+    SVA_HIP(hipMemcpy2DAsync(b->hp_out, sizeof(float) * n, b->voc.d_pcm, sizeof(float) * 2048 * b->voc.Tv, sizeof(float) * n, B, hipMemcpyDeviceToHost, st));
     SVA_HIP(hipStreamSynchronize(st));
     SVA_TRY(check_ar_fail(b));
     memcpy(pcm_out, b->hp_out, sizeof(float) * (size_t)B * n);
@@ -1687,13 +1666,13 @@ extern "C" int sva_step_device(sva_batch* b, const float* d_pcm_in, float* d_pcm
     b->gemm_flops = 0; b->gemm_launches = 0; b->gemm_bytes = 0;
     b->allow_pipe = true;
     b->out_stream = st;
-    b->pcm_dst = direct ? d_pcm_out : nullptr; b->pcm_dst_bstride = n; b->pcm_direct_done = false;
+    b->voc.pcm_dst = direct ? d_pcm_out : nullptr; b->voc.pcm_dst_bstride = n; b->voc.pcm_direct_done = false;
     const int rc = step_body(b);
     b->allow_pipe = false;
-    b->step_src = nullptr; b->pcm_dst = nullptr;
+    b->step_src = nullptr; b->voc.pcm_dst = nullptr;
     if (rc) return rc;
-    if (!b->pcm_direct_done)     // delay warm-up steps run no vocoder: their zeros come from d_pcm
-        SVA_HIP(hipMemcpy2DAsync(d_pcm_out, sizeof(float) * n, b->d_pcm, sizeof(float) * 2048 * b->Tv, sizeof(float) * n, B, hipMemcpyDeviceToDevice,
+    if (!b->voc.pcm_direct_done)     // delay warm-up steps run no vocoder: their zeros come from d_pcm
+        SVA_HIP(hipMemcpy2DAsync(d_pcm_out, sizeof(float) * n, b->voc.d_pcm, sizeof(float) * 2048 * b->voc.Tv, sizeof(float) * n, B, hipMemcpyDeviceToDevice,
                                  b->out_stream));
     return 0;
 }
@@ -2136,7 +2115,7 @@ extern "C" long sva_get_tap(sva_batch* b, const char* what, void* out, long out_
     else if (w == "z") { src = b->tr_z; bytes = sizeof(float) * (long)B * b->T2 * c.tr_dim; }
     else if (w == "ar_fail") { src = b->d_ar_fail; bytes = b->d_ar_fail ? (long)sizeof(int) : 0; if (!src) { set_error("ar_fail: the persistent decode kernel is not in use"); return -1; } }
     else if (w == "ar_timing") { src = b->d_ar_dbg; bytes = b->d_ar_dbg ? 1024L * (long)sizeof(long long) : 0; if (!src) { set_error("ar_timing: set SVA_AR_TIMING=1"); return -1; } }
-    else if (w == "voc_z") { src = b->pin.p; bytes = sizeof(float) * (long)B * b->pin.bstride; }
+    else if (w == "voc_z") { src = b->voc.pin.p; bytes = sizeof(float) * (long)B * b->voc.pin.bstride; }
     else { set_error("unknown tap " + w); return -1; }
     if (out_bytes < bytes) { set_error("tap buffer too small"); return -1; }
     if (hipStreamSynchronize(b->stream) != hipSuccess || hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) {

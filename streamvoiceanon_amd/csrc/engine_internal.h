@@ -97,8 +97,30 @@ int ar_build_prompt_rows(sva_batch* b, int slot, int R, float* x, int rows);
 int ar_prefill_slot(sva_batch* b, int slot, int R, bool tap_logits = false);
 int ar_delay_fill(sva_batch* b, const std::vector<int>& slots);
 int ar_delay_fill(sva_batch* b);
-bool voc_level_is_fused(const sva_batch* b, int C);
-int vocode(sva_batch* b, int T, bool shift, int part = 0);
+// which seams of the streaming vocoder a vocode() call runs (FsqOnly / AfterFsq: the pipelined stage graphs are cut where the step's codes are released)
+enum class VocPart { All = 0, QuantizerDecode = 1, Head = 2, FsqOnly = 3, AfterFsq = 4 };
+int vocode(sva_batch* b, int T, bool shift, VocPart part = VocPart::All);
 int register_shift(sva_batch* b, Act& a, int rows_per_frame);
+// The streaming state of the vocoder -- every tensor whose history rows carry over from call to call -- once, in the order of the ShiftDesc table:
+// f(Act&, unsigned short*& planes (null where the tensor has none), int rows_per_frame, VocForm of its level) -> int, non-zero ends the walk
+template <class F>
+int for_each_voc_state(VocWorkspace& v, F&& f) {
+    unsigned short* none = nullptr;
+    SVA_TRY(f(v.u0, none, 2, VocForm::Rows));
+    SVA_TRY(f(v.u1, none, 4, VocForm::Rows));
+    SVA_TRY(f(v.pin, none, 4, VocForm::Rows));
+    SVA_TRY(f(v.S[0], none, 4, VocForm::Rows));
+    for (int i = 0; i < 5; ++i) {
+        VocLevel& l = v.lv[i];
+        SVA_TRY(f(l.X, l.XP, l.rpf, l.form));
+        for (int br = 0; br < 3; ++br)
+            for (int j = 0; j < 3; ++j) {
+                SVA_TRY(f(l.tb[br][j], l.tbP[br][j], l.rpf, l.form));
+                if (j < 2) SVA_TRY(f(l.yb[br][j], l.ybP[br][j], l.rpf, l.form));
+            }
+        SVA_TRY(f(v.S[i + 1], none, l.rpf, VocForm::Rows));
+    }
+    return 0;
+}
 
 }  // namespace sva

@@ -11,6 +11,27 @@
 using namespace sva;
 
 namespace sva {
+// One launch of the conv-GEMM family.  With b->prof_on (bench.py roofline leg) it is bracketed with hipEvents on the launch stream and leaves its
+// table row {M, N, K, taps, flags}; the kernel family the launcher reports (plan_report_kind) is added to the flags as 256 * (kind + 1), for the
+// per-pipe roofline.
+template <class F>
+static int profiled_launch(sva_batch* b, std::array<int, 5> row, F&& launch) {
+    if (!b->prof_on) return launch(nullptr);
+    if (b->prof_n + 2 > (int)b->prof_ev.size()) {
+        const size_t old = b->prof_ev.size();
+        b->prof_ev.resize(old + 512);
+        for (size_t i = old; i < b->prof_ev.size(); ++i) SVA_HIP(hipEventCreate(&b->prof_ev[i]));
+    }
+    b->prof_shapes.push_back(row);
+    SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n], b->stream));
+    int kind = -1;
+    const int rc = launch(&kind);
+    SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n + 1], b->stream));
+    b->prof_shapes.back()[4] += 256 * (kind + 1);
+    b->prof_n += 2;
+    return rc;
+}
+
 int gemm_call(sva_batch* b, const float* A, long a_bstride, long a_off, int lda, int nb, int T, int stride, int dil,
               int taps, int Cin, const Lin& w, float* C, long c_bstride, long c_off, int ldc, ConvGemm proto) {
     ConvGemm g = proto;
@@ -28,22 +49,8 @@ int gemm_call(sva_batch* b, const float* A, long a_bstride, long a_off, int lda,
     // algorithmic bytes: every operand element once (input rows incl. the tap halo, weights, outputs, residual)
     b->gemm_bytes += 4.0 * ((double)nb * ((double)(T - 1) * stride + (taps - 1) * dil + 1) * Cin + (double)g.N * w.K +
                             (double)g.M * (g.w13 ? g.N / 2 : g.N) * (g.res ? 2 : 1));
-    if (b->prof_on) {        // bench.py roofline leg: bracket every conv-GEMM launch with hipEvents on the launch stream
-        if (b->prof_n + 2 > (int)b->prof_ev.size()) {
-            const size_t old = b->prof_ev.size();
-            b->prof_ev.resize(old + 512);
-            for (size_t i = old; i < b->prof_ev.size(); ++i) SVA_HIP(hipEventCreate(&b->prof_ev[i]));
-        }
-        b->prof_shapes.push_back({g.M, g.N, w.K, taps, g.w13 * 8 + g.a_silu * 4 + (g.res ? 2 : 0) + (g.act == ACT_GELU ? 1 : 0)});
-        SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n], b->stream));
-        int kind = -1;
-        int rc = launch_conv_gemm(g, b->stream, &kind);
-        SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n + 1], b->stream));
-        b->prof_shapes.back()[4] += 256 * (kind + 1);        // kernel family of the launch (plan_report_kind), for the per-pipe roofline
-        b->prof_n += 2;
-        return rc;
-    }
-    return launch_conv_gemm(g, b->stream);
+    return profiled_launch(b, {g.M, g.N, w.K, taps, g.w13 * 8 + g.a_silu * 4 + (g.res ? 2 : 0) + (g.act == ACT_GELU ? 1 : 0)},
+                           [&](int* kind) { return launch_conv_gemm(g, b->stream, kind); });
 }
 
 // fork / join of independent sub-chains on side streams (captured into the hipGraph as parallel branches)
@@ -79,9 +86,10 @@ int conv_desc(sva_batch* b, const Act& in, int T_out, int dil, int taps, const L
 // n <= 3 same-shape problems in one launch (bookkeeping as gemm_call: one "launch", summed FLOPs)
 int gemm_group_call(sva_batch* b, const ConvGemm* gs, int n) {
     double fl = 0;
-    int kmax = 0, tmax = 0;
+    int kmax = 0, tmax = 0, ksum = 0;
     for (int i = 0; i < n; ++i) {
         fl += 2.0 * gs[i].M * (double)gs[i].N * gs[i].taps * gs[i].Cin;
+        ksum += gs[i].taps * gs[i].Cin;
         if (gs[i].taps * gs[i].Cin > kmax) { kmax = gs[i].taps * gs[i].Cin; tmax = gs[i].taps; }
     }
     b->gemm_flops += fl;
@@ -89,25 +97,9 @@ int gemm_group_call(sva_batch* b, const ConvGemm* gs, int n) {
     for (int i = 0; i < n; ++i)
         b->gemm_bytes += 4.0 * ((double)(gs[i].M / gs[i].T) * ((double)(gs[i].T - 1) + (gs[i].taps - 1) * gs[i].dil + 1) * gs[i].Cin +
                                 (double)gs[i].N * gs[i].taps * gs[i].Cin + (double)gs[i].M * gs[i].N * (gs[i].res ? 2 : 1));
-    if (b->prof_on) {
-        if (b->prof_n + 2 > (int)b->prof_ev.size()) {
-            const size_t old = b->prof_ev.size();
-            b->prof_ev.resize(old + 512);
-            for (size_t i = old; i < b->prof_ev.size(); ++i) SVA_HIP(hipEventCreate(&b->prof_ev[i]));
-        }
-        // table row: the group as one problem with the summed K (its FLOPs = 2 M N sum K)
-        int ksum = 0;
-        for (int i = 0; i < n; ++i) ksum += gs[i].taps * gs[i].Cin;
-        b->prof_shapes.push_back({gs[0].M, gs[0].N, ksum, tmax, 16 + gs[0].a_silu * 4 + (gs[0].res ? 2 : 0)});
-        SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n], b->stream));
-        int kind = -1;
-        int rc = launch_conv_gemm_group(gs, n, b->stream, &kind);
-        SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n + 1], b->stream));
-        b->prof_shapes.back()[4] += 256 * (kind + 1);
-        b->prof_n += 2;
-        return rc;
-    }
-    return launch_conv_gemm_group(gs, n, b->stream);
+    // table row: the group as one problem with the summed K (its FLOPs = 2 M N sum K)
+    return profiled_launch(b, {gs[0].M, gs[0].N, ksum, tmax, 16 + gs[0].a_silu * 4 + (gs[0].res ? 2 : 0)},
+                           [&](int* kind) { return launch_conv_gemm_group(gs, n, b->stream, kind); });
 }
 
 // one voc_conv_kernel launch (three branches of one conv stage of a narrow level), bookkeeping as gemm_group_call
@@ -123,20 +115,9 @@ int voc_conv_call(sva_batch* b, const VocConvGroup& gg, int C, int pmode) {
     b->gemm_flops += fl;
     b->gemm_launches += 1;
     b->gemm_bytes += by;
-    if (b->prof_on) {
-        if (b->prof_n + 2 > (int)b->prof_ev.size()) {
-            const size_t old = b->prof_ev.size();
-            b->prof_ev.resize(old + 512);
-            for (size_t i = old; i < b->prof_ev.size(); ++i) SVA_HIP(hipEventCreate(&b->prof_ev[i]));
-        }
-        b->prof_shapes.push_back({gg.B * gg.T, C, ksum, 11, 16 + (gg.g[0].res ? 2 : 0) + 256 * ((pmode == PLANES_H3 ? 9 : 10) + 1)});
-        SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n], b->stream));
-        int rc = launch_voc_conv(gg, C, pmode, b->enc_cus, b->stream);
-        SVA_HIP(hipEventRecord(b->prof_ev[b->prof_n + 1], b->stream));
-        b->prof_n += 2;
-        return rc;
-    }
-    return launch_voc_conv(gg, C, pmode, b->enc_cus, b->stream);
+    // (the launcher reports no family: the row carries voc_conv_kernel's fixed number)
+    return profiled_launch(b, {gg.B * gg.T, C, ksum, 11, 16 + (gg.g[0].res ? 2 : 0) + 256 * ((pmode == PLANES_H3 ? 9 : 10) + 1)},
+                           [&](int*) { return launch_voc_conv(gg, C, pmode, b->enc_cus, b->stream); });
 }
 
 // Two chained GEMMs of `rows` rows can hand their intermediate tensor over as operand planes (gemm_planes.hip) when both weights carry
@@ -842,198 +823,194 @@ int ar_delay_fill(sva_batch* b) {
     return ar_delay_fill(b, all);
 }
 
-// Which HiFiGAN levels run as the fused LDS-resident kernel (voc_fused.hip).  Measured on MI355X (profiles/r02_voc_fused.txt): the
-// C = 16 level takes 27-33 us fused against 7 launches / ~70 us at one stream and breaks even around 4-8 streams; from there on,
-// and for C = 32 at any batch, the tap-split GEMM formulation is faster (the fused kernel recomputes an 18 (k - 1)-row halo per
-// tile and runs one workgroup per CU), so the default fuses C = 16 for <= 4 streams.  SVA_DEBUG=voc_fused_mask=M (bit 0: C = 16,
-// bit 1: C = 32) / sva_debug_configure override it for the parity tests.
-bool voc_level_is_fused(const sva_batch* b, int C) {
-    if (!b->voc_fused || !voc_level_supported(C)) return false;
-    if (b->voc_fused_mask >= 0) return (b->voc_fused_mask & (C == 16 ? 1 : 2)) != 0;
-    return C == 16 && b->B <= 4;
+// ---- V: streaming vocoder on T new code frames held in voc.d_vcodes [B][8][Tv] -------------------------------
+
+// firefly.quantizer.decode, first half: FSQ decode of the codes into zq
+static int voc_fsq(sva_batch* b, int T) {
+    sva_engine* e = b->e;
+    VocWorkspace& v = b->voc;
+    const int V = e->cfg.voc_dim, G = e->cfg.num_codebooks;
+    if (v.codes) SVA_TRY(launch_fsq_decode(v.codes, v.codes_bstride, v.codes_gstride, b->B, T, G, V / G, e->fsq_W, e->fsq_b, v.zq.p, v.zq.bstride, 0, V, b->stream));
+    else SVA_TRY(launch_fsq_decode(v.d_vcodes, (long)G * v.Tv, v.Tv, b->B, T, G, V / G, e->fsq_W, e->fsq_b, v.zq.p, v.zq.bstride, 0, V, b->stream));
+    if (v.codes_event) SVA_HIP(hipEventRecord(v.codes_event, b->stream));
+    return 0;
 }
 
-// ---- V: streaming vocoder on T new code frames held in d_vcodes [B][8][Tv] -------------------------------
-// part 0: the whole vocoder; 1: firefly.quantizer.decode only (FSQ decode + upsampler, output = rows [pin.H, pin.H + 4T) of
-// b->pin); 2: firefly.head only (HiFiGAN on those rows)
-int vocode(sva_batch* b, int T, bool shift, int part) {
+// ... second half, upsample.0/1: ConvTranspose k=s=2 (stateless) + ConvNeXtBlock  (fsq.py:61-74); output = rows [pin.H, pin.H + 4T) of voc.pin
+static int voc_upsampler(sva_batch* b, int T) {
     sva_engine* e = b->e;
-    const sva_config& c = e->cfg;
-    const int B = b->B, V = c.voc_dim, G = c.num_codebooks;
-    hipStream_t st = b->stream;
-    SVA_CHECK(T >= 1 && T <= b->Tv, "vocode: T out of range");
-    // parts 3 / 4: the FSQ decode alone / everything behind it (the pipelined stage graphs are cut where the step's codes are released)
-    if (part != 2) {
-    if (part != 4) {
-    if (b->voc_codes) SVA_TRY(launch_fsq_decode(b->voc_codes, b->voc_codes_bstride, b->voc_codes_gstride, B, T, G, V / G, e->fsq_W, e->fsq_b, b->zq.p, b->zq.bstride, 0, V, st));
-    else SVA_TRY(launch_fsq_decode(b->d_vcodes, (long)G * b->Tv, b->Tv, B, T, G, V / G, e->fsq_W, e->fsq_b, b->zq.p, b->zq.bstride, 0, V, st));
-    if (b->voc_codes_event) SVA_HIP(hipEventRecord(b->voc_codes_event, st));
-    }
-    if (part == 3) return 0;
-    // upsample.0/1: ConvTranspose k=s=2 (stateless) + ConvNeXtBlock  (fsq.py:61-74)
-    SVA_TRY(gemm_call(b, b->zq.p, b->zq.bstride, 0, V, B, T, 1, 1, 1, V, e->up_conv[0], b->u0.p, b->u0.bstride, (long)b->u0.H * V, 2 * V));
-    SVA_TRY(cnx_block(b, e->up_cnx[0], b->u0, 2 * T, b->vh1, b->vh2, &b->v0));
-    SVA_TRY(gemm_call(b, b->v0.p, b->v0.bstride, 0, V, B, 2 * T, 1, 1, 1, V, e->up_conv[1], b->u1.p, b->u1.bstride,
-                      (long)b->u1.H * V, 2 * V));
-    SVA_TRY(cnx_block(b, e->up_cnx[1], b->u1, 4 * T, b->vh1, b->vh2, &b->pin));
-    }
-    if (part == 1) return 0;
-    // conv_pre k13 (reads the upsampler output with 12 history rows) -> S[0]
-    SVA_TRY(conv_act(b, b->pin, 4 * T, 1, 1, e->pre_k, e->conv_pre, b->S[0]));
-    long Tl = 4L * T;
-    for (int i = 0; i < 5; ++i) {
-        const int s = e->ups_s[i];
-        const int Cout = b->X[i].C;
-        // SiLU -> ConvTranspose (k = 2s): 2-tap GEMM over rows q-1, q with N = s*Cout  (firefly.py:284-285, 131-138)
-        {
-            ConvGemm p;
-            p.a_silu = 1;
-            SVA_CHECK(b->S[i].H >= 1, "ups: history");
-            SVA_TRY(gemm_call(b, b->S[i].p, b->S[i].bstride, (long)(b->S[i].H - 1) * b->S[i].C, b->S[i].C, B, (int)Tl, 1, 1, 2, b->S[i].C,
-                              e->ups[i], b->X[i].p, b->X[i].bstride, (long)b->X[i].H * Cout, s * Cout, p));
-        }
-        Tl *= s;
-        // ParallelBlock = mean of three ResBlock1 (firefly.py:183-190, 214-215).  The three branches are independent
-        // chains of 6 convs of one shape per stage: every form below runs a conv stage of all three in one launch and
-        // takes the mean of the branch outputs y3 in a kernel of its own (fixed order => deterministic sum).
-        Act& out = b->S[i + 1];
-        if (voc_level_is_fused(b, Cout)) {
-            // narrow levels: the whole ParallelBlock in one launch (three branches x time tiles x streams), intermediates in LDS,
-            // the level input's history (18 (k - 1) rows) as the only streaming state
-            const float* W[3][6]; const float* bs[3][6]; float* y3[3];
-            for (int br = 0; br < 3; ++br) {
-                for (int j = 0; j < 3; ++j) {
-                    const ResConv& rcv = e->res[i][br][j];
-                    SVA_CHECK(rcv.k == kResK[br] && rcv.dil == kResD[j], "voc_level: unexpected ResBlock geometry");
-                    W[br][2 * j] = rcv.c1.W; bs[br][2 * j] = rcv.c1.b; W[br][2 * j + 1] = rcv.c2.W; bs[br][2 * j + 1] = rcv.c2.b;
-                }
-                y3[br] = b->y3[i][br].p;
-            }
-            SVA_TRY(launch_voc_level(b->X[i].p, b->X[i].bstride, b->X[i].H, Cout, B, (int)Tl, W, bs, kResD, y3, b->y3[i][0].bstride, b->d_voc_frames,
-                                     b->voc_rpf[i], st));
-            {   // bookkeeping as one conv-GEMM launch: algorithmic FLOPs of the 18 convs, bytes = input (+ history) + weights + output
-                double kk = 0;
-                for (int br = 0; br < 3; ++br) kk += 6.0 * kResK[br];
-                b->gemm_flops += 2.0 * B * (double)Tl * Cout * Cout * kk;
-                b->gemm_launches += 1;
-                b->gemm_bytes += 4.0 * ((double)B * (Tl + b->X[i].H) * Cout + kk * Cout * Cout + 3.0 * B * (double)Tl * Cout);
-            }
-            const long n4 = Tl * Cout / 4;
-            SVA_TRY(launch_mean3(b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p, b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4, B, st));
-            continue;
-        }
-        if (b->voc_dma[i] == 2) {
-            // narrow level (C = 16 / 32) of a large batch: every conv stage of the three branches as ONE voc_conv_kernel launch (gemm_planes.hip: the
-            // tile's input rows + halo and the branch's whole weight resident in LDS), activations between the convs as ROW-MAJOR operand planes
-            const int pm = b->voc_pmode;
-            SVA_TRY(launch_to_planes_act(b->X[i].p, B, b->X[i].rows, b->X[i].H, (int)Tl, Cout, b->XP[i], (long)B * b->X[i].bstride, pm, 1, st, 0));
-            Act* y[3] = {&b->X[i], &b->X[i], &b->X[i]};
-            const unsigned short* yp[3] = {b->XP[i], b->XP[i], b->XP[i]};
-            for (int j = 0; j < 3; ++j) {
-                VocConvGroup g1, g2;
-                g1.B = g2.B = B; g1.T = g2.T = (int)Tl; g1.ovf = g2.ovf = b->d_mm_ovf; g1.n = g2.n = 3;
-                for (int br = 0; br < 3; ++br) {
-                    const ResConv& rcv = e->res[i][br][j];
-                    const int padL = (rcv.k - 1) * rcv.dil;
-                    Act& t = b->tb[i][br][j];
-                    SVA_CHECK(y[br]->H >= padL && t.H >= padL, "voc_conv: not enough history rows");
-                    VocConv& a = g1.g[br];
-                    a.Ap = yp[br]; a.ap_pstride = (long)B * y[br]->bstride; a.a_rows_b = y[br]->rows; a.a_row0 = y[br]->H - padL; a.a_rows_total = (long)B * y[br]->rows;
-                    a.Wp = rcv.q1; a.wp_pstride = (long)Cout * rcv.Kq; a.wp_inv = rcv.q1_inv; a.bias = rcv.c1.b; a.taps = rcv.k; a.dil = rcv.dil;
-                    a.Cp = b->tbP[i][br][j]; a.cp_pstride = (long)B * t.bstride; a.c_rows_b = t.rows; a.c_row0 = t.H;
-                    Act& dst = j < 2 ? b->yb[i][br][j] : b->y3[i][br];
-                    VocConv& c2 = g2.g[br];
-                    c2.Ap = b->tbP[i][br][j]; c2.ap_pstride = (long)B * t.bstride; c2.a_rows_b = t.rows; c2.a_row0 = t.H - padL; c2.a_rows_total = (long)B * t.rows;
-                    c2.Wp = rcv.q2; c2.wp_pstride = (long)Cout * rcv.Kq; c2.wp_inv = rcv.q2_inv; c2.bias = rcv.c2.b; c2.taps = rcv.k; c2.dil = rcv.dil;
-                    c2.res = y[br]->p; c2.r_bstride = y[br]->bstride; c2.r_off = (long)y[br]->H * Cout;
-                    c2.Cf = dst.p; c2.c_bstride = dst.bstride; c2.c_off = (long)dst.H * Cout;
-                    if (j < 2) { c2.Cp = b->ybP[i][br][j]; c2.cp_pstride = (long)B * dst.bstride; c2.c_rows_b = dst.rows; c2.c_row0 = dst.H; }
-                }
-                SVA_TRY(voc_conv_call(b, g1, Cout, pm));
-                SVA_TRY(voc_conv_call(b, g2, Cout, pm));
-                for (int br = 0; br < 3 && j < 2; ++br) { y[br] = &b->yb[i][br][j]; yp[br] = b->ybP[i][br][j]; }
-            }
-            const long n4 = Tl * Cout / 4;
-            SVA_TRY(launch_mean3(b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p, b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4, B, st));
-            continue;
-        }
-        if (b->voc_dma[i]) {
-            // wide level of a large batch: every conv on the LDS-DMA planes kernel, the three branches' tiles as one sequence per conv stage.
-            // Operands are planes throughout: silu(X) from a split pass over the new rows, then each conv's epilogue writes the parts of
-            // silu(output) for its consumer (c1: only those; c2: also the fp32 sum the next residual / the mean reads)
-            const int pm = b->voc_pmode;
-            auto planes_in = [&](ConvGemm& g, const Act& a, const unsigned short* P) {
-                g.A = nullptr; g.a_silu = 0;
-                g.Ap = P; g.ap_pstride = (long)B * a.bstride; g.ap_rows = (long)B * a.rows;
-            };
-            auto planes_out = [&](ConvGemm& g, const Act& a, unsigned short* P) {
-                g.Cp = P; g.cp_pstride = (long)B * a.bstride; g.cp_rows = (long)B * a.rows; g.cp_silu = 1;
-            };
-            SVA_TRY(launch_to_planes_act(b->X[i].p, B, b->X[i].rows, b->X[i].H, (int)Tl, Cout, b->XP[i], (long)B * b->X[i].bstride, pm, 1, st));
-            Act* y[3] = {&b->X[i], &b->X[i], &b->X[i]};
-            const unsigned short* yp[3] = {b->XP[i], b->XP[i], b->XP[i]};
-            for (int j = 0; j < 3; ++j) {
-                ConvGemm g1[3], g2[3];
-                for (int br = 0; br < 3; ++br) {
-                    const ResConv& rcv = e->res[i][br][j];
-                    Act& t = b->tb[i][br][j];
-                    SVA_TRY(conv_desc(b, *y[br], (int)Tl, rcv.dil, rcv.k, rcv.c1, t, g1[br]));
-                    planes_in(g1[br], *y[br], yp[br]);
-                    planes_out(g1[br], t, b->tbP[i][br][j]);
-                    g1[br].C = nullptr;
-                    Act& dst = j < 2 ? b->yb[i][br][j] : b->y3[i][br];
-                    g2[br].res = y[br]->p; g2[br].r_bstride = y[br]->bstride; g2[br].r_off = (long)y[br]->H * Cout; g2[br].ldr = Cout;
-                    SVA_TRY(conv_desc(b, t, (int)Tl, rcv.dil, rcv.k, rcv.c2, dst, g2[br]));
-                    planes_in(g2[br], t, b->tbP[i][br][j]);
-                    if (j < 2) planes_out(g2[br], dst, b->ybP[i][br][j]);
-                    g1[br].cu_limit = g2[br].cu_limit = b->enc_cus;
-                }
-                SVA_TRY(gemm_group_call(b, g1, 3));
-                SVA_TRY(gemm_group_call(b, g2, 3));
-                for (int br = 0; br < 3 && j < 2; ++br) { y[br] = &b->yb[i][br][j]; yp[br] = b->ybP[i][br][j]; }
-            }
-            const long n4 = Tl * Cout / 4;
-            SVA_TRY(launch_mean3(b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p, b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4, B, st));
-            continue;
-        }
-        // fp32 rows: one launch per conv stage for the three branches (same M, N, Cin; k = 3 / 7 / 11 taps), 12 launches + the mean per
-        // level -- at small B the step is bound by the number of kernels
-        Act* y[3] = {&b->X[i], &b->X[i], &b->X[i]};
+    VocWorkspace& v = b->voc;
+    const int B = b->B, V = e->cfg.voc_dim;
+    SVA_TRY(gemm_call(b, v.zq.p, v.zq.bstride, 0, V, B, T, 1, 1, 1, V, e->up_conv[0], v.u0.p, v.u0.bstride, (long)v.u0.H * V, 2 * V));
+    SVA_TRY(cnx_block(b, e->up_cnx[0], v.u0, 2 * T, v.vh1, v.vh2, &v.v0));
+    SVA_TRY(gemm_call(b, v.v0.p, v.v0.bstride, 0, V, B, 2 * T, 1, 1, 1, V, e->up_conv[1], v.u1.p, v.u1.bstride, (long)v.u1.H * V, 2 * V));
+    return cnx_block(b, e->up_cnx[1], v.u1, 4 * T, v.vh1, v.vh2, &v.pin);
+}
+
+// A narrow level in the Fused form: the whole ParallelBlock in one launch (three branches x time tiles x streams), intermediates in LDS,
+// the level input's history (18 (k - 1) rows) as the only streaming state
+static int voc_level_fused(sva_batch* b, int i, int Tl) {
+    sva_engine* e = b->e;
+    VocLevel& l = b->voc.lv[i];
+    const int B = b->B, C = l.X.C;
+    const float* W[3][6]; const float* bs[3][6]; float* y3[3];
+    double kk = 0;
+    for (int br = 0; br < 3; ++br) {
         for (int j = 0; j < 3; ++j) {
-            ConvGemm g1[3], g2[3];
-            for (int br = 0; br < 3; ++br) {
-                const ResConv& rcv = e->res[i][br][j];
-                g1[br].a_silu = 1;
-                SVA_TRY(conv_desc(b, *y[br], (int)Tl, rcv.dil, rcv.k, rcv.c1, b->tb[i][br][j], g1[br]));
-                Act& dst = j < 2 ? b->yb[i][br][j] : b->y3[i][br];
-                g2[br].a_silu = 1;
-                g2[br].res = y[br]->p; g2[br].r_bstride = y[br]->bstride; g2[br].r_off = (long)y[br]->H * Cout; g2[br].ldr = Cout;
-                SVA_TRY(conv_desc(b, b->tb[i][br][j], (int)Tl, rcv.dil, rcv.k, rcv.c2, dst, g2[br]));
-            }
+            const ResConv& rcv = e->res[i][br][j];
+            SVA_CHECK(rcv.k == kResK[br] && rcv.dil == kResD[j], "voc_level: unexpected ResBlock geometry");
+            W[br][2 * j] = rcv.c1.W; bs[br][2 * j] = rcv.c1.b; W[br][2 * j + 1] = rcv.c2.W; bs[br][2 * j + 1] = rcv.c2.b;
+        }
+        y3[br] = l.y3[br].p;
+        kk += 6.0 * kResK[br];
+    }
+    SVA_TRY(launch_voc_level(l.X.p, l.X.bstride, l.X.H, C, B, Tl, W, bs, kResD, y3, l.y3[0].bstride, b->voc.d_frames, l.rpf, b->stream));
+    // bookkeeping as one conv-GEMM launch: algorithmic FLOPs of the 18 convs, bytes = input (+ history) + weights + output
+    b->gemm_flops += 2.0 * B * (double)Tl * C * C * kk;
+    b->gemm_launches += 1;
+    b->gemm_bytes += 4.0 * ((double)B * (Tl + l.X.H) * C + kk * C * C + 3.0 * B * (double)Tl * C);
+    return 0;
+}
+
+// One conv stage of one ResBlock1 branch: c1: in -> mid, c2: mid (+ residual in) -> dst, each tensor with its operand planes (null: none)
+struct VocTensor {
+    Act* a;
+    unsigned short* P;
+};
+struct VocStage {
+    VocTensor in, mid, dst;
+    const ResConv& rcv;
+};
+
+// ... as a conv-GEMM pair: fp32 rows with SiLU on load, or (planes) K-blocked operand planes in and out -- silu(in) comes from a split pass over
+// the new rows, then each conv's epilogue writes the parts of silu(output) for its consumer (c1: only those; c2: also the fp32 sum the next
+// residual / the mean reads)
+static int describe_gemm_pair(sva_batch* b, const VocStage& s, int Tl, bool planes, ConvGemm& g1, ConvGemm& g2) {
+    const long B = b->B;
+    const Act &in = *s.in.a, &mid = *s.mid.a;
+    g1.a_silu = g2.a_silu = planes ? 0 : 1;
+    SVA_TRY(conv_desc(b, in, Tl, s.rcv.dil, s.rcv.k, s.rcv.c1, *s.mid.a, g1));
+    g2.res = in.p; g2.r_bstride = in.bstride; g2.r_off = (long)in.H * in.C; g2.ldr = in.C;
+    SVA_TRY(conv_desc(b, mid, Tl, s.rcv.dil, s.rcv.k, s.rcv.c2, *s.dst.a, g2));
+    if (!planes) return 0;        // (the fp32-rows form leaves cu_limit at its default: conv_desc does not set it)
+    auto planes_in = [&](ConvGemm& g, const VocTensor& t) {
+        g.A = nullptr;
+        g.Ap = t.P; g.ap_pstride = B * t.a->bstride; g.ap_rows = B * t.a->rows;
+    };
+    auto planes_out = [&](ConvGemm& g, const VocTensor& t) {
+        g.Cp = t.P; g.cp_pstride = B * t.a->bstride; g.cp_rows = B * t.a->rows; g.cp_silu = 1;
+    };
+    planes_in(g1, s.in);
+    planes_out(g1, s.mid);
+    g1.C = nullptr;               // (only this form nulls c1's fp32 output: nothing reads tb as rows)
+    planes_in(g2, s.mid);
+    if (s.dst.P) planes_out(g2, s.dst);
+    g1.cu_limit = g2.cu_limit = b->enc_cus;
+    return 0;
+}
+
+// ... as a voc_conv_kernel pair (gemm_planes.hip: the tile's input rows + halo and the branch's whole weight resident in LDS), activations
+// between the convs as ROW-MAJOR operand planes
+static int describe_voc_conv_pair(sva_batch* b, const VocStage& s, VocConv& c1, VocConv& c2) {
+    const long B = b->B;
+    const ResConv& rcv = s.rcv;
+    const Act &in = *s.in.a, &mid = *s.mid.a, &dst = *s.dst.a;
+    const int C = in.C, padL = (rcv.k - 1) * rcv.dil;
+    SVA_CHECK(in.H >= padL && mid.H >= padL, "voc_conv: not enough history rows");
+    c1.Ap = s.in.P; c1.ap_pstride = B * in.bstride; c1.a_rows_b = in.rows; c1.a_row0 = in.H - padL; c1.a_rows_total = B * in.rows;
+    c1.Wp = rcv.q1; c1.wp_pstride = (long)C * rcv.Kq; c1.wp_inv = rcv.q1_inv; c1.bias = rcv.c1.b; c1.taps = rcv.k; c1.dil = rcv.dil;
+    c1.Cp = s.mid.P; c1.cp_pstride = B * mid.bstride; c1.c_rows_b = mid.rows; c1.c_row0 = mid.H;
+    c2.Ap = s.mid.P; c2.ap_pstride = B * mid.bstride; c2.a_rows_b = mid.rows; c2.a_row0 = mid.H - padL; c2.a_rows_total = B * mid.rows;
+    c2.Wp = rcv.q2; c2.wp_pstride = (long)C * rcv.Kq; c2.wp_inv = rcv.q2_inv; c2.bias = rcv.c2.b; c2.taps = rcv.k; c2.dil = rcv.dil;
+    c2.res = in.p; c2.r_bstride = in.bstride; c2.r_off = (long)in.H * C;
+    c2.Cf = dst.p; c2.c_bstride = dst.bstride; c2.c_off = (long)dst.H * C;
+    if (s.dst.P) { c2.Cp = s.dst.P; c2.cp_pstride = B * dst.bstride; c2.c_rows_b = dst.rows; c2.c_row0 = dst.H; }
+    return 0;
+}
+
+// The three ResBlock1 branches of level i in an unfused form: independent chains of 6 convs of one shape per stage.  y = X; per stage j:
+// c1: y -> tb[j], c2: tb[j] (+ residual y) -> y_{j+1} (yb[j], at last y3), every conv stage of the three branches as one launch -- 12 launches
+// per level; at small B the step is bound by the number of kernels.
+static int voc_level_chain(sva_batch* b, int i, int Tl) {
+    VocLevel& l = b->voc.lv[i];
+    const int B = b->B, C = l.X.C, pm = b->voc.pmode;
+    if (voc_form_planes(l.form))
+        SVA_TRY(launch_to_planes_act(l.X.p, B, l.X.rows, l.X.H, Tl, C, l.XP, (long)B * l.X.bstride, pm, 1, b->stream, l.form == VocForm::PlanesDma ? 1 : 0));
+    VocTensor y[3] = {{&l.X, l.XP}, {&l.X, l.XP}, {&l.X, l.XP}};
+    for (int j = 0; j < 3; ++j) {
+        ConvGemm g1[3], g2[3];
+        VocConvGroup v1, v2;
+        v1.B = v2.B = B; v1.T = v2.T = Tl; v1.ovf = v2.ovf = b->d_mm_ovf; v1.n = v2.n = 3;
+        for (int br = 0; br < 3; ++br) {
+            const VocTensor dst = j < 2 ? VocTensor{&l.yb[br][j], l.ybP[br][j]} : VocTensor{&l.y3[br], nullptr};
+            const VocStage s{y[br], {&l.tb[br][j], l.tbP[br][j]}, dst, b->e->res[i][br][j]};
+            if (l.form == VocForm::PlanesHalo) SVA_TRY(describe_voc_conv_pair(b, s, v1.g[br], v2.g[br]));
+            else SVA_TRY(describe_gemm_pair(b, s, Tl, l.form == VocForm::PlanesDma, g1[br], g2[br]));
+            y[br] = dst;
+        }
+        if (l.form == VocForm::PlanesHalo) {
+            SVA_TRY(voc_conv_call(b, v1, C, pm));
+            SVA_TRY(voc_conv_call(b, v2, C, pm));
+        } else {
             SVA_TRY(gemm_group_call(b, g1, 3));
             SVA_TRY(gemm_group_call(b, g2, 3));
-            for (int br = 0; br < 3; ++br) y[br] = j < 2 ? &b->yb[i][br][j] : &b->y3[i][br];
         }
-        const long n4 = Tl * Cout / 4;
-        SVA_TRY(launch_mean3(b->y3[i][0].p, b->y3[i][1].p, b->y3[i][2].p, b->y3[i][0].bstride, out.p, out.bstride, (long)out.H * Cout, n4, B, st));
     }
-    SVA_TRY(launch_conv_post_tanh(b->S[5].p, b->S[5].bstride, (long)(b->S[5].H - (e->post_k - 1)) * b->S[5].C, B, (int)Tl, b->S[5].C, e->post_k,
-                                  e->post_w, e->post_b, b->pcm_dst ? b->pcm_dst : b->d_pcm, b->pcm_dst ? b->pcm_dst_bstride : 2048L * b->Tv, 0, st, b->d_slot_flag));
-    if (b->pcm_dst) b->pcm_direct_done = true;
-    if (shift) {
-        // update T in the descriptors if it changed (host table re-uploaded; rare)
-        bool dirty = false;
-        for (auto& d : b->shift_host) {
-            const int t = (int)((long)T * d.pad);      // pad holds rows-per-code-frame of this tensor
-            if (d.T != t) { d.T = t; dirty = true; }
-        }
-        if (dirty) {
-            SVA_HIP(hipMemcpyAsync(b->d_shift, b->shift_host.data(), sizeof(ShiftDesc) * b->shift_host.size(), hipMemcpyHostToDevice, st));
-            SVA_HIP(hipStreamSynchronize(st));
-        }
-        SVA_TRY(launch_shift_history(b->d_shift, (int)b->shift_host.size(), B, st, b->B <= 8 ? 4 : 1));
-        SVA_TRY(launch_add_i32(b->d_voc_frames, T, st));      // (the fused levels ask whether their halo lies inside the stream)
+    return 0;
+}
+
+// firefly.head (HiFiGANGenerator.forward, firefly.py:280-293) on rows [pin.H, pin.H + 4T) of voc.pin, then (shift) the history shift of the whole vocoder
+static int voc_head(sva_batch* b, int T, bool shift) {
+    sva_engine* e = b->e;
+    VocWorkspace& v = b->voc;
+    const int B = b->B;
+    hipStream_t st = b->stream;
+    // conv_pre k13 (reads the upsampler output with 12 history rows) -> S[0]
+    SVA_TRY(conv_act(b, v.pin, 4 * T, 1, 1, e->pre_k, e->conv_pre, v.S[0]));
+    long Tl = 4L * T;
+    for (int i = 0; i < 5; ++i) {
+        VocLevel& l = v.lv[i];
+        const Act &in = v.S[i], &out = v.S[i + 1];
+        const int s = e->ups_s[i], C = l.X.C;
+        // SiLU -> ConvTranspose (k = 2s): 2-tap GEMM over rows q-1, q with N = s*C  (firefly.py:284-285, 131-138)
+        ConvGemm p;
+        p.a_silu = 1;
+        SVA_CHECK(in.H >= 1, "ups: history");
+        SVA_TRY(gemm_call(b, in.p, in.bstride, (long)(in.H - 1) * in.C, in.C, B, (int)Tl, 1, 1, 2, in.C, e->ups[i], l.X.p, l.X.bstride, (long)l.X.H * C, s * C, p));
+        Tl *= s;
+        // ParallelBlock = mean of three ResBlock1 (firefly.py:183-190, 214-215): every form leaves the branch outputs in y3 and their mean is
+        // taken in a kernel of its own (fixed order => deterministic sum)
+        if (l.form == VocForm::Fused) SVA_TRY(voc_level_fused(b, i, (int)Tl));
+        else SVA_TRY(voc_level_chain(b, i, (int)Tl));
+        SVA_TRY(launch_mean3(l.y3[0].p, l.y3[1].p, l.y3[2].p, l.y3[0].bstride, out.p, out.bstride, (long)out.H * C, Tl * C / 4, B, st));
     }
+    SVA_TRY(launch_conv_post_tanh(v.S[5].p, v.S[5].bstride, (long)(v.S[5].H - (e->post_k - 1)) * v.S[5].C, B, (int)Tl, v.S[5].C, e->post_k,
+                                  e->post_w, e->post_b, v.pcm_dst ? v.pcm_dst : v.d_pcm, v.pcm_dst ? v.pcm_dst_bstride : 2048L * v.Tv, 0, st, b->d_slot_flag));
+    if (v.pcm_dst) v.pcm_direct_done = true;
+    if (!shift) return 0;
+    // update T in the descriptors if it changed (host table re-uploaded; rare)
+    bool dirty = false;
+    for (auto& d : v.shift_host) {
+        const int t = (int)((long)T * d.pad);      // pad holds rows-per-code-frame of this tensor
+        if (d.T != t) { d.T = t; dirty = true; }
+    }
+    if (dirty) {
+        SVA_HIP(hipMemcpyAsync(v.d_shift, v.shift_host.data(), sizeof(ShiftDesc) * v.shift_host.size(), hipMemcpyHostToDevice, st));
+        SVA_HIP(hipStreamSynchronize(st));
+    }
+    SVA_TRY(launch_shift_history(v.d_shift, (int)v.shift_host.size(), B, st, B <= 8 ? 4 : 1));
+    return launch_add_i32(v.d_frames, T, st);      // (the fused levels ask whether their halo lies inside the stream)
+}
+
+static bool runs_fsq(VocPart p) { return p == VocPart::All || p == VocPart::QuantizerDecode || p == VocPart::FsqOnly; }
+static bool runs_upsampler(VocPart p) { return p == VocPart::All || p == VocPart::QuantizerDecode || p == VocPart::AfterFsq; }
+static bool runs_head(VocPart p) { return p == VocPart::All || p == VocPart::Head || p == VocPart::AfterFsq; }
+
+int vocode(sva_batch* b, int T, bool shift, VocPart part) {
+    SVA_CHECK(T >= 1 && T <= b->voc.Tv, "vocode: T out of range");
+    if (runs_fsq(part)) SVA_TRY(voc_fsq(b, T));
+    if (runs_upsampler(part)) SVA_TRY(voc_upsampler(b, T));
+    if (runs_head(part)) SVA_TRY(voc_head(b, T, shift));
     return 0;
 }
 
@@ -1041,7 +1018,7 @@ int register_shift(sva_batch* b, Act& a, int rows_per_frame) {
     if (a.H == 0) return 0;
     ShiftDesc d;
     d.ptr = a.p; d.bstride = a.bstride; d.H = a.H; d.T = 0; d.C = a.C; d.pad = rows_per_frame;
-    b->shift_host.push_back(d);
+    b->voc.shift_host.push_back(d);
     return 0;
 }
 

@@ -177,6 +177,33 @@ def test_vocoder_resblock_convs_on_operand_planes_window_and_stream(weights0, vo
     eng.close()
 
 
+@pytest.mark.parametrize("setting", ["voc_dma=-1,voc_fused_mask=-1", "voc_dma=-1,voc_fused_mask=0", "voc_dma=1,voc_fused_mask=0", "voc_dma=1,voc_fused_mask=3"])
+def test_vocode_window_is_stateless_in_every_form(eng, setting):
+    """A window pass leaves no trace in the vocoder's streaming state, whatever form the levels run in (fused C = 16 level + fp32 rows; fp32 rows
+    alone; operand planes on every level, K-blocked and row-major; planes on the wide levels + both narrow levels fused): the same codes give the
+    same bits before and after a pass over other codes.  A history tensor or plane that sva_vocode_reset leaves out would carry rows of the second
+    pass into the third."""
+    from streamvoiceanon_amd import engine as E
+
+    lib = E.load_library()
+    c = load_golden("vocoder_s0")["codes"].astype(np.int32)
+    A = np.ascontiguousarray(np.concatenate([c[:, :, 0:3], c[:, :, 3:6]], axis=0))
+    B = np.ascontiguousarray(np.concatenate([c[:, :, 6:9], c[:, :, 9:12]], axis=0))
+    assert not np.array_equal(A, B)
+    lib.sva_debug_configure(setting.encode())      # read at batch creation
+    try:
+        b = E.Batch(eng, n_streams=2, voc_max_frames=4)
+    finally:
+        lib.sva_debug_configure(b"voc_dma=-1,voc_fused_mask=-1")
+    first = b.vocode_window(A)
+    other = b.vocode_window(B)
+    third = b.vocode_window(A)
+    b.close()
+    assert first.shape == (2, 3 * 2048) and np.abs(first).max() > 0
+    assert not np.array_equal(first, other)
+    assert np.array_equal(first, third)
+
+
 def _stream_vs_golden(eng, W, name, forced=False, device_rng=False, n_limit=None, use_graph=False, n_streams=1, slot=0):
     """n_streams > 1: the fixture's utterance in every slot of a batch (the batched kernels); taps are taken from `slot`."""
     from oracle import sva_oracle as O
