@@ -210,6 +210,38 @@ int sva_stream_get_sampling(sva_batch* b, int slot, float* temperature, float* t
  * host wall time of the last activation -- prompt prefill, delay fill, vocoder priming -- taken after its final synchronise (0 before the first) */
 int sva_stream_activations(sva_batch* b, long counts[2], float* last_ms);
 
+/* ---- I/O adaptor: feed and read a running batch at a caller-chosen sample rate, in blocks of any length, as float32 or int16 ----
+ * Every slot is fed n samples per call at io_rate and gets n samples back at io_rate; everything between the caller's buffer and the engine's
+ * 44.1 kHz chunk runs on the device (csrc/io/).  The filter is the one audio_io.resample states: torchaudio 2.4 sinc_interp_hann,
+ * lowpass_filter_width 6, rolloff 0.99, weights computed in float64 and rounded once to fp32.  Let x be everything pushed into a slot
+ * (samples before the slot's last restart count as zeros): the engine's k-th chunk is resample(x, io_rate, 44100)[k * 2048c : (k + 1) * 2048c],
+ * and the caller receives L zeros followed by resample(Y, 44100, io_rate), Y being the concatenated step outputs.  A sample is produced as
+ * soon as the last input sample its phase reads has arrived (taps at the clip of the window, weight ~4e-33, are left out), each in one
+ * fixed-order fmaf chain, so the result does not depend on how the signal is cut into calls.  L -- the smallest delay with which every call
+ * that pushes n can pop n -- depends on io_rate and chunk_frames only.  io_rate == 44100 is a re-blocking pass-through: samples are copied.
+ * int16: x / 32768 on load; round-to-nearest-even of y * 32768 saturated to [-32768, 32767] on store.
+ * Accepted rates: an integer in 8000 .. 96000 whose ratio to 44100, reduced by their gcd, has both terms <= 640; others are refused.
+ * One adaptor per batch, opened after sva_streams_begin.  While it is open, sva_step / sva_step_device / sva_step_device_on /
+ * sva_stream_chunks and sva_streams_begin on the batch are refused (they would desynchronise the FIFOs); sva_stream_restart also zeroes the
+ * slot's two filter histories and its share of the chunk staging, sva_stream_retire needs nothing beyond its flags (a retired slot's input
+ * is not read); every other slot stays bit-identical.  sva_batch_destroy closes a forgotten adaptor. */
+typedef struct sva_io sva_io;
+/* fmt: 0 float32, 1 int16.  max_block: largest n of one call.  Opening finds L by walking three periods of the counters' pattern sample by
+ * sample on the host (a period is io_rate / gcd * 2048c / gcd(44100 / gcd, 2048c) samples): 10-45 ms at chunk_frames 1-4, about 0.7 s at 64. */
+int sva_io_open(sva_batch* b, int io_rate, int fmt, int max_block, sva_io** out);
+void sva_io_close(sva_io* io);
+/* host arrays [B][n] in and out; runs the planned steps (0, 1 or several, the sva_step_device path, pipelined if the batch is); synchronised on
+ * return; steps_run may be NULL.  n outside 1 .. max_block is refused with the state unchanged. */
+int sva_io_process(sva_io* io, const void* pcm_in, void* pcm_out, int n, int* steps_run);
+/* device pointers; asynchronous, no host synchronisation; ordering as for sva_step_device_on: the engine waits on caller_stream before its
+ * first access to d_in and d_out (NULL is the default stream, ordered like any other), join_output != 0 makes caller_stream wait for the
+ * output; sva_sync / sva_join_stream apply.
+ * Both process calls advance the adaptor's sample counters before they launch: if a launch or an engine step then fails, counters and
+ * device state have diverged, and every later call on this adaptor is refused with an error that says so (close it, open a new one). */
+int sva_io_process_device(sva_io* io, const void* d_in, void* d_out, int n, void* caller_stream, int join_output);
+/* L in io-rate samples; the part of it that is filter delay (what L would be with an engine that consumed single samples) */
+int sva_io_latency(sva_io* io, int* total, int* filter_only);
+
 /* AR seams with caller-supplied content codes (chunk_frames == 1):
  *   ARVCWrapper.prefill_src_condition4delay (modules/arvc_wrapper.py:114-119): codes int64[B][delay]
  *   ARVCWrapper.decode_one (:121-126 -> dual_ar_stream.py:817-837): code int64[B] -> codes_out int32[B][8],
@@ -388,6 +420,18 @@ int sva_test_conv_gemm(int device, int n, const long long* desc, const float* fp
  * n_redo, redo[B] | n_rewind, rewind[B] x {slot, position} | n_activated, activated[B] | vocoder priming frames (begin: of the batch; a step:
  * of its first activated slot; else -1).  Unused list entries are -1; the lists are what the step planned before it carried them out. */
 int sva_test_slot_book(const int* cfg, const int* ops, int n_ops, int* trace);
+/* The adaptor's planner (csrc/io/io_plan.h) without a batch and without a GPU: a stream at io_rate fed blocks[n_blocks] samples.
+ * out: 12 header ints {L, filter part of L, chunk staging buffers, history samples at io_rate, history samples at 44100, output FIFO
+ * samples, period of the counters' pattern in pushed samples, in orig, in new, in width, out width, max block}, then 5 ints per block:
+ * {model-rate samples made ready, engine steps, io-rate samples produced, model-rate samples staged after the call, output FIFO fill after
+ * the call's pop}.  Returns the ints written; < 0 for an unsupported rate or a short out. */
+int sva_test_io_plan(int io_rate, int chunk_frames, const int* blocks, int n_blocks, int* out, int out_cap);
+/* Kernel hook of the adaptor: one stream-free run over host arrays x [B][n] (fmt_in) -> y [B][y_cap] (fmt_out), the input cut into calls
+ * at splits[n_splits] (ascending sample indices inside 0 .. n).  to_rate == 44100: io_resample_in_kernel through its chunk staging;
+ * from_rate == 44100: io_resample_out_kernel through its FIFO; both 44100: one after the other, as the pass-through does.  int16 is
+ * accepted where the adaptor has it: the input of the first, the output of the second.  n_out: samples per slot that were ready. */
+int sva_test_resample(int device, int from_rate, int to_rate, int fmt_in, int fmt_out, int B, const void* x, long n, const int* splits,
+                      int n_splits, void* y, long y_cap, long* n_out);
 /* The book's stored prompt: a prompt of R frames (content code i at frame i, audio code 1000 q + i in codebook q) stored truncated to Rt
  * frames; out [ncb][n] = frames [first, first + n) of the last P stored frames (what primes a vocoder), stored[4] = {ref_len, content codes
  * kept, audio codes kept, last content code kept}. */

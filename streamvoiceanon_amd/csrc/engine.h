@@ -361,6 +361,9 @@ struct sva_batch {
 
     sva::VocWorkspace voc;
     const float* step_src = nullptr;       // device-buffer step: ring_write reads the caller's chunk directly (no staging copy)
+    // the I/O adaptor (sva_io_open): while one is open only it may step the batch (io_stepping marks its own calls)
+    sva_io* io = nullptr;
+    bool io_stepping = false;
 
     // pinned staging
     float *hp_in = nullptr, *hp_out = nullptr;

@@ -7,6 +7,7 @@
 // arithmetic runs in the HIP kernels of gemm.hip / kernels.hip.
 #include "engine_internal.h"
 #include "engine_kernels.h"
+#include "io/resample.h"
 #include <map>
 #include <mutex>
 
@@ -702,6 +703,7 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
 extern "C" void sva_batch_destroy(sva_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->e->device);
+    if (b->io) sva_io_close(b->io);
     (void)quiesce(b);
     {   // (a later batch may be allocated at this address: the chain's "same batch, no wait" test must not match it)
         std::lock_guard<std::mutex> lk(b->e->mega_mu);
@@ -888,6 +890,7 @@ extern "C" int sva_vocoder_head(sva_batch* b, const float* z, int T, float* pcm_
 
 extern "C" int sva_streams_begin(sva_batch* b) {
     SVA_CHECK(b, "null batch");
+    SVA_CHECK(!b->io, "sva_streams_begin: an I/O adaptor is open on this batch; close it first (its FIFOs belong to the running streams)");
     SVA_HIP(hipSetDevice(b->e->device));
     (void)hipGetLastError();
     SVA_TRY(quiesce(b));
@@ -1517,6 +1520,7 @@ int step_body(sva_batch* b) {
 }  // namespace
 
 static int check_ar_fail(sva_batch* b);
+static int io_restart_slot(sva_io* io, int slot);
 
 // drained streams, main stream current: what the slot calls below change is read by the next step's launches
 static int drain_for_slot_call(sva_batch* b) {
@@ -1565,6 +1569,7 @@ extern "C" int sva_stream_restart(sva_batch* b, int slot, const int64_t* ref_con
     P_.timbre.assign(timbre, timbre + (size_t)c.timbre_tokens * c.timbre_dim);
     P_.R = R; P_.seed = noise_seed;
     b->slots.restart(slot, std::move(P_), nspk, kSlotOutputMuted);      // (... and back to the batch's sampling pair)
+    if (b->io) SVA_TRY(io_restart_slot(b->io, slot));
     SVA_TRY(upload_slot_position(b, slot));
     SVA_TRY(upload_slot_sampling(b, slot));
     return upload_slot_flag(b, slot);
@@ -1615,6 +1620,7 @@ extern "C" int sva_stream_activations(sva_batch* b, long counts[2], float* last_
 
 extern "C" int sva_step(sva_batch* b, const float* pcm_in, float* pcm_out, const float* noise, const int32_t* forced_codes) {
     SVA_CHECK(b && pcm_in && pcm_out && b->begun, "sva_step: bad argument or sva_streams_begin not called");
+    SVA_CHECK(!b->io, "sva_step: an I/O adaptor is open on this batch (sva_io_open): stepping it directly would desynchronise the adaptor's FIFOs -- use sva_io_process or close the adaptor");
     SVA_HIP(hipSetDevice(b->e->device));
     (void)hipGetLastError();
     SVA_TRY(quiesce(b));
@@ -1649,6 +1655,7 @@ extern "C" int sva_step(sva_batch* b, const float* pcm_in, float* pcm_out, const
 
 extern "C" int sva_step_device(sva_batch* b, const float* d_pcm_in, float* d_pcm_out) {
     SVA_CHECK(b && d_pcm_in && d_pcm_out && b->begun, "sva_step_device: bad argument");
+    SVA_CHECK(!b->io || b->io_stepping, "sva_step_device: an I/O adaptor is open on this batch (sva_io_open): stepping it directly would desynchronise the adaptor's FIFOs -- use sva_io_process or close the adaptor");
     SVA_HIP(hipSetDevice(b->e->device));
     (void)hipGetLastError();
     const int B = b->B, n = 2048 * b->p.chunk_frames;
@@ -1682,6 +1689,7 @@ extern "C" int sva_step_device(sva_batch* b, const float* d_pcm_in, float* d_pcm
 // engine keeps streams of its own; these entry points tie them to the caller's stream with events instead of host synchronisation.
 extern "C" int sva_step_device_on(sva_batch* b, const float* d_pcm_in, float* d_pcm_out, void* caller_stream, int join_output) {
     SVA_CHECK(b && b->begun, "sva_step_device_on: bad argument");
+    SVA_CHECK(!b->io, "sva_step_device_on: an I/O adaptor is open on this batch (sva_io_open): stepping it directly would desynchronise the adaptor's FIFOs -- use sva_io_process or close the adaptor");
     SVA_HIP(hipSetDevice(b->e->device));
     hipStream_t cs = (hipStream_t)caller_stream;
     {   // everything already enqueued on the caller's stream happens before the engine's first access to d_pcm_in
@@ -1717,6 +1725,7 @@ extern "C" int sva_join_stream(sva_batch* b, void* caller_stream) {
 
 extern "C" int sva_stream_chunks(sva_batch* b, const float* pcm_in, float* pcm_out, int n_chunks) {
     SVA_CHECK(b && pcm_in && pcm_out && b->begun && n_chunks >= 1, "sva_stream_chunks: bad argument");
+    SVA_CHECK(!b->io, "sva_stream_chunks: an I/O adaptor is open on this batch (sva_io_open): stepping it directly would desynchronise the adaptor's FIFOs -- use sva_io_process or close the adaptor");
     SVA_HIP(hipSetDevice(b->e->device));
     (void)hipGetLastError();
     SVA_TRY(quiesce(b));
@@ -2199,5 +2208,178 @@ extern "C" int sva_get_gemm_stats(sva_batch* b, double* flops, long* launches) {
     SVA_CHECK(b && flops && launches, "null argument");
     *flops = b->gemm_flops;
     *launches = b->gemm_launches;
+    return 0;
+}
+
+// ============================================================================================
+// I/O adaptor (include/sva.h: sva_io_*): the plan is IoPlan's (io/io_plan.h), the two kernels are io/resample.hip's
+// ============================================================================================
+struct sva_io {
+    sva_batch* b = nullptr;
+    IoPlan plan;
+    int fmt = 0;
+    size_t esize = 4;                      // bytes of a caller sample
+    ResampleDev din, dout;
+    float* hist_in[2] = {nullptr, nullptr};      // [B][plan.hist_in], alternating per call
+    float* hist_out[2] = {nullptr, nullptr};     // [B][plan.hist_out], alternating per step
+    int par_in = 0, par_out = 0;
+    float* stage = nullptr;                // [nbuf][B][2048c] chunk staging
+    float* step_out = nullptr;             // [B][2048c] the step's PCM
+    void* fifo = nullptr;                  // [B][fifo_cap] output FIFO (fmt)
+    void *d_in = nullptr, *d_out = nullptr;      // [B][max_block] device copies of sva_io_process's host arrays
+    bool failed = false;                   // a launch or a step failed behind the plan's counters: plan and device state have diverged
+};
+
+static int io_free(sva_io* io) {
+    for (void* p : {(void*)io->hist_in[0], (void*)io->hist_in[1], (void*)io->hist_out[0], (void*)io->hist_out[1], (void*)io->stage, (void*)io->step_out,
+                    io->fifo, io->d_in, io->d_out})
+        if (p) (void)hipFree(p);
+    resample_free(&io->din);
+    resample_free(&io->dout);
+    delete io;
+    return 0;
+}
+
+extern "C" int sva_io_open(sva_batch* b, int io_rate, int fmt, int max_block, sva_io** out) {
+    SVA_CHECK(b && out, "sva_io_open: null argument");
+    SVA_CHECK(b->begun, "sva_io_open: the batch has not begun (sva_streams_begin)");
+    SVA_CHECK(!b->io, "sva_io_open: this batch already has an adaptor (one per batch)");
+    SVA_CHECK(fmt == kIoFmtF32 || fmt == kIoFmtI16, "sva_io_open: fmt is 0 (float32) or 1 (int16)");
+    SVA_CHECK(max_block >= 1 && max_block <= (1 << 20), "sva_io_open: max_block outside 1 .. 2^20");
+    SVA_CHECK(io_rate_supported(io_rate), std::string("sva_io_open: unsupported io_rate ") + std::to_string(io_rate) + ": " + kIoRateRule);
+    SVA_TRY(drain_for_slot_call(b));
+    sva_io* io = new sva_io();
+    io->b = b; io->fmt = fmt; io->esize = fmt == kIoFmtI16 ? 2 : 4;
+    if (!io->plan.open(io_rate, b->p.chunk_frames, max_block)) { delete io; SVA_CHECK(false, "sva_io_open: the planner refused this rate"); }
+    const IoPlan& pl = io->plan;
+    const size_t B = (size_t)b->B;
+    auto zalloc = [&](void** p, size_t bytes) -> int {
+        SVA_HIP(hipMalloc(p, bytes));
+        SVA_HIP(hipMemset(*p, 0, bytes));
+        return 0;
+    };
+    int rc = resample_upload(pl.in, &io->din);
+    if (!rc) rc = resample_upload(pl.out, &io->dout);
+    for (int k = 0; k < 2 && !rc; ++k) {
+        rc = zalloc((void**)&io->hist_in[k], sizeof(float) * B * pl.hist_in);
+        if (!rc) rc = zalloc((void**)&io->hist_out[k], sizeof(float) * B * pl.hist_out);
+    }
+    if (!rc) rc = zalloc((void**)&io->stage, sizeof(float) * B * pl.stage_cap);
+    if (!rc) rc = zalloc((void**)&io->step_out, sizeof(float) * B * pl.chunk);
+    if (!rc) rc = zalloc(&io->fifo, io->esize * B * pl.fifo_cap);              // (zeros: the L samples in front of the first output)
+    if (!rc) rc = zalloc(&io->d_in, io->esize * B * max_block);
+    if (!rc) rc = zalloc(&io->d_out, io->esize * B * max_block);
+    if (rc) { io_free(io); return rc; }
+    b->io = io;
+    *out = io;
+    return 0;
+}
+
+extern "C" void sva_io_close(sva_io* io) {
+    if (!io) return;
+    sva_batch* b = io->b;
+    (void)hipSetDevice(b->e->device);
+    (void)drain_for_slot_call(b);          // (the adaptor's kernels run on the batch's streams)
+    b->io = nullptr;
+    io_free(io);
+}
+
+// sva_stream_restart: what the slot received and produced so far counts as zeros
+static int io_restart_slot(sva_io* io, int slot) {
+    sva_batch* b = io->b;
+    const IoPlan& pl = io->plan;
+    hipStream_t st = b->stream;
+    for (int k = 0; k < 2; ++k) {
+        SVA_HIP(hipMemsetAsync(io->hist_in[k] + (size_t)slot * pl.hist_in, 0, sizeof(float) * pl.hist_in, st));
+        SVA_HIP(hipMemsetAsync(io->hist_out[k] + (size_t)slot * pl.hist_out, 0, sizeof(float) * pl.hist_out, st));
+    }
+    for (int k = 0; k < pl.nbuf; ++k) SVA_HIP(hipMemsetAsync(io->stage + ((size_t)k * b->B + slot) * pl.chunk, 0, sizeof(float) * pl.chunk, st));
+    SVA_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+// One call of the adaptor on device buffers.  ev_caller (may be null: the buffers are the adaptor's own, filled on the main stream): the main
+// stream already waits for it, and so must the stream of the pop.  Runs behind the plan's counters: an error from here on leaves the adaptor failed.
+static int io_run(sva_io* io, const void* d_in, void* d_out, int n, hipEvent_t ev_caller) {
+    sva_batch* b = io->b;
+    IoPlan& pl = io->plan;
+    const int B = b->B, C = pl.chunk;
+    hipStream_t se = b->main_stream;
+    const long long n0 = pl.N, s0 = pl.S;
+    const IoCall c = pl.push(n);
+    {
+        ResampleCall rc_;
+        rc_.n0 = n0; rc_.j0 = c.m0; rc_.j1 = c.m1; rc_.n = n;
+        rc_.hist_old = io->hist_in[io->par_in]; rc_.hist_new = io->hist_in[io->par_in ^ 1]; rc_.slot_flag = b->d_slot_flag;
+        io->par_in ^= 1;
+        SVA_TRY(launch_io_resample_in(io->din, rc_, B, d_in, io->fmt, io->stage, C, pl.nbuf, se));
+    }
+    for (int s_ = 0; s_ < c.steps; ++s_) {
+        const long long k = s0 + s_;
+        b->io_stepping = true;
+        const int src = sva_step_device(b, io->stage + (size_t)(k % pl.nbuf) * B * C, io->step_out);
+        b->io_stepping = false;
+        if (src) return src;
+        ResampleCall rc_;
+        rc_.n0 = k * C; rc_.j0 = pl.out.ready(k * C); rc_.j1 = pl.out.ready((k + 1) * C); rc_.n = C;
+        rc_.hist_old = io->hist_out[io->par_out]; rc_.hist_new = io->hist_out[io->par_out ^ 1];
+        io->par_out ^= 1;
+        // on the chain that holds the step's PCM: the next step's vocoder overwrites step_out behind this read
+        SVA_TRY(launch_io_resample_out(io->dout, rc_, B, io->step_out, C, io->fifo, io->fmt, pl.fifo_cap, pl.L, b->out_stream ? b->out_stream : se));
+    }
+    // pop [n0, n0 + n) behind the last write of the FIFO
+    hipStream_t so = b->out_stream ? b->out_stream : se;
+    if (ev_caller && so != se) SVA_HIP(hipStreamWaitEvent(so, ev_caller, 0));
+    const size_t es = io->esize;
+    const int at = (int)(n0 % pl.fifo_cap), first = std::min(n, pl.fifo_cap - at);
+    SVA_HIP(hipMemcpy2DAsync(d_out, es * n, (const char*)io->fifo + es * at, es * pl.fifo_cap, es * first, B, hipMemcpyDeviceToDevice, so));
+    if (first < n)
+        SVA_HIP(hipMemcpy2DAsync((char*)d_out + es * first, es * n, io->fifo, es * pl.fifo_cap, es * (n - first), B, hipMemcpyDeviceToDevice, so));
+    return 0;
+}
+static int io_check_call(sva_io* io, const void* in, void* out, int n, const char* who) {
+    SVA_CHECK(io && in && out, std::string(who) + ": null argument");
+    SVA_CHECK(n >= 1 && n <= io->plan.max_block, std::string(who) + ": n outside 1 .. max_block");
+    SVA_CHECK(!io->failed, std::string(who) + ": an earlier call of this adaptor failed after its counters had advanced; close it and open a new one");
+    return 0;
+}
+
+extern "C" int sva_io_process_device(sva_io* io, const void* d_in, void* d_out, int n, void* caller_stream, int join_output) {
+    SVA_TRY(io_check_call(io, d_in, d_out, n, "sva_io_process_device"));
+    sva_batch* b = io->b;
+    SVA_HIP(hipSetDevice(b->e->device));
+    // everything already enqueued on the caller's stream (NULL is a stream too: the default one) happens before the engine's first access to
+    // d_in and d_out, as in sva_step_device_on
+    hipEvent_t ev_caller = next_event(b);
+    SVA_HIP(hipEventRecord(ev_caller, (hipStream_t)caller_stream));
+    SVA_HIP(hipStreamWaitEvent(b->main_stream, ev_caller, 0));
+    io->failed = true;
+    SVA_TRY(io_run(io, d_in, d_out, n, ev_caller));
+    if (join_output) SVA_TRY(sva_join_stream(b, caller_stream));
+    io->failed = false;
+    return 0;
+}
+
+extern "C" int sva_io_process(sva_io* io, const void* pcm_in, void* pcm_out, int n, int* steps_run) {
+    SVA_TRY(io_check_call(io, pcm_in, pcm_out, n, "sva_io_process"));
+    sva_batch* b = io->b;
+    SVA_HIP(hipSetDevice(b->e->device));
+    (void)hipGetLastError();
+    const size_t bytes = io->esize * (size_t)b->B * n;
+    const long long s0 = io->plan.S;
+    SVA_HIP(hipMemcpyAsync(io->d_in, pcm_in, bytes, hipMemcpyHostToDevice, b->main_stream));
+    io->failed = true;
+    SVA_TRY(io_run(io, io->d_in, io->d_out, n, nullptr));
+    SVA_TRY(sva_sync(b));                  // (joins every chain into the main stream first)
+    SVA_HIP(hipMemcpy(pcm_out, io->d_out, bytes, hipMemcpyDeviceToHost));
+    io->failed = false;
+    if (steps_run) *steps_run = (int)(io->plan.S - s0);
+    return 0;
+}
+
+extern "C" int sva_io_latency(sva_io* io, int* total, int* filter_only) {
+    SVA_CHECK(io, "sva_io_latency: null adaptor");
+    if (total) *total = io->plan.L;
+    if (filter_only) *filter_only = io->plan.L_filter;
     return 0;
 }

@@ -84,6 +84,14 @@ def load_library():
     lib.sva_step_device.argtypes = [vp, vp, vp]
     lib.sva_step_device_on.argtypes = [vp, vp, vp, vp, C.c_int]
     lib.sva_join_stream.argtypes = [vp, vp]
+    lib.sva_io_open.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
+    lib.sva_io_close.argtypes = [vp]
+    lib.sva_io_close.restype = None
+    lib.sva_io_process.argtypes = [vp, vp, vp, i32, C.POINTER(C.c_int)]
+    lib.sva_io_process_device.argtypes = [vp, vp, vp, i32, vp, i32]
+    lib.sva_io_latency.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.sva_test_io_plan.argtypes = [i32, i32, vp, i32, vp, i32]
+    lib.sva_test_resample.argtypes = [i32, i32, i32, i32, i32, i32, vp, C.c_long, vp, i32, vp, C.c_long, C.POINTER(C.c_long)]
     lib.sva_batch_uses_persistent_decode.argtypes = [vp]
     lib.sva_test_force_ar_timeout.argtypes = [vp]
     lib.sva_test_kv_rows.argtypes = [vp, i32, i32, i32, vp]
@@ -160,6 +168,7 @@ EXPORTED_SYMBOLS = [
     "sva_op_cam_context", "sva_op_mul", "sva_op_add", "sva_op_conv2d", "sva_op_cf_to_rows", "sva_op_fbank_power", "sva_op_stft_mag", "sva_op_attention",
     "sva_op_geglu", "sva_op_l2norm", "sva_ops_capture_begin", "sva_ops_capture_end", "sva_ops_graph_launch", "sva_ops_graph_free",
     "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_prefill_attention_runs", "sva_test_prefill_pack", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_test_sampler_launch", "sva_test_sampler_rows", "sva_test_ar_device", "sva_test_gemv", "sva_test_token_ops", "sva_test_step_ops", "sva_test_voc_level", "sva_test_voc_conv", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
+    "sva_io_open", "sva_io_close", "sva_io_process", "sva_io_process_device", "sva_io_latency", "sva_test_io_plan", "sva_test_resample",
 ]
 
 
@@ -301,6 +310,7 @@ class Batch:
         p.slot_priming = int(slot_priming)
         self.p = p
         self.B, self.chunk = n_streams, chunk_frames
+        self.io = None                             # the I/O adaptor, once open_io() has opened one
         self.h = C.c_void_p()
         _check(self.lib.sva_batch_create(engine.h, C.byref(p), C.byref(self.h)), "sva_batch_create")
         engine._batches.add(self)
@@ -309,6 +319,9 @@ class Batch:
 
     def close(self):
         if self.h:
+            if self.io is not None:
+                self.io.h = None                   # (sva_batch_destroy closes a forgotten adaptor)
+                self.io = None
             self.lib.sva_batch_destroy(self.h)
             self.h = None
 
@@ -317,6 +330,13 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+    def open_io(self, io_rate, fmt="f32", max_block=4096):
+        """sva_io_open: feed and read this (begun) batch at `io_rate` in blocks of any length up to max_block, as float32 ("f32") or int16
+        ("i16") -> BatchIO.  While it is open the batch is stepped through it alone; BatchIO.close() gives step() back."""
+        assert self.io is None, "one adaptor per batch"
+        self.io = BatchIO(self, io_rate, fmt, max_block)
+        return self.io
 
     def prefill_prompt(self, slot, ref_content_codes, ref_audio_codes, style, timbre, noise_seed=0):
         cc = np.ascontiguousarray(ref_content_codes, dtype=np.int64).reshape(-1)
@@ -601,6 +621,95 @@ class Batch:
         f, n = C.c_double(), C.c_long()
         _check(self.lib.sva_get_gemm_stats(self.h, C.byref(f), C.byref(n)), "sva_get_gemm_stats")
         return f.value, n.value
+
+
+IO_FORMATS = {"f32": (0, np.float32), "i16": (1, np.int16)}
+
+
+def io_rate_supported(io_rate) -> bool:
+    """the rule sva_io_open states: an integer in 8000 .. 96000 whose ratio to 44100, reduced by their gcd, has both terms <= 640"""
+    r = int(io_rate)
+    if r != io_rate or not 8000 <= r <= 96000:
+        return False
+    g = math.gcd(r, 44100)
+    return r // g <= 640 and 44100 // g <= 640
+
+
+class BatchIO:
+    """The I/O adaptor of a batch (include/sva.h: sva_io_*): every call pushes n samples per slot at io_rate and pops n samples at io_rate, the
+    output delayed by `latency` samples; resampling, format conversion and re-blocking run on the device."""
+
+    def __init__(self, batch: Batch, io_rate, fmt="f32", max_block=4096):
+        self.batch, self.lib = batch, batch.lib
+        self.io_rate, self.max_block = int(io_rate), int(max_block)
+        self.fmt, self.dtype = IO_FORMATS[fmt]
+        self.h = C.c_void_p()
+        _check(self.lib.sva_io_open(batch.h, self.io_rate, self.fmt, self.max_block, C.byref(self.h)), "sva_io_open")
+        total, filt = C.c_int(), C.c_int()
+        _check(self.lib.sva_io_latency(self.h, C.byref(total), C.byref(filt)), "sva_io_latency")
+        self.latency, self.filter_latency = int(total.value), int(filt.value)
+        self.steps_run = 0                         # engine steps of the last process() call
+
+    def process(self, x):
+        """[B, n] (or [n] for one stream) at io_rate -> the same shape and dtype; runs the engine steps that became due (0, 1 or several)"""
+        a = np.ascontiguousarray(x, dtype=self.dtype)
+        b = a.reshape(self.batch.B, -1)
+        out = np.empty_like(b)
+        steps = C.c_int()
+        _check(self.lib.sva_io_process(self.h, _ptr(b), _ptr(out), b.shape[1], C.byref(steps)), "sva_io_process")
+        self.steps_run = int(steps.value)
+        return out.reshape(a.shape)
+
+    def process_device(self, d_in_ptr, d_out_ptr, n, stream=None, join_output=True):
+        """sva_io_process_device on device buffers [B, n]: asynchronous, stream-ordered like Batch.step_device_on"""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+        _check(self.lib.sva_io_process_device(self.h, C.c_void_p(d_in_ptr), C.c_void_p(d_out_ptr), int(n), C.c_void_p(stream), int(bool(join_output))),
+               "sva_io_process_device")
+
+    def close(self):
+        if self.h:
+            self.lib.sva_io_close(self.h)
+            self.h = None
+            self.batch.io = None
+
+    def __del__(self):
+        try:
+            if self.batch.h:
+                self.close()
+        except Exception:
+            pass
+
+
+IO_PLAN_HEAD = ("L", "L_filter", "nbuf", "hist_in", "hist_out", "fifo_cap", "period", "orig", "new", "width_in", "width_out", "max_block")
+
+
+def test_io_plan(io_rate, chunk_frames, blocks):
+    """the adaptor's planner for a stream fed `blocks` (include/sva.h: sva_test_io_plan), no GPU needed -> (header dict, int32 [n_blocks, 5] rows
+    of {model-rate samples made ready, steps, io-rate samples produced, staged model-rate samples, output FIFO fill})"""
+    bl = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1)
+    out = np.zeros(12 + 5 * bl.size, np.int32)
+    n = load_library().sva_test_io_plan(int(io_rate), int(chunk_frames), _ptr(bl), bl.size, _ptr(out), out.size)
+    if n < 0:
+        _check(n, "sva_test_io_plan")
+    return dict(zip(IO_PLAN_HEAD, (int(v) for v in out[:12]))), out[12:].reshape(-1, 5)
+
+
+def test_resample(x, from_rate, to_rate, splits=(), fmt_in="f32", fmt_out="f32", device=0):
+    """either kernel of the adaptor over a host array [B, n] cut into calls at `splits` (include/sva.h: sva_test_resample) -> [B, n_ready]"""
+    fi, di = IO_FORMATS[fmt_in]
+    fo, do = IO_FORMATS[fmt_out]
+    a = np.ascontiguousarray(x, dtype=di)
+    assert a.ndim == 2
+    B, n = a.shape
+    cap = int(math.ceil(n * to_rate / from_rate)) + 8
+    y = np.zeros((B, cap), do)
+    sp = np.ascontiguousarray(splits, dtype=np.int32).reshape(-1)
+    n_out = C.c_long()
+    _check(load_library().sva_test_resample(device, int(from_rate), int(to_rate), fi, fo, B, _ptr(a), n, _ptr(sp) if sp.size else None, sp.size, _ptr(y), cap,
+                                            C.byref(n_out)), "sva_test_resample")
+    return y[:, :n_out.value].copy()
 
 
 def test_gemm(A, W, bias=None, device=0):

@@ -340,7 +340,11 @@ class InferenceWrapper:
         print(f"Setting delay to {self.delay} frames")
 
     def setup_stream_caches(self, encode_window_frames=96, decode_window_frames=64, max_seq_frames=768, buffer_frames=32,
-                            decode_chunk_frames=1, delay=None, pipeline=False):
+                            decode_chunk_frames=1, delay=None, pipeline=False, io_rate=None, io_fmt="f32", io_max_block=4096):
+        """io_rate (None = 44100 Hz float32 in whole chunks, as the reference): open the batch's I/O adaptor (engine.Batch.open_io), so that
+        process_one_chunk takes blocks of any length up to io_max_block at io_rate, float32 or int16 (io_fmt "f32" / "i16"), and returns
+        blocks of the same rate, length and format -- the GUI's sr_device mode (real-time-gui.py:1222-1230, 1340-1341), resampled on the
+        device; the output lags by self.batch.io.latency samples."""
         assert self._prompt is not None, "call prefill_prompt first (as stream_infer does, :631-645)"
         if delay is not None:
             self.delay = int(delay)
@@ -354,6 +358,8 @@ class InferenceWrapper:
         ac, cc, st, tm = self._prompt
         self.batch.prefill_prompt(0, cc.reshape(-1), ac.reshape(8, -1), st.reshape(-1), tm.reshape(32, -1), noise_seed=self._noise_seed)
         self.batch.begin()
+        if io_rate is not None:
+            self.batch.open_io(int(io_rate), io_fmt, int(io_max_block))
 
     # ---- files ---------------------------------------------------------------------------
     def _load_src(self, src):
@@ -517,10 +523,12 @@ class InferenceWrapper:
 
     # ---- per chunk ---------------------------------------------------------------------------------------
     def process_one_chunk(self, src_wav_chunk, pitch_shift=0.0):
-        """src_wav_chunk [1, 2048*c] (torch or numpy) -> same type/shape (:492-596): zeros for the first `delay` chunks."""
+        """src_wav_chunk [1, 2048*c] (torch or numpy) -> same type/shape (:492-596): zeros for the first `delay` chunks.  With an I/O
+        adaptor (setup_stream_caches(io_rate=...)): [1, n] of any n at the adaptor's rate and format -> the same shape."""
         is_torch = hasattr(src_wav_chunk, "detach")
         x = src_wav_chunk.detach().cpu().numpy() if is_torch else np.asarray(src_wav_chunk)
-        out = self.batch.step(x.reshape(1, -1).astype(np.float32))
+        io = getattr(self.batch, "io", None)
+        out = io.process(x.reshape(1, -1)) if io is not None else self.batch.step(x.reshape(1, -1).astype(np.float32))
         if is_torch:
             import torch
 

@@ -58,25 +58,63 @@ class RealtimeSession:
         self.reference_wav_name = ""
         self.decode_chunk_frames = 0
         self.prefills = 0                    # how many times the prompt was rebuilt (tests, diagnostics)
+        self.io = None                       # (samplerate, format, max block) of the open I/O adaptor
 
-    def custom_infer(self, model_set, reference_wav, new_reference_wav_name, input_wav, n_frame_delay=2, alpha=0.7):
+    def custom_infer(self, model_set, reference_wav, new_reference_wav_name, input_wav, n_frame_delay=2, alpha=0.7, samplerate=44100,
+                     block_frame=1, max_block=None):
         """reference_wav: float array at 44.1 kHz; input_wav: [2048 * k] block (torch tensor or array) -> converted block of the
-        same kind and length (zeros while the decoder delay fills, infer_arvc.py:519-525)."""
+        same kind and length (zeros while the decoder delay fills, infer_arvc.py:519-525).
+
+        samplerate != 44100 is the GUI's sr_device mode (real-time-gui.py:1222-1230, 1340-1341: the sound device's own rate): input_wav is
+        a block of ANY length at that rate, float32 or int16, and the converted block comes back at that rate, length and format, resampled
+        on the device (engine.BatchIO) and delayed by model_set.batch.io.latency samples.  block_frame = decode chunk frames of the engine
+        underneath; max_block = the longest block that will come (default: twice this one, at least 4096).  With max_block given the adaptor
+        is used at 44100 too: its pass-through takes any block length and int16 there."""
+        if int(samplerate) != 44100 or max_block is not None:      # (max_block: the caller asks for the adaptor, also for its 44.1 kHz pass-through)
+            return self._infer_at_rate(model_set, reference_wav, new_reference_wav_name, input_wav, n_frame_delay, alpha, int(samplerate),
+                                       int(block_frame), max_block)
         n = int(input_wav.shape[-1])
         assert n % 2048 == 0 and n > 0, "block size must be a whole number of 2048-sample frames"
         frames = n // 2048
-        if self.reference_wav_name != new_reference_wav_name or self.decode_chunk_frames != frames:
+        if self.reference_wav_name != new_reference_wav_name or self.decode_chunk_frames != frames or self.io is not None:
             ref = np.asarray(reference_wav.detach().cpu().numpy() if hasattr(reference_wav, "detach") else reference_wav, dtype=np.float32)
             model_set.prefill_prompt(ref.reshape(-1), max_prompt_frames=64, delay=n_frame_delay, alpha=alpha)
             model_set.setup_stream_caches(encode_window_frames=64, decode_window_frames=64, max_seq_frames=768, buffer_frames=32,
                                           decode_chunk_frames=frames)
             self.reference_wav_name = new_reference_wav_name
             self.decode_chunk_frames = frames
+            self.io = None
             self.prefills += 1
         is_torch = hasattr(input_wav, "detach")
         block = input_wav.reshape(1, -1) if not is_torch else input_wav.reshape(1, -1)
         pred = model_set.process_one_chunk(block)
         return pred.squeeze() if is_torch else np.asarray(pred).reshape(-1)
+
+    def _infer_at_rate(self, model_set, reference_wav, new_reference_wav_name, input_wav, n_frame_delay, alpha, samplerate, block_frame, max_block):
+        is_torch = hasattr(input_wav, "detach")
+        x = input_wav.detach().cpu().numpy() if is_torch else np.asarray(input_wav)
+        fmt = "i16" if x.dtype == np.int16 else "f32"
+        n = int(x.shape[-1])
+        assert n > 0, "empty block"
+        io = self.io
+        if (self.reference_wav_name != new_reference_wav_name or self.decode_chunk_frames != block_frame or io is None or io[:2] != (samplerate, fmt)
+                or n > io[2]):
+            ref = np.asarray(reference_wav.detach().cpu().numpy() if hasattr(reference_wav, "detach") else reference_wav, dtype=np.float32)
+            cap = int(max_block) if max_block else max(4096, 2 * n)
+            assert n <= cap, "block longer than max_block"
+            model_set.prefill_prompt(ref.reshape(-1), max_prompt_frames=64, delay=n_frame_delay, alpha=alpha)
+            model_set.setup_stream_caches(encode_window_frames=64, decode_window_frames=64, max_seq_frames=768, buffer_frames=32,
+                                          decode_chunk_frames=block_frame, io_rate=samplerate, io_fmt=fmt, io_max_block=cap)
+            self.reference_wav_name = new_reference_wav_name
+            self.decode_chunk_frames = block_frame
+            self.io = (samplerate, fmt, cap)
+            self.prefills += 1
+        pred = np.asarray(model_set.process_one_chunk(x.reshape(1, -1))).reshape(-1)
+        if is_torch:
+            import torch
+
+            return torch.from_numpy(pred).to(input_wav.device)
+        return pred
 
 
     def run_block(self, model_set, reference_wav, reference_wav_name, input_wav, settings: GuiSettings):
@@ -90,6 +128,8 @@ class RealtimeSession:
 _default = RealtimeSession()
 
 
-def custom_infer(model_set, reference_wav, new_reference_wav_name, input_wav, n_frame_delay=2, alpha=0.7):
+def custom_infer(model_set, reference_wav, new_reference_wav_name, input_wav, n_frame_delay=2, alpha=0.7, samplerate=44100, block_frame=1,
+                 max_block=None):
     """real-time-gui.py:32-49 with the module-global state of the reference (one default session)."""
-    return _default.custom_infer(model_set, reference_wav, new_reference_wav_name, input_wav, n_frame_delay=n_frame_delay, alpha=alpha)
+    return _default.custom_infer(model_set, reference_wav, new_reference_wav_name, input_wav, n_frame_delay=n_frame_delay, alpha=alpha,
+                                 samplerate=samplerate, block_frame=block_frame, max_block=max_block)

@@ -13,10 +13,14 @@ Protocol (little endian, one TCP connection = one `RealtimeSession`):
         kind 2 CONF   payload = float32 alpha | i32 block_frame | i32 n_frame_delay (the three GUI settings a preset writes, :645-660)
         kind 3 BLOCK  payload = float32[2048 * block_frame] source samples
         kind 4 BYE
+        kind 5 IOCONF payload = i32 sample_rate | i32 fmt (0 float32, 1 int16) | i32 max_block: from here on a BLOCK is max_block or fewer
+                      samples of that format at that rate (any length: a 10 ms sound-card or telephony callback) and is answered with as
+                      many samples of that format at that rate, resampled on the device (engine.BatchIO; the GUI's sr_device mode);
+                      sample_rate 44100 with fmt 0 goes back to whole-chunk float32 blocks (44100 with fmt 1 is the adaptor's pass-through).  block_frame of CONF stays the engine's chunk.
     server -> client   for every BLOCK: u32 3 | u32 nbytes | float32[2048 * block_frame] converted samples (zeros while the delay fills)
                        for REF / CONF:  u32 kind | u32 0
                        on error:        u32 0xffffffff | u32 nbytes | utf-8 message (the connection stays open)
-    Frame sizes are bounded per kind (CONF = 12 bytes, BLOCK <= 64 frames of 2048 samples, REF <= 60 s of 44.1 kHz audio + a 1 KiB name);
+    Frame sizes are bounded per kind (CONF = IOCONF = 12 bytes, BLOCK <= 64 frames of 2048 samples -- after an IOCONF: max_block samples --, REF <= 60 s of 44.1 kHz audio + a 1 KiB name);
     an oversize or unknown frame is answered with an error and the connection is closed (its payload cannot be skipped safely).
 
 One connection is served at a time per process (the reference's GUI is single-session too); the engine and its weights stay
@@ -28,11 +32,13 @@ import struct
 
 import numpy as np
 
+from .engine import io_rate_supported
 from .realtime import GuiSettings, RealtimeSession
 
-KIND_REF, KIND_CONF, KIND_BLOCK, KIND_BYE, KIND_ERR = 1, 2, 3, 4, 0xFFFFFFFF
+KIND_REF, KIND_CONF, KIND_BLOCK, KIND_BYE, KIND_IOCONF, KIND_ERR = 1, 2, 3, 4, 5, 0xFFFFFFFF
 MAX_BLOCK_FRAMES = 64
-MAX_PAYLOAD = {KIND_REF: 1024 + 1 + 4 * 44100 * 60, KIND_CONF: 12, KIND_BLOCK: 4 * 2048 * MAX_BLOCK_FRAMES, KIND_BYE: 0}
+MAX_PAYLOAD = {KIND_REF: 1024 + 1 + 4 * 44100 * 60, KIND_CONF: 12, KIND_BLOCK: 4 * 2048 * MAX_BLOCK_FRAMES, KIND_BYE: 0, KIND_IOCONF: 12}
+IO_DTYPES = {0: "<f4", 1: "<i2"}
 
 
 class ProtocolError(Exception):
@@ -57,10 +63,12 @@ def serve_connection(conn, model_set):
     """The audio loop of real-time-gui.py:1313-1330 for one client: every BLOCK goes through RealtimeSession.run_block."""
     sess, settings = RealtimeSession(), GuiSettings()
     ref_name, ref_wav = "", None
+    ioconf = None                            # (sample_rate, fmt, max_block) of the last IOCONF, None: 44.1 kHz float32 in whole chunks
     while True:
         kind, nbytes = struct.unpack("<II", _recv_exact(conn, 8))
-        if kind not in MAX_PAYLOAD or nbytes > MAX_PAYLOAD[kind]:
-            msg = f"frame kind {kind} with {nbytes} bytes refused (limits: {MAX_PAYLOAD})"
+        limits = MAX_PAYLOAD if ioconf is None else {**MAX_PAYLOAD, KIND_BLOCK: ioconf[2] * np.dtype(IO_DTYPES[ioconf[1]]).itemsize}
+        if kind not in limits or nbytes > limits[kind]:
+            msg = f"frame kind {kind} with {nbytes} bytes refused (limits: {limits})"
             _send(conn, KIND_ERR, ("ProtocolError: " + msg).encode("utf-8"))
             raise ProtocolError(msg)
         payload = _recv_exact(conn, nbytes) if nbytes else b""
@@ -80,6 +88,25 @@ def serve_connection(conn, model_set):
                     raise ValueError(f"block_frame must be 1..{MAX_BLOCK_FRAMES} and n_frame_delay >= 1")
                 settings = GuiSettings(alpha=float(alpha), block_frame=int(bf), n_frame_delay=int(nd))
                 _send(conn, KIND_CONF)
+            elif kind == KIND_IOCONF:
+                rate, fmt, max_block = struct.unpack("<iii", payload)
+                if fmt not in IO_DTYPES or not 1 <= max_block <= 2048 * MAX_BLOCK_FRAMES:
+                    raise ValueError(f"fmt must be 0 (float32) or 1 (int16) and max_block 1..{2048 * MAX_BLOCK_FRAMES}")
+                if not io_rate_supported(rate):
+                    raise ValueError(f"sample_rate {rate} refused: an integer in 8000 .. 96000 whose ratio to 44100, reduced by their gcd, "
+                                     "has both terms <= 640")
+                ioconf = None if (rate, fmt) == (44100, 0) else (int(rate), int(fmt), int(max_block))
+                _send(conn, KIND_IOCONF)
+            elif kind == KIND_BLOCK and ioconf is not None:
+                if ref_wav is None:
+                    raise ValueError("send a reference (kind 1) before the first block")
+                dt = np.dtype(IO_DTYPES[ioconf[1]])
+                if len(payload) % dt.itemsize or not payload:
+                    raise ValueError("block payload is not a whole, positive number of samples")
+                block = np.frombuffer(payload, dtype=dt).astype(dt.newbyteorder("="))
+                out = sess.custom_infer(model_set, ref_wav, ref_name, block, n_frame_delay=settings.n_frame_delay, alpha=settings.alpha,
+                                        samplerate=ioconf[0], block_frame=settings.block_frame, max_block=ioconf[2])
+                _send(conn, KIND_BLOCK, np.ascontiguousarray(out, dtype=dt).tobytes())
             elif kind == KIND_BLOCK:
                 if ref_wav is None:
                     raise ValueError("send a reference (kind 1) before the first block")
@@ -137,8 +164,14 @@ class Client:
     def configure(self, alpha=0.7, block_frame=1, n_frame_delay=2):
         self._roundtrip(KIND_CONF, struct.pack("<fii", alpha, block_frame, n_frame_delay))
 
+    def configure_io(self, sample_rate=44100, fmt=0, max_block=4096):
+        """IOCONF: blocks of any length up to max_block at sample_rate, float32 (fmt 0) or int16 (fmt 1)"""
+        self._roundtrip(KIND_IOCONF, struct.pack("<iii", sample_rate, fmt, max_block))
+        self.dtype = IO_DTYPES[fmt]
+
     def convert(self, block):
-        return np.frombuffer(self._roundtrip(KIND_BLOCK, np.ascontiguousarray(block, dtype="<f4").tobytes()), dtype="<f4").copy()
+        dt = getattr(self, "dtype", "<f4")
+        return np.frombuffer(self._roundtrip(KIND_BLOCK, np.ascontiguousarray(block, dtype=dt).tobytes()), dtype=dt).copy()
 
     def close(self):
         try:
