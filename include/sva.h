@@ -210,6 +210,43 @@ int sva_stream_get_sampling(sva_batch* b, int slot, float* temperature, float* t
  * host wall time of the last activation -- prompt prefill, delay fill, vocoder priming -- taken after its final synchronise (0 before the first) */
 int sva_stream_activations(sva_batch* b, long counts[2], float* last_ms);
 
+/* ---- save and resume single streams ------------------------------------------------------------------------------------------
+ * A snapshot ("blob") holds everything one slot's stream consists of -- csrc/snapshot/slot_state.h lists it, DESIGN.md 5d tabulates it: the
+ * audio window, the encoder's histories and token cache, the content and prediction histories, the slow KV rows 0 .. last_pos, the speaker
+ * operands and cached embeddings, position, frame and content counters, noise seed, sampling pair, the vocoder's history rows, and the stored
+ * prompt -- in a versioned little-endian container (csrc/snapshot/snapshot_format.h: magic "SVASNAP1", two signatures, a checksum).  Two
+ * saves of an unchanged slot are byte-identical.
+ * Bit-identical continuation: run a stream for K0 steps in slot s of batch A, save it, load it into slot t of a batch D created from the same
+ * engine with the same sva_config and sva_stream_params (n_streams included), feed it chunks K0, K0 + 1, ...: it produces bit for bit the PCM,
+ * content codes, audio codes, positions and frame counts slot s of A produces for those chunks, whatever D's other slots carry and however
+ * many steps D has run.  D may be A itself (the same slot at a later step is a rollback).
+ * A batch with another n_streams is accepted exactly when its layout signature equals the blob's (the forms of its vocoder levels, the
+ * history geometry); the state is then transferred bit-exactly, and the outputs agree with the source as two batches of different size
+ * ever agree: their GEMM tilings differ.
+ * What does not travel: sampler edits (a batch property; the sampling pair is a slot property and does travel -- unlike sva_stream_restart,
+ * a load restores the blob's pair), the I/O adaptor's FIFOs and phase counters (batch-wide: both calls are refused while one is open), and
+ * the weights: they are NOT fingerprinted, loading a blob into an engine with other weights is the caller's error.
+ * Captured graphs stay valid: only device memory behind fixed pointers changes.  Both calls drain the batch's streams and run on its main
+ * stream, never beside a step.
+ * Refusals change nothing and name their reason through sva_last_error: a batch that has not begun, a slot out of range, an open I/O adaptor,
+ * a batch whose persistent AR kernel has timed out; save: a slot that is not decoding (phase 2), a buffer that is too small; load: a batch
+ * whose lock-step delay has not filled yet, a blob that is truncated, has a wrong magic or version or fails a checksum (-10 .. -14), a blob
+ * whose configuration (-15) or layout (-16) signature differs from the batch's -- the message names the first differing field -- and a blob
+ * whose slot fields contradict each other or whose code tables (content and prediction histories, prompt tail, stored prompt) hold a value
+ * outside its embedding table (-13): a checksum is no proof of origin, so what a load installs as gather indices is range-checked. */
+/* bytes sva_stream_save would write for this slot now (grows with the slot's KV position); < 0 on error */
+long sva_stream_save_size(sva_batch* b, int slot);
+/* Snapshot of one DECODING slot (phase 2) of a begun batch into caller memory.  Read-only: the slot and every other slot go on
+ * bit-identically.  cap < needed: fails, *written = needed, nothing written. */
+int sva_stream_save(sva_batch* b, int slot, void* blob, long cap, long* written);
+/* Replace whatever `slot` holds (any phase) by the stream in the blob.  From the next step on the slot continues that stream: phase 2,
+ * its frame count, KV position, content count, noise seed and counter, sampling pair, stored prompt, code history.  Every other slot is
+ * bit-identical to a run without the call.  Everything is validated before any state changes. */
+int sva_stream_load(sva_batch* b, int slot, const void* blob, long nbytes);
+/* GPU-free: parse and validate a blob (header and payload checksums).  info[8] = {format version, frames decoded, last_pos, content count,
+ * ref_len, ar_dtype, chunk_frames, payload bytes}; < 0 for a blob that is truncated, corrupt or of another version */
+int sva_stream_blob_info(const void* blob, long nbytes, long* info);
+
 /* ---- I/O adaptor: feed and read a running batch at a caller-chosen sample rate, in blocks of any length, as float32 or int16 ----
  * Every slot is fed n samples per call at io_rate and gets n samples back at io_rate; everything between the caller's buffer and the engine's
  * 44.1 kHz chunk runs on the device (csrc/io/).  The filter is the one audio_io.resample states: torchaudio 2.4 sinc_interp_hann,
@@ -224,7 +261,9 @@ int sva_stream_activations(sva_batch* b, long counts[2], float* last_ms);
  * One adaptor per batch, opened after sva_streams_begin.  While it is open, sva_step / sva_step_device / sva_step_device_on /
  * sva_stream_chunks and sva_streams_begin on the batch are refused (they would desynchronise the FIFOs); sva_stream_restart also zeroes the
  * slot's two filter histories and its share of the chunk staging, sva_stream_retire needs nothing beyond its flags (a retired slot's input
- * is not read); every other slot stays bit-identical.  sva_batch_destroy closes a forgotten adaptor. */
+ * is not read); every other slot stays bit-identical.  sva_batch_destroy closes a forgotten adaptor.
+ * The adaptor's FIFOs and phase counters are batch-wide, not a slot's: they are not part of a stream snapshot, and sva_stream_save /
+ * sva_stream_load are refused while an adaptor is open. */
 typedef struct sva_io sva_io;
 /* fmt: 0 float32, 1 int16.  max_block: largest n of one call.  Opening finds L by walking three periods of the counters' pattern sample by
  * sample on the host (a period is io_rate / gcd * 2048c / gcd(44100 / gcd, 2048c) samples): 10-45 ms at chunk_frames 1-4, about 0.7 s at 64. */
@@ -415,11 +454,34 @@ int sva_test_conv_gemm(int device, int n, const long long* desc, const float* fp
 /* The host-side book of the per-slot stream state (csrc/slot_book.h: phases, KV positions, frame and content counters, what a step plans),
  * scripted without a batch and without a GPU.  cfg[7] = {B, chunk_frames, delay, max_seq_frames, buffer_frames, decode_window_frames,
  * speaker prefix rows (timbre tokens + 1)}; ops: n_ops x 3 ints {op, slot, R} with op 0 = begin, 1 = prefilled(slot, R frames),
- * 2 = one chunk step, 3 = restart(slot, R frames), 4 = retire(slot), 5 = prefilled(slot, delay + 1 + R frames) stored truncated to R frames; the other prompts are stored untruncated.  trace: n_ops rows of 8 B + 6 ints, the
+ * 2 = one chunk step, 3 = restart(slot, R frames), 4 = retire(slot), 5 = prefilled(slot, delay + 1 + R frames) stored truncated to R frames; the other prompts are stored untruncated;
+ * 6 = stage the counters of the next adopt {last_pos = the slot field, nframes = the R field; ncontent = nframes + delay}, 7 = adopt(slot, a stored
+ * prompt of R frames): the transition of sva_stream_load.  trace: n_ops rows of 8 B + 6 ints, the
  * state after the op:  B x {phase, last_pos, nframes, ncontent} | delay_filled | one-pass re-prefill possible (-1: none planned) |
  * n_redo, redo[B] | n_rewind, rewind[B] x {slot, position} | n_activated, activated[B] | vocoder priming frames (begin: of the batch; a step:
  * of its first activated slot; else -1).  Unused list entries are -1; the lists are what the step planned before it carried them out. */
 int sva_test_slot_book(const int* cfg, const int* ops, int n_ops, int* trace);
+/* slot_pack_kernel / slot_unpack_kernel alone (csrc/snapshot/slot_pack.hip), nothing of an engine involved.  table: n_seg x 9 longs {byte
+ * offset of slot 0's first row in the source arena, the same in the destination arena, slot stride, row stride, row bytes, rows, kind (0 plain,
+ * 1 ring, 2 KV prefix, 3 blocked plane), element bytes (2 | 4), ring: elements the origin advances per step}.  Packs slot_src of arena_src at
+ * chunk counter step_src into image_out (image_bytes = the sum of the segments' lengths, each padded to 16), then unpacks that image into
+ * slot_dst of arena_dst (uploaded as given, returned as the kernel left it) at chunk counter step_dst.  cus sizes the grid.  A table that
+ * would leave an arena is refused before anything is launched. */
+int sva_test_slot_pack(int device, const long* table, int n_seg, const void* arena_src, long src_bytes, void* arena_dst, long dst_bytes, int slot_src,
+                       int slot_dst, int step_src, int step_dst, void* image_out, long image_bytes, int cus);
+/* The snapshot container (csrc/snapshot/snapshot_format.h) without a GPU.  sig = n_cfg configuration values, then n_layout layout values.
+ * op 0, build: desc[9] = {n_cfg, n_layout, frames, last_pos, content count, ar_dtype, chunk_frames, ncb, ref_len}; sig continues with ref_len
+ *   stored content codes and ncb x ref_len stored audio codes; bytes / nbytes = the payload (a multiple of 16); the blob goes to out,
+ *   result[0] = its length.
+ * op 1, check: bytes / nbytes = a caller-supplied byte string, sig = the signatures of a scripted batch, desc[2] = the payload bytes its
+ *   segments hold (< 0: not compared).  result[12] = {refusal code (0 accepted), index of the first differing signature value (-1 none),
+ *   format version, frames, last_pos, content count, ref_len, ar_dtype, chunk_frames, payload bytes, ncb, header bytes} (-1 where unknown). */
+/* The split of the batch's last sva_stream_save / sva_stream_load: ms[4] = {pack or unpack kernel (hipEvents around the launch), the host <->
+ * device copy of the image (wall), everything else of the call (wall: drain, validation, table upload, checksum, header, mirrors), -1};
+ * counts[2] = {image bytes of that call, steps this batch has run in the pipelined regime since it was created}.  measure_d2d != 0: ms[3] =
+ * one hipMemcpyDtoDAsync of the same byte count out of the batch's image buffer, between the same events on the same stream. */
+int sva_test_snapshot_timings(sva_batch* b, int measure_d2d, float* ms, long* counts);
+int sva_test_snapshot_header(int op, const long* desc, const long* sig, const void* bytes, long nbytes, void* out, long out_cap, long* result);
 /* The adaptor's planner (csrc/io/io_plan.h) without a batch and without a GPU: a stream at io_rate fed blocks[n_blocks] samples.
  * out: 12 header ints {L, filter part of L, chunk staging buffers, history samples at io_rate, history samples at 44100, output FIFO
  * samples, period of the counters' pattern in pushed samples, in orig, in new, in width, out width, max block}, then 5 ints per block:

@@ -96,6 +96,7 @@ struct EncMerged {
     float *h1 = nullptr, *h2 = nullptr;    // ConvNeXt scratch [B][R0][512], [B][R0][2048]
     ShiftDesc* d_shift = nullptr;
     int n_shift = 0;
+    std::vector<ShiftDesc> shift_host;     // host copy of d_shift (the slot inventory of snapshot/slot_state.h)
 };
 
 // ConvNeXtEncoder (firefly.py:443-520) + the quantizer's 2x (conv k2 s2 + ConvNeXtBlock) downsampler: the tokenizer
@@ -364,6 +365,15 @@ struct sva_batch {
     // the I/O adaptor (sva_io_open): while one is open only it may step the batch (io_stepping marks its own calls)
     sva_io* io = nullptr;
     bool io_stepping = false;
+    // sva_stream_save / sva_stream_load: the device image one slot is packed into (hipMalloc of its own: allocated on first use, grown on demand,
+    // freed with the batch) and the device copy of the segment table that drives the pack kernels
+    void* snap_image = nullptr;
+    long snap_image_cap = 0;
+    void* snap_table = nullptr;
+    long snap_table_cap = 0;
+    float snap_ms[3] = {0, 0, 0};          // last save / load: pack or unpack kernel (events), host <-> device copy of the image, host work (wall)
+    long snap_last_bytes = 0;              //   ... and its image bytes (sva_test_snapshot_timings)
+    long n_pipe_steps = 0;                 // steps that ran through steady_pipelined since the batch was created (tests ask whether the regime was reached)
 
     // pinned staging
     float *hp_in = nullptr, *hp_out = nullptr;

@@ -8,6 +8,8 @@
 #include "engine_internal.h"
 #include "engine_kernels.h"
 #include "io/resample.h"
+#include "snapshot/slot_pack.h"
+#include "snapshot/snapshot_format.h"
 #include <map>
 #include <mutex>
 
@@ -553,6 +555,7 @@ static int batch_create_impl(sva_engine* e, const sva_stream_params* p, sva_batc
         SVA_TRY(dev_alloc(A, &M.h1, (size_t)B * R0 * Dm));
         SVA_TRY(dev_alloc(A, &M.h2, (size_t)B * R0 * 4 * Dm));
         M.n_shift = (int)sd.size();
+        M.shift_host = sd;
         SVA_TRY(dev_alloc(A, &M.d_shift, sd.size()));
         SVA_HIP(hipMemcpy(M.d_shift, sd.data(), sizeof(ShiftDesc) * sd.size(), hipMemcpyHostToDevice));
     }
@@ -730,6 +733,8 @@ extern "C" void sva_batch_destroy(sva_batch* b) {
     for (auto& ge : b->pipe_graph_a) if (ge) (void)hipGraphExecDestroy(ge);
     for (hipGraphExec_t ge : {b->gEm[0], b->gEm[1], b->gEs[0], b->gEs[1], b->gT0, b->gT1[0], b->gT1[1], b->gV}) if (ge) (void)hipGraphExecDestroy(ge);
     for (void* p : b->allocs.chunks) (void)hipFree(p);
+    if (b->snap_image) (void)hipFree(b->snap_image);
+    if (b->snap_table) (void)hipFree(b->snap_table);
     if (sva_batch* w = b->prime_ws) {        // the priming workspace: arena chunks and its event pool (streams and the overflow flag are the owner's)
         for (void* p : w->allocs.chunks) (void)hipFree(p);
         for (int i = 0; i < 64; ++i) if (w->evpool[i]) (void)hipEventDestroy(w->evpool[i]);
@@ -1273,6 +1278,7 @@ int steady_pipelined(sva_batch* b) {
     if (stage_ev) SVA_HIP(hipEventRecord(b->ev[3], sv));
     SVA_TRY(mark(8, sv));
     b->trace_steps += 1;
+    b->n_pipe_steps += 1;
     b->pipe_dirty = true;
     b->out_stream = sv;
     return 0;
@@ -1615,6 +1621,239 @@ extern "C" int sva_stream_activations(sva_batch* b, long counts[2], float* last_
     counts[0] = b->n_act_local;
     counts[1] = b->n_act_whole;
     if (last_ms) *last_ms = b->last_act_ms;
+    return 0;
+}
+
+// ---- save / load single streams (sva_stream_save / sva_stream_load): the inventory is snapshot/slot_state.h, the container
+// snapshot/snapshot_format.h, the kernels snapshot/slot_pack.hip; the mirrors change through SlotBook::adopt alone ----
+namespace {
+const char* snap_reason(int rc) {
+    switch (rc) {
+        case snap::kTruncated: return "the blob is truncated (fewer bytes than its header needs or states)";
+        case snap::kBadMagic: return "not a stream snapshot (wrong magic)";
+        case snap::kBadVersion: return "the blob has another format version";
+        case snap::kBadHeader: return "the blob's header is corrupt (a length contradicts another, or its checksum fails)";
+        case snap::kBadChecksum: return "the blob's payload fails its checksum";
+        case snap::kConfigMismatch: return "the blob's configuration differs from the batch's";
+        case snap::kLayoutMismatch: return "the blob's layout differs from the batch's";
+        case snap::kSizeMismatch: return "the blob's payload length is not what this batch's segments hold at the blob's KV position";
+        default: return "unknown refusal";
+    }
+}
+int snap_cus(sva_batch* b, int* cus) {
+    SVA_HIP(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, b->e->device));
+    if (b->ar_partitioned && b->enc_cus > 0) *cus = std::min(*cus, b->enc_cus);      // the main stream's CU mask
+    return 0;
+}
+// room for an image and a segment table in the batch's own device buffers; the table uploaded (the caller's stream is drained: plain copies)
+int snap_prepare(sva_batch* b, const SlotSegments& L) {
+    SVA_TRY(check_slot_segments(L));
+    if (b->snap_image_cap < L.image_bytes) {
+        if (b->snap_image) SVA_HIP(hipFree(b->snap_image));
+        b->snap_image = nullptr; b->snap_image_cap = 0;
+        SVA_HIP(hipMalloc(&b->snap_image, (size_t)L.image_bytes));
+        b->snap_image_cap = L.image_bytes;
+    }
+    const long tb = (long)(sizeof(SlotSegment) * L.seg.size());
+    if (b->snap_table_cap < tb) {
+        if (b->snap_table) SVA_HIP(hipFree(b->snap_table));
+        b->snap_table = nullptr; b->snap_table_cap = 0;
+        SVA_HIP(hipMalloc(&b->snap_table, (size_t)tb));
+        b->snap_table_cap = tb;
+    }
+    SVA_HIP(hipMemcpyAsync(b->snap_table, L.seg.data(), (size_t)tb, hipMemcpyHostToDevice, b->stream));
+    SVA_HIP(hipStreamSynchronize(b->stream));
+    return 0;
+}
+int snap_check_batch(sva_batch* b, int slot, const char* who) {
+    const std::string w(who);
+    SVA_CHECK(b, (w + ": null batch").c_str());
+    SVA_CHECK(b->begun, (w + ": the batch has not begun").c_str());
+    SVA_CHECK(slot >= 0 && slot < b->B, (w + ": slot out of range").c_str());
+    SVA_CHECK(!b->io, (w + ": an I/O adaptor is open on this batch; its FIFOs and phase counters are batch-wide and do not travel (close it first)").c_str());
+    SVA_CHECK(!b->ar_failed && !(b->h_ar_fail && *reinterpret_cast<volatile int*>(b->h_ar_fail) != 0),
+              (w + ": this batch's persistent AR decode kernel timed out: sva_streams_begin restarts its streams").c_str());
+    return 0;
+}
+// the split of the call that just ended: kernel between the events ev[0] / ev[1], copy = [c0, c1] on the wall clock, host work = the rest of the call
+typedef std::chrono::steady_clock::time_point snap_tp;
+void snap_record_times(sva_batch* b, snap_tp begin, snap_tp c0, snap_tp c1, long bytes) {
+    float k = 0.f;
+    if (hipEventElapsedTime(&k, b->ev[0], b->ev[1]) != hipSuccess) { (void)hipGetLastError(); k = 0.f; }
+    const float copy = std::chrono::duration<float, std::milli>(c1 - c0).count();
+    const float total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - begin).count();
+    b->snap_ms[0] = k; b->snap_ms[1] = copy; b->snap_ms[2] = std::max(0.f, total - k - copy);
+    b->snap_last_bytes = bytes;
+}
+snap::Fields snap_fields(sva_batch* b, int slot) {
+    const SlotHost& h = b->slots.s[slot];
+    snap::Fields f;
+    f.nframes = h.nframes; f.last_pos = h.last_pos; f.ncontent = h.ncontent; f.ar_dtype = b->e->cfg.ar_dtype; f.chunk_frames = b->p.chunk_frames;
+    f.temperature = h.temperature; f.inv_temp = h.samp[0]; f.top_p = h.samp[1];
+    f.ncb = b->e->cfg.num_codebooks;
+    f.ref_content = h.ref_content; f.ref_audio = h.ref_audio;
+    return f;
+}
+}  // namespace
+
+extern "C" long sva_stream_save_size(sva_batch* b, int slot) {
+    SVA_TRY(snap_check_batch(b, slot, "sva_stream_save_size"));
+    const SlotHost& h = b->slots.s[slot];
+    SVA_CHECK(h.phase == kSlotDecoding, "sva_stream_save_size: only a decoding slot (phase 2) can be saved");
+    SlotSegments L;
+    SVA_TRY(slot_segments(b, h.last_pos + 1, &L));
+    const size_t n_cfg = config_signature(b->e->cfg, b->p).size(), n_layout = layout_signature(b, L).size();
+    return (long)snap::header_bytes_for(n_cfg, n_layout, h.ref_content.size(), (uint64_t)b->e->cfg.num_codebooks) + L.image_bytes;
+}
+
+extern "C" int sva_stream_save(sva_batch* b, int slot, void* blob, long cap, long* written) {
+    SVA_TRY(snap_check_batch(b, slot, "sva_stream_save"));
+    SVA_CHECK(written, "sva_stream_save: null argument");
+    SVA_CHECK(b->slots.s[slot].phase == kSlotDecoding, "sva_stream_save: only a decoding slot (phase 2) can be saved");
+    const auto t_begin = std::chrono::steady_clock::now();
+    SVA_TRY(drain_for_slot_call(b));
+    const SlotHost& h = b->slots.s[slot];
+    SlotSegments L;
+    SVA_TRY(slot_segments(b, h.last_pos + 1, &L));
+    const std::vector<int64_t> cfg = config_signature(b->e->cfg, b->p), layout = layout_signature(b, L);
+    const snap::Fields f = snap_fields(b, slot);
+    const long hb = (long)snap::header_bytes_for(cfg.size(), layout.size(), f.ref_content.size(), (uint64_t)f.ncb);
+    *written = hb + L.image_bytes;
+    SVA_CHECK(blob && cap >= *written, "sva_stream_save: the buffer is smaller than the snapshot (*written holds the bytes needed)");
+    SVA_TRY(snap_prepare(b, L));
+    int cus = 0;
+    SVA_TRY(snap_cus(b, &cus));
+    // the three parts are timed (sva_test_snapshot_timings): the kernel between two events, the copy and the host work on the wall clock
+    SVA_HIP(hipEventRecord(b->ev[0], b->stream));
+    SVA_TRY(launch_slot_pack(static_cast<const SlotSegment*>(b->snap_table), (int)L.seg.size(), slot, b->d_step, b->snap_image, L.image_bytes, cus, b->stream));
+    SVA_HIP(hipEventRecord(b->ev[1], b->stream));
+    SVA_HIP(hipStreamSynchronize(b->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    uint8_t* out = static_cast<uint8_t*>(blob);
+    SVA_HIP(hipMemcpyAsync(out + hb, b->snap_image, (size_t)L.image_bytes, hipMemcpyDeviceToHost, b->stream));
+    SVA_HIP(hipStreamSynchronize(b->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    snap::write_header(out, cfg, layout, f, (uint64_t)L.image_bytes, snap::fnv1a64_words(out + hb, (size_t)L.image_bytes));
+    snap_record_times(b, t_begin, t0, t1, L.image_bytes);
+    return 0;
+}
+
+extern "C" int sva_stream_blob_info(const void* blob, long nbytes, long* info) {
+    SVA_CHECK(blob && info, "sva_stream_blob_info: null argument");
+    snap::Header h;
+    const int rc = snap::parse(blob, nbytes, true, &h);
+    if (rc) { set_error(std::string("sva_stream_blob_info: ") + snap_reason(rc)); return rc; }
+    info[0] = h.version; info[1] = h.f.nframes; info[2] = h.f.last_pos; info[3] = h.f.ncontent; info[4] = (long)h.f.ref_content.size();
+    info[5] = h.f.ar_dtype; info[6] = h.f.chunk_frames; info[7] = (long)h.payload_bytes;
+    return 0;
+}
+
+extern "C" int sva_stream_load(sva_batch* b, int slot, const void* blob, long nbytes) {
+    SVA_TRY(snap_check_batch(b, slot, "sva_stream_load"));
+    SVA_CHECK(blob, "sva_stream_load: null argument");
+    const auto t_begin = std::chrono::steady_clock::now();
+    SVA_CHECK(b->slots.delay_filled, "sva_stream_load: the batch's lock-step delay has not filled yet (step it ceil(delay / chunk) times first)");
+    const sva_config& c = b->e->cfg;
+    snap::Header h;
+    int rc = snap::parse(blob, nbytes, true, &h);
+    if (rc) { set_error(std::string("sva_stream_load: ") + snap_reason(rc)); return rc; }
+    {
+        std::vector<std::string> names;
+        const std::vector<int64_t> cfg = config_signature(c, b->p, &names);
+        const long d = snap::first_difference(h.cfg, cfg);
+        if (d >= 0) {
+            const std::string nm = d < (long)names.size() ? names[(size_t)d] : std::string("number of fields");
+            set_error(std::string("sva_stream_load: ") + snap_reason(snap::kConfigMismatch) + ": first differing field " + std::to_string(d) + " (" + nm + ")" +
+                      (d < (long)h.cfg.size() && d < (long)cfg.size() ? ": blob " + std::to_string(h.cfg[(size_t)d]) + ", batch " + std::to_string(cfg[(size_t)d]) : ""));
+            return snap::kConfigMismatch;
+        }
+    }
+    const snap::Fields& f = h.f;
+    // a decoding stream's counters hang together: its position lies behind its stored prompt's prefill and delay fill, it has seen at least
+    // `delay` content codes and has decoded no more frames than the codes beyond them
+    const long ref_len = (long)f.ref_content.size(), nspk = c.timbre_tokens + 1;
+    bool fields_ok = f.last_pos >= 0 && f.last_pos + 2 * b->p.chunk_frames < c.max_seq_len && f.nframes >= 0 && f.ncontent >= 0 && f.ncb == c.num_codebooks &&
+                     ref_len >= 1 && ref_len <= b->p.max_prompt_frames && f.ar_dtype == c.ar_dtype && f.chunk_frames == b->p.chunk_frames &&
+                     std::isfinite(f.temperature) && std::isfinite(f.inv_temp) && std::isfinite(f.top_p) && f.inv_temp > 0.f && f.top_p >= 0.f &&
+                     f.last_pos >= nspk + 2 * ref_len - 1 + 2 * b->p.delay - 1 && f.ncontent >= b->p.delay && f.nframes <= f.ncontent - b->p.delay;
+    // ... and the stored prompt's codes index the embedding tables (re-prefill, vocoder priming)
+    for (size_t i = 0; fields_ok && i < f.ref_content.size(); ++i) fields_ok = f.ref_content[i] >= 0 && f.ref_content[i] < c.ar_vocab;
+    for (size_t i = 0; fields_ok && i < f.ref_audio.size(); ++i) fields_ok = f.ref_audio[i] >= 0 && f.ref_audio[i] < c.codebook_size;
+    if (!fields_ok) { set_error(std::string("sva_stream_load: ") + snap_reason(snap::kBadHeader) + ": a slot field is out of range for this batch"); return snap::kBadHeader; }
+    SlotSegments L;
+    SVA_TRY(slot_segments(b, f.last_pos + 1, &L));
+    {
+        std::vector<std::string> names;
+        const std::vector<int64_t> layout = layout_signature(b, L, &names);
+        const long d = snap::first_difference(h.layout, layout);
+        if (d >= 0) {
+            const std::string nm = d < (long)names.size() ? names[(size_t)d] : std::string("number of fields");
+            set_error(std::string("sva_stream_load: ") + snap_reason(snap::kLayoutMismatch) + ": first differing field " + std::to_string(d) + " (" + nm + ")");
+            return snap::kLayoutMismatch;
+        }
+    }
+    if ((long)h.payload_bytes != L.image_bytes) { set_error(std::string("sva_stream_load: ") + snap_reason(snap::kSizeMismatch)); return snap::kSizeMismatch; }
+    const uint8_t* in = static_cast<const uint8_t*>(blob);
+    // The integer tables of the payload are gather indices of the delay fill and the re-prefill (content_emb[code], codebook_emb[q * size + code]):
+    // a checksum is no proof of origin, so every entry is range-checked here, on the host, before anything changes.  (Unused ring entries are
+    // zeros: the rings are allocated zeroed and only ever receive codes.)
+    for (size_t i = 0; i < L.seg.size(); ++i) {
+        const std::string& nm = L.name[i];
+        const int hi = nm == "d_content_hist" ? c.ar_vocab : (nm == "d_pred_hist" || nm == "d_ref_tail") ? c.codebook_size : 0;
+        if (!hi) continue;
+        const uint8_t* q = in + h.header_bytes + L.seg[i].img_off;
+        for (long k = 0; k < seg_payload(L.seg[i]); k += 4) {
+            const int32_t v = (int32_t)snap::get_u32(q + k);
+            if (v < 0 || v >= hi) {
+                set_error(std::string("sva_stream_load: ") + snap_reason(snap::kBadHeader) + ": a code in " + nm + " is outside its embedding table");
+                return snap::kBadHeader;
+            }
+        }
+    }
+    // ---- everything is validated: from here on state changes ----
+    SVA_TRY(drain_for_slot_call(b));
+    SVA_TRY(snap_prepare(b, L));
+    int cus = 0;
+    SVA_TRY(snap_cus(b, &cus));
+    const auto t0 = std::chrono::steady_clock::now();
+    SVA_HIP(hipMemcpyAsync(b->snap_image, in + h.header_bytes, (size_t)L.image_bytes, hipMemcpyHostToDevice, b->stream));
+    SVA_HIP(hipStreamSynchronize(b->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    SVA_HIP(hipEventRecord(b->ev[0], b->stream));
+    SVA_TRY(launch_slot_unpack(static_cast<const SlotSegment*>(b->snap_table), (int)L.seg.size(), slot, b->d_step, b->snap_image, L.image_bytes, cus, b->stream));
+    SVA_HIP(hipEventRecord(b->ev[1], b->stream));
+    SVA_HIP(hipStreamSynchronize(b->stream));
+    std::vector<int64_t> rc_(f.ref_content);
+    std::vector<int32_t> ra_(f.ref_audio);
+    b->slots.adopt(slot, f.last_pos, f.nframes, f.ncontent, std::move(rc_), std::move(ra_), f.temperature, f.inv_temp, f.top_p);
+    // the device words the mirrors stand for, from the mirrors (they arrived in the payload too: a blob cannot leave the two apart)
+    const SlotHost& sh = b->slots.s[slot];
+    SVA_HIP(hipMemcpyAsync(b->d_nframes + slot, &sh.nframes, sizeof(int), hipMemcpyHostToDevice, b->stream));
+    SVA_HIP(hipMemcpyAsync(b->d_ncontent + slot, &sh.ncontent, sizeof(int), hipMemcpyHostToDevice, b->stream));
+    SVA_TRY(upload_slot_position(b, slot));
+    SVA_TRY(upload_slot_sampling(b, slot));
+    SVA_TRY(upload_slot_flag(b, slot));
+    snap_record_times(b, t_begin, t0, t1, L.image_bytes);
+    return 0;
+}
+
+// Timings of the batch's last sva_stream_save / sva_stream_load (include/sva.h)
+extern "C" int sva_test_snapshot_timings(sva_batch* b, int measure_d2d, float* ms, long* counts) {
+    SVA_CHECK(b && ms && counts, "sva_test_snapshot_timings: null argument");
+    ms[0] = b->snap_ms[0]; ms[1] = b->snap_ms[1]; ms[2] = b->snap_ms[2]; ms[3] = -1.f;
+    counts[0] = b->snap_last_bytes; counts[1] = b->n_pipe_steps;
+    if (!measure_d2d) return 0;
+    SVA_CHECK(b->snap_image && b->snap_last_bytes > 0, "sva_test_snapshot_timings: no save or load has run on this batch");
+    SVA_TRY(drain_for_slot_call(b));
+    void* tmp = nullptr;
+    SVA_HIP(hipMalloc(&tmp, (size_t)b->snap_last_bytes));
+    hipError_t e1 = hipEventRecord(b->ev[0], b->stream);
+    if (e1 == hipSuccess) e1 = hipMemcpyDtoDAsync(tmp, b->snap_image, (size_t)b->snap_last_bytes, b->stream);
+    if (e1 == hipSuccess) e1 = hipEventRecord(b->ev[1], b->stream);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(b->stream);
+    if (e1 == hipSuccess) e1 = hipEventElapsedTime(&ms[3], b->ev[0], b->ev[1]);
+    (void)hipFree(tmp);
+    SVA_HIP(e1);
     return 0;
 }
 

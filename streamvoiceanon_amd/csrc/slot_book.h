@@ -201,6 +201,23 @@ struct SlotBook {
         h.pending = PendingPrompt();
         h.flag = 0;
     }
+    // sva_stream_load: whatever the slot held, it is now the decoding stream a snapshot describes -- its position, counters, stored prompt and
+    // sampling pair (inv_temp as the source's samplers read it, not re-derived), no restart pending, nothing muted.  The lock-step state of the
+    // batch is not touched (a load needs delay_filled).
+    void adopt(int slot, int last_pos, int nframes, int ncontent, std::vector<int64_t>&& ref_content, std::vector<int32_t>&& ref_audio, float temperature,
+               float inv_temp, float top_p) {
+        SlotHost& h = s[slot];
+        h.phase = kSlotDecoding;
+        h.restarted = false;
+        h.prefilled = true;
+        h.pending = PendingPrompt();
+        h.flag = 0;
+        h.last_pos = last_pos; h.nframes = nframes; h.ncontent = ncontent;
+        h.ref_len = (int)ref_content.size();
+        h.ref_content = std::move(ref_content);
+        h.ref_audio = std::move(ref_audio);
+        h.temperature = temperature; h.samp[0] = inv_temp; h.samp[1] = top_p;
+    }
     // decoded frames of a live stream (sva_stream_state)
     long stream_frames(int slot) const { return s[slot].phase == kSlotDecoding ? s[slot].nframes : 0; }
 };

@@ -1955,6 +1955,7 @@ extern "C" int sva_test_slot_book(const int* cfg, const int* ops, int n_ops, int
     SlotBook book;
     book.reset(B);
     bool begun = false;
+    int adopt_pos = -1, adopt_frames = -1;
     auto prefill = [&](int slot, int R) {          // one codebook of zeros stands for the prompt: only its length matters here
         const std::vector<int64_t> cc((size_t)R, 0);
         const std::vector<int32_t> ac((size_t)R, 0);
@@ -2009,6 +2010,11 @@ extern "C" int sva_test_slot_book(const int* cfg, const int* ops, int n_ops, int
             const std::vector<int64_t> cc((size_t)(delay + 1 + R), 0);
             const std::vector<int32_t> ac((size_t)(delay + 1 + R), 0);
             book.prefilled(slot, nspk, delay + 1 + R, R, 1, cc.data(), ac.data());
+        } else if (op == 6) {          // stage the counters of the next adopt: last_pos = slot field, nframes = R field (ncontent = nframes + delay)
+            adopt_pos = slot; adopt_frames = R;
+        } else if (op == 7) {          // SlotBook::adopt (sva_stream_load): a decoding stream with a stored prompt of R frames and the staged counters
+            SVA_CHECK(slot >= 0 && slot < B && R >= 1 && adopt_pos >= 0 && adopt_frames >= 0, "sva_test_slot_book: adopt needs a slot, a stored prompt and staged counters (op 6)");
+            book.adopt(slot, adopt_pos, adopt_frames, adopt_frames + delay, std::vector<int64_t>((size_t)R, 0), std::vector<int32_t>((size_t)R, 0), 0.7f, 1.0f / 0.7f, 0.7f);
         } else {
             SVA_CHECK(false, "sva_test_slot_book: unknown op");
         }

@@ -80,6 +80,14 @@ def load_library():
     lib.sva_stream_set_sampling.argtypes = [vp, i32, C.c_float, C.c_float]
     lib.sva_stream_get_sampling.argtypes = [vp, i32, f32p, f32p]
     lib.sva_stream_activations.argtypes = [vp, C.POINTER(C.c_long), f32p]
+    lib.sva_stream_save_size.argtypes = [vp, i32]
+    lib.sva_stream_save_size.restype = C.c_long
+    lib.sva_stream_save.argtypes = [vp, i32, vp, C.c_long, C.POINTER(C.c_long)]
+    lib.sva_stream_load.argtypes = [vp, i32, vp, C.c_long]
+    lib.sva_stream_blob_info.argtypes = [vp, C.c_long, C.POINTER(C.c_long)]
+    lib.sva_test_slot_pack.argtypes = [i32, vp, i32, vp, C.c_long, vp, C.c_long, i32, i32, i32, i32, vp, C.c_long, i32]
+    lib.sva_test_snapshot_timings.argtypes = [vp, i32, f32p, C.POINTER(C.c_long)]
+    lib.sva_test_snapshot_header.argtypes = [i32, vp, vp, vp, C.c_long, vp, C.c_long, vp]
     lib.sva_step.argtypes = [vp, vp, vp, vp, vp]
     lib.sva_step_device.argtypes = [vp, vp, vp]
     lib.sva_step_device_on.argtypes = [vp, vp, vp, vp, C.c_int]
@@ -169,6 +177,7 @@ EXPORTED_SYMBOLS = [
     "sva_op_geglu", "sva_op_l2norm", "sva_ops_capture_begin", "sva_ops_capture_end", "sva_ops_graph_launch", "sva_ops_graph_free",
     "sva_get_gemm_stats", "sva_get_gemm_bytes", "sva_stream_codes", "sva_profile_gemm", "sva_get_gemm_profile", "sva_get_gemm_profile_table", "sva_test_gemm", "sva_test_gemm_choice", "sva_test_gemm_plan", "sva_test_conv_gemm", "sva_test_slot_book", "sva_test_slot_prompt_tail", "sva_test_gemm_f16w", "sva_test_gemm_planes", "sva_test_gemm_h16", "sva_test_prefill_attention", "sva_test_pair_attention", "sva_test_prefill_attention_runs", "sva_test_prefill_pack", "sva_test_decode_attention", "sva_test_enc_attention", "sva_test_rowop", "sva_test_bsq", "sva_test_stft_ring", "sva_test_fsq", "sva_test_conv_post", "sva_test_sampler_launch", "sva_test_sampler_rows", "sva_test_ar_device", "sva_test_gemv", "sva_test_token_ops", "sva_test_step_ops", "sva_test_voc_level", "sva_test_voc_conv", "sva_set_sampler_edits", "sva_bench_gemm", "sva_bench_gemm_choice", "sva_test_sampler", "sva_host_launch_cost",
     "sva_io_open", "sva_io_close", "sva_io_process", "sva_io_process_device", "sva_io_latency", "sva_test_io_plan", "sva_test_resample",
+    "sva_stream_save_size", "sva_stream_save", "sva_stream_load", "sva_stream_blob_info", "sva_test_slot_pack", "sva_test_snapshot_header", "sva_test_snapshot_timings",
 ]
 
 
@@ -393,6 +402,39 @@ class Batch:
         counts, ms = (C.c_long * 2)(), C.c_float()
         _check(self.lib.sva_stream_activations(self.h, counts, C.byref(ms)), "sva_stream_activations")
         return int(counts[0]), int(counts[1]), float(ms.value)
+
+    def save_size(self, slot):
+        """sva_stream_save_size: bytes save_stream(slot) would return now"""
+        n = self.lib.sva_stream_save_size(self.h, int(slot))
+        if n < 0:
+            _check(int(n), "sva_stream_save_size")
+        return int(n)
+
+    def save_stream(self, slot) -> bytes:
+        """sva_stream_save: the decoding stream in `slot` as a snapshot (include/sva.h, "save and resume single streams").  Read-only."""
+        n = self.save_size(slot)
+        buf = np.empty(n, dtype=np.uint8)
+        wr = C.c_long()
+        _check(self.lib.sva_stream_save(self.h, int(slot), _ptr(buf), n, C.byref(wr)), "sva_stream_save")
+        return buf[:int(wr.value)].tobytes()
+
+    def load_stream(self, slot, blob):
+        """sva_stream_load: `slot` continues the stream of the snapshot from the next step on, bit-identically in a batch of the same
+        configuration; every other slot is unaffected.  A refusal (RuntimeError) changes nothing."""
+        buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+        _check(self.lib.sva_stream_load(self.h, int(slot), _ptr(buf) if buf.size else (C.c_char * 1)(), buf.size), "sva_stream_load")
+
+    def move_stream(self, slot, dst_batch, dst_slot):
+        """save_stream(slot), dst_batch.load_stream(dst_slot), then retire the source slot (only once the load has succeeded)"""
+        dst_batch.load_stream(dst_slot, self.save_stream(slot))
+        self.retire(slot)
+
+    def snapshot_timings(self, measure_d2d=False):
+        """sva_test_snapshot_timings -> dict(kernel_ms, copy_ms, host_ms, d2d_ms (None unless measured), bytes, pipelined_steps) of the last save / load"""
+        ms, cnt = (C.c_float * 4)(), (C.c_long * 2)()
+        _check(self.lib.sva_test_snapshot_timings(self.h, int(bool(measure_d2d)), ms, cnt), "sva_test_snapshot_timings")
+        return dict(kernel_ms=float(ms[0]), copy_ms=float(ms[1]), host_ms=float(ms[2]), d2d_ms=float(ms[3]) if measure_d2d else None,
+                    bytes=int(cnt[0]), pipelined_steps=int(cnt[1]))
 
     def step(self, pcm_in, noise=None, forced_codes=None):
         x = np.ascontiguousarray(pcm_in, dtype=np.float32).reshape(self.B, 2048 * self.chunk)
@@ -1263,6 +1305,79 @@ def test_slot_prompt_tail(R, Rt, ncb, P, first, n):
     out, stored = (C.c_int * max(ncb * n, 1))(), (C.c_int * 4)()
     _check(load_library().sva_test_slot_prompt_tail(R, Rt, ncb, P, first, n, out, stored), "sva_test_slot_prompt_tail")
     return np.array(out[:ncb * n], dtype=np.int32).reshape(ncb, n), tuple(stored)
+
+
+SNAPSHOT_INFO = ("version", "frames", "last_pos", "ncontent", "ref_len", "ar_dtype", "chunk_frames", "payload_bytes")
+SNAPSHOT_REFUSALS = {0: "ok", -10: "truncated", -11: "bad_magic", -12: "bad_version", -13: "bad_header", -14: "bad_checksum", -15: "config_mismatch",
+                     -16: "layout_mismatch", -17: "size_mismatch"}
+SEG_PLAIN, SEG_RING, SEG_KV_PREFIX, SEG_BLOCKED_PLANE = 0, 1, 2, 3
+
+
+def stream_blob_info(blob) -> dict:
+    """sva_stream_blob_info: the header of a snapshot, validated without a GPU (ValueError for a truncated, corrupt or foreign blob)"""
+    buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+    info = (C.c_long * 8)()
+    lib = load_library()
+    rc = lib.sva_stream_blob_info(_ptr(buf) if buf.size else (C.c_char * 1)(), buf.size, info)
+    if rc != 0:
+        raise ValueError(f"not a valid stream snapshot (rc={rc}): {lib.sva_last_error().decode('utf-8', 'replace')}")
+    return dict(zip(SNAPSHOT_INFO, (int(v) for v in info)))
+
+
+def idle_batch(engine, n_streams, prompt, **params):
+    """A begun, steady batch with every slot retired: the landing batch of Batch.load_stream / move_stream ("beginning a batch with empty
+    slots" is not supported: this prefills a throw-away prompt (ac, cc, style, timbre) everywhere, begins, steps ceil(delay / chunk) times on
+    silence so that the lock-step delay is filled, and retires every slot)."""
+    ac, cc, style, timbre = prompt
+    b = Batch(engine, n_streams=n_streams, **params)
+    for s in range(n_streams):
+        b.prefill_prompt(s, cc, ac, style, timbre, noise_seed=0)
+    b.begin()
+    zeros = np.zeros((n_streams, 2048 * b.chunk), np.float32)
+    for _ in range(-(-b.p.delay // b.chunk)):
+        b.step(zeros)
+    for s in range(n_streams):
+        b.retire(s)
+    return b
+
+
+def test_slot_pack(table, arena_src, arena_dst, slot_src, slot_dst, step_src=0, step_dst=0, cus=8, device=0):
+    """include/sva.h: sva_test_slot_pack.  table [n_seg][9] int64, arenas uint8 -> (image uint8, destination arena after the unpack)"""
+    t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 9)
+    src = np.ascontiguousarray(arena_src, dtype=np.uint8)
+    dst = np.ascontiguousarray(arena_dst, dtype=np.uint8).copy()
+    nbytes = int(sum((int(r[5]) * int(r[4]) + 15) // 16 * 16 for r in t))
+    img = np.zeros(max(nbytes, 1), np.uint8)
+    _check(load_library().sva_test_slot_pack(device, _ptr(t), t.shape[0], _ptr(src), src.size, _ptr(dst), dst.size, int(slot_src), int(slot_dst),
+                                             int(step_src), int(step_dst), _ptr(img), nbytes, int(cus)), "sva_test_slot_pack")
+    return img[:nbytes], dst
+
+
+def test_snapshot_build(cfg, layout, fields, ref_content, ref_audio, payload=b""):
+    """include/sva.h: sva_test_snapshot_header op 0 -> blob bytes.  fields = (frames, last_pos, ncontent, ar_dtype, chunk_frames); no GPU needed"""
+    ra = np.asarray(ref_audio, dtype=np.int64)
+    ncb, ref_len = (ra.shape if ra.ndim == 2 else (0, len(ref_content)))
+    desc = np.array([len(cfg), len(layout), *fields, ncb, ref_len], dtype=np.int64)
+    sig = np.array([*cfg, *layout, *ref_content, *ra.reshape(-1)], dtype=np.int64)
+    pl = np.frombuffer(bytes(payload), dtype=np.uint8)
+    out = np.zeros(4096 + 8 * sig.size + pl.size, np.uint8)
+    res = np.full(12, -1, np.int64)
+    _check(load_library().sva_test_snapshot_header(0, _ptr(desc), _ptr(sig) if sig.size else None, _ptr(pl) if pl.size else None, pl.size, _ptr(out),
+                                                   out.size, _ptr(res)), "sva_test_snapshot_header")
+    return out[:int(res[0])].tobytes()
+
+
+def test_snapshot_check(data, cfg, layout, payload_bytes=-1):
+    """include/sva.h: sva_test_snapshot_header op 1 -> (refusal code, first differing signature index, info dict); no GPU needed"""
+    desc = np.array([len(cfg), len(layout), payload_bytes], dtype=np.int64)
+    sig = np.array([*cfg, *layout], dtype=np.int64)
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    res = np.full(12, -1, np.int64)
+    keep = np.zeros(1, np.uint8)
+    _check(load_library().sva_test_snapshot_header(1, _ptr(desc), _ptr(sig) if sig.size else None, _ptr(buf) if buf.size else _ptr(keep), buf.size, None, 0,
+                                                   _ptr(res)), "sva_test_snapshot_header")
+    info = dict(zip(SNAPSHOT_INFO + ("ncb", "header_bytes"), (int(v) for v in res[2:])))
+    return int(res[0]), int(res[1]), info
 
 
 def host_launch_cost(device=0, iters=300):

@@ -361,6 +361,50 @@ class InferenceWrapper:
         if io_rate is not None:
             self.batch.open_io(int(io_rate), io_fmt, int(io_max_block))
 
+    # ---- save / resume the one-slot streaming batch (engine.Batch.save_stream / load_stream) ----------------
+    def save_stream(self) -> bytes:
+        """Snapshot of the stream setup_stream_caches started (its slot must be decoding: the delay has filled)."""
+        assert self.batch is not None and self.batch.B == 1, "no one-slot streaming batch (setup_stream_caches)"
+        return self.batch.save_stream(0)
+
+    def load_stream(self, blob, encode_window_frames=96, decode_window_frames=64, max_seq_frames=768, buffer_frames=32, decode_chunk_frames=1,
+                    delay=None, max_prompt_frames=None, pipeline=False):
+        """The streaming batch continues the stream of `blob` from its next chunk on, without a prompt: no reference is encoded and nothing is
+        prefilled for it.  The one-slot batch is kept when it was set up with these stream parameters; otherwise it is replaced by a landing
+        batch (engine.idle_batch, primed with a throw-away prompt of zeros).  The blob's header is validated, and its chunk size and AR dtype
+        compared, before anything of the wrapper changes; delay / max_prompt_frames become the wrapper's only once the engine has accepted the
+        blob.  A blob the engine itself refuses (RuntimeError: another configuration, a corrupt payload) leaves the live batch as it was when
+        that batch was kept, and a landing batch with a retired slot otherwise -- callers that track a session clear it then (RealtimeSession.load)."""
+        d = int(self.delay if delay is None else delay)
+        mpf = int(self.max_prompt_frames if max_prompt_frames is None else max_prompt_frames)
+        try:
+            info = E.stream_blob_info(blob)
+        except ValueError as ex:
+            raise RuntimeError(f"load_stream refused: {ex}") from None
+        if info["chunk_frames"] != decode_chunk_frames or info["ar_dtype"] != self.engine.cfg.ar_dtype:
+            raise RuntimeError(f"load_stream refused: the blob has chunk_frames {info['chunk_frames']} and ar_dtype {info['ar_dtype']}, "
+                               f"this stream {decode_chunk_frames} and {self.engine.cfg.ar_dtype}")
+        want = dict(encode_window_frames=encode_window_frames, decode_window_frames=decode_window_frames, chunk_frames=decode_chunk_frames,
+                    delay=d, max_seq_frames=max_seq_frames, buffer_frames=buffer_frames, max_prompt_frames=mpf)
+        b = self.batch
+        keep = b is not None and b.B == 1 and b.io is None and all(getattr(b.p, k) == v for k, v in want.items())
+        if keep:
+            try:
+                keep = b.stream_state(0)[0] != 1            # (begun, and not still filling its lock-step delay)
+            except RuntimeError:
+                keep = False
+        if not keep:
+            if b is not None:
+                b.close()
+            R = min(64, mpf)
+            cfg = self.engine.cfg
+            zeros = (np.zeros((cfg.num_codebooks, R), np.int32), np.zeros(R, np.int64), np.zeros(cfg.style_dim, np.float32),
+                     np.zeros((cfg.timbre_tokens, cfg.timbre_dim), np.float32))
+            self.decode_chunk_frames = decode_chunk_frames
+            self.batch = E.idle_batch(self.engine, 1, zeros, use_graph=self.use_graph, pipeline=pipeline and not self.use_graph, **want)
+        self.batch.load_stream(0, blob)
+        self.delay, self.max_prompt_frames = d, mpf
+
     # ---- files (SURVEY.md §8f N2) ---------------------------------------------------------------------------
     def _load_src(self, src):
         """librosa.load(src_path, sr=self.sr) (:274, 615) when given a path; arrays pass through."""

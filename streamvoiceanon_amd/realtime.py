@@ -16,6 +16,7 @@ The GUI itself (customtkinter / sounddevice, :61-1461) is a caller of this bound
 """
 import dataclasses
 import json
+import struct
 
 import numpy as np
 
@@ -53,6 +54,12 @@ def apply_preset(settings: GuiSettings, name: str, presets: dict) -> GuiSettings
     return out
 
 
+# the stream parameters of the GUI (real-time-gui.py:36-47), in ONE place: custom_infer sets its caches up with them and a loaded snapshot must
+# have been taken under them (a second copy that drifted would turn every load into a configuration refusal)
+MAX_PROMPT_FRAMES = 64
+STREAM_CACHES = dict(encode_window_frames=64, decode_window_frames=64, max_seq_frames=768, buffer_frames=32)
+
+
 class RealtimeSession:
     def __init__(self):
         self.reference_wav_name = ""
@@ -78,9 +85,8 @@ class RealtimeSession:
         frames = n // 2048
         if self.reference_wav_name != new_reference_wav_name or self.decode_chunk_frames != frames or self.io is not None:
             ref = np.asarray(reference_wav.detach().cpu().numpy() if hasattr(reference_wav, "detach") else reference_wav, dtype=np.float32)
-            model_set.prefill_prompt(ref.reshape(-1), max_prompt_frames=64, delay=n_frame_delay, alpha=alpha)
-            model_set.setup_stream_caches(encode_window_frames=64, decode_window_frames=64, max_seq_frames=768, buffer_frames=32,
-                                          decode_chunk_frames=frames)
+            model_set.prefill_prompt(ref.reshape(-1), max_prompt_frames=MAX_PROMPT_FRAMES, delay=n_frame_delay, alpha=alpha)
+            model_set.setup_stream_caches(decode_chunk_frames=frames, **STREAM_CACHES)
             self.reference_wav_name = new_reference_wav_name
             self.decode_chunk_frames = frames
             self.io = None
@@ -102,9 +108,8 @@ class RealtimeSession:
             ref = np.asarray(reference_wav.detach().cpu().numpy() if hasattr(reference_wav, "detach") else reference_wav, dtype=np.float32)
             cap = int(max_block) if max_block else max(4096, 2 * n)
             assert n <= cap, "block longer than max_block"
-            model_set.prefill_prompt(ref.reshape(-1), max_prompt_frames=64, delay=n_frame_delay, alpha=alpha)
-            model_set.setup_stream_caches(encode_window_frames=64, decode_window_frames=64, max_seq_frames=768, buffer_frames=32,
-                                          decode_chunk_frames=block_frame, io_rate=samplerate, io_fmt=fmt, io_max_block=cap)
+            model_set.prefill_prompt(ref.reshape(-1), max_prompt_frames=MAX_PROMPT_FRAMES, delay=n_frame_delay, alpha=alpha)
+            model_set.setup_stream_caches(decode_chunk_frames=block_frame, io_rate=samplerate, io_fmt=fmt, io_max_block=cap, **STREAM_CACHES)
             self.reference_wav_name = new_reference_wav_name
             self.decode_chunk_frames = block_frame
             self.io = (samplerate, fmt, cap)
@@ -116,6 +121,49 @@ class RealtimeSession:
             return torch.from_numpy(pred).to(input_wav.device)
         return pred
 
+
+    # ---- save / resume: the engine's snapshot of the session's stream in a small envelope ----
+    # b"SVARTS1\0" | u32 name bytes | u32 chunk frames | u32 n_frame_delay | utf-8 reference name | engine blob   (little endian)
+    ENVELOPE_MAGIC = b"SVARTS1\0"
+
+    def save(self, model_set) -> bytes:
+        """The session's live stream (engine.Batch.save_stream) with what custom_infer keys its lazy re-prefill on.  Needs a stream whose
+        delay has filled; refused while an I/O adaptor is open (its FIFOs are batch-wide and do not travel)."""
+        if self.io is not None:
+            raise RuntimeError("save refused: an I/O adaptor is open on this session; its FIFOs and phase counters are batch-wide and do not travel")
+        if not self.reference_wav_name or not self.decode_chunk_frames:
+            raise RuntimeError("save refused: the session has no stream yet (send a reference and a block first)")
+        name = self.reference_wav_name.encode("utf-8")
+        return self.ENVELOPE_MAGIC + struct.pack("<III", len(name), self.decode_chunk_frames, int(model_set.delay)) + name + model_set.save_stream()
+
+    def load(self, model_set, data):
+        """Continue the stream of a save() envelope: the next custom_infer with that reference name (and block size) does NOT re-prefill
+        (`prefills` unchanged) -- the reference is neither encoded nor prefilled again."""
+        if self.io is not None:
+            raise RuntimeError("load refused: an I/O adaptor is open on this session; its FIFOs and phase counters are batch-wide and do not travel")
+        data = bytes(data)
+        m = len(self.ENVELOPE_MAGIC)
+        if len(data) < m + 12 or data[:m] != self.ENVELOPE_MAGIC:
+            raise ValueError("not a session envelope (RealtimeSession.save)")
+        n_name, frames, delay = struct.unpack("<III", data[m:m + 12])
+        if n_name > 1024 or len(data) < m + 12 + n_name or not 1 <= frames <= 64 or delay < 1:
+            raise ValueError("session envelope: bad name length, chunk frames or delay")
+        name = data[m + 12:m + 12 + n_name].decode("utf-8")
+        # A refused blob leaves the session as it was when the wrapper kept its live batch.  When the wrapper had to replace the batch by a
+        # landing batch first, the session forgets its stream: the next block then re-prefills from its reference instead of stepping a
+        # retired slot.
+        keep, before = (self.reference_wav_name, self.decode_chunk_frames), getattr(model_set, "batch", None)
+        self.reference_wav_name, self.decode_chunk_frames = "", 0
+        try:
+            model_set.load_stream(data[m + 12 + n_name:], decode_chunk_frames=int(frames), delay=int(delay), max_prompt_frames=MAX_PROMPT_FRAMES,
+                                  **STREAM_CACHES)
+        except Exception:
+            if before is not None and getattr(model_set, "batch", None) is before:
+                self.reference_wav_name, self.decode_chunk_frames = keep
+            raise
+        self.reference_wav_name = name
+        self.decode_chunk_frames = int(frames)
+        return name, int(frames), int(delay)
 
     def run_block(self, model_set, reference_wav, reference_wav_name, input_wav, settings: GuiSettings):
         """One audio-callback block under the GUI's current settings (real-time-gui.py:1313-1330 passes gui_config.n_frame_delay and

@@ -17,10 +17,16 @@ Protocol (little endian, one TCP connection = one `RealtimeSession`):
                       samples of that format at that rate (any length: a 10 ms sound-card or telephony callback) and is answered with as
                       many samples of that format at that rate, resampled on the device (engine.BatchIO; the GUI's sr_device mode);
                       sample_rate 44100 with fmt 0 goes back to whole-chunk float32 blocks (44100 with fmt 1 is the adaptor's pass-through).  block_frame of CONF stays the engine's chunk.
+        kind 6 SAVE   no payload: the session's live stream is answered as an envelope (RealtimeSession.save: reference name, chunk frames,
+                      delay, then the engine's snapshot -- include/sva.h, sva_stream_save); the stream goes on
+        kind 7 LOAD   payload = such an envelope: the session continues that stream; the BLOCKs that follow need no REF and do not re-prefill
+                      (the envelope's reference name and chunk frames become the session's; a later REF with another name starts afresh)
+                      SAVE and LOAD are refused after an IOCONF: the adaptor's FIFOs and phase counters are batch-wide and do not travel
     server -> client   for every BLOCK: u32 3 | u32 nbytes | float32[2048 * block_frame] converted samples (zeros while the delay fills)
-                       for REF / CONF:  u32 kind | u32 0
+                       for REF / CONF / IOCONF / LOAD:  u32 kind | u32 0;   for SAVE:  u32 6 | u32 nbytes | envelope
                        on error:        u32 0xffffffff | u32 nbytes | utf-8 message (the connection stays open)
-    Frame sizes are bounded per kind (CONF = IOCONF = 12 bytes, BLOCK <= 64 frames of 2048 samples -- after an IOCONF: max_block samples --, REF <= 60 s of 44.1 kHz audio + a 1 KiB name);
+    Frame sizes are bounded per kind (CONF = IOCONF = 12 bytes, BLOCK <= 64 frames of 2048 samples -- after an IOCONF: max_block samples --, REF <= 60 s of 44.1 kHz audio + a 1 KiB name,
+    LOAD <= the engine's largest possible snapshot -- every KV position of the cache -- + 16 MiB for everything else + the envelope);
     an oversize or unknown frame is answered with an error and the connection is closed (its payload cannot be skipped safely).
 
 One connection is served at a time per process (the reference's GUI is single-session too); the engine and its weights stay
@@ -35,10 +41,21 @@ import numpy as np
 from .engine import io_rate_supported
 from .realtime import GuiSettings, RealtimeSession
 
-KIND_REF, KIND_CONF, KIND_BLOCK, KIND_BYE, KIND_IOCONF, KIND_ERR = 1, 2, 3, 4, 5, 0xFFFFFFFF
+KIND_REF, KIND_CONF, KIND_BLOCK, KIND_BYE, KIND_IOCONF, KIND_SAVE, KIND_LOAD, KIND_ERR = 1, 2, 3, 4, 5, 6, 7, 0xFFFFFFFF
 MAX_BLOCK_FRAMES = 64
 MAX_PAYLOAD = {KIND_REF: 1024 + 1 + 4 * 44100 * 60, KIND_CONF: 12, KIND_BLOCK: 4 * 2048 * MAX_BLOCK_FRAMES, KIND_BYE: 0, KIND_IOCONF: 12}
 IO_DTYPES = {0: "<f4", 1: "<i2"}
+
+
+IO_REFUSAL = "refused after an IOCONF: the I/O adaptor's FIFOs and phase counters are batch-wide and do not travel with a stream"
+
+
+def max_load_bytes(model_set):
+    """Size bound of a LOAD frame: the engine's largest possible snapshot (KV rows up to the end of the cache dominate; everything else together is
+    a few MB) plus the envelope.  A model set without an engine (a stub) gets the bound of the default configuration."""
+    cfg = getattr(getattr(model_set, "engine", None), "cfg", None)
+    layers, heads, seq, half = (cfg.ar_layers, cfg.ar_heads, cfg.max_seq_len, cfg.ar_dtype == 1) if cfg is not None else (12, 12, 2048, False)
+    return layers * 2 * heads * 64 * (2 if half else 4) * seq + (16 << 20) + 2048
 
 
 class ProtocolError(Exception):
@@ -63,10 +80,13 @@ def serve_connection(conn, model_set):
     """The audio loop of real-time-gui.py:1313-1330 for one client: every BLOCK goes through RealtimeSession.run_block."""
     sess, settings = RealtimeSession(), GuiSettings()
     ref_name, ref_wav = "", None
+    loaded = False                           # a LOAD gave the session its stream: BLOCKs need no REF until one arrives
     ioconf = None                            # (sample_rate, fmt, max_block) of the last IOCONF, None: 44.1 kHz float32 in whole chunks
     while True:
         kind, nbytes = struct.unpack("<II", _recv_exact(conn, 8))
-        limits = MAX_PAYLOAD if ioconf is None else {**MAX_PAYLOAD, KIND_BLOCK: ioconf[2] * np.dtype(IO_DTYPES[ioconf[1]]).itemsize}
+        limits = {**MAX_PAYLOAD, KIND_SAVE: 0, KIND_LOAD: max_load_bytes(model_set)}
+        if ioconf is not None:
+            limits[KIND_BLOCK] = ioconf[2] * np.dtype(IO_DTYPES[ioconf[1]]).itemsize
         if kind not in limits or nbytes > limits[kind]:
             msg = f"frame kind {kind} with {nbytes} bytes refused (limits: {limits})"
             _send(conn, KIND_ERR, ("ProtocolError: " + msg).encode("utf-8"))
@@ -79,6 +99,7 @@ def serve_connection(conn, model_set):
                 z = payload.index(b"\0")
                 ref_name = payload[:z].decode("utf-8")
                 ref_wav = np.frombuffer(payload[z + 1:], dtype="<f4").astype(np.float32)
+                loaded = False
                 if ref_wav.size < 2048 * 3:
                     raise ValueError("reference shorter than three frames")
                 _send(conn, KIND_REF)
@@ -97,6 +118,16 @@ def serve_connection(conn, model_set):
                                      "has both terms <= 640")
                 ioconf = None if (rate, fmt) == (44100, 0) else (int(rate), int(fmt), int(max_block))
                 _send(conn, KIND_IOCONF)
+            elif kind == KIND_SAVE:
+                if ioconf is not None or sess.io is not None:
+                    raise ValueError("SAVE " + IO_REFUSAL)
+                _send(conn, KIND_SAVE, sess.save(model_set))
+            elif kind == KIND_LOAD:
+                if ioconf is not None or sess.io is not None:
+                    raise ValueError("LOAD " + IO_REFUSAL)
+                ref_name = sess.load(model_set, payload)[0]
+                loaded = True
+                _send(conn, KIND_LOAD)
             elif kind == KIND_BLOCK and ioconf is not None:
                 if ref_wav is None:
                     raise ValueError("send a reference (kind 1) before the first block")
@@ -108,7 +139,7 @@ def serve_connection(conn, model_set):
                                         samplerate=ioconf[0], block_frame=settings.block_frame, max_block=ioconf[2])
                 _send(conn, KIND_BLOCK, np.ascontiguousarray(out, dtype=dt).tobytes())
             elif kind == KIND_BLOCK:
-                if ref_wav is None:
+                if ref_wav is None and not loaded:
                     raise ValueError("send a reference (kind 1) before the first block")
                 if len(payload) % 4:
                     raise ValueError("block payload is not a whole number of float32 samples")
@@ -168,6 +199,14 @@ class Client:
         """IOCONF: blocks of any length up to max_block at sample_rate, float32 (fmt 0) or int16 (fmt 1)"""
         self._roundtrip(KIND_IOCONF, struct.pack("<iii", sample_rate, fmt, max_block))
         self.dtype = IO_DTYPES[fmt]
+
+    def save(self) -> bytes:
+        """SAVE: the session's live stream as an envelope (RealtimeSession.save)"""
+        return self._roundtrip(KIND_SAVE, b"")
+
+    def load(self, envelope):
+        """LOAD: continue the stream of a save() envelope; no set_reference is needed before the next convert"""
+        self._roundtrip(KIND_LOAD, bytes(envelope))
 
     def convert(self, block):
         dt = getattr(self, "dtype", "<f4")
